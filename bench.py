@@ -15,6 +15,10 @@ records.
 Rank 0 prints ONE JSON line with the contract keys plus
   roofline     algorithmic HBM bytes of the dominant kernel / its measured time
   cpu_baseline the oracle (CPU port of the reference) timed on host cores
+
+`--dump-outputs DIR` keeps what the last timed step returned (DIR/records.npy, the
+result table); the spectra and libraries are seeded, so two builds of the library
+can be compared output for output.
 """
 import argparse
 import json
@@ -31,7 +35,7 @@ if REPO not in sys.path:
 
 from rvspecfit_amd import synth  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec
 GRID_KW = dict(nteff=7, nlogg=7, nfeh=7, nalpha=7)
 RESOL = 3000.
 ARMS = ('b', 'r', 'z')
@@ -514,6 +518,30 @@ def dry_launch():
 
 
 # ------------------------------------------------------------------ main
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of `arrays` (name -> [rows, ...]) as
+    dirname/<name>.npy in float64 (float32 stays float32).  The files together
+    stay under DUMP_MAX_BYTES: an array over its share keeps a fixed, seeded sample
+    of its rows, in ascending order, whose indices go to <name>_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays) - 512   # (two .npy headers)
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        x = np.ascontiguousarray(x, dtype=np.float32 if x.dtype == np.float32
+                                 else np.float64)
+        if x.nbytes > share:
+            # (a row and its entry of <name>_rows.npy)
+            rows = np.sort(np.random.RandomState(20260917).choice(
+                x.shape[0], share // (x[:1].nbytes + 8), replace=False))
+            np.save(os.path.join(dirname, name + '_rows.npy'),
+                    rows.astype(np.float64))
+            x = x[rows]
+        np.save(os.path.join(dirname, name + '.npy'), x)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -588,9 +616,13 @@ def main():
                     help='build one template per spectrum (rounds 1-2) instead of '
                          'one per CCF node shared by the spectra that selected it; '
                          'same records bit for bit')
-    ap.add_argument('--dump-records', type=str, default='',
-                    help='rank 0 saves the gathered [n_gpus * spectra, 16] result '
-                         'table of the last step as .npy (tests)')
+    ap.add_argument('--dump-outputs', type=str, default='',
+                    help='rank 0 writes what the last timed step returned into this '
+                         'directory as <name>.npy (float64): records.npy, the '
+                         'gathered [n_gpus * spectra, 16] result table, columns = '
+                         'pipeline.RECORD_FIELDS.  Spectra and libraries are '
+                         'seeded, so two builds run with the same arguments are '
+                         'comparable output for output')
     ap.add_argument('--seed-rank', type=int, default=-1,
                     help='generate the spectra rank R of a multi-rank run would '
                          'generate (tests: a 1-rank run that reproduces one shard)')
@@ -598,6 +630,8 @@ def main():
                     help='with --gpus N: every rank prints the environment it '
                          'was started with and exits (no GPU, no torch)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps: at least one timed step; --warmup: zero or more')
     global ARMS, EVALUATOR, GRID_KW
     if args.workload == 'cfg2':
         ARMS = ('c', )
@@ -752,6 +786,9 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=tdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # what step() handed back the last time the clock saw it run
+        dump_outputs(args.dump_outputs, dict(records=rec.cpu().numpy()))
 
     # one extra, untimed, instrumented step for the per-stage breakdown
     timers = {}
@@ -811,8 +848,6 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
-    if args.dump_records:
-        np.save(args.dump_records, rec.cpu().numpy())
 
     value = world * S * args.steps / dt
     # ---- roofline of the dominant kernel -------------------------------

@@ -898,11 +898,13 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
             if key not in _EARLY_STREAMS:
                 _EARLY_STREAMS[key] = torch.cuda.Stream(device=dev)
             st_side = _EARLY_STREAMS[key]
-            ev = torch.cuda.Event()
-            ev.record(st_main)
             xs, ns, fs_ = nm['x'][fin].clone(), nm['nit'][fin].clone(), \
                 nm['nfev'][fin].clone()
             stat_fin = pobj.status[fin].clone()
+            # (the event goes behind the copies: they are launches on this stream like
+            # any other, and the side stream reads what they write)
+            ev = torch.cuda.Event()
+            ev.record(st_main)
             box = {}
 
             def run_side():

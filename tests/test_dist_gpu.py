@@ -37,22 +37,42 @@ def test_two_ranks_on_one_gpu_equal_two_single_rank_runs(tmp_path):
     S = 300
     common = ['--spectra', str(S), '--steps', '1', '--warmup', '0',
               '--no-cpu-baseline']
-    f2 = str(tmp_path / 'two.npy')
-    line = _run(['--gpus', '2', '--dump-records', f2] + common,
+    f2 = str(tmp_path / 'two')
+    line = _run(['--gpus', '2', '--dump-outputs', f2] + common,
                 RVS_SHARE_GPU='1', RVS_DIST_BACKEND='gloo')
     assert line['n_gpus'] == 2
     assert line['config']['parallelism'] == 'spectra-sharded x2'
-    two = np.load(f2)
+    two = np.load(os.path.join(f2, 'records.npy'))
     assert two.shape == (2 * S, 16)
     for r in range(2):
-        f1 = str(tmp_path / ('one%d.npy' % r))
-        one = _run(['--gpus', '1', '--seed-rank', str(r), '--dump-records', f1]
+        f1 = str(tmp_path / ('one%d' % r))
+        one = _run(['--gpus', '1', '--seed-rank', str(r), '--dump-outputs', f1]
                    + common)
         assert one['n_gpus'] == 1
         # rank r's shard sits at rows [r S, (r+1) S) of the gathered table
-        np.testing.assert_array_equal(two[r * S:(r + 1) * S], np.load(f1))
+        np.testing.assert_array_equal(two[r * S:(r + 1) * S],
+                                      np.load(os.path.join(f1, 'records.npy')))
     # the shards are different spectra
     assert not np.array_equal(two[:S], two[S:])
+
+
+def test_dump_outputs_same_arguments_same_table(tmp_path):
+    """`bench.py --dump-outputs DIR`: records.npy is the float64 table the last
+    timed step returned, and a second run with the same arguments starts from the
+    same spectra and writes the same table, bit for bit"""
+    S = 300
+    argv = ['--gpus', '1', '--spectra', str(S), '--steps', '2', '--warmup', '0',
+            '--no-cpu-baseline']
+    tabs = []
+    for k in range(2):
+        d = str(tmp_path / ('out%d' % k))
+        line = _run(argv + ['--dump-outputs', d])
+        assert line['steps'] == 2
+        assert os.listdir(d) == ['records.npy']
+        tabs.append(np.load(os.path.join(d, 'records.npy')))
+        assert tabs[k].dtype == np.float64 and tabs[k].shape == (S, 16)
+    np.testing.assert_array_equal(tabs[0], tabs[1])
+    assert np.isfinite(tabs[0][:, 7]).all() and tabs[0][:, 7].std() > 10   # best_vel
 
 
 def test_rccl_group_of_one_runs_the_gather(tmp_path):

@@ -63,25 +63,52 @@ def test_synth_batch_equals_scalar():
     np.testing.assert_allclose(a, b, rtol=1e-14)
 
 
-@pytest.mark.skipif(not (os.path.exists('/opt/conda/bin/python3.9')
-                         and os.path.exists('/tmp/golden_work/templ/interp_gold_b.h5')),
-                    reason='needs the build container (h5py interpreter + the '
-                           'reference artefacts made by make_golden.py)')
+def _python_with_h5py():
+    """an interpreter that can read the reference's HDF5 files: this one, or (h5py is
+    not installed next to torch in the build image) a python3.9 / conda one"""
+    import importlib.util
+    import sys
+    if importlib.util.find_spec('h5py') is not None:
+        return sys.executable
+    for exe in (shutil.which('python3.9'), '/opt/conda/bin/python3.9',
+                '/opt/conda/bin/python'):
+        if exe and os.path.exists(exe) and subprocess.run(
+                [exe, '-W', 'ignore', '-c', 'import h5py, numpy'],
+                capture_output=True).returncode == 0:
+            return exe
+    return None
+
+
 def test_convert_artefacts_reproduces_reference_loader(tmp_path):
-    src = '/tmp/golden_work/templ'
+    """tools/convert_artefacts.py on the template directory of the golden setup: the
+    HDF5 files as the reference's prep pipeline wrote them (tests/golden/templ_gold_b,
+    make_golden_convert.py: regular-grid library, CCF set, --nocontinuum CCF set)
+    and, in the reference's file formats (make_nd.py:176, make_ccf.py:483-493), the
+    arrays lib_gold_b.npz / lib_nocont_gold_b.npz hold -- against what the reference's
+    own loader returned for that directory, i.e. those two fixtures: every key, bit
+    for bit"""
+    exe = _python_with_h5py()
+    if exe is None:
+        pytest.skip('no interpreter with h5py')
+    gold = os.path.join(REPO, 'tests', 'golden')
+    fixtures = [np.load(os.path.join(gold, 'lib_gold_b.npz')),
+                np.load(os.path.join(gold, 'lib_nocont_gold_b.npz'))]
+    src = os.path.join(gold, 'templ_gold_b')
+    assert sorted(os.listdir(src)) == ['ccf_gold_b.h5', 'ccf_nocont_gold_b.h5',
+                                       'interp_gold_b.h5']
     for f in os.listdir(src):
-        if 'gold_b' in f and not f.startswith('rvsgpu_'):
-            shutil.copy(os.path.join(src, f), tmp_path)
-    subprocess.check_call(['/opt/conda/bin/python3.9', '-W', 'ignore',
+        shutil.copy(os.path.join(src, f), tmp_path)
+    np.save(os.path.join(tmp_path, 'interpdat_gold_b.npy'), fixtures[0]['dats'])
+    for b, pref, key in ((fixtures[0], '', 'ccf_'), (fixtures[1], 'nocont_', 'ccfnc_')):
+        np.savez(os.path.join(tmp_path, 'ccfdat_%sgold_b.npz' % pref),
+                 fft=b[key + 'fft'], fft2=b[key + 'fft2'])
+        np.save(os.path.join(tmp_path, 'ccfmod_%sgold_b.npy' % pref), b[key + 'mod'])
+    subprocess.check_call([exe, '-W', 'ignore',
                            os.path.join(REPO, 'tools', 'convert_artefacts.py'),
                            str(tmp_path), 'gold_b'], stdout=subprocess.DEVNULL)
     a = np.load(os.path.join(tmp_path, 'rvsgpu_gold_b.npz'))
-    fixtures = [np.load(os.path.join(REPO, 'tests', 'golden', 'lib_gold_b.npz'))]
-    if os.path.exists(os.path.join(src, 'ccf_nocont_gold_b.h5')):
-        # the --nocontinuum set (make_golden_nocont.py) lands under ccfnc_*
-        fixtures.append(np.load(os.path.join(REPO, 'tests', 'golden',
-                                             'lib_nocont_gold_b.npz')))
-        assert 'ccfnc_fft' in a.files
+    # the --nocontinuum set (make_golden_nocont.py) lands under ccfnc_*
+    assert 'ccfnc_fft' in a.files
     for b in fixtures:
         for k in b.files:
             x, y = a[k], b[k]
@@ -90,6 +117,37 @@ def test_convert_artefacts_reproduces_reference_loader(tmp_path):
                 assert np.array_equal(x, y), k
             else:
                 np.testing.assert_array_equal(x, y, err_msg=k)
+
+
+def test_bench_dump_outputs_files_and_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float .npy per array; past the size limit a
+    fixed sample of rows (ascending, the same on every call) and its indices"""
+    import bench
+    rng = np.random.RandomState(6)
+    rec = rng.standard_normal((1000, 16))
+    rec[3, 6] = np.nan
+    d = str(tmp_path / 'all')
+    bench.dump_outputs(d, dict(records=rec, ids=np.arange(5, dtype=np.int32),
+                               f32=rec[:7].astype(np.float32)))
+    assert sorted(os.listdir(d)) == ['f32.npy', 'ids.npy', 'records.npy']
+    np.testing.assert_array_equal(np.load(os.path.join(d, 'records.npy')), rec)
+    assert np.load(os.path.join(d, 'ids.npy')).dtype == np.float64
+    assert np.load(os.path.join(d, 'f32.npy')).dtype == np.float32
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 20000)
+    got = []
+    for k in range(2):
+        d = str(tmp_path / ('cap%d' % k))
+        bench.dump_outputs(d, dict(records=rec))
+        rows = np.load(os.path.join(d, 'records_rows.npy'))
+        x = np.load(os.path.join(d, 'records.npy'))
+        assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0)
+        assert 100 < len(rows) < 1000
+        np.testing.assert_array_equal(x, rec[rows.astype(int)])
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) \
+            <= 20000
+        got.append(rows)
+    np.testing.assert_array_equal(got[0], got[1])
 
 
 def test_lockstep_neldermead_equals_scipy():

@@ -85,8 +85,11 @@ extern "C" {
  *      device), rvs_chisq_grid_resol_g (resolution matrices on grid sets),
  *      rvs_template_tri_buckets (find_simplex through a bucket grid);
  *      rvs_nm_objective grew by `tri` (Delaunay libraries inside rvs_nm_run),
- *      rvs_nm_state by `stop_below` */
-#define RVS_ABI_VERSION 12
+ *      rvs_nm_state by `stop_below`
+ *  13: rvs_objective_fused(_n) / rvs_objective_from_template(_n) -- and with them
+ *      rvs_nm_run / rvs_bfgs_run -- apply pt.taps (until now RVS_E_ARG) where
+ *      rvs_objective_resol_ok (added) admits the arm */
+#define RVS_ABI_VERSION 13
 int rvs_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -470,8 +473,9 @@ int rvs_chisq_point(const rvs_point_arm *arms, int narm, int npoly,
  * spline record goes to HBM.  Replaces, for the optimiser's ~850 calls per
  * spectrum, the chain rvs_template_polylinear -> rvs_vsini_convolve ->
  * rvs_spline_construct -> rvs_chisq_point (same arithmetic per phase).
- * Per arm: `pt` as in rvs_chisq_point (coef, penalty, taps unused; no
- * fast_interp), the polylinear library as in rvs_template_polylinear, the
+ * Per arm: `pt` as in rvs_chisq_point (coef, penalty unused; no fast_interp;
+ * taps / taps_stride / nd as there: the band runs over the pixels' spline values
+ * in LDS, the sum over d ascending as rvs_chisq_point forms it), the polylinear library as in rvs_template_polylinear, the
  * rvs_spline_factors of the template grid, ln-step of the grid for the
  * rotational kernel.  params [J, ndim], vsini [J] (nullable = no rotation),
  * vel [J]; scratch: rvs_objective_work_size(J, narm) bytes;
@@ -482,7 +486,13 @@ int rvs_chisq_point(const rvs_point_arm *arms, int narm, int npoly,
  * RVS_E_ARG: ntp < 32 or > rvs_objective_max_ntp(npoly); and, from npoly = 11 on
  * (the waves' partial sums live in the template's LDS), an arm with
  * 2*npix > ntp or 2*ntp < 8*(npoly*(npoly+3)/2 + 1) -- use the chain of
- * stand-alone kernels there.
+ * stand-alone kernels there.  With a resolution matrix on any arm: every arm must
+ * pass rvs_objective_resol_ok(npoly, npix, ntp, nd) (an arm without taps among
+ * them counts as nd = 1) -- nd odd and <= 33, 2*npix <= ntp and
+ * npix + nd - 1 <= ntp (spline values, their zero margins and the sigma-scaled
+ * pair live in the template's LDS), and from npoly = 11 on
+ * ntp >= 8*(npoly*(npoly+3)/2 + 1); else RVS_E_ARG and the chain as before (the
+ * 377 diagonals of an R = 50 matrix, tests/test_sdss.py).
  * ---------------------------------------------------------------------- */
 #define RVS_OBJ_STATUS_STORE 2
 /* bit 2: the per-arm results stay in `scratch` ([narm, J] chi^2, [narm, J] outside,
@@ -503,6 +513,9 @@ typedef struct rvs_objective_arm {
   int32_t exp_flag;
 } rvs_objective_arm;
 int rvs_objective_max_ntp(int npoly); /* largest template grid that fits LDS */
+/* 1: the objective kernel applies a resolution matrix of nd diagonals on an arm of
+ * this geometry (host arithmetic only: no device is touched) */
+int rvs_objective_resol_ok(int npoly, int npix, int ntp, int nd);
 int64_t rvs_objective_work_size(int J, int narm);
 int rvs_objective_fused(const rvs_objective_arm *arms, int narm, int npoly,
                         const double *params, const double *vsini,

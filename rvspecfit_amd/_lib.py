@@ -73,6 +73,7 @@ SIGNATURES = {
     'rvs_bfgs_run_bytes': (L, []),
     'rvs_bfgs_run': (I, [P, P, I, P, P]),
     'rvs_objective_max_ntp': (I, [I]),
+    'rvs_objective_resol_ok': (I, [I, I, I, I]),
     'rvs_objective_work_size': (L, [I, I]),
     'rvs_objective_fused': (I, [P, I, I, P, P, P, I, P, D, I, P, P, P, P]),
     'rvs_objective_from_template': (I, [P, I, I, P, P, P, P, I, P, D, I, P, P, P,
@@ -100,7 +101,7 @@ SIGNATURES = {
 
 _lib = None
 # RVS_ABI_VERSION of the include/rvsgpu.h these signatures mirror
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class RvsGpuError(RuntimeError):

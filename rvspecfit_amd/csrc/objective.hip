@@ -257,7 +257,11 @@ __global__ void __launch_bounds__(OBJ_ORD_NT)
 // INBLK: grids of more than 4 dimensions (no cell record: the search runs in
 // the block; its dynamically indexed descriptor costs every instantiation that
 // contains it 168 B of scratch per lane, so it is a variant of its own)
-template <int P, bool FROMT, bool INBLK = false>
+// RESOL: arms with a banded resolution matrix (rvs_point_arm.taps: A9,
+// spec_fit.py:920-929) -- the pixels' spline values stay in LDS and the band runs
+// over them ahead of the normal equations; a variant of its own so that the
+// instantiations without a matrix stay the code they were
+template <int P, bool FROMT, bool INBLK = false, bool RESOL = false>
 __global__ void __launch_bounds__(OBJ_NT)
     objective_kernel(ObjArms A, ObjTempl TT, const double *__restrict__ locrec,
                      const int32_t *__restrict__ perm,
@@ -881,7 +885,8 @@ __global__ void __launch_bounds__(OBJ_NT)
   constexpr int PU = 6;
   double qlm[PU], qwk[PU];
   double2 qsg[PU];
-  const bool cached = 2 * npix <= N;
+  // (RESOL: the launcher admits the cached geometry only, rvs_objective_resol_ok)
+  const bool cached = RESOL || 2 * npix <= N;
   if (cached) {
 #pragma unroll
     for (int u = 0; u < PU; u++) {
@@ -957,7 +962,21 @@ __global__ void __launch_bounds__(OBJ_NT)
   // of a thread with each round of loads issued together (pixel terms, then
   // the knot terms that depend on the interval index): two L2 round trips for
   // six pixels instead of two per pixel.
-  double *tcache = bufC;
+  // RESOL: the first pass leaves the spline values themselves in the factor buffer,
+  // raw[k] at bufC[hb + k] between two runs of hb = (nd - 1) / 2 zeros (a term of the
+  // band whose pixel lies outside [0, npix) multiplies a zero that is loaded: as in the
+  // FIR, no range test per element, and fma(t, 0, v) = v is the term skipped).  Behind
+  // a barrier template and second derivatives are dead, and the band's sums go where
+  // the second of them was, in the layout the passes below read: [npix] t/e, [npix] s/e.
+  // (The wave totals of P > 10 live in the FIRST buffer: the launcher keeps them inside
+  // it for this form.)
+  const int rnd = (RESOL && S.taps) ? S.nd : 1, hb = (rnd - 1) >> 1;
+  double *tcache = RESOL ? bufB : bufC;
+  double *raw = bufC + hb;
+  if (RESOL && tid < hb) {
+    bufC[tid] = 0.0;
+    raw[npix + tid] = 0.0;
+  }
   if (cached) {
     constexpr int U = 6;
     for (int kb = tid; kb < npix; kb += U * OBJ_NT) {
@@ -1006,13 +1025,72 @@ __global__ void __launch_bounds__(OBJ_NT)
         const double c2 = 0.5 * zi, c3 = (zi1 - zi) * t1;
         const double tv = fma(fma(fma(c3, dl, c2), dl, cb), dl, yi);
         if (k < npix) {
-          tcache[k] = tv * sg[u].x;
-          tcache[npix + k] = sg[u].y;
+          if constexpr (RESOL) {
+            raw[k] = tv;
+          } else {
+            tcache[k] = tv * sg[u].x;
+            tcache[npix + k] = sg[u].y;
+          }
         }
       }
     }
   }
   OBJ_T(7);
+  if constexpr (RESOL) {
+    // ---- A9: model[k] = sum_d taps[s, k, d] raw[k - hb + d], d ascending from 0 as
+    // point_block_kernel forms it (chisq.hip), then t/e.  Threads are pixels: a lane's
+    // nd taps are one contiguous run on an 8-byte boundary, taken two per request.
+    __syncthreads();
+    const double *tps = S.taps ? S.taps + (int64_t)s * S.taps_stride : nullptr;
+    typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
+    constexpr int U = 6;
+    for (int kb = tid; kb < npix; kb += U * OBJ_NT) {
+      const double *tk[U], *rk[U];
+      double2 sg[U];
+      double acc[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int k = min(kb + u * OBJ_NT, npix - 1);
+        tk[u] = tps + (int64_t)k * rnd;
+        rk[u] = bufC + k;   // raw[k - hb]
+        if (kb == tid)
+          sg[u] = qsg[u];
+        else
+          sg[u] = sig[k];
+        acc[u] = 0;
+      }
+      if (tps) {
+        int d = 0;
+        for (; d + 2 <= rnd; d += 2) {
+          d2u t2[U];
+#pragma unroll
+          for (int u = 0; u < U; u++) t2[u] = *reinterpret_cast<const d2u *>(tk[u] + d);
+#pragma unroll
+          for (int u = 0; u < U; u++) {
+            acc[u] = fma(t2[u].x, rk[u][d], acc[u]);
+            acc[u] = fma(t2[u].y, rk[u][d + 1], acc[u]);
+          }
+        }
+        double t1[U];   // (nd is odd: the last tap)
+#pragma unroll
+        for (int u = 0; u < U; u++) t1[u] = tk[u][d];
+#pragma unroll
+        for (int u = 0; u < U; u++) acc[u] = fma(t1[u], rk[u][d], acc[u]);
+      } else {   // (an arm without a matrix beside arms that have one)
+#pragma unroll
+        for (int u = 0; u < U; u++) acc[u] = rk[u][0];
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int k = kb + u * OBJ_NT;
+        if (k < npix) {
+          tcache[k] = acc[u] * sg[u].x;
+          tcache[npix + k] = sg[u].y;
+        }
+      }
+    }
+    OBJ_T(10);   // (debug) the resolution band
+  }
   // Normal equations: rows [I0, I1) of the packed matrix + right-hand side, summed
   // over this thread's pixels, reduced over the wave by halving, wave totals into
   // red[w][].  One pass over the pixels up to P = 10 (65 sums: 130 registers); from
@@ -1401,6 +1479,21 @@ extern "C" int rvs_objective_max_ntp(int npoly) {
   return n > 8192 ? 8192 : (n < 0 ? 0 : n);
 }
 
+// Arms with a resolution matrix of nd diagonals (rvs_point_arm.taps): what
+// objective_kernel<.., RESOL> needs of the arm's geometry.  The band is applied to
+// the pixels' spline values in LDS, so they and the sigma-scaled pair behind them
+// must fit the template's buffers (2 npix <= ntp), the values with (nd - 1) / 2 zeros
+// on both sides, and from npoly = 11 on the wave totals must stay inside the first
+// buffer.  The one statement of the condition: the launcher refuses what it
+// excludes, the callers (engine.can_fuse_objective) keep the kernel chain there.
+extern "C" int rvs_objective_resol_ok(int npoly, int npix, int ntp, int nd) {
+  if (npoly < 1 || npoly > 16 || npix < 1 || ntp < 32 || ntp > 8192) return 0;
+  if (nd < 1 || nd > 33 || !(nd & 1)) return 0;
+  if (2 * (int64_t)npix > ntp || (int64_t)npix + nd - 1 > ntp) return 0;
+  if (npoly > 10 && ntp < OBJ_NW * (npoly * (npoly + 1) / 2 + npoly + 1)) return 0;
+  return 1;
+}
+
 extern "C" int64_t rvs_objective_work_size(int J, int narm) {
   if (J < 1 || narm < 1) return 0;
   // per (arm, job): chi^2, outside, status (padded to 8 bytes) + the cell-search
@@ -1424,13 +1517,15 @@ static int objective_launch(const rvs_objective_arm *arms, int narm, int npoly,
   ObjTempl TT = {};
   if (tt) TT = *tt;
   size_t shm = 0;
+  bool resol = false;   // an arm carries a resolution matrix: objective_kernel<.., RESOL>
   for (int i = 0; i < narm; i++) {
     A.a[i] = arms[i];
     // (ntp >= 32: the FIR window and the spline chunks read up to 24 doubles behind a
     // thread's own rows without testing, inside the block's three template buffers)
     if (arms[i].pt.npix < 1 || arms[i].ntp < 32 || arms[i].ntp > 8192 ||
-        arms[i].pt.taps || arms[i].pt.fast_interp || !arms[i].factors)
+        arms[i].pt.fast_interp || !arms[i].factors)
       return RVS_E_ARG;
+    if (arms[i].pt.taps) resol = true;
     if (tt) {
       if (!TT.templ[i] || !TT.outside[i]) return RVS_E_ARG;
     } else if (arms[i].ndim < 1 || arms[i].ndim > MAXDIM) {
@@ -1451,6 +1546,11 @@ static int objective_launch(const rvs_objective_arm *arms, int narm, int npoly,
   dim3 grid(J, narm);
   if (shm > (size_t)(3 * rvs_objective_max_ntp(npoly) + 2 * OBJ_FIR_PAD) * sizeof(double))
     return RVS_E_ARG;
+  if (resol)   // (an arm without a matrix among them: a band of one diagonal)
+    for (int i = 0; i < narm; i++)
+      if (!rvs_objective_resol_ok(npoly, arms[i].pt.npix, arms[i].ntp,
+                                  arms[i].pt.taps ? arms[i].pt.nd : 1))
+        return RVS_E_ARG;
   if (npoly > 10)   // (the wave totals share the template buffer: RED_DYN)
     for (int i = 0; i < narm; i++)
       // (... which the model pass has left: template and second derivatives, two
@@ -1511,20 +1611,25 @@ static int objective_launch(const rvs_objective_arm *arms, int narm, int npoly,
     }
   }
 #endif
-#define RVS_LAUNCH_OBJ(PP, FT, IB)                                                 \
+#define RVS_LAUNCH_OBJ_R(PP, FT, IB, RS)                                         \
   {                                                                            \
     static bool attr_set = false;                                              \
     if (!attr_set) {                                                           \
-      (void)hipFuncSetAttribute((const void *)objective_kernel<PP, FT, IB>,    \
+      (void)hipFuncSetAttribute((const void *)objective_kernel<PP, FT, IB, RS>, \
                                 hipFuncAttributeMaxDynamicSharedMemorySize,    \
                                 160 * 1024 - 1024);                            \
       (void)hipGetLastError();                                                 \
       attr_set = true;                                                         \
     }                                                                          \
-    hipLaunchKernelGGL((objective_kernel<PP, FT, IB>), grid, dim3(OBJ_NT), shm,  \
+    hipLaunchKernelGGL((objective_kernel<PP, FT, IB, RS>), grid, dim3(OBJ_NT), shm, \
                        st,                                                     \
                        A, TT, loc, perm, live, params, vsini, job_spec, J, vel, 0.6, \
                        armchi, armst, armout);                                 \
+  }
+#define RVS_LAUNCH_OBJ(PP, FT, IB)                                             \
+  {                                                                            \
+    if (resol) RVS_LAUNCH_OBJ_R(PP, FT, IB, true)                              \
+    else RVS_LAUNCH_OBJ_R(PP, FT, IB, false)                                   \
   }
 #define RVS_CASE(PP)                                                           \
   case PP:                                                                     \
@@ -1539,6 +1644,7 @@ static int objective_launch(const rvs_objective_arm *arms, int narm, int npoly,
   }
 #undef RVS_CASE
 #undef RVS_LAUNCH_OBJ
+#undef RVS_LAUNCH_OBJ_R
   if (outside_penalty & RVS_OBJ_NO_SUM) {   // the caller sums the arms (nm.hip)
     RVS_LAUNCH_CHECK();
     return 0;

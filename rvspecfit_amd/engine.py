@@ -946,26 +946,32 @@ def set_point_grid(p, arm, npoly):
     p.pen_scale = ps.data_ptr() if ps is not None else None
 
 
-def fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys=0.0):
+def fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys=0.0, resols=None):
     """rvs_objective_arm descriptors of every arm (ctypes array `arr`); returns
-    the tensors that must stay alive while the descriptors are used"""
+    the tensors that must stay alive while the descriptors are used.  `resols`:
+    the `resol_params` override per arm (spec_fit._resols); without it the
+    spectra's own resolution matrices, as chisq_point wires them."""
     keep = []
     esys = _per_arm(espec_sys, len(batch.arms))
     for ia, arm in enumerate(batch.arms):
         lib = libs[arm.name]
         work = arm.work(lib, esys[ia])
         polysT = arm.basis(npoly, rbf)
-        keep.append((work, polysT))
+        rs = _arm_resol(arm, ia, resols)   # A9: banded resolution matrix
+        keep.append((work, polysT, rs))
         a = arr[ia]
         p = a.pt
         p.lam, p.polysT = arm.lam.data_ptr(), polysT.data_ptr()
         p.spec, p.espec = arm.spec.data_ptr(), arm.espec.data_ptr()
         p.work, p.knots = work.data_ptr(), lib.knots.data_ptr()
-        p.coef = p.penalty = p.taps = None
-        p.taps_stride, p.espec_sys = 0, esys[ia]
+        p.coef = p.penalty = None
+        p.taps = rs['taps'].data_ptr() if rs is not None else None
+        p.taps_stride = rs['stride'] if rs is not None else 0
+        p.espec_sys = esys[ia]
         p.npix, p.S, p.ntp = arm.npix, arm.S, lib.ntp
         set_point_grid(p, arm, npoly)
-        p.log_step, p.nd, p.fast_interp = int(lib.log_step), 0, 0
+        p.log_step, p.fast_interp = int(lib.log_step), 0
+        p.nd = rs['nd'] if rs is not None else 0
         a.factors = lib.spline_factors.data_ptr()
         a.lnstep = lib.lnstep
         a.ntp, a.ndim = lib.ntp, lib.ndim
@@ -990,9 +996,13 @@ _max_ntp = {}
 def can_fuse_objective(batch, libs, resols=None, fast_interp=False, npoly=10,
                        from_template=False):
     """the single-kernel objective needs a (log-)uniform template grid that fits
-    LDS, and neither resolution matrices nor fast_interp; with the gather inside
-    the kernel (rvs_objective_fused) regular-grid libraries, with the template
-    handed over (from_template: rvs_objective_from_template) any evaluator"""
+    LDS and no fast_interp; with the gather inside the kernel
+    (rvs_objective_fused) regular-grid libraries, with the template handed over
+    (from_template: rvs_objective_from_template) any evaluator.  Resolution
+    matrices (the spectra's own or the `resols` override) go into the kernel
+    where the library's rvs_objective_resol_ok admits the arm -- a band of up to
+    33 diagonals on an arm whose pixels fit the template's buffers twice; wider
+    matrices (the R = 50 ones of SDSS: 377 diagonals) keep the kernel chain."""
     if fast_interp or not FUSED_OBJECTIVE:
         return False
     if npoly not in _max_ntp:
@@ -1008,19 +1018,31 @@ def can_fuse_objective(batch, libs, resols=None, fast_interp=False, npoly=10,
         if npoly > 10 and (2 * arm.npix > lib.ntp or
                            2 * lib.ntp < 8 * (npoly * (npoly + 3) // 2 + 1)):
             return False   # (objective_kernel<P > 10>: csrc/objective.hip, RED_DYN)
-        if _arm_resol(arm, ia, resols) is not None:
+    rss = [_arm_resol(arm, ia, resols) for ia, arm in enumerate(batch.arms)]
+    if any(rs is not None for rs in rss):
+        if not FUSED_OBJECTIVE_RESOL:
             return False
+        ok = _lib.lib().rvs_objective_resol_ok
+        for arm, rs in zip(batch.arms, rss):
+            # (an arm without a matrix beside arms that have one: one diagonal)
+            if not ok(npoly, arm.npix, libs[arm.name].ntp,
+                      rs['nd'] if rs is not None else 1):
+                return False
     return True
 
 
 # False: the chain of stand-alone kernels also for regular-grid libraries
 # (tests/test_gpu_parity.py::test_objective_fused compares the two)
 FUSED_OBJECTIVE = True
+# False: arms with a resolution matrix keep the kernel chain (template, FIR,
+# spline record, rvs_chisq_point with taps) as they did before the kernel applied
+# the band (tests/test_resol_objective.py and A/B runs put the two side by side)
+FUSED_OBJECTIVE_RESOL = True
 
 
 def objective_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
                     job_spec=None, espec_sys=0.0, outside_penalty=True,
-                    njobs=None, out=None):
+                    njobs=None, out=None, resols=None):
     """get_chisq for J (spectrum, parameters, vsini, velocity) jobs as ONE kernel
     per call (rvs_objective_fused): no template or spline record in HBM.
     Returns chisq [J], status int32 [J].  `njobs` (int32 device tensor, one
@@ -1034,7 +1056,7 @@ def objective_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
     J = vel.shape[0]
     narm = len(batch.arms)
     arr = (_lib.ObjectiveArm * narm)()
-    keep = fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys)
+    keep = fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys, resols)
     if out is None:
         out = torch.empty(J, dtype=torch.float64, device=dev)
     status = torch.zeros(J, dtype=torch.int32, device=dev)
@@ -1057,7 +1079,7 @@ def objective_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
 
 def objective_from_template(batch, libs, templs, outsides, vsini, vel, npoly=5,
                             rbf=True, job_spec=None, espec_sys=0.0,
-                            outside_penalty=True):
+                            outside_penalty=True, resols=None):
     """objective_fused for evaluators that are no grid gather: templs[a]
     [J, ntp_a] (unbroadened), outsides[a] [J] (rvs_objective_from_template)."""
     import ctypes
@@ -1067,7 +1089,7 @@ def objective_from_template(batch, libs, templs, outsides, vsini, vel, npoly=5,
     J = vel.shape[0]
     narm = len(batch.arms)
     arr = (_lib.ObjectiveArm * narm)()
-    keep = fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys)
+    keep = fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys, resols)
     out = torch.empty(J, dtype=torch.float64, device=dev)
     status = torch.zeros(J, dtype=torch.int32, device=dev)
     nb = L.rvs_objective_work_size(J, narm)

@@ -140,7 +140,8 @@ class ProcessObjective:
         if self.fused or self.from_templ:
             self.oarr = (_lib.ObjectiveArm * narm)()
             self._keep = engine.fill_objective_arms(self.oarr, batch, libs,
-                                                    self.npoly, self.rbf, 0.0)
+                                                    self.npoly, self.rbf, 0.0,
+                                                    resols)
             nb = L.rvs_objective_work_size(cap, narm)
             self.oscratch = torch.empty((nb + 7) // 8, **f64)
         # MLP libraries on every arm: the rounds can run inside rvs_nm_run too

@@ -509,7 +509,8 @@ def chisq_jobs(batch, idx, vel, params, vsini, options, config,
         return engine.objective_fused(batch, libs, params, vsini, vel,
                                       npoly=npoly, rbf=rbf, job_spec=js,
                                       espec_sys=esys,
-                                      outside_penalty=outside_penalty)
+                                      outside_penalty=outside_penalty,
+                                      resols=resols)
     if engine.can_fuse_objective(batch, libs, resols, npoly=npoly,
                                  from_template=True):
         # MLP / Delaunay evaluators: template rows from their own kernel, then
@@ -528,7 +529,7 @@ def chisq_jobs(batch, idx, vel, params, vsini, options, config,
                 batch, libs, [t[0] for t in tt], [t[1] for t in tt],
                 None if vsini is None else vsini[a:b], vel[a:b], npoly=npoly,
                 rbf=rbf, job_spec=js[a:b], espec_sys=esys,
-                outside_penalty=outside_penalty)
+                outside_penalty=outside_penalty, resols=resols)
             del tt
         return out, st
     coefs, outs = [], []

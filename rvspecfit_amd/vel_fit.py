@@ -628,7 +628,8 @@ def param_uncertainties(specdata, vel, atm_params, vsini=None, options=None,
 PROCESS_STREAMS = int(os.environ.get('RVS_PROCESS_STREAMS', '2'))
 # the second minimiser's rounds on the device (rvs_bfgs_run) wherever the library
 # launches the objective itself; False: the host machines around the Python objective
-# (what Delaunay evaluators and resolution matrices take anyway) -- the two run the
+# (what Delaunay evaluators without a bucket grid and resolution matrices wider than
+# the objective kernel's band take anyway) -- the two run the
 # same state machine (test_process_bfgs_device_equals_host)
 BFGS_ON_DEVICE = os.environ.get('RVS_BFGS_ON_DEVICE', '1') != '0'
 # (64: the stellar targets of one DESI petal are 100-200 spectra -- split, 100 spectra
@@ -759,10 +760,11 @@ def _process_split(batch, paramDict0, kwargs):
 
 def _rounds_run_in_c(batch, config, resolParams, options=None):
     """the optimiser's rounds of this batch run inside the library (rvs_nm_run:
-    regular-grid and MLP libraries, no resolution matrix); only then do two host
-    threads help -- rounds driven from Python (Delaunay evaluators, resolution
-    matrices) share the interpreter lock (round 3, NN rounds still in Python:
-    432 against 586 spectra/s split in two)"""
+    regular-grid, MLP and bucketed Delaunay libraries, with resolution matrices
+    where engine.can_fuse_objective admits them); only then do two host threads
+    help -- rounds driven from Python (other evaluators, resolution matrices wider
+    than the objective kernel's band) share the interpreter lock (round 3, NN
+    rounds still in Python: 432 against 586 spectra/s split in two)"""
     libs = spec_inter.get_libs(batch.names, config)
     npoly = (options or {}).get('npoly') or 5
     rs = spec_fit._resols(batch, resolParams)

@@ -16,6 +16,10 @@ run --resolution-matrix --steps 2 --warmup 1 --no-cpu-baseline
 # --process-no-bfgs is the Nelder-Mead-only add-on)
 run --spectra 2000 --steps 1 --warmup 1 --cpu-sample 8 --process 2000 --process-cpu-sample 8
 run --spectra 2000 --steps 1 --warmup 1 --no-cpu-baseline --process 2000 --process-no-bfgs
+# (vel_fit.process with the spectra's own 11-diagonal resolution matrices: the chain of
+# stand-alone kernels and the objective kernel with the band, alternating -- the
+# --process add-on of bench.py fits its sub-batch without the matrices)
+python tools/perf/resol_ab.py --reps 1 --spectra 2000 2>/dev/null >> $out
 run --spectra 2000 --steps 1 --warmup 1 --no-cpu-baseline --desi-file 500
 run --spectra 2000 --steps 1 --warmup 1 --no-cpu-baseline --desi-file 500 --process-no-bfgs
 run --spectra 2000 --steps 1 --warmup 1 --no-cpu-baseline --desi-file 500 --desi-nfiles 16

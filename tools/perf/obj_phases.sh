@@ -14,8 +14,9 @@ L = _lib.lib()
 buf = (ctypes.c_ulonglong * 24)()
 L.rvs_dbg_read.argtypes = [ctypes.c_void_p]
 L.rvs_dbg_read(ctypes.addressof(buf))
-t = np.array(buf[:10], dtype=float)
-names = ['locate', 'gather+exp', 'vsini', 'spline', 'tv+normal', 'cholesky+solve', 'resid', 'model pass', 'wave reduce', 'fold']
+t = np.array(buf[:11], dtype=float)
+names = ['locate', 'gather+exp', 'vsini', 'spline', 'tv+normal', 'cholesky+solve', 'resid', 'model pass', 'wave reduce', 'fold',
+         'resolution band']
 # (indices 18..23: wave 0 inside 'cholesky+solve', clocked without barriers)
 sub = np.array(buf[18:24], dtype=float)
 tot = t.sum() + sub.sum()

@@ -82,8 +82,8 @@ def minimize_lockstep_native(func, x0, hess_inv0=None, max_rows=None, gtol=1e-5,
 def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.9,
                              xrtol=0, maxiter=None, sync_every=4):
     """The runs on the device (csrc/bfgs_dev.hip, rvs_bfgs_run) around an
-    optimizer.ProcessObjective whose rounds the library drives (pobj.fused or
-    pobj.nn_native): x0 [S, n] device tensor, hess_inv0 [n, n] array.  Returns
+    optimizer.ProcessObjective whose rounds the library drives (pobj.native):
+    x0 [S, n] device tensor, hess_inv0 [n, n] array.  Returns
     device tensors x [S, n], fun, nit, nfev, status [S] and the statistics of the
     run (rounds, objective calls, rows launched)."""
     import ctypes
@@ -122,7 +122,7 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     pobj.calls += int(st3[1])
     nfev = keep['nfev'].long()
     pobj.jobs += int(nfev.sum().item())
-    pobj.slots = getattr(pobj, 'slots', 0) + int(st3[2])
+    pobj.slots += int(st3[2])
     return dict(x=keep['x'], fun=keep['fun'], nit=keep['nit'].long(), nfev=nfev,
                 status=keep['status'].long(), rounds=int(st3[0]),
                 calls=int(st3[1]), rows_launched=int(st3[2]))

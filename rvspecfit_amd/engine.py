@@ -903,30 +903,14 @@ def chisq_point(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
     keep = []
     esys = _per_arm(espec_sys, narm)
     for ia, arm in enumerate(batch.arms):
-        lib = libs[arm.name]
-        work = arm.work(lib, esys[ia])
-        polysT = arm.basis(npoly, rbf)
         o = outsides[ia]
         if job_templ is not None:
             o = o[job_templ.long()]
         pen = o * batch.badchi_jobs(job_spec) if outside_penalty else torch.where(
             torch.isfinite(o), torch.zeros_like(o), o)
-        pen = pen.contiguous()
-        coef = coefs[ia]
-        keep.append((work, polysT, pen, coef))
-        a = arr[ia]
-        a.lam, a.polysT = arm.lam.data_ptr(), polysT.data_ptr()
-        a.spec, a.espec = arm.spec.data_ptr(), arm.espec.data_ptr()
-        a.work, a.knots = work.data_ptr(), lib.knots.data_ptr()
-        a.coef, a.penalty = coef.data_ptr(), pen.data_ptr()
-        a.npix, a.S, a.ntp = arm.npix, arm.S, lib.ntp
-        set_point_grid(a, arm, npoly)
-        a.log_step = int(lib.log_step)
-        a.espec_sys, a.fast_interp = esys[ia], int(bool(fast_interp))
-        rs = _arm_resol(arm, ia, resols)
-        if rs is not None:
-            a.taps, a.taps_stride, a.nd = rs['taps'].data_ptr(), rs['stride'], \
-                rs['nd']
+        keep.append(fill_point_arm(arr[ia], arm, libs[arm.name], npoly, rbf,
+                                   esys[ia], _arm_resol(arm, ia, resols),
+                                   coefs[ia], pen.contiguous(), fast_interp))
     with _ktime('chisq_point', J):
         rc = L.rvs_chisq_point(ctypes.addressof(arr), narm, npoly,
                                _lib.ptr(job_spec), _lib.ptr(job_templ), J,
@@ -937,13 +921,33 @@ def chisq_point(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
     return out, status
 
 
-def set_point_grid(p, arm, npoly):
-    """grid-set fields of an rvs_point_arm (include/rvsgpu.h)"""
+def fill_point_arm(p, arm, lib, npoly, rbf, espec_sys=0.0, resol=None, coef=None,
+                   penalty=None, fast_interp=False):
+    """every field of one rvs_point_arm (include/rvsgpu.h) `p` for `arm` against
+    `lib`; returns the tensors that must stay alive while the descriptor is used.
+    resol: the arm's banded resolution matrix (_arm_resol) or None; coef /
+    penalty: the spline records and the outside penalties of the jobs, for the
+    kernels that read them (rvs_chisq_point)."""
+    work = arm.work(lib, espec_sys)
+    polysT = arm.basis(npoly, rbf)
+    p.lam, p.polysT = arm.lam.data_ptr(), polysT.data_ptr()
+    p.spec, p.espec = arm.spec.data_ptr(), arm.espec.data_ptr()
+    p.work, p.knots = work.data_ptr(), lib.knots.data_ptr()
+    p.coef = coef.data_ptr() if coef is not None else None
+    p.penalty = penalty.data_ptr() if penalty is not None else None
+    p.npix, p.S, p.ntp = arm.npix, arm.S, lib.ntp
+    p.log_step = int(lib.log_step)
+    p.espec_sys, p.fast_interp = float(espec_sys), int(bool(fast_interp))
+    # A9: banded resolution matrix
+    p.taps = resol['taps'].data_ptr() if resol is not None else None
+    p.taps_stride = resol['stride'] if resol is not None else 0
+    p.nd = resol['nd'] if resol is not None else 0
+    # grid sets
     p.G = arm.G
     p.grid_id = arm.grid_id.data_ptr() if arm.G > 1 else None
     p.polys_stride = arm.basis_stride(npoly)
-    ps = getattr(arm, 'pen_scale', None)
-    p.pen_scale = ps.data_ptr() if ps is not None else None
+    p.pen_scale = arm.pen_scale.data_ptr() if arm.pen_scale is not None else None
+    return work, polysT, coef, penalty, resol
 
 
 def fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys=0.0, resols=None):
@@ -955,23 +959,9 @@ def fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys=0.0, resols=None
     esys = _per_arm(espec_sys, len(batch.arms))
     for ia, arm in enumerate(batch.arms):
         lib = libs[arm.name]
-        work = arm.work(lib, esys[ia])
-        polysT = arm.basis(npoly, rbf)
-        rs = _arm_resol(arm, ia, resols)   # A9: banded resolution matrix
-        keep.append((work, polysT, rs))
         a = arr[ia]
-        p = a.pt
-        p.lam, p.polysT = arm.lam.data_ptr(), polysT.data_ptr()
-        p.spec, p.espec = arm.spec.data_ptr(), arm.espec.data_ptr()
-        p.work, p.knots = work.data_ptr(), lib.knots.data_ptr()
-        p.coef = p.penalty = None
-        p.taps = rs['taps'].data_ptr() if rs is not None else None
-        p.taps_stride = rs['stride'] if rs is not None else 0
-        p.espec_sys = esys[ia]
-        p.npix, p.S, p.ntp = arm.npix, arm.S, lib.ntp
-        set_point_grid(p, arm, npoly)
-        p.log_step, p.fast_interp = int(lib.log_step), 0
-        p.nd = rs['nd'] if rs is not None else 0
+        keep.append(fill_point_arm(a.pt, arm, lib, npoly, rbf, esys[ia],
+                                   _arm_resol(arm, ia, resols)))
         a.factors = lib.spline_factors.data_ptr()
         a.lnstep = lib.lnstep
         a.ntp, a.ndim = lib.ntp, lib.ndim
@@ -1040,19 +1030,45 @@ FUSED_OBJECTIVE = True
 FUSED_OBJECTIVE_RESOL = True
 
 
-def objective_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
-                    job_spec=None, espec_sys=0.0, outside_penalty=True,
-                    njobs=None, out=None, resols=None):
-    """get_chisq for J (spectrum, parameters, vsini, velocity) jobs as ONE kernel
-    per call (rvs_objective_fused): no template or spline record in HBM.
-    Returns chisq [J], status int32 [J].  `njobs` (int32 device tensor, one
-    element): only the first njobs[0] jobs are evaluated, `out` (given by the
-    caller) keeps its values behind them (rvs_objective_fused_n)."""
+def objective_form(batch, libs, resols, npoly, fast_interp=False):
+    """the form the optimiser's objective takes for this batch: 'fused' -- one
+    kernel with the grid gather inside (rvs_objective_fused), 'from_template' --
+    one kernel behind the evaluator's template rows (MLP, Delaunay:
+    rvs_objective_from_template), 'chain' -- the stand-alone kernels (template,
+    FIR, spline record, rvs_chisq_point).  Everything that evaluates the
+    objective (spec_fit.chisq_jobs, optimizer.ProcessObjective) goes by it."""
+    if can_fuse_objective(batch, libs, resols, fast_interp, npoly):
+        return 'fused'
+    if can_fuse_objective(batch, libs, resols, fast_interp, npoly,
+                          from_template=True):
+        return 'from_template'
+    return 'chain'
+
+
+def rounds_in_library(batch, libs, form):
+    """whether the optimisers' rounds over an objective of this form run inside
+    the library (rvs_nm_run, rvs_bfgs_run): the fused form, and the from-template
+    form where the library builds the rows of a round itself -- MLP libraries on
+    every arm, or Delaunay libraries with a bucket grid for find_simplex"""
+    if form != 'from_template':
+        return form == 'fused'
+    ls = [libs[arm.name] for arm in batch.arms]
+    return all(lib.kind == 'nn' for lib in ls) or all(
+        lib.kind == 'triangulation' and lib._tri_bk is not None for lib in ls)
+
+
+def _objective_once(batch, libs, vsini, vel, npoly, rbf, job_spec, espec_sys,
+                    outside_penalty, resols, params=None, njobs=None, out=None,
+                    templs=None, outsides=None):
+    """one call of the single-kernel objective: the gather inside the kernel
+    (params [J, ndim]; njobs, out) or behind the evaluator's rows (templs,
+    outsides per arm).  Returns chisq [J], status int32 [J]."""
     import ctypes
     L = _lib.lib()
     dev = batch.device
     vel = vel.to(device=dev, dtype=torch.float64).contiguous()
-    params = params.to(device=dev, dtype=torch.float64).contiguous()
+    if templs is None:
+        params = params.to(device=dev, dtype=torch.float64).contiguous()
     J = vel.shape[0]
     narm = len(batch.arms)
     arr = (_lib.ObjectiveArm * narm)()
@@ -1064,17 +1080,39 @@ def objective_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
     scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
     if vsini is not None:
         vsini = vsini.to(device=dev, dtype=torch.float64).contiguous()
-    with _ktime('objective_fused', J):
-        rc = L.rvs_objective_fused_n(ctypes.addressof(arr), narm, npoly,
-                                     _lib.ptr(params), _lib.ptr(vsini),
-                                     _lib.ptr(job_spec), J, _lib.ptr(njobs),
-                                     _lib.ptr(vel), float(batch.badchi),
-                                     int(outside_penalty), _lib.ptr(scratch),
-                                     _lib.ptr(out), _lib.ptr(status),
-                                     _lib.stream())
-        _lib.check(rc, 'rvs_objective_fused')
+    tail = (_lib.ptr(vel), float(batch.badchi), int(outside_penalty),
+            _lib.ptr(scratch), _lib.ptr(out), _lib.ptr(status), _lib.stream())
+    if templs is None:
+        with _ktime('objective_fused', J):
+            rc = L.rvs_objective_fused_n(ctypes.addressof(arr), narm, npoly,
+                                         _lib.ptr(params), _lib.ptr(vsini),
+                                         _lib.ptr(job_spec), J, _lib.ptr(njobs),
+                                         *tail)
+            _lib.check(rc, 'rvs_objective_fused')
+    else:
+        tp = (ctypes.c_void_p * narm)(*[t.data_ptr() for t in templs])
+        op = (ctypes.c_void_p * narm)(*[o.data_ptr() for o in outsides])
+        with _ktime('objective_from_template', J):
+            rc = L.rvs_objective_from_template(
+                ctypes.addressof(arr), narm, npoly,
+                ctypes.cast(tp, ctypes.c_void_p), ctypes.cast(op, ctypes.c_void_p),
+                _lib.ptr(vsini), _lib.ptr(job_spec), J, *tail)
+            _lib.check(rc, 'rvs_objective_from_template')
     del keep
     return out, status
+
+
+def objective_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
+                    job_spec=None, espec_sys=0.0, outside_penalty=True,
+                    njobs=None, out=None, resols=None):
+    """get_chisq for J (spectrum, parameters, vsini, velocity) jobs as ONE kernel
+    per call (rvs_objective_fused): no template or spline record in HBM.
+    Returns chisq [J], status int32 [J].  `njobs` (int32 device tensor, one
+    element): only the first njobs[0] jobs are evaluated, `out` (given by the
+    caller) keeps its values behind them (rvs_objective_fused_n)."""
+    return _objective_once(batch, libs, vsini, vel, npoly, rbf, job_spec,
+                           espec_sys, outside_penalty, resols, params=params,
+                           njobs=njobs, out=out)
 
 
 def objective_from_template(batch, libs, templs, outsides, vsini, vel, npoly=5,
@@ -1082,31 +1120,9 @@ def objective_from_template(batch, libs, templs, outsides, vsini, vel, npoly=5,
                             outside_penalty=True, resols=None):
     """objective_fused for evaluators that are no grid gather: templs[a]
     [J, ntp_a] (unbroadened), outsides[a] [J] (rvs_objective_from_template)."""
-    import ctypes
-    L = _lib.lib()
-    dev = batch.device
-    vel = vel.to(device=dev, dtype=torch.float64).contiguous()
-    J = vel.shape[0]
-    narm = len(batch.arms)
-    arr = (_lib.ObjectiveArm * narm)()
-    keep = fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys, resols)
-    out = torch.empty(J, dtype=torch.float64, device=dev)
-    status = torch.zeros(J, dtype=torch.int32, device=dev)
-    nb = L.rvs_objective_work_size(J, narm)
-    scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
-    if vsini is not None:
-        vsini = vsini.to(device=dev, dtype=torch.float64).contiguous()
-    tp = (ctypes.c_void_p * narm)(*[t.data_ptr() for t in templs])
-    op = (ctypes.c_void_p * narm)(*[o.data_ptr() for o in outsides])
-    with _ktime('objective_from_template', J):
-        rc = L.rvs_objective_from_template(
-            ctypes.addressof(arr), narm, npoly, ctypes.cast(tp, ctypes.c_void_p),
-            ctypes.cast(op, ctypes.c_void_p), _lib.ptr(vsini), _lib.ptr(job_spec),
-            J, _lib.ptr(vel), float(batch.badchi), int(outside_penalty),
-            _lib.ptr(scratch), _lib.ptr(out), _lib.ptr(status), _lib.stream())
-        _lib.check(rc, 'rvs_objective_from_template')
-    del keep
-    return out, status
+    return _objective_once(batch, libs, vsini, vel, npoly, rbf, job_spec,
+                           espec_sys, outside_penalty, resols, templs=templs,
+                           outsides=outsides)
 
 
 _ar_cache = {}

@@ -7,7 +7,9 @@ every `sync_every` rounds (to shrink its launch bound, to run parked shrinks and
 to notice that everything has converged).  `ProcessObjective` is chisq_func of
 vel_fit.py:229-254 as a fixed launch sequence on preallocated buffers:
 rvs_proc_map -> per arm rvs_template_polylinear, rvs_vsini_convolve,
-rvs_spline_construct -> rvs_chisq_point (all arms) -> rvs_proc_finish.
+rvs_spline_construct -> rvs_chisq_point (all arms) -> rvs_proc_finish (the 'chain'
+form of engine.objective_form; in the 'fused' and 'from_template' forms one
+objective kernel stands between the map and the finish).
 
 tests/refmachines/neldermead_torch.py is the same state machine in torch: the CPU
 suite pins it to scipy (identical nit, nfev, final simplex), the GPU suite pins
@@ -19,6 +21,7 @@ import ctypes
 import torch
 
 from . import _lib
+from . import engine
 
 
 def _p(t):
@@ -30,7 +33,6 @@ class ProcessObjective:
 
     def __init__(self, batch, libs, names, pd0, fixParam, fitVsini, config,
                  options, priors, safe_params, resols=None):
-        from . import engine
         L = _lib.lib()
         self.L = L
         self.batch, self.libs = batch, libs
@@ -87,75 +89,113 @@ class ProcessObjective:
         self.chi = torch.zeros(cap, **f64)
         self.jstatus = torch.zeros(cap, **i32)
         self.status = torch.zeros(S, **i32)
-        self.arm_buf = []
-        narm = len(batch.arms)
-        self.arr = (_lib.PointArm * narm)()
         self.badchi = float(batch.badchi)
         # (which form the objective takes decides which row buffers exist: the one-kernel
         # objective keeps no template or spline record in HBM, the from-template form
         # only the evaluator's rows -- 0.6 GB per 1000 rows less to allocate for the
         # sub-batches of vel_fit._post_nm)
-        self.fused = engine.can_fuse_objective(batch, libs, resols,
-                                               npoly=self.npoly)
-        self.from_templ = (not self.fused) and engine.can_fuse_objective(
-            batch, libs, resols, npoly=self.npoly, from_template=True)
-        chain = not (self.fused or self.from_templ)
-        for ia, arm in enumerate(batch.arms):
+        self.form = engine.objective_form(batch, libs, resols, self.npoly)
+        # the optimisers' rounds can run inside the library (rvs_nm_run, rvs_bfgs_run)
+        self.native = engine.rounds_in_library(batch, libs, self.form)
+        chain = self.form == 'chain'
+        narm = len(batch.arms)
+        self.arm_buf = []
+        for arm in batch.arms:
             lib = libs[arm.name]
-            b = dict(templ=None if self.fused else torch.empty((cap, lib.ntp), **f64),
-                     templ2=torch.empty((cap, lib.ntp), **f64)
-                     if (self.has_vsini and chain) else None,
-                     coef=torch.empty((cap, lib.ntp, 4), **f64) if chain else None,
-                     outside=torch.empty(cap, **f64),
-                     sx=torch.empty(cap, **i32),
-                     nn=None if lib.kind != 'nn' else dict(
-                         a0=torch.empty((cap, lib.nn_width()),
-                                        dtype=torch.float32, device=dev),
-                         a1=torch.empty((cap, lib.nn_width()),
-                                        dtype=torch.float32, device=dev)),
-                     pen=torch.empty(cap, **f64),
-                     work=arm.work(lib, 0.0), polysT=arm.basis(self.npoly,
-                                                               self.rbf))
-            self.arm_buf.append(b)
-            a = self.arr[ia]
-            a.lam, a.polysT = arm.lam.data_ptr(), b['polysT'].data_ptr()
-            a.spec, a.espec = arm.spec.data_ptr(), arm.espec.data_ptr()
-            a.work, a.knots = b['work'].data_ptr(), lib.knots.data_ptr()
-            a.coef = b['coef'].data_ptr() if chain else None
-            a.penalty = b['pen'].data_ptr()
-            a.npix, a.S, a.ntp = arm.npix, arm.S, lib.ntp
-            engine.set_point_grid(a, arm, self.npoly)
-            a.log_step = int(lib.log_step)
-            # A9: the spectra's own resolution matrices or the resol_params
-            # override, as engine.chisq_point wires them
-            rs = engine._arm_resol(arm, ia, resols)
-            if rs is not None:
-                a.taps, a.taps_stride, a.nd = rs['taps'].data_ptr(), \
-                    rs['stride'], rs['nd']
-                self._resol_keep = getattr(self, '_resol_keep', []) + [rs]
-        nb = L.rvs_chisq_point_work_size(cap, narm)
-        self.scratch = torch.empty((nb + 7) // 8, **f64)
-        # (from_templ: evaluators that are no grid gather (MLP, Delaunay) -- the
-        # template rows of a round from their own kernel, everything behind them in one)
-        if self.fused or self.from_templ:
+            self.arm_buf.append(dict(
+                templ=None if self.form == 'fused' else
+                torch.empty((cap, lib.ntp), **f64),
+                templ2=torch.empty((cap, lib.ntp), **f64)
+                if (self.has_vsini and chain) else None,
+                coef=torch.empty((cap, lib.ntp, 4), **f64) if chain else None,
+                pen=torch.empty(cap, **f64) if chain else None,
+                outside=torch.empty(cap, **f64),
+                sx=torch.empty(cap, **i32),
+                nn=None if lib.kind != 'nn' else dict(
+                    a0=torch.empty((cap, lib.nn_width()),
+                                   dtype=torch.float32, device=dev),
+                    a1=torch.empty((cap, lib.nn_width()),
+                                   dtype=torch.float32, device=dev))))
+        if chain:
+            # rvs_chisq_point reads the spline records and penalties of a round
+            self.arr = (_lib.PointArm * narm)()
+            self._keep = [engine.fill_point_arm(
+                self.arr[ia], arm, libs[arm.name], self.npoly, self.rbf, 0.0,
+                engine._arm_resol(arm, ia, resols), b['coef'], b['pen'])
+                for ia, (arm, b) in enumerate(zip(batch.arms, self.arm_buf))]
+            nb = L.rvs_chisq_point_work_size(cap, narm)
+        else:
             self.oarr = (_lib.ObjectiveArm * narm)()
             self._keep = engine.fill_objective_arms(self.oarr, batch, libs,
                                                     self.npoly, self.rbf, 0.0,
                                                     resols)
             nb = L.rvs_objective_work_size(cap, narm)
-            self.oscratch = torch.empty((nb + 7) // 8, **f64)
-        # MLP libraries on every arm: the rounds can run inside rvs_nm_run too
-        self.nn_native = self.from_templ and all(
-            libs[arm.name].kind == 'nn' for arm in batch.arms)
-        # ... and Delaunay libraries (find_simplex through the bucket grid)
-        self.tri_native = self.from_templ and all(
-            libs[arm.name].kind == 'triangulation' and
-            libs[arm.name]._tri_bk is not None for arm in batch.arms)
+        self.scratch = torch.empty((nb + 7) // 8, **f64)
+        # the evaluators whose rows of a round the library builds itself (from-template
+        # form, rounds in the library): MLP or Delaunay libraries on every arm
+        self.nn_arr = self.tri_arr = None
+        if self.native and self.form == 'from_template':
+            if libs[batch.arms[0].name].kind == 'nn':
+                self.nn_arr = self._nn_arms()
+            else:
+                self.tri_arr = self._tri_arms()
         self.streams = [torch.cuda.Stream(device=dev) for _ in batch.arms]
         self.ev_in = torch.cuda.Event()
         self.ev_out = [torch.cuda.Event() for _ in batch.arms]
-        self.calls = 0
-        self.jobs = 0
+        self.calls = 0    # objective calls,
+        self.jobs = 0     # function values computed
+        self.slots = 0    # and rows launched by the rounds inside the library
+
+    def _nn_arms(self):
+        """rvs_nm_nn_arm descriptors: the MLP of every arm and its row buffers"""
+        arr = (_lib.NmNNArm * len(self.arm_buf))()
+        self._nn_keep = []
+        for ia, (arm, b) in enumerate(zip(self.batch.arms, self.arm_buf)):
+            lib = self.libs[arm.name]
+            a = arr[ia]
+            nl = len(lib.nn_W)
+            Wp = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in lib.nn_W])
+            bp = (ctypes.c_void_p * nl)(*[x.data_ptr() for x in lib.nn_b])
+            self._nn_keep += [Wp, bp]
+            a.M, a.S = lib.nn_M.data_ptr(), lib.nn_S.data_ptr()
+            a.W = ctypes.cast(Wp, ctypes.c_void_p)
+            a.b = ctypes.cast(bp, ctypes.c_void_p)
+            a.dims = lib.nn_dims.ctypes.data
+            a.act0 = b['nn']['a0'].data_ptr()
+            a.act1 = b['nn']['a1'].data_ptr()
+            a.templ, a.outside = b['templ'].data_ptr(), b['outside'].data_ptr()
+            hull = lib.hull_device()
+            if hull is None:
+                a.xeqs = a.yeqs = None
+                a.nfx = a.nfy = 0
+            else:
+                a.xeqs, a.yeqs = hull[0].data_ptr(), hull[1].data_ptr()
+                a.nfx, a.nfy = hull[0].shape[0], hull[1].shape[0]
+            a.nlayer, a.log_mask = nl, lib.log_mask
+        return arr
+
+    def _tri_arms(self):
+        """rvs_nm_tri_arm descriptors: the triangulation of every arm and its row
+        buffers"""
+        arr = (_lib.NmTriArm * len(self.arm_buf))()
+        for ia, (arm, b) in enumerate(zip(self.batch.arms, self.arm_buf)):
+            lib = self.libs[arm.name]
+            a = arr[ia]
+            a.dats, a.transform = lib.dats.data_ptr(), lib.tri_transform.data_ptr()
+            a.extraflags = lib.tri_extraflags.data_ptr()
+            a.simplices = lib.tri_simplices.data_ptr()
+            a.templ, a.outside = b['templ'].data_ptr(), b['outside'].data_ptr()
+            # (arms on ONE triangulation share the simplex ids: rvs_nm_run searches
+            # once for all of them)
+            first = [k for k in range(ia + 1) if self.libs[
+                self.batch.arms[k].name].tri_transform.data_ptr() ==
+                lib.tri_transform.data_ptr() and self.libs[
+                self.batch.arms[k].name].log_mask == lib.log_mask][0]
+            a.simplex = self.arm_buf[first]['sx'].data_ptr()
+            a.buckets = lib._tri_bk
+            a.ntp, a.nsimplex = lib.ntp, lib.tri_nsimplex
+            a.exp_flag, a.log_mask = lib.exp_flag, lib.log_mask
+        return arr
 
     def native_desc(self):
         """rvs_nm_objective: this objective for the C round driver"""
@@ -168,7 +208,7 @@ class ProcessObjective:
                      ('extra', self.extra), ('chi', self.chi),
                      ('job_spec', self.job_spec), ('bad', self.bad),
                      ('jstatus', self.jstatus), ('status', self.status),
-                     ('scratch', self.oscratch)):
+                     ('scratch', self.scratch)):
             setattr(o, k, None if t is None else t.data_ptr())
         o.min_vel, o.max_vel = self.min_vel, self.max_vel
         o.max_vsini, o.badchi = self.max_vsini, self.badchi
@@ -176,64 +216,17 @@ class ProcessObjective:
         o.n, o.ndim, o.vsini_col = self.n, self.ndim, self.vsini_col
         for i in range(8):
             o.src[i] = self.src[i] if i < self.ndim else -1
-        o.nn = None
-        if self.nn_native:
-            narm = len(self.arm_buf)
-            self._nn_arr = (_lib.NmNNArm * narm)()
-            self._nn_keep = []
-            for ia, (arm, b) in enumerate(zip(self.batch.arms, self.arm_buf)):
-                lib = self.libs[arm.name]
-                a = self._nn_arr[ia]
-                nl = len(lib.nn_W)
-                Wp = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in lib.nn_W])
-                bp = (ctypes.c_void_p * nl)(*[x.data_ptr() for x in lib.nn_b])
-                self._nn_keep += [Wp, bp]
-                a.M, a.S = lib.nn_M.data_ptr(), lib.nn_S.data_ptr()
-                a.W = ctypes.cast(Wp, ctypes.c_void_p)
-                a.b = ctypes.cast(bp, ctypes.c_void_p)
-                a.dims = lib.nn_dims.ctypes.data
-                a.act0 = b['nn']['a0'].data_ptr()
-                a.act1 = b['nn']['a1'].data_ptr()
-                a.templ, a.outside = b['templ'].data_ptr(), b['outside'].data_ptr()
-                hull = lib.hull_device()
-                if hull is None:
-                    a.xeqs = a.yeqs = None
-                    a.nfx = a.nfy = 0
-                else:
-                    a.xeqs, a.yeqs = hull[0].data_ptr(), hull[1].data_ptr()
-                    a.nfx, a.nfy = hull[0].shape[0], hull[1].shape[0]
-                a.nlayer, a.log_mask = nl, lib.log_mask
-            o.nn = ctypes.addressof(self._nn_arr)
-        o.tri = None
-        if self.tri_native:
-            narm = len(self.arm_buf)
-            self._tri_arr = (_lib.NmTriArm * narm)()
-            for ia, (arm, b) in enumerate(zip(self.batch.arms, self.arm_buf)):
-                lib = self.libs[arm.name]
-                a = self._tri_arr[ia]
-                a.dats, a.transform = lib.dats.data_ptr(), lib.tri_transform.data_ptr()
-                a.extraflags = lib.tri_extraflags.data_ptr()
-                a.simplices = lib.tri_simplices.data_ptr()
-                a.templ, a.outside = b['templ'].data_ptr(), b['outside'].data_ptr()
-                # (arms on ONE triangulation share the simplex ids: rvs_nm_run searches
-                # once for all of them)
-                first = [k for k in range(ia + 1) if self.libs[
-                    self.batch.arms[k].name].tri_transform.data_ptr() ==
-                    lib.tri_transform.data_ptr() and self.libs[
-                    self.batch.arms[k].name].log_mask == lib.log_mask][0]
-                a.simplex = self.arm_buf[first]['sx'].data_ptr()
-                a.buckets = lib._tri_bk
-                a.ntp, a.nsimplex = lib.ntp, lib.tri_nsimplex
-                a.exp_flag, a.log_mask = lib.exp_flag, lib.log_mask
-            o.tri = ctypes.addressof(self._tri_arr)
+        o.nn = None if self.nn_arr is None else ctypes.addressof(self.nn_arr)
+        o.tri = None if self.tri_arr is None else ctypes.addressof(self.tri_arr)
         return o
 
     def eval(self, list_t, X, J, counts, cidx, F):
         """F[:J] = chisq_func(X[j]) for spectrum list_t[j]; rows >= the device
-        count counts[cidx] are padding: the fused objective skips them, F there
+        count counts[cidx] are padding: the one-kernel objective skips them, F there
         is whatever it was."""
         L = self.L
         st = _lib.stream()
+        narm = len(self.arm_buf)
         rc = L.rvs_proc_map(J, self.n, self.ndim, _p(X), _p(list_t), self.src,
                             self.vsini_col, _p(self.fixed),
                             _p(self.vsini_fixed), _p(self.safe),
@@ -242,72 +235,50 @@ class ProcessObjective:
                             _p(self.job_spec), _p(self.vel), _p(self.vsini),
                             _p(self.params), _p(self.extra), _p(self.bad), st)
         _lib.check(rc, 'rvs_proc_map')
-        if self.fused:   # one kernel: gather, FIR, spline solve, chi^2
-            # 1 | RVS_OBJ_STATUS_STORE: jstatus is overwritten, no clearing launch
-            live = None if counts is None else \
-                counts.data_ptr() + 4 * int(cidx)
+        live = None if counts is None else counts.data_ptr() + 4 * int(cidx)
+        # (the one-kernel forms -- 3 = 1 | RVS_OBJ_STATUS_STORE: outside penalty on,
+        # jstatus is overwritten, no clearing launch)
+        if self.form == 'fused':   # gather, FIR, spline solve, chi^2
             rc = L.rvs_objective_fused_n(
-                ctypes.addressof(self.oarr), len(self.arm_buf), self.npoly,
-                _p(self.params), _p(self.vsini), _p(self.job_spec), J, live,
-                _p(self.vel), self.badchi, 3, _p(self.oscratch), _p(self.chi),
-                _p(self.jstatus), st)
+                ctypes.addressof(self.oarr), narm, self.npoly, _p(self.params),
+                _p(self.vsini), _p(self.job_spec), J, live, _p(self.vel),
+                self.badchi, 3, _p(self.scratch), _p(self.chi), _p(self.jstatus),
+                st)
             _lib.check(rc, 'rvs_objective_fused')
-            rc = L.rvs_proc_finish(J, _p(counts), cidx, _p(self.chi),
-                                   _p(self.extra), _p(self.bad),
-                                   _p(self.job_spec), _p(self.jstatus), _p(F),
-                                   _p(self.status), st)
-            _lib.check(rc, 'rvs_proc_finish')
-            self.calls += 1
-            self.jobs += J
-            return
-        if self.from_templ and self.nn_native:
-            # MLP libraries on every arm: one grouped launch chain
-            if getattr(self, '_nn_arr', None) is None:
-                self.native_desc()
-            rc = L.rvs_template_nn_arms_n(
-                _p(self.params), J,
-                None if counts is None else counts.data_ptr() + 4 * int(cidx),
-                self.ndim, len(self.arm_buf), ctypes.addressof(self._nn_arr), st)
-            _lib.check(rc, 'rvs_template_nn_arms')
-        elif self.from_templ:
-            main = torch.cuda.current_stream()
-            self.ev_in.record(main)
-            for arm, b, side, ev in zip(self.batch.arms, self.arm_buf,
-                                        self.streams, self.ev_out):
-                lib = self.libs[arm.name]
-                side.wait_event(self.ev_in)
-                scr = b['sx']
-                if b['nn'] is not None:
-                    scr = dict(b['nn'], torch_stream=side)
-                lib.eval_into(self.params, J, b['templ'], b['outside'],
-                              ctypes.c_void_p(side.cuda_stream), scratch=scr)
-                ev.record(side)
-            for ev in self.ev_out:
-                main.wait_event(ev)
-        if self.from_templ:
-            narm = len(self.arm_buf)
+        elif self.form == 'from_template':
+            if self.nn_arr is not None:   # one grouped launch chain for all arms
+                rc = L.rvs_template_nn_arms_n(
+                    _p(self.params), J, live, self.ndim, narm,
+                    ctypes.addressof(self.nn_arr), st)
+                _lib.check(rc, 'rvs_template_nn_arms')
+            else:
+                self._rows_per_arm(J)
             tp = (ctypes.c_void_p * narm)(*[b['templ'].data_ptr()
                                             for b in self.arm_buf])
             op = (ctypes.c_void_p * narm)(*[b['outside'].data_ptr()
                                             for b in self.arm_buf])
-            live = None if counts is None else \
-                counts.data_ptr() + 4 * int(cidx)
             rc = L.rvs_objective_from_template_n(
                 ctypes.addressof(self.oarr), narm, self.npoly,
                 ctypes.cast(tp, ctypes.c_void_p),
                 ctypes.cast(op, ctypes.c_void_p), _p(self.vsini),
                 _p(self.job_spec), J, live, _p(self.vel), self.badchi, 3,
-                _p(self.oscratch), _p(self.chi), _p(self.jstatus), st)
+                _p(self.scratch), _p(self.chi), _p(self.jstatus), st)
             _lib.check(rc, 'rvs_objective_from_template')
-            rc = L.rvs_proc_finish(J, _p(counts), cidx, _p(self.chi),
-                                   _p(self.extra), _p(self.bad),
-                                   _p(self.job_spec), _p(self.jstatus), _p(F),
-                                   _p(self.status), st)
-            _lib.check(rc, 'rvs_proc_finish')
-            self.calls += 1
-            self.jobs += J
-            return
-        # the arms are independent until the point kernel: one stream each
+        else:
+            self._rows_per_arm(J)
+            self._chisq_point(J, st)
+        rc = L.rvs_proc_finish(J, _p(counts), cidx, _p(self.chi), _p(self.extra),
+                               _p(self.bad), _p(self.job_spec), _p(self.jstatus),
+                               _p(F), _p(self.status), st)
+        _lib.check(rc, 'rvs_proc_finish')
+        self.calls += 1
+        self.jobs += J
+
+    def _rows_per_arm(self, J):
+        """the template rows of every arm from its evaluator and -- chain -- the
+        broadening, spline records and penalties behind them: the arms are
+        independent until the kernel that sums them, one stream each"""
+        L = self.L
         main = torch.cuda.current_stream()
         self.ev_in.record(main)
         for arm, b, side, ev in zip(self.batch.arms, self.arm_buf, self.streams,
@@ -320,25 +291,29 @@ class ProcessObjective:
                 scr = dict(b['nn'], torch_stream=side)
             lib.eval_into(self.params, J, b['templ'], b['outside'], ss,
                           scratch=scr)
-            y = b['templ']
-            if self.has_vsini:
-                rc = L.rvs_vsini_convolve(_p(y), _p(self.vsini), _p(b['outside']),
-                                          lib.lnstep, 0.6, lib.ntp, J,
-                                          _p(b['templ2']), ss)
-                _lib.check(rc, 'rvs_vsini_convolve')
-                y = b['templ2']
-            rc = L.rvs_spline_construct(_p(lib.knots), _p(y), lib.ntp, J,
-                                        lib.spline_form, _p(lib.spline_factors),
-                                        _p(b['coef']), ss)
-            _lib.check(rc, 'rvs_spline_construct')
-            with torch.cuda.stream(side):
-                torch.mul(b['outside'], self.badchi, out=b['pen'])
-                if self.batch.pen_scale is not None:   # grid sets (engine.SpecBatch)
-                    b['pen'][:J] *= self.batch.pen_scale[self.job_spec[:J].long()]
+            if self.form == 'chain':
+                y = b['templ']
+                if self.has_vsini:
+                    rc = L.rvs_vsini_convolve(_p(y), _p(self.vsini),
+                                              _p(b['outside']), lib.lnstep, 0.6,
+                                              lib.ntp, J, _p(b['templ2']), ss)
+                    _lib.check(rc, 'rvs_vsini_convolve')
+                    y = b['templ2']
+                rc = L.rvs_spline_construct(_p(lib.knots), _p(y), lib.ntp, J,
+                                            lib.spline_form,
+                                            _p(lib.spline_factors), _p(b['coef']),
+                                            ss)
+                _lib.check(rc, 'rvs_spline_construct')
+                with torch.cuda.stream(side):
+                    torch.mul(b['outside'], self.badchi, out=b['pen'])
+                    if self.batch.pen_scale is not None:   # grid sets (SpecBatch)
+                        b['pen'][:J] *= self.batch.pen_scale[self.job_spec[:J].long()]
             ev.record(side)
         for ev in self.ev_out:
             main.wait_event(ev)
-        from . import engine
+
+    def _chisq_point(self, J, st):
+        """chain: chi[:J], jstatus[:J] from the arms' spline records"""
         if self.npoly > engine.POINT_MAXP:
             # 17 ... 32 basis functions: beyond the point kernel's 16 per lane, the
             # arms' values come from rvs_chisq_full (engine.chisq_point)
@@ -351,17 +326,11 @@ class ProcessObjective:
             self.jstatus[:J] = stj
         else:
             self.jstatus.zero_()
-            rc = L.rvs_chisq_point(ctypes.addressof(self.arr), len(self.arm_buf),
-                                   self.npoly, _p(self.job_spec), None, J,
-                                   _p(self.vel), self.badchi, _p(self.scratch),
-                                   _p(self.chi), _p(self.jstatus), st)
+            rc = self.L.rvs_chisq_point(
+                ctypes.addressof(self.arr), len(self.arm_buf), self.npoly,
+                _p(self.job_spec), None, J, _p(self.vel), self.badchi,
+                _p(self.scratch), _p(self.chi), _p(self.jstatus), st)
             _lib.check(rc, 'rvs_chisq_point')
-        rc = L.rvs_proc_finish(J, _p(counts), cidx, _p(self.chi), _p(self.extra),
-                               _p(self.bad), _p(self.job_spec), _p(self.jstatus),
-                               _p(F), _p(self.status), st)
-        _lib.check(rc, 'rvs_proc_finish')
-        self.calls += 1
-        self.jobs += J
 
 
 # False: the rounds of a fused objective are driven from Python (one_round below,
@@ -426,7 +395,7 @@ class DeviceNelderMead:
         self.fsim.copy_(fsim)
         fs = self.fsim
         if NATIVE_ROUNDS and isinstance(objective, ProcessObjective) and \
-                (objective.fused or objective.nn_native or objective.tri_native):
+                objective.native:
             # the rounds in C (rvs_nm_run): same launches, no interpreter
             m = _lib.NmState()
             for k, t in (('sim', sim), ('fsim', fs), ('X1', self.X1),
@@ -518,7 +487,7 @@ class DeviceNelderMead:
         # (rows of a launch behind the device count are skipped); `slots` =
         # rows launched
         objective.jobs += int((self.nfev.sum() - nfev0).item())
-        objective.slots = getattr(objective, 'slots', 0) + int(st3[2])
+        objective.slots += int(st3[2])
         if stats is not None:
             stats['rounds'] = stats.get('rounds', 0) + int(st3[0])
         success = (self.flags & 2) != 0

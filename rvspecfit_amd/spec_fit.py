@@ -505,14 +505,14 @@ def chisq_jobs(batch, idx, vel, params, vsini, options, config,
     esys = float(espec_systematic) if espec_systematic is not None else 0.0
     resols = _resols(batch, resol_params)
     js = idx.to(torch.int32).contiguous()
-    if engine.can_fuse_objective(batch, libs, resols, npoly=npoly):
+    form = engine.objective_form(batch, libs, resols, npoly)
+    if form == 'fused':
         return engine.objective_fused(batch, libs, params, vsini, vel,
                                       npoly=npoly, rbf=rbf, job_spec=js,
                                       espec_sys=esys,
                                       outside_penalty=outside_penalty,
                                       resols=resols)
-    if engine.can_fuse_objective(batch, libs, resols, npoly=npoly,
-                                 from_template=True):
+    if form == 'from_template':
         # MLP / Delaunay evaluators: template rows from their own kernel, then
         # broadening + spline + chi^2 in one kernel.  The rows ([J, ntp] float64
         # per arm) go through HBM: in chunks, so that the Hessian stage's 33+

@@ -20,6 +20,7 @@ import torch
 
 from . import engine
 from . import numdiff
+from . import optimizer
 from . import spec_fit
 from . import spec_inter
 from .engine import SpecBatch
@@ -767,17 +768,18 @@ def _rounds_run_in_c(batch, config, resolParams, options=None):
     rounds still in Python: 432 against 586 spectra/s split in two)"""
     libs = spec_inter.get_libs(batch.names, config)
     npoly = (options or {}).get('npoly') or 5
-    rs = spec_fit._resols(batch, resolParams)
-    if engine.can_fuse_objective(batch, libs, rs, npoly=npoly):
-        return True
-    # MLP libraries on every arm: rvs_nm_run drives rvs_template_nn +
-    # rvs_objective_from_template itself
-    def native(kind):
-        return all(libs[a.name].kind == kind for a in batch.arms)
-    return (native('nn') or (native('triangulation') and all(
-        libs[a.name]._tri_bk is not None for a in batch.arms))) and \
-        engine.can_fuse_objective(batch, libs, rs, npoly=npoly,
-                                  from_template=True)
+    form = engine.objective_form(batch, libs,
+                                 spec_fit._resols(batch, resolParams), npoly)
+    return engine.rounds_in_library(batch, libs, form)
+
+
+def _process_objective(ctx, batch, pd0, priors, curparam):
+    """the optimisers' objective (optimizer.ProcessObjective) of `batch`: the batch
+    of `ctx` or a subset of its spectra, with their pd0, priors and curparam"""
+    return optimizer.ProcessObjective(
+        batch, ctx['libs'], ctx['names'], pd0, ctx['fixParam'], ctx['fitVsini'],
+        ctx['config'], ctx['options'], priors, curparam,
+        resols=spec_fit._resols(batch, ctx['resolParams']))
 
 
 def process(specdata, paramDict0, fixParam=None, options=None, config=None,
@@ -870,25 +872,22 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
     stats = {}
     # vel_fit.py:624-649: a second run restarts from the final simplex
     libs = spec_inter.get_libs(batch.names, config)
-    from . import optimizer
+    ctx = dict(batch=batch, pd0=pd0, priors=priors, curparam=curparam, names=names,
+               fixParam=fixParam, fitVsini=fitVsini, vsiniMapper=vsiniMapper,
+               config=config, options=options, resolParams=resolParams, libs=libs,
+               st0=st0.reshape(S, -1)[:, 0], tick=_tick, is_batch=is_batch)
 
     # The spectra that leave the simplex stage first do not wait for the slowest
     # simplex (_early_split): their BFGS polish, refinement and Hessian run on a second
     # stream under the stage's latency-bound last rounds.
     early = (EARLY_SPLIT and is_batch and timers is None and S >= EARLY_SPLIT_MIN
              and optimizer.NATIVE_ROUNDS)
-    pobj = optimizer.ProcessObjective(
-        batch, libs, names, pd0, fixParam, fitVsini, config, options, priors,
-        curparam, resols=spec_fit._resols(batch, resolParams))
+    pobj = _process_objective(ctx, batch, pd0, priors, curparam)
     nmdev = optimizer.DeviceNelderMead(S, simplex.shape[2], dev)
-    early = early and (pobj.fused or pobj.nn_native or pobj.tri_native)
+    early = early and pobj.native
     kw_nm = dict(stop_below=max(1, int(EARLY_SPLIT_FRAC * S))) if early else {}
     nm = nmdev.minimize(pobj, simplex, fatol=1e-3, xatol=1e-2, maxiter=NM_MAXITER,
                         stats=stats, **kw_nm)
-    ctx = dict(batch=batch, pd0=pd0, priors=priors, curparam=curparam, names=names,
-               fixParam=fixParam, fitVsini=fitVsini, vsiniMapper=vsiniMapper,
-               config=config, options=options, resolParams=resolParams, libs=libs,
-               st0=st0.reshape(S, -1)[:, 0], tick=_tick, is_batch=is_batch)
     side = None
     if nm.get('paused'):
         fin = torch.nonzero(nm['finished']).reshape(-1)
@@ -925,7 +924,7 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
         nm = nmdev.resume(pobj, stats=stats)
     obj.status |= pobj.status
     obj.nfev += pobj.jobs
-    slots = getattr(pobj, 'slots', 0)
+    slots = pobj.slots
     success = nm['success']
     x, nit, nfev = nm['x'], nm['nit'], nm['nfev']
     redo = torch.nonzero(~success).reshape(-1)
@@ -934,16 +933,15 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
         # unconverged spectra form a batch of their own on the same kernels
         pri2 = _subset_priors(priors, redo)
         sub = batch.subset(redo)
-        pobj2 = optimizer.ProcessObjective(
-            sub, libs, names, {k_: v[redo].contiguous() for k_, v in pd0.items()},
-            fixParam, fitVsini, config, options, pri2, curparam[redo].contiguous(),
-            resols=spec_fit._resols(sub, resolParams))
+        pobj2 = _process_objective(
+            ctx, sub, {k_: v[redo].contiguous() for k_, v in pd0.items()}, pri2,
+            curparam[redo].contiguous())
         nm2 = optimizer.DeviceNelderMead(sub.S, simplex.shape[2], dev).minimize(
             pobj2, nm['final_simplex'][0][redo].contiguous(), fatol=1e-3,
             xatol=1e-2, maxiter=NM_MAXITER, stats=stats)
         obj.status[redo] |= pobj2.status
         obj.nfev += pobj2.jobs
-        slots += getattr(pobj2, 'slots', 0)
+        slots += pobj2.slots
         x[redo] = nm2['x']
         success[redo] = nm2['success']
         nit[redo] += nm2['nit']
@@ -992,7 +990,6 @@ def _post_nm(ctx, idx, x, success, nit, nfev, status_nm, pobj, nmstats):
     """vel_fit.py:653-737 behind the simplex stage, for the spectra `idx` of the
     batch (None: all of them, on the simplex stage's own objective `pobj`): BFGS
     polish, velocity refinement, full output, Hessian, the result dict."""
-    from . import optimizer
     batch, pd0, priors, curparam = ctx['batch'], ctx['pd0'], ctx['priors'], \
         ctx['curparam']
     names, fixParam, fitVsini = ctx['names'], ctx['fixParam'], ctx['fitVsini']
@@ -1019,19 +1016,17 @@ def _post_nm(ctx, idx, x, success, nit, nfev, status_nm, pobj, nmstats):
         t0 = time.time()
         hess_inv0 = get_hess_inv(mapper.get_fitted_params())
         if pobj is None and BFGS_ON_DEVICE and optimizer.NATIVE_ROUNDS:
-            pobj = optimizer.ProcessObjective(
-                batch, ctx['libs'], names, pd0, fixParam, fitVsini, config, options,
-                priors, curparam, resols=spec_fit._resols(batch, resolParams))
-        if BFGS_ON_DEVICE and optimizer.NATIVE_ROUNDS and pobj is not None and (
-                pobj.fused or pobj.nn_native or pobj.tri_native):
+            pobj = _process_objective(ctx, batch, pd0, priors, curparam)
+        if BFGS_ON_DEVICE and optimizer.NATIVE_ROUNDS and pobj is not None and \
+                pobj.native:
             # the rounds inside the library (rvs_bfgs_run), on the objective the
             # simplex stage ran on
             jobs_before = pobj.jobs
-            slots_before = getattr(pobj, 'slots', 0)
+            slots_before = pobj.slots
             br = bfgs.minimize_lockstep_device(pobj, x, hess_inv0=hess_inv0)
             obj.status |= pobj.status
             obj.nfev += pobj.jobs - jobs_before
-            slots += getattr(pobj, 'slots', 0) - slots_before
+            slots += pobj.slots - slots_before
             x = br['x']
             bfgs_info = dict(nit=br['nit'].cpu().numpy(),
                              nfev=br['nfev'].cpu().numpy(),

@@ -73,10 +73,7 @@ def child(args):
     cfg['second_minimizer'] = not args.no_bfgs
     opt = bench.OPTIONS
     libs = spec_inter.get_libs(batch.names, cfg)
-    kw = dict(npoly=opt['npoly'])
-    form = ('fused' if engine.can_fuse_objective(batch, libs, None, **kw) else
-            'from_template' if engine.can_fuse_objective(
-                batch, libs, None, from_template=True, **kw) else 'chain')
+    form = engine.objective_form(batch, libs, None, opt['npoly'])
     vel_fit.process(batch, pd0, options=opt, config=cfg)   # warm-up
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -90,8 +87,8 @@ def child(args):
     dt1 = time.perf_counter() - t1
     fin = torch.isfinite(r['chisq'])
     print(json.dumps(dict(
-        which=args.child, objective=form, rounds_in_library=bool(
-            vel_fit._rounds_run_in_c(batch, cfg, None, opt)),
+        which=args.child, objective=form,
+        rounds_in_library=bool(engine.rounds_in_library(batch, libs, form)),
         spectra=S, evaluator=args.evaluator, npoly=opt['npoly'],
         second_minimizer=not args.no_bfgs, diagonals=11,
         spectra_per_s=round(S / dt, 1), seconds=round(dt, 3),

@@ -88,8 +88,10 @@ extern "C" {
  *      rvs_nm_state by `stop_below`
  *  13: rvs_objective_fused(_n) / rvs_objective_from_template(_n) -- and with them
  *      rvs_nm_run / rvs_bfgs_run -- apply pt.taps (until now RVS_E_ARG) where
- *      rvs_objective_resol_ok (added) admits the arm */
-#define RVS_ABI_VERSION 13
+ *      rvs_objective_resol_ok (added) admits the arm
+ *  14: removed: rvs_nm_state.stop_below (and its padding word), options "xc_ws1",
+ *      "nm_glue", "nm_bucket" */
+#define RVS_ABI_VERSION 14
 int rvs_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -102,10 +104,6 @@ int rvs_abi_version(void);
  * switches exist so that tests can hold one kernel path against another.
  *   "xc_ws"          1  rvs_ccf_xcorr: the wave-specialised persistent kernels
  *                       where they apply; 0 = one block per (spectrum, template)
- *   "xc_ws1"         0  nfft 4096: 1 = one template per iteration (not two)
- *   "nm_glue"        1  rvs_nm_run: a round as three bookkeeping kernels; 0 = the
- *                       chain of stand-alone kernels (rvs_nm_begin / _decide / ...)
- *   "nm_bucket"      0  rvs_nm_run: launch bounds rounded up to buckets
  *   "nm_split_min" 1024 rvs_nm_run: rounds of at least this many rows (and the test
  *                       of all simplices at the start and after a shrink, for at
  *                       least this many simplices) run their bookkeeping as a
@@ -823,12 +821,6 @@ typedef struct rvs_nm_state {
   double *sim, *fsim, *X1, *X2, *F1, *F2;
   int32_t *nit, *nfev, *flags, *list1, *list2, *list3, *cases, *pos2, *counts;
   int32_t S, N;
-  /* > 0: rvs_nm_run returns at its first look that finds at most this many simplices
-   * running (none parked); a second call with the same state (and 0 here) runs the
-   * rest -- every call starts by testing all simplices and listing the running ones,
-   * so the rounds continue where they stopped, bit for bit.  What a caller gains: the
-   * spectra that are done can go on while the stragglers' last rounds run. */
-  int32_t stop_below, reserved_;
 } rvs_nm_state;
 /* One arm's MLP evaluator for rvs_nm_run: the arguments of rvs_template_nn and
  * rvs_nn_outside (xeqs == NULL: no hull, outside = 0), and the buffers the

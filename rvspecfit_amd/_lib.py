@@ -101,7 +101,7 @@ SIGNATURES = {
 
 _lib = None
 # RVS_ABI_VERSION of the include/rvsgpu.h these signatures mirror
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class RvsGpuError(RuntimeError):
@@ -160,8 +160,7 @@ class NmState(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in
                 ('sim', 'fsim', 'X1', 'X2', 'F1', 'F2', 'nit', 'nfev', 'flags',
                  'list1', 'list2', 'list3', 'cases', 'pos2', 'counts')] + [
-                    ('S', ctypes.c_int32), ('N', ctypes.c_int32),
-                    ('stop_below', ctypes.c_int32), ('reserved_', ctypes.c_int32)]
+                    ('S', ctypes.c_int32), ('N', ctypes.c_int32)]
 
 
 class NmNNArm(ctypes.Structure):

@@ -1214,9 +1214,6 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
         (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<12, false>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
                                   159 * 1024);
-        (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<11, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  159 * 1024);
         (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<12, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
                                   159 * 1024);
@@ -1251,13 +1248,6 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
       }
       if (p12)
         hipLaunchKernelGGL((ccf_xcorr_ws_kernel<12, false>), dim3(B), dim3(XW_NT), shmw, st,
-                           reinterpret_cast<const double2 *>(work),
-                           reinterpret_cast<const double2 *>(tfft),
-                           reinterpret_cast<const double2 *>(tfft2), T, tw, lag_pos,
-                           lag_vel, nlag, ilo, vgrid, nvel, beta, prune, chisq);
-      else if (rvs_opt(RVS_OPT_XC_WS1))   // (one template per iteration: measured 1.10
-                                          // ms per 1000 spectra against 0.84; per pair 1.34)
-        hipLaunchKernelGGL((ccf_xcorr_ws_kernel<11, false>), dim3(B), dim3(XW_NT), shmw, st,
                            reinterpret_cast<const double2 *>(work),
                            reinterpret_cast<const double2 *>(tfft),
                            reinterpret_cast<const double2 *>(tfft2), T, tw, lag_pos,

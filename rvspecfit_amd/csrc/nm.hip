@@ -2,7 +2,8 @@
 // parameter mapping of vel_fit.chisq_func around the batched objective.
 //
 // vel_fit.process runs scipy's Nelder-Mead once per spectrum (vel_fit.py:627-637);
-// here the S state machines live in HBM and advance together.  One round is
+// here the S state machines live in HBM and advance together.  One round, as the
+// stand-alone entry points that optimizer.py's DeviceNelderMead.minimize drives, is
 //   rvs_nm_begin   termination test, centroid, reflection point  -> list1, X1
 //   <objective>    F1 = f(X1)
 //   rvs_nm_decide  branch per simplex; expansion / contraction point -> list2, X2
@@ -15,6 +16,8 @@
 // has seen as an upper bound (active sets only shrink) and refreshes that bound
 // every few rounds.  List entries beyond the live count are padded with a copy
 // of entry 0, so the objective kernels in between can run the full bound.
+// rvs_nm_run (below) runs the same rounds from C, with the bookkeeping between two
+// objective kernels in one kernel; the stand-alone entry points are its reference.
 //
 // The branch structure, constants (rho=1, chi=2, psi=0.5, sigma=0.5), stable
 // vertex ordering (NaN last) and the order of the floating-point operations
@@ -690,6 +693,40 @@ extern "C" int rvs_proc_finish(int J, const int32_t *counts, int cidx,
 // its host thread but not the interpreter (ctypes releases the GIL), so two
 // optimiser instances on two streams can be driven by two Python threads.
 // ---------------------------------------------------------------------------
+
+// The objective of the rows that are mapped already (o->params, o->vel, ...; J = launch
+// bound, `live` = their count on the device, null = all J): the template rows from the
+// evaluator where the library builds them, then the objective kernel.  With
+// RVS_OBJ_NO_SUM in `flags` the per-arm results stay in o->scratch for the bookkeeping
+// kernels (chi, jstatus null); with RVS_OBJ_STATUS_STORE their sum goes to chi / jstatus.
+static int nm_objective_rows(const rvs_nm_objective *o, int J, const int32_t *live,
+                             int flags, double *chi, int32_t *jstatus, hipStream_t st) {
+  if (!o->nn && !o->tri)   // regular grids: the gather happens inside the kernel
+    return rvs_objective_fused_n(o->arms, o->narm, o->npoly, o->params, o->vsini,
+                                 o->job_spec, J, live, o->vel, o->badchi, flags,
+                                 o->scratch, chi, jstatus, st);
+  // MLP libraries: the round's template rows and outside flags per arm; Delaunay
+  // libraries: find_simplex + blend per arm; then broadening + spline + chi^2 in one
+  // kernel (optimizer.py's from_template form)
+  const double *tp[8], *op[8];
+  if (o->narm > 8) return RVS_E_ARG;
+  // (one grouped launch chain for the arms.  Forked onto side streams the
+  // per-arm chains overlapped inside one optimiser instance -- Nelder-Mead
+  // 2.53 -> 2.36 s per 2000 spectra -- but two instances on two host threads,
+  // which is how vel_fit.process runs a large batch, then took 3.5 s for 2.4)
+  int rc = o->nn ? rvs_template_nn_arms_n(o->params, J, live, o->ndim, o->narm, o->nn, st)
+                 : rvs_internal_template_tri_arms_n(o->params, J, live, o->ndim,
+                                                    o->narm, o->tri, st);
+  if (rc) return rc;
+  for (int a = 0; a < o->narm; a++) {
+    tp[a] = o->nn ? o->nn[a].templ : o->tri[a].templ;
+    op[a] = o->nn ? o->nn[a].outside : o->tri[a].outside;
+  }
+  return rvs_objective_from_template_n(o->arms, o->narm, o->npoly, tp, op, o->vsini,
+                                       o->job_spec, J, live, o->vel, o->badchi, flags,
+                                       o->scratch, chi, jstatus, st);
+}
+
 int rvs_internal_nm_eval(const rvs_nm_objective *o, const int32_t *list,
                          const double *X, int J, const int32_t *counts, int cidx,
                          double *F, hipStream_t st) {
@@ -704,47 +741,8 @@ int rvs_internal_nm_eval(const rvs_nm_objective *o, const int32_t *list,
   // the objective blocks of a run (tools/perf/nm_waste.py).  (Sizing the second
   // launch exactly by one more look per round: 2390-2445 against 2398 spectra/s,
   // no difference -- a block behind the count costs next to nothing.)
-  const int32_t *live = counts ? counts + cidx : nullptr;
-  if (o->nn) {
-    // MLP libraries: the round's template rows and outside flags per arm, then
-    // broadening + spline + chi^2 in one kernel (optimizer.py's from_templ path)
-    const double *tp[8], *op[8];
-    if (o->narm > 8) return RVS_E_ARG;
-    // (one grouped launch chain for the arms.  Forked onto side streams the
-    // per-arm chains overlapped inside one optimiser instance -- Nelder-Mead
-    // 2.53 -> 2.36 s per 2000 spectra -- but two instances on two host threads,
-    // which is how vel_fit.process runs a large batch, then took 3.5 s for 2.4)
-    rc = rvs_template_nn_arms_n(o->params, J, live, o->ndim, o->narm, o->nn, st);
-    if (rc) return rc;
-    for (int a = 0; a < o->narm; a++) {
-      tp[a] = o->nn[a].templ;
-      op[a] = o->nn[a].outside;
-    }
-    rc = rvs_objective_from_template_n(o->arms, o->narm, o->npoly, tp, op,
-                                       o->vsini, o->job_spec, J, live, o->vel,
-                                       o->badchi, 1 | RVS_OBJ_STATUS_STORE,
-                                       o->scratch, o->chi, o->jstatus, st);
-  } else if (o->tri) {
-    // Delaunay libraries: find_simplex + blend per arm, then the same kernel
-    const double *tp[8], *op[8];
-    if (o->narm > 8) return RVS_E_ARG;
-    rc = rvs_internal_template_tri_arms_n(o->params, J, live, o->ndim, o->narm, o->tri,
-                                          st);
-    if (rc) return rc;
-    for (int a = 0; a < o->narm; a++) {
-      tp[a] = o->tri[a].templ;
-      op[a] = o->tri[a].outside;
-    }
-    rc = rvs_objective_from_template_n(o->arms, o->narm, o->npoly, tp, op,
-                                       o->vsini, o->job_spec, J, live, o->vel,
-                                       o->badchi, 1 | RVS_OBJ_STATUS_STORE,
-                                       o->scratch, o->chi, o->jstatus, st);
-  } else {
-    rc = rvs_objective_fused_n(o->arms, o->narm, o->npoly, o->params, o->vsini,
-                               o->job_spec, J, live, o->vel, o->badchi,
-                               1 | RVS_OBJ_STATUS_STORE, o->scratch, o->chi,
-                               o->jstatus, st);
-  }
+  rc = nm_objective_rows(o, J, counts ? counts + cidx : nullptr,
+                         1 | RVS_OBJ_STATUS_STORE, o->chi, o->jstatus, st);
   if (rc) return rc;
   return rvs_proc_finish(J, counts, cidx, o->chi, o->extra, o->bad, o->job_spec,
                          o->jstatus, F, o->status, st);
@@ -754,13 +752,14 @@ int rvs_internal_nm_eval(const rvs_nm_objective *o, const int32_t *list,
 // ---------------------------------------------------------------------------
 // The round as rvs_nm_run launches it: THREE launches per function evaluation --
 // cell search, job order, objective kernel -- and one bookkeeping kernel between two
-// evaluations, where the chain above takes seven (begin | decide | update, map,
-// cell search, order, objective, sum over the arms, finish).  Between two objective
-// kernels of a stream nothing else runs, and late in a run -- a few dozen simplices
-// left, an objective launch of 40 us -- the chain WAS the round: 141 us of small
-// launches per evaluation (tools/perf/trace_rounds.py).  One block does, for all
-// rows, what the separate kernels did (same device functions, same order of the
-// arithmetic, lists in the same order):
+// evaluations, where a round of the stand-alone entry points (rvs_nm_begin / _decide /
+// _update around the objective, as optimizer.py drives them) takes seven (begin |
+// decide | update, map, cell search, order, objective, sum over the arms, finish).
+// Between two objective kernels of a stream nothing else runs, and late in a run -- a
+// few dozen simplices left, an objective launch of 40 us -- that chain of launches WAS
+// the round: 141 us of small launches per evaluation (tools/perf/trace_rounds.py).  One
+// block does, for all rows, what the stand-alone kernels do (same device functions, same
+// order of the arithmetic, lists in the same order):
 //   nm_glue_begin     termination test + reflection point of every running simplex,
 //                     list1 / X1, and the parameter mapping of those rows
 //   nm_glue_decide    F1 = sum over the arms + priors of the rows just evaluated;
@@ -1383,67 +1382,11 @@ __global__ void __launch_bounds__(NM_NT) nm_glue_update_pack_kernel(NmGlue G, in
   }
 }
 
-static int nm_bucket(int n, int S) {
-  // quantised launch bound (1/8 steps of the next power of two), as optimizer.py
-  if (n <= 64) return S < 64 ? S : 64;
-  int p2 = 1;
-  while (p2 < n) p2 <<= 1;
-  const int stepq = (p2 / 8 > 1) ? p2 / 8 : 1;
-  const int b = ((n + stepq - 1) / stepq) * stepq;
-  return b < S ? b : S;
-}
-
-// the evaluation of the rows the last bookkeeping kernel mapped (J = launch bound,
-// `live` = their count on the device); the per-arm results stay in o->scratch
-static int nm_objective_rows(const rvs_nm_objective *o, int J, const int32_t *live,
-                             hipStream_t st) {
-  if (o->nn) {
-    const double *tp[8], *op[8];
-    if (o->narm > 8) return RVS_E_ARG;
-    int rc = rvs_template_nn_arms_n(o->params, J, live, o->ndim, o->narm, o->nn, st);
-    if (rc) return rc;
-    for (int a = 0; a < o->narm; a++) {
-      tp[a] = o->nn[a].templ;
-      op[a] = o->nn[a].outside;
-    }
-    return rvs_objective_from_template_n(o->arms, o->narm, o->npoly, tp, op,
-                                         o->vsini, o->job_spec, J, live, o->vel,
-                                         o->badchi, 1 | RVS_OBJ_NO_SUM, o->scratch,
-                                         nullptr, nullptr, st);
-  }
-  if (o->tri) {
-    const double *tp[8], *op[8];
-    if (o->narm > 8) return RVS_E_ARG;
-    int rc = rvs_internal_template_tri_arms_n(o->params, J, live, o->ndim, o->narm,
-                                              o->tri, st);
-    if (rc) return rc;
-    for (int a = 0; a < o->narm; a++) {
-      tp[a] = o->tri[a].templ;
-      op[a] = o->tri[a].outside;
-    }
-    return rvs_objective_from_template_n(o->arms, o->narm, o->npoly, tp, op,
-                                         o->vsini, o->job_spec, J, live, o->vel,
-                                         o->badchi, 1 | RVS_OBJ_NO_SUM, o->scratch,
-                                         nullptr, nullptr, st);
-  }
-  return rvs_objective_fused_n(o->arms, o->narm, o->npoly, o->params, o->vsini,
-                               o->job_spec, J, live, o->vel, o->badchi,
-                               1 | RVS_OBJ_NO_SUM, o->scratch, nullptr, nullptr, st);
-}
-
-static int nm_run_chain(const rvs_nm_state *m, const rvs_nm_objective *o,
-                        double xatol, double fatol, int maxiter, int sync_every,
-                        int64_t *stats, void *stream);
-
 extern "C" int rvs_nm_run(const rvs_nm_state *m, const rvs_nm_objective *o,
                           double xatol, double fatol, int maxiter,
                           int sync_every, int64_t *stats, void *stream) {
   if (!m || !o || m->S < 1 || m->N < 1 || m->N > NM_MAXN || sync_every < 1)
     return RVS_E_ARG;
-  // nm_glue = 0: the round as a chain of the stand-alone kernels (a test hook:
-  // tests/test_gpu_parity.py::test_nm_round_kernels_equal_chain)
-  if (!rvs_opt(RVS_OPT_NM_GLUE))
-    return nm_run_chain(m, o, xatol, fatol, maxiter, sync_every, stats, stream);
   hipStream_t st = rvs_stream(stream);
   const int S = m->S, N = m->N;
   int64_t rounds = 0, calls = 0, jobs = 0;
@@ -1471,6 +1414,10 @@ extern "C" int rvs_nm_run(const rvs_nm_state *m, const rvs_nm_objective *o,
     } else {
       hipLaunchKernelGGL(nm_glue_begin_kernel, dim3(1), dim3(NM_UNT), 0, st, G);
     }
+  };
+  // the rows the last bookkeeping kernel mapped: their per-arm results stay in o->scratch
+  auto evaluate = [&](int J, const int32_t *live) {
+    return nm_objective_rows(o, J, live, 1 | RVS_OBJ_NO_SUM, nullptr, nullptr, st);
   };
   begin();
   RVS_LAUNCH_CHECK();
@@ -1502,8 +1449,6 @@ extern "C" int rvs_nm_run(const rvs_nm_state *m, const rvs_nm_objective *o,
       continue;
     }
     if (live == 0) break;
-    // (the caller takes the finished spectra on and calls again for the rest)
-    if (m->stop_below > 0 && live <= m->stop_below) break;
     // the live count only falls between two looks (finished and parked
     // simplices leave the list), so it bounds the launches of the window
     const int jb = live;
@@ -1521,7 +1466,7 @@ extern "C" int rvs_nm_run(const rvs_nm_state *m, const rvs_nm_objective *o,
       hipLaunchKernelGGL(nm_glue_spec_prep_kernel, dim3(1), dim3(NM_SNT), 0, st, G, jb);
       RVS_LAUNCH_CHECK();
       for (int r = 0; r < window; r++) {
-        rc = nm_objective_rows(o, 4 * jb, m->counts + 5, st);
+        rc = evaluate(4 * jb, m->counts + 5);
         if (rc) return rc;
         hipLaunchKernelGGL(nm_glue_spec_kernel, dim3(1), dim3(NM_SNT), 0, st, G, jb);
         RVS_LAUNCH_CHECK();
@@ -1536,7 +1481,7 @@ extern "C" int rvs_nm_run(const rvs_nm_state *m, const rvs_nm_objective *o,
       // (from a few thousand rows up the bookkeeping is row-parallel + pack)
       const bool split = jb >= rvs_opt(RVS_OPT_NM_SPLIT_MIN);
       const dim3 rgrid((jb + NM_ROWS_NT - 1) / NM_ROWS_NT);
-      rc = nm_objective_rows(o, jb, m->counts, st);
+      rc = evaluate(jb, m->counts);
       if (rc) return rc;
       if (split) {
         hipLaunchKernelGGL(nm_glue_decide_rows_kernel, rgrid, dim3(NM_ROWS_NT), 0, st,
@@ -1547,7 +1492,7 @@ extern "C" int rvs_nm_run(const rvs_nm_state *m, const rvs_nm_objective *o,
         hipLaunchKernelGGL(nm_glue_decide_kernel, dim3(1), dim3(NM_NT), 0, st, G, jb);
       }
       RVS_LAUNCH_CHECK();
-      rc = nm_objective_rows(o, jb, m->counts + 1, st);
+      rc = evaluate(jb, m->counts + 1);
       if (rc) return rc;
       if (split) {
         hipLaunchKernelGGL(nm_glue_update_rows_kernel, rgrid, dim3(NM_ROWS_NT), 0, st,
@@ -1570,73 +1515,3 @@ extern "C" int rvs_nm_run(const rvs_nm_state *m, const rvs_nm_objective *o,
   }
   return 0;
 }
-
-static int nm_run_chain(const rvs_nm_state *m, const rvs_nm_objective *o,
-                        double xatol, double fatol, int maxiter, int sync_every,
-                        int64_t *stats, void *stream) {
-  hipStream_t st = rvs_stream(stream);
-  const int S = m->S, N = m->N;
-  int64_t rounds = 0, calls = 0, jobs = 0;
-  int32_t c[8];
-  int rc = rvs_nm_begin(S, N, xatol, fatol, maxiter, m->sim, m->fsim, m->nit,
-                        m->flags, m->list1, m->X1, m->counts, S, st);
-  if (rc) return rc;
-  while (true) {
-    if (hipMemcpyAsync(c, m->counts, sizeof(c), hipMemcpyDeviceToHost, st) !=
-            hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return RVS_E_LAUNCH;
-    const int live = c[0], parked = c[4];
-    if (parked > 0) {  // scipy's shrink step for the parked simplices
-      rc = rvs_nm_collect(S, m->flags, m->list3, m->counts, st);
-      if (rc) return rc;
-      for (int k = 1; k <= N; k++) {
-        rc = rvs_nm_shrink_point(N, k, m->sim, m->list3, m->X2, m->counts,
-                                 parked, st);
-        if (rc) return rc;
-        rc = rvs_internal_nm_eval(o, m->list3, m->X2, parked, m->counts, 2, m->F2, st);
-        if (rc) return rc;
-        calls++;
-        jobs += parked;
-        rc = rvs_nm_shrink_store(N, k, m->sim, m->fsim, m->nit, m->nfev,
-                                 m->flags, m->list3, m->F2, m->counts, parked,
-                                 st);
-        if (rc) return rc;
-      }
-      rc = rvs_nm_begin(S, N, xatol, fatol, maxiter, m->sim, m->fsim, m->nit,
-                        m->flags, m->list1, m->X1, m->counts, S, st);
-      if (rc) return rc;
-      continue;
-    }
-    if (live == 0) break;
-    // the live count only falls between two looks (finished and parked
-    // simplices leave the list), so it bounds the launches of the window
-    const int jb = rvs_opt(RVS_OPT_NM_BUCKET) ? nm_bucket(live, S) : live;
-    for (int r = 0; r < sync_every; r++) {
-      rc = rvs_nm_begin(S, N, xatol, fatol, maxiter, m->sim, m->fsim, m->nit,
-                        m->flags, m->list1, m->X1, m->counts, jb, st);
-      if (rc) return rc;
-      rc = rvs_internal_nm_eval(o, m->list1, m->X1, jb, m->counts, 0, m->F1, st);
-      if (rc) return rc;
-      rc = rvs_nm_decide(N, m->sim, m->fsim, m->list1, m->F1, m->cases,
-                         m->pos2, m->list2, m->X2, m->counts, jb, st);
-      if (rc) return rc;
-      rc = rvs_internal_nm_eval(o, m->list2, m->X2, jb, m->counts, 1, m->F2, st);
-      if (rc) return rc;
-      rc = rvs_nm_update(N, m->sim, m->fsim, m->nit, m->nfev, m->list1, m->X1,
-                         m->F1, m->cases, m->pos2, m->X2, m->F2, m->flags,
-                         m->counts, jb, st);
-      if (rc) return rc;
-      calls += 2;
-      jobs += 2 * (int64_t)jb;
-    }
-    rounds += sync_every;
-  }
-  if (stats) {
-    stats[0] = rounds;
-    stats[1] = calls;
-    stats[2] = jobs;
-  }
-  return 0;
-}
-

@@ -21,19 +21,15 @@ struct OptDef {
   const char *name;   // rvs_option_set's name; the variable is RVS_<NAME>
   const char *env;
   int dflt;
-  bool env_presence;  // the variable's presence alone means 1
 };
 const OptDef kDefs[RVS_OPT_COUNT] = {
-    {"xc_ws", "RVS_XC_WS", 1, false},
-    {"xc_ws1", "RVS_XC_WS1", 0, true},
-    {"nm_glue", "RVS_NM_GLUE", 1, false},
-    {"nm_bucket", "RVS_NM_BUCKET", 0, true},
-    {"obj_inblk_max", "RVS_OBJ_INBLK_MAX", 768, false},
-    {"obj_sort", "RVS_OBJ_SORT", 1, false},
-    {"nn_pipe", "RVS_NN_PIPE", 1, false},
-    {"nm_split_min", "RVS_NM_SPLIT_MIN", 1024, false},
-    {"nm_spec_max", "RVS_NM_SPEC_MAX", 21, false},
-    {"nm_tail_window", "RVS_NM_TAIL_WINDOW", 16, false},
+    {"xc_ws", "RVS_XC_WS", 1},
+    {"obj_inblk_max", "RVS_OBJ_INBLK_MAX", 768},
+    {"obj_sort", "RVS_OBJ_SORT", 1},
+    {"nn_pipe", "RVS_NN_PIPE", 1},
+    {"nm_split_min", "RVS_NM_SPLIT_MIN", 1024},
+    {"nm_spec_max", "RVS_NM_SPEC_MAX", 21},
+    {"nm_tail_window", "RVS_NM_TAIL_WINDOW", 16},
 };
 std::atomic<int> g_val[RVS_OPT_COUNT];
 std::once_flag g_once;
@@ -42,7 +38,7 @@ void init_table() {
   for (int i = 0; i < RVS_OPT_COUNT; i++) {
     int v = kDefs[i].dflt;
     if (const char *ev = std::getenv(kDefs[i].env))
-      v = kDefs[i].env_presence ? 1 : std::atoi(ev);
+      v = std::atoi(ev);
     g_val[i].store(v, std::memory_order_relaxed);
   }
 }

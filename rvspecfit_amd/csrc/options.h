@@ -5,9 +5,6 @@
 
 enum {
   RVS_OPT_XC_WS,          // wave-specialised cross-correlation where it applies
-  RVS_OPT_XC_WS1,         // nfft 4096: one template per iteration instead of two
-  RVS_OPT_NM_GLUE,        // optimiser rounds as three bookkeeping kernels
-  RVS_OPT_NM_BUCKET,      // launch bounds rounded to buckets (measurement hook)
   RVS_OPT_OBJ_INBLK_MAX,  // launches of <= this many blocks search their cell in-block
   RVS_OPT_OBJ_SORT,       // objective jobs in grid-cell order
   RVS_OPT_NN_PIPE,        // MLP wide last layer: the kernel with the pipelined epilogue

@@ -93,7 +93,7 @@ class ProcessObjective:
         # (which form the objective takes decides which row buffers exist: the one-kernel
         # objective keeps no template or spline record in HBM, the from-template form
         # only the evaluator's rows -- 0.6 GB per 1000 rows less to allocate for the
-        # sub-batches of vel_fit._post_nm)
+        # sub-batches of vel_fit.process: its halves, the spectra of a second run)
         self.form = engine.objective_form(batch, libs, resols, self.npoly)
         # the optimisers' rounds can run inside the library (rvs_nm_run, rvs_bfgs_run)
         self.native = engine.rounds_in_library(batch, libs, self.form)
@@ -377,11 +377,7 @@ class DeviceNelderMead:
         self.counts = torch.zeros(8, **i32)
 
     def minimize(self, objective, simplex, fatol=1e-3, xatol=1e-2,
-                 maxiter=10000, sync_every=4, stats=None, stop_below=0):
-        """stop_below > 0 (rounds inside the library only): return at the first look
-        that finds at most that many simplices running -- the result then carries
-        paused = True and finished [S] (converged and out of the rounds); resume()
-        runs the rest."""
+                 maxiter=10000, sync_every=4, stats=None):
         L = _lib.lib()
         S, N = self.S, self.N
         sim = simplex.clone().to(torch.float64).contiguous()
@@ -407,11 +403,20 @@ class DeviceNelderMead:
                          ('counts', self.counts)):
                 setattr(m, k, t.data_ptr())
             m.S, m.N = S, N
-            m.stop_below = int(stop_below)
             o = objective.native_desc()
-            self._native = (m, o, sim, fs, float(xatol), float(fatol), int(maxiter),
-                            int(sync_every))
-            return self._run_native(objective, stats)
+            st3 = (ctypes.c_int64 * 3)()
+            nfev0 = self.nfev.sum()
+            rc = L.rvs_nm_run(ctypes.addressof(m), ctypes.addressof(o), float(xatol),
+                              float(fatol), int(maxiter), int(sync_every), st3,
+                              _lib.stream())
+            _lib.check(rc, 'rvs_nm_run')
+            objective.calls += int(st3[1])
+            # evaluations performed = the function values scipy's algorithm counts
+            # (rows of a launch behind the device count are skipped); `slots` =
+            # rows launched
+            objective.jobs += int((self.nfev.sum() - nfev0).item())
+            objective.slots += int(st3[2])
+            return self._result(sim, fs, int(st3[0]), stats)
 
         def one_round(jb):
             st = _lib.stream()
@@ -467,43 +472,15 @@ class DeviceNelderMead:
             for _ in range(sync_every):
                 one_round(jb)
             rounds += sync_every
+        return self._result(sim, fs, rounds, stats)
+
+    def _result(self, sim, fs, rounds, stats):
         if stats is not None:
             stats['rounds'] = stats.get('rounds', 0) + rounds
         success = (self.flags & 2) != 0
         return dict(x=sim[:, 0].clone(), fun=fs.min(dim=1)[0],
                     nit=self.nit.long(), nfev=self.nfev.long(), success=success,
                     final_simplex=(sim, fs))
-
-    def _run_native(self, objective, stats):
-        L = _lib.lib()
-        m, o, sim, fs, xatol, fatol, maxiter, sync_every = self._native
-        st3 = (ctypes.c_int64 * 3)()
-        nfev0 = self.nfev.sum()
-        rc = L.rvs_nm_run(ctypes.addressof(m), ctypes.addressof(o), xatol, fatol,
-                          maxiter, sync_every, st3, _lib.stream())
-        _lib.check(rc, 'rvs_nm_run')
-        objective.calls += int(st3[1])
-        # evaluations performed = the function values scipy's algorithm counts
-        # (rows of a launch behind the device count are skipped); `slots` =
-        # rows launched
-        objective.jobs += int((self.nfev.sum() - nfev0).item())
-        objective.slots += int(st3[2])
-        if stats is not None:
-            stats['rounds'] = stats.get('rounds', 0) + int(st3[0])
-        success = (self.flags & 2) != 0
-        out = dict(x=sim[:, 0].clone(), fun=fs.min(dim=1)[0],
-                   nit=self.nit.long(), nfev=self.nfev.long(),
-                   success=success, final_simplex=(sim, fs))
-        if m.stop_below > 0:
-            running = (self.flags & 5) != 0      # active, or parked for a shrink
-            out['paused'] = bool(running.any().item())
-            out['finished'] = (~running) & success
-        return out
-
-    def resume(self, objective, stats=None):
-        """the rest of a run that minimize(stop_below > 0) returned from"""
-        self._native[0].stop_below = 0
-        return self._run_native(objective, stats)
 
     def _shrink(self, objective, sim, parked):
         """scipy's shrink step for the parked simplices: N objective calls"""

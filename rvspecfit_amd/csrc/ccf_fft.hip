@@ -30,6 +30,72 @@
 // does not survive in L1 beside the operand stream).
 #define XC_NTW(n2) ((n2) >> 3)
 
+// Dynamic LDS of the cross-correlation kernels.  A kernel places its arrays and
+// rvs_ccf_xcorr sizes the launch from the SAME function: written out twice, the
+// launcher of ccf_xcorr_ws_kernel left out the 8 bytes by which an odd nlag pads c0
+// to a whole double2, and cA[nlag - 1] (the mode without continuum normalisation)
+// lay beyond the request.  Offsets count double2 from the start of the block's LDS.
+struct XcLds {
+  int t1;        // T1 [XC_NTW(n2)] double2, behind the image(s)
+  int c0;        // the lag values, doubles: c0 | c1 [nlag] each (per pair),
+                 // c0 [nlag] (ws), c0 [2][nlag] (ws2: one row per template)
+  int t1c;       // ws: T1c [XW_NT1C] double2, the twiddles of pass 1 and of the fold
+  int ca;        // ws, RATIO: cA [nlag] doubles
+  size_t bytes;  // of the launch
+};
+#define XW_NT1C 73   // 64 + 8 twiddles and one spare entry
+#define XC_LDS_MAX (159 * 1024)   // dynamic LDS a block may ask for
+// ccf_xcorr_kernel; nlag = 0: ccf_rfft_kernel (the image and T1)
+__host__ __device__ constexpr XcLds xc_lds_pair(int n2, int nlag) {
+  const int t1 = n2, c0 = t1 + XC_NTW(n2);
+  return {t1, c0, 0, 0, sizeof(double2) * (size_t)c0 + sizeof(double) * 2 * (size_t)nlag};
+}
+// ccf_xcorr_ws_kernel: two images; c0 is rounded up to whole double2
+__host__ __device__ constexpr XcLds xc_lds_ws(int n2, int nlag, bool ratio) {
+  const int t1 = 2 * n2, c0 = t1 + XC_NTW(n2), t1c = c0 + ((nlag + 1) >> 1),
+            ca = t1c + XW_NT1C;
+  return {t1, c0, t1c, ca,
+          sizeof(double2) * (size_t)ca + (ratio ? sizeof(double) * (size_t)nlag : 0)};
+}
+// ccf_xcorr_ws2_kernel: four images
+__host__ __device__ constexpr XcLds xc_lds_ws2(int n2, int nlag) {
+  const int t1 = 4 * n2, c0 = t1 + XC_NTW(n2);
+  return {t1, c0, 0, 0, sizeof(double2) * (size_t)c0 + sizeof(double) * 2 * (size_t)nlag};
+}
+// every array of a layout lies behind the one before it and inside `bytes`
+// (nimg images, nrow rows of nlag doubles at c0), for every nlag a launch can carry
+__host__ __device__ constexpr bool xc_lds_fits(const XcLds &L, int n2, int nimg,
+                                               int nrow, int nlag, bool ws, bool ratio) {
+  const size_t D2 = sizeof(double2), D = sizeof(double);
+  size_t end = D2 * (size_t)nimg * n2;
+  if (D2 * L.t1 < end) return false;
+  end = D2 * (L.t1 + XC_NTW(n2));
+  if (D2 * L.c0 < end) return false;
+  end = D2 * L.c0 + D * (size_t)nrow * nlag;
+  if (ws) {
+    if (D2 * L.t1c < end) return false;
+    end = D2 * (L.t1c + 72);
+    if (D2 * L.ca < end) return false;
+    end = D2 * L.ca + (ratio ? D * (size_t)nlag : 0);
+  }
+  return end <= L.bytes && L.bytes <= XC_LDS_MAX;
+}
+constexpr bool xc_lds_check() {
+  for (int nlag = 2; nlag <= 512; nlag++)
+    for (int n2 = 2048; n2 <= 4096; n2 *= 2) {
+      for (int ratio = 0; ratio < 2; ratio++)
+        if (!xc_lds_fits(xc_lds_ws(n2, nlag, ratio), n2, 2, 1, nlag, true, ratio))
+          return false;
+      if (n2 == 2048 && !xc_lds_fits(xc_lds_ws2(n2, nlag), n2, 4, 2, nlag, false, false))
+        return false;
+      if (!xc_lds_fits(xc_lds_pair(n2, nlag), n2, 1, 2, nlag, false, false))
+        return false;
+    }
+  return true;
+}
+static_assert(xc_lds_check(), "an LDS array of a cross-correlation kernel overlaps "
+                              "its neighbour or ends beyond the launch's request");
+
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
   return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
@@ -483,8 +549,8 @@ __global__ void __launch_bounds__(XB_NT)
                      double *__restrict__ chisq, int B, int G) {
   extern __shared__ double2 fa[];
   const int n2 = nfft >> 1, npair = n2 >> 1;
-  double *c0 = reinterpret_cast<double *>(fa + n2 + XC_NTW(n2));  // [nlag]
-  double *c1 = c0 + nlag;                                        // [nlag]
+  double *c0 = reinterpret_cast<double *>(fa + xc_lds_pair(n2, nlag).c0);  // [nlag]
+  double *c1 = c0 + nlag;                                                 // [nlag]
   int t = blockIdx.x, b = blockIdx.y;
   if (G > 0 && !xc_job(blockIdx.x, T, B, G, b, t)) return;
   const int tid = threadIdx.x;
@@ -742,11 +808,12 @@ __global__ void __launch_bounds__(XW_NT)
   constexpr bool P12 = (LOG2N == 12);
   static_assert(LOG2N == 12 || LOG2N == 11, "plans 8,8,8,8 and 8,8,8,4 only");
   auto img = [&](int i) -> double2 * { return fa + (i & 1) * n2; };
-  const double2 *T1 = fa + 2 * n2;                         // [n2 / 8]
-  double *c0 = reinterpret_cast<double *>(fa + 2 * n2 + XC_NTW(n2));  // [nlag]
+  const XcLds lds = xc_lds_ws(n2, nlag, RATIO);
+  const double2 *T1 = fa + lds.t1;                         // [n2 / 8]
+  double *c0 = reinterpret_cast<double *>(fa + lds.c0);    // [nlag]
   // pass 1's 64 twiddles and the folded pass's 8, side by side (xw_pass)
-  double2 *T1c = fa + 2 * n2 + XC_NTW(n2) + ((nlag + 1) >> 1);   // [64 + 8]
-  double *cA = reinterpret_cast<double *>(T1c + 73);   // RATIO: c0 at the lags [nlag]
+  double2 *T1c = fa + lds.t1c;                             // [64 + 8]
+  double *cA = reinterpret_cast<double *>(fa + lds.ca);    // RATIO: c0 at the lags [nlag]
   const int TI = RATIO ? 2 * T : T;   // image iterations
   const int b = blockIdx.x, tid = threadIdx.x;
   const bool producer = tid >= XW_HALF;
@@ -1031,8 +1098,9 @@ __global__ void __launch_bounds__(XW_NT)
   constexpr int NBAR = 5;
   // images: iteration parity i, template j of the iteration
   auto img = [&](int i, int j) -> double2 * { return fa + (((i & 1) << 1) + j) * n2; };
-  const double2 *T1 = fa + 4 * n2;                         // [n2 / 8]
-  double *c0 = reinterpret_cast<double *>(fa + 4 * n2 + XC_NTW(n2));  // [2][nlag]
+  const XcLds lds = xc_lds_ws2(n2, nlag);
+  const double2 *T1 = fa + lds.t1;                         // [n2 / 8]
+  double *c0 = reinterpret_cast<double *>(fa + lds.c0);    // [2][nlag]
   const int b = blockIdx.x, tid = threadIdx.x;
   const bool producer = tid >= XW_HALF;
   const int pt = tid & (XW_HALF - 1);
@@ -1183,19 +1251,19 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
   if ((2 << log2n) != nfft || nfft < 64 || nfft > 16384) return RVS_E_ARG;
   if (B < 1 || T < 1 || T > 65535 || nlag < 2 || nvel < 1) return RVS_E_ARG;
   const int n2 = nfft >> 1;
-  const size_t shm1 = sizeof(double2) * (size_t)(n2 + XC_NTW(n2));
-  const size_t shm2 = shm1 + sizeof(double) * 2 * (size_t)nlag;
-  if (shm2 > 159 * 1024) return RVS_E_ARG;
+  const size_t shm1 = xc_lds_pair(n2, 0).bytes;      // ccf_rfft_kernel
+  const size_t shm2 = xc_lds_pair(n2, nlag).bytes;   // ccf_xcorr_kernel
+  if (shm2 > XC_LDS_MAX) return RVS_E_ARG;
   hipStream_t st = rvs_stream(stream);
   const double2 *tw = reinterpret_cast<const double2 *>(twid_);
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void *)ccf_rfft_kernel,
                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                              159 * 1024);
+                              XC_LDS_MAX);
     (void)hipFuncSetAttribute((const void *)ccf_xcorr_kernel,
                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                              159 * 1024);
+                              XC_LDS_MAX);
     (void)hipGetLastError();
     attr_set = true;
   }
@@ -1213,23 +1281,20 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
       if (!ws_attr) {
         (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<12, false>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  159 * 1024);
+                                  XC_LDS_MAX);
         (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<12, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  159 * 1024);
+                                  XC_LDS_MAX);
         (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<11, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  159 * 1024);
+                                  XC_LDS_MAX);
         (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws2_kernel,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  159 * 1024);
+                                  XC_LDS_MAX);
         (void)hipGetLastError();
         ws_attr = true;
       }
-      const size_t shmw = sizeof(double2) * (size_t)(2 * n2 + XC_NTW(n2)) +
-                          sizeof(double) * (size_t)nlag +
-                          sizeof(double2) * (72 + 1) +   // (+ pass 1's twiddles: T1c)
-                          (continuum ? 0 : sizeof(double) * (size_t)nlag);   // (cA)
+      const size_t shmw = xc_lds_ws(n2, nlag, !continuum).bytes;
 #define RVS_XW_ARGS                                                                 \
   reinterpret_cast<const double2 *>(work), reinterpret_cast<const double2 *>(tfft),  \
       reinterpret_cast<const double2 *>(tfft2), T, tw, lag_pos, lag_vel, nlag, ilo,  \
@@ -1254,9 +1319,8 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
                            lag_vel, nlag, ilo, vgrid, nvel, beta, prune, chisq);
       else
         hipLaunchKernelGGL(ccf_xcorr_ws2_kernel, dim3(B), dim3(XW_NT),
-                           sizeof(double2) * (size_t)(4 * n2 + XC_NTW(n2)) +
-                               sizeof(double) * 2 * (size_t)nlag,
-                           st, reinterpret_cast<const double2 *>(work),
+                           xc_lds_ws2(n2, nlag).bytes, st,
+                           reinterpret_cast<const double2 *>(work),
                            reinterpret_cast<const double2 *>(tfft),
                            reinterpret_cast<const double2 *>(tfft2), T, tw, lag_pos,
                            lag_vel, nlag, ilo, vgrid, nvel, beta, chisq);

@@ -41,6 +41,7 @@ extern "C" {
 #define RVS_ST_ALLMASKED 0x40     /* every pixel masked in CCF preprocessing (make_ccf.py:311-315)  */
 #define RVS_ST_QUAD_ASSERT 0x80   /* parabola vertex outside its bracket (spec_fit.py:1014 assert)  */
 #define RVS_ST_ILLCOND 0x100      /* rvs_chisq_grid: normal matrix pivots span > 1e9 (long stretch of weightless pixels); re-evaluate the job with rvs_chisq_point */
+#define RVS_ST_NONPOS_MEDIAN 0x200 /* rvs_ccf_models_build: median of the model row <= 0 (make_ccf.py:133-138) */
 
 /* library version / build probe (host).  RVS_ABI_VERSION changes whenever the
  * meaning of an argument, a status bit or a work-size formula changes; a caller
@@ -90,8 +91,10 @@ extern "C" {
  *      rvs_nm_run / rvs_bfgs_run -- apply pt.taps (until now RVS_E_ARG) where
  *      rvs_objective_resol_ok (added) admits the arm
  *  14: removed: rvs_nm_state.stop_below (and its padding word), options "xc_ws1",
- *      "nm_glue", "nm_bucket" */
-#define RVS_ABI_VERSION 14
+ *      "nm_glue", "nm_bucket"
+ *  15: rvs_ccf_models_build, rvs_ccf_model_rows (CCF template sets from model rows);
+ *      status bit 0x200 = RVS_ST_NONPOS_MEDIAN */
+#define RVS_ABI_VERSION 15
 int rvs_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -711,6 +714,53 @@ int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar, int nfft,
                   const double *vgrid, int nvel, double beta,
                   const uint8_t *prune, double *chisq, double *work,
                   void *stream);
+
+/* ------------------------------------------------------------------------
+ * CCF template sets; replaces make_ccf.preprocess_model (make_ccf.py:167-221) with
+ * get_continuum / fit_resid (:105-164) for M model rows (template x vsini) at once,
+ * and the two np.fft.rfft of ccf_executor (:474-475).  One block per row.
+ *
+ * rows float64 [M, ntp]  flux on the library's template grid (already broadened by
+ *        rvs_vsini_convolve where vsini is neither None nor 0)
+ * f32row uint8 [M] (nullable)  != 0: the row holds float32 numbers -- np.exp of a
+ *        float32 array (make_ccf.py:464-465) that no vsini kernel touched; numpy then
+ *        takes medians, m * 1e-5 and (without continuum) interp1d's y_hi - y_lo in
+ *        float32, and so does the kernel
+ * erows float64 [M, ntp] (nullable)  the errors of get_continuum's caller; NULL:
+ *        preprocess_model's max(1e-5 m, 1e-2 median(m))
+ * Eb, El, Cinv, istart, nnode, bin_start  the tables of rvs_ccf_preprocess for the
+ *        TEMPLATE grid (nodes from its own lam.min() / lam.max(), make_ccf.py:
+ *        123-131); nnode <= 48.  Not read when continuum == 0.
+ * lnlam float64 [ntp] = log(lam); logl float64 [npoints] = the FFT grid;
+ * ihi int32 [npoints]  clip(searchsorted(lnlam, logl), 1, ntp - 1), or -1 where logl
+ *        lies outside [lnlam[0], lnlam[ntp-1]] (interp1d fill_value = 1)
+ * twid complex128 [npoints/2]  exp(+2 pi i k / npoints), as rvs_ccf_xcorr's
+ * outputs: model [M, npoints]; fft, fft2 complex128 [M, npoints/2 + 1] = rfft(model),
+ *        rfft(model^2) in numpy's order and sign (both NULL: no transforms; else
+ *        npoints must be a power of two, 64 ... 16384); cont [M, ntp] (nullable): the
+ *        fitted continuum, get_continuum's return value (before the floor at a
+ *        hundredth of its median); pfit [M, nnode] (nullable): its node values;
+ *        status int32 [M] (nullable, OR-ed into): RVS_ST_NONPOS_MEDIAN
+ * Limits: 12 <= ntp <= RVS_CCF_MODEL_MAX_NTP (the row and the model values of the
+ * fit's last evaluation live in LDS); RVS_E_ARG beyond, before any launch.
+ * ---------------------------------------------------------------------- */
+#define RVS_CCF_MODEL_MAX_NTP 9216
+/* the rows of a call: rows[b] = dats[sel[b]] (dats float32 [ngrid, ntp], sel int64 [M]
+ * on the device; a row number outside the library gives NaN), through numpy's float32
+ * exp when exp_flag (specs[inds], np.exp(specs): make_ccf.py:459-465).  An entry point
+ * of its own because that exp is neither expf nor torch's: numpy's float32 exp is not
+ * correctly rounded, the non-normalised sets are held to the reference at 1e-12, and
+ * rvs_vsini_convolve stands between this step and rvs_ccf_models_build. */
+int rvs_ccf_model_rows(const float *dats, int64_t ngrid, const int64_t *sel,
+                       int exp_flag, int ntp, int M, double *rows, void *stream);
+int rvs_ccf_models_build(const double *rows, const uint8_t *f32row,
+                         const double *erows, int ntp, int M, int continuum,
+                         const double *Eb, const int32_t *El, const double *Cinv,
+                         const int32_t *istart, int nnode, const int32_t *bin_start,
+                         const double *lnlam, const double *logl, const int32_t *ihi,
+                         int npoints, const double *twid, double *model, double *fft,
+                         double *fft2, double *cont, double *pfit, int32_t *status,
+                         void *stream);
 
 /* argmin over (template, velocity) + 3-point parabola (fitter_ccf.py:218-236).
  * sse [B] is added to every entry (total_sse).  res [B,4] = best_id, best_vel,

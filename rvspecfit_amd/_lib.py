@@ -93,6 +93,9 @@ SIGNATURES = {
     'rvs_ccf_xcorr': (I, [P, P, I, I, P, P, I, P, I, P, P, I, P, P, I, D, P, P,
                           P, P]),
     'rvs_ccf_select': (I, [P, P, I, I, I, P, I, P, P, P, P]),
+    'rvs_ccf_model_rows': (I, [P, L, P, I, I, I, P, P]),
+    'rvs_ccf_models_build': (I, [P, P, P, I, I, I, P, P, P, P, I, P, P, P, P, I, P,
+                                 P, P, P, P, P, P, P]),
     'rvs_template_nn': (I, [P, I, I, U, P, P, I, P, P, P, P, P, P, P]),
     'rvs_template_nn_arms': (I, [P, I, I, I, P, P]),
     'rvs_template_nn_arms_n': (I, [P, I, P, I, I, P, P]),
@@ -101,7 +104,7 @@ SIGNATURES = {
 
 _lib = None
 # RVS_ABI_VERSION of the include/rvsgpu.h these signatures mirror
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class RvsGpuError(RuntimeError):
@@ -273,3 +276,4 @@ ST_CCF_FAILED = 0x20
 ST_ALLMASKED = 0x40
 ST_QUAD_ASSERT = 0x80
 ST_ILLCOND = 0x100
+ST_NONPOS_MEDIAN = 0x200

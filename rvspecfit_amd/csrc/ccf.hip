@@ -9,6 +9,8 @@
 //      normalisation, 2-point rebin with ivar propagation onto the log-lambda
 //      FFT grid.  The medians are exact order statistics found by selection
 //      (block-wide histogram rounds, wave-level bisection for the bins).
+//  ccf_model_kernel       one block per CCF template row (make_ccf.py:167-221): the
+//      same continuum fit, the row divided by it and put on the FFT grid.
 //  (the FFT cross-correlation itself lives in ccf_fft.hip)
 //  ccf_select_kernel      argmin over (template, velocity) + parabola.
 #include "common.h"
@@ -324,8 +326,12 @@ extern "C" int rvs_dbg_read_pp(unsigned long long *out) {
              ? 0
              : -1;
 }
+#define PP_TPARAM , unsigned long long &t_prev
+#define PP_TPASS , t_prev
 #else
 #define PP_T(i)
+#define PP_TPARAM
+#define PP_TPASS
 #endif
 
 #define CCF_MAXNODE 24
@@ -333,16 +339,27 @@ extern "C" int rvs_dbg_read_pp(unsigned long long *out) {
 #define RVS_LM_MAXIT 60
 #endif
 
-struct LMShared {
-  double p[CCF_MAXNODE];                  // node values (start / result)
-  double c[CCF_MAXNODE], cn[CCF_MAXNODE], dl[CCF_MAXNODE];  // B-spline coeffs
-  double bvec[CCF_MAXNODE];               // gradient, B-spline space
-  double Bd[CCF_MAXNODE * 3];             // banded normal matrix: diag, sub1, sub2
-  double Lb[CCF_MAXNODE * 3];             // its LDL^T factor: d, l1, l2
-  double isum[CCF_MAXNODE * 9];           // per knot-interval partial sums
+// (the model rows of ccf_model_kernel span the padded template grid: more nodes than
+// a spectrum, and one block per CU anyway -- its LM state is the larger instance)
+#define CCF_MODEL_MAXNODE 48
+template <int MN>
+struct LMSharedT {
+  double p[MN];                  // node values (start / result)
+  double c[MN], cn[MN], dl[MN];  // B-spline coeffs
+  double bvec[MN];               // gradient, B-spline space
+  double Bd[MN * 3];             // banded normal matrix: diag, sub1, sub2
+  double Lb[MN * 3];             // its LDL^T factor: d, l1, l2
+  double isum[MN * 9];           // per knot-interval partial sums
   double red[PP_NW];
   double lamd, medv, mederr, medspec;
   int flag, ngood, firstgood, lastgood, nval, stop, ok;
+};
+typedef LMSharedT<CCF_MAXNODE> LMShared;
+// The error of pixel k (value s): a spectrum brings its own array; a model row's is
+// a function of the value (ErrModel, at ccf_model_kernel)
+struct ErrArray {
+  const double *ce;
+  __device__ __forceinline__ double operator()(int k, double) const { return ce[k]; }
 };
 
 // The continuum is exp(clip(S(lam))) with S the k=2 INTERPOLATING spline
@@ -374,9 +391,10 @@ struct LMPix {
 #define LM_PIX 1
 #endif
 
+template <class LM, class ERR>
 __device__ __forceinline__ double lm_eval(
-    LMShared &S, const double *cc, const double *__restrict__ Eb,
-    const int32_t *__restrict__ El, int npix, const double *cs, const double *ce,
+    LM &S, const double *cc, const double *__restrict__ Eb,
+    const int32_t *__restrict__ El, int npix, const double *cs, const ERR ce,
     double *wm, bool store, const LMPix (&px)[LM_PIX]) {
   __syncthreads();  // cc (LDS) was just written
   double c = 0;
@@ -391,8 +409,8 @@ __device__ __forceinline__ double lm_eval(
       const bool clipped = (s < -100.0) || (s > 100.0);
       s = fmin(fmax(s, -100.0), 100.0);
       const double mod = exp(s);
-      const double e = ce[k];
-      const double f = (mod - cs[k]) / e;
+      const double sk = cs[k], e = ce(k, sk);
+      const double f = (mod - sk) / e;
       const double z = f * f;
       const double r = sqrt(1 + z);
       c += 2 * (r - 1);
@@ -407,8 +425,8 @@ __device__ __forceinline__ double lm_eval(
     const bool clipped = (s < -100.0) || (s > 100.0);
     s = fmin(fmax(s, -100.0), 100.0);
     const double mod = exp(s);
-    const double e = ce[k];
-    const double f = (mod - cs[k]) / e;
+    const double sk = cs[k], e = ce(k, sk);
+    const double f = (mod - sk) / e;
     const double z = f * f;
     const double r = sqrt(1 + z);
     c += 2 * (r - 1);
@@ -419,9 +437,10 @@ __device__ __forceinline__ double lm_eval(
 
 // Gauss-Newton system in B-SPLINE space: the pentadiagonal E^T W E (S.Bd: diag,
 // first and second sub-diagonal) and the gradient E^T gw (S.bvec).
-__device__ void lm_normal(LMShared &S, const double *__restrict__ Eb,
+template <class LM, class ERR>
+__device__ void lm_normal(LM &S, const double *__restrict__ Eb,
                           const int32_t *__restrict__ istart, int m,
-                          const double *wm, const double *cs, const double *ce) {
+                          const double *wm, const double *cs, const ERR ce) {
   const int nint = m - 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __syncthreads();
@@ -447,8 +466,8 @@ __device__ void lm_normal(LMShared &S, const double *__restrict__ Eb,
         if (k < k1) {
           const double e0 = e[c][0], e1 = e[c][1], e2 = e[c][2];
           // the weights of lm_eval's formulas, from the stored model value
-          const double mod = wm[k], e = ce[k];
-          const double f = (mod - cs[k]) / e;
+          const double mod = wm[k], sk = cs[k], e = ce(k, sk);
+          const double f = (mod - sk) / e;
           const double z = f * f;
           const double r = sqrt(1 + z);
           const double d = mod / e;   // (mod = 0: clipped exponent, no weight)
@@ -514,7 +533,8 @@ __device__ inline double lane_put(double dst, double v, int lane) {
   return ((int)(threadIdx.x & 63) == lane) ? v : dst;
 }
 
-__device__ void lm_band_solve(LMShared &S, int m) {
+template <class LM>
+__device__ void lm_band_solve(LM &S, int m) {
   const int lane = threadIdx.x & 63;
   const int r = min(lane, m - 1);
   const double ld = 1.0 + S.lamd;
@@ -562,6 +582,159 @@ __device__ void lm_band_solve(LMShared &S, int m) {
     S.cn[lane] = S.c[lane] + dl;
   }
   if (lane == 0) S.ok = ok ? 1 : 0;
+}
+
+// ---- binned medians -> p0 (make_ccf.py:141-143), left in S.p[0..m) -----------
+// f32: the values are float32 numbers held as doubles (a model row exponentiated in
+// float32); np.median then rounds the mean of the two middle values to float32.
+template <class LM>
+__device__ __forceinline__ void lm_binned_start(LM &S, SelShared &Q, const double *cs,
+                                                const int32_t *__restrict__ bin_start,
+                                                int m, bool f32) {
+  const int tid = threadIdx.x;
+  // bins of <= 256 pixels (the usual case: ~140): a wave takes a whole bin, four
+  // values per lane in registers, 8 bins at a time, no block barriers;
+  // otherwise the block-wide selection, bin after bin
+  bool small = true;
+  for (int jb = 0; jb < m; jb++)
+    if (bin_start[jb + 1] - bin_start[jb] > 256) small = false;
+  if (small) {
+    const int lane = tid & 63, wv = tid >> 6;
+    for (int jb = wv; jb < m; jb += PP_NW) {
+      const int b0 = bin_start[jb], cnt = bin_start[jb + 1] - b0;
+      double x[4];
+#pragma unroll
+      for (int h = 0; h < 4; h++) {
+        const int q = lane + 64 * h;
+        x[h] = (q < cnt) ? cs[b0 + q] : 0.0;
+      }
+      double stat = wave_median256(x, cnt);
+      if (f32) stat = (double)(float)stat;
+      if (lane == 0) {
+        double p0 = log(fmax(stat, 1e-3 * S.medspec));
+        if (!(stat == stat)) p0 = stat;  // np.maximum propagates NaN
+        if (!(fabs(p0) <= 1.79e308)) p0 = log(S.medspec);
+        S.p[jb] = p0;
+      }
+    }
+  } else {
+    // a bin of more than 256 pixels: np.median of each bin by the block-wide
+    // selection (block_median: exact order statistics, NaN if the bin holds
+    // one), bin after bin
+    for (int jb = 0; jb < m; jb++) {
+      const int b0 = bin_start[jb], cnt = bin_start[jb + 1] - b0;
+      double stat = block_median(cs + b0, cnt, false, Q);
+      if (f32) stat = (double)(float)stat;
+      if (tid == 0) {
+        double p0 = log(fmax(stat, 1e-3 * S.medspec));
+        if (!(stat == stat)) p0 = stat;  // np.maximum propagates NaN
+        if (!(fabs(p0) <= 1.79e308)) p0 = log(S.medspec);
+        S.p[jb] = p0;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// ---- Levenberg-Marquardt on the soft-L1 objective from S.p; the B-spline
+// coefficients of the fit are left in S.c[0..m) (every thread may read them) ------
+template <class LM, class ERR>
+__device__ __forceinline__ void lm_fit(LM &S, const double *__restrict__ Eb,
+                                       const int32_t *__restrict__ El,
+                                       const double *__restrict__ Cinv,
+                                       const int32_t *__restrict__ istart, int m,
+                                       int npix, const double *cs, const ERR ce,
+                                       double *wm PP_TPARAM) {
+  const int tid = threadIdx.x;
+  // unknowns: the B-spline coefficients c = C^-1 p of the interpolating spline
+  // (a linear bijection of the reference's node values p, same minimum)
+  if (tid < m) {
+    double s = 0;
+    for (int jj = 0; jj < m; jj++) s = fma(Cinv[tid * m + jj], S.p[jj], s);
+    S.c[tid] = s;
+  }
+  if (tid == 0) {
+#ifndef RVS_LM_LAMBDA0
+#define RVS_LM_LAMBDA0 1e-3
+#endif
+    S.lamd = RVS_LM_LAMBDA0;
+    S.stop = 0;
+  }
+  LMPix px[LM_PIX];
+#pragma unroll
+  for (int i = 0; i < LM_PIX; i++) {
+    const int k = min(tid + i * PP_NT, npix - 1);
+    px[i].e0 = Eb[3 * k];
+    px[i].e1 = Eb[3 * k + 1];
+    px[i].e2 = Eb[3 * k + 2];
+    px[i].l = El[k];
+  }
+  double cost = lm_eval(S, S.c, Eb, El, npix, cs, ce, wm, true, px);
+  PP_T(7);  // (debug) LM set-up + first evaluation
+  for (int it = 0; it < RVS_LM_MAXIT; it++) {
+    lm_normal(S, Eb, istart, m, wm, cs, ce);
+    PP_T(8);  // (debug) normal equations
+    if (it == 0) {
+      // least_squares' gtol exit at the starting point (make_ccf.py:146-150,
+      // gtol = 1e-8 absolute): with |J^T rho' f|_inf below it TRF returns p0
+      // untouched -- what happens when the errors dwarf the flux.  The
+      // gradient with respect to the node values p is C^-T (E^T gw).
+      if (tid < 64) {
+        double g = 0;
+        if (tid < m)
+          for (int i = 0; i < m; i++) g = fma(Cinv[i * m + tid], S.bvec[i], g);
+        g = fabs(g);
+        if (!(g == g)) g = 1.0;  // NaN gradient: not an exit
+        for (int o = 32; o > 0; o >>= 1) g = fmax(g, __shfl_xor(g, o));
+        if (tid == 0 && g < 1e-8) S.stop = 1;
+      }
+      __syncthreads();
+      if (S.stop) break;
+    }
+    // damped step; retry with larger damping until the cost does not grow.
+    // The trial evaluation leaves its model values in wm: they are
+    // read by the NEXT iteration's lm_normal only (a retry re-solves the banded
+    // system in S), so an accepted trial needs no second evaluation -- one
+    // pass over the pixels less per iteration, same values.
+    bool accepted = false;
+    for (int tries = 0; tries < 40; tries++) {
+      if (tid < 64) lm_band_solve(S, m);
+      PP_T(9);  // (debug) band solve
+      const double cn =
+          lm_eval(S, S.cn, Eb, El, npix, cs, ce, wm, true, px);
+      PP_T(10);  // (debug) trial evaluation
+      if (cn <= cost) {  // accept (block-uniform decision)
+        accepted = true;
+        double mx = 0;
+        for (int i = 0; i < m; i++) mx = fmax(mx, fabs(S.dl[i]));
+        const double rel = (cost - cn) / fmax(cost, 1e-300);
+        __syncthreads();
+        if (tid == 0) {
+          for (int i = 0; i < m; i++) S.c[i] = S.cn[i];
+          S.lamd = fmax(S.lamd / 8, 1e-12);
+          // converged: the accepted step moved no coefficient (log flux) by
+          // 1e-9 or lowered the cost by less than 1e-12 of itself -- four orders
+          // inside least_squares' own ftol = xtol = 1e-8 (make_ccf.py:146-150)
+          if (mx < 1e-9 || rel < 1e-12) S.stop = 1;
+        }
+        cost = cn;
+        break;
+      }
+      __syncthreads();
+      if (tid == 0) {
+        S.lamd *= 4;
+        if (S.lamd > 1e12) S.stop = 1;
+      }
+      __syncthreads();
+      if (S.stop) break;
+    }
+    __syncthreads();
+    if (S.stop) break;
+    if (!accepted)  // (40 rejected trials: the weights of the kept point again)
+      cost = lm_eval(S, S.c, Eb, El, npix, cs, ce, wm, true, px);
+    PP_T(11);  // (debug) accept
+  }
+  __syncthreads();
 }
 
 __global__ void __launch_bounds__(PP_NT)
@@ -620,7 +793,6 @@ __global__ void __launch_bounds__(PP_NT)
   const int b = blockIdx.x, tid = threadIdx.x;
   const double *sp0 = spec + (int64_t)b * npix_s;
   const double *es0 = espec + (int64_t)b * npix_s;
-  const double nanv = __builtin_nan("");
 #ifdef RVS_PP_TIMING
   unsigned long long t_prev = wall_clock64();
 #endif
@@ -740,139 +912,10 @@ __global__ void __launch_bounds__(PP_NT)
   if (continuum) {
     const int m = nnode;
     PP_T(2);  // median sort
-    // ---- binned medians -> p0 (make_ccf.py:141-143) -------------------------
-    // bins of <= 256 pixels (the usual case: ~140): a wave takes a whole bin, four
-    // values per lane in registers, 8 bins at a time, no block barriers;
-    // otherwise the block-wide selection, bin after bin
-    bool small = true;
-    for (int jb = 0; jb < m; jb++)
-      if (bin_start[jb + 1] - bin_start[jb] > 256) small = false;
-    if (small) {
-      const int lane = tid & 63, wv = tid >> 6;
-      for (int jb = wv; jb < m; jb += PP_NW) {
-        const int b0 = bin_start[jb], cnt = bin_start[jb + 1] - b0;
-        double x[4];
-#pragma unroll
-        for (int h = 0; h < 4; h++) {
-          const int q = lane + 64 * h;
-          x[h] = (q < cnt) ? cs[b0 + q] : 0.0;
-        }
-        const double stat = wave_median256(x, cnt);
-        if (lane == 0) {
-          double p0 = log(fmax(stat, 1e-3 * S.medspec));
-          if (!(stat == stat)) p0 = nanv;  // np.maximum propagates NaN
-          if (!(fabs(p0) <= 1.79e308)) p0 = log(S.medspec);
-          S.p[jb] = p0;
-        }
-      }
-    } else {
-      // a bin of more than 256 pixels: np.median of each bin by the block-wide
-      // selection (block_median: exact order statistics, NaN if the bin holds
-      // one), bin after bin
-      for (int jb = 0; jb < m; jb++) {
-        const int b0 = bin_start[jb], cnt = bin_start[jb + 1] - b0;
-        const double stat = block_median(cs + b0, cnt, false, Q);
-        if (tid == 0) {
-          double p0 = log(fmax(stat, 1e-3 * S.medspec));
-          if (!(stat == stat)) p0 = nanv;  // np.maximum propagates NaN
-          if (!(fabs(p0) <= 1.79e308)) p0 = log(S.medspec);
-          S.p[jb] = p0;
-        }
-      }
-    }
-    __syncthreads();
+    lm_binned_start(S, Q, cs, bin_start, m, false);
 
     PP_T(3);  // binned-median sort
-    // ---- Levenberg-Marquardt on the soft-L1 objective -----------------------
-    // unknowns: the B-spline coefficients c = C^-1 p of the interpolating spline
-    // (a linear bijection of the reference's node values p, same minimum)
-    if (tid < m) {
-      double s = 0;
-      for (int jj = 0; jj < m; jj++) s = fma(Cinv[tid * m + jj], S.p[jj], s);
-      S.c[tid] = s;
-    }
-    if (tid == 0) {
-#ifndef RVS_LM_LAMBDA0
-#define RVS_LM_LAMBDA0 1e-3
-#endif
-      S.lamd = RVS_LM_LAMBDA0;
-      S.stop = 0;
-    }
-    LMPix px[LM_PIX];
-#pragma unroll
-    for (int i = 0; i < LM_PIX; i++) {
-      const int k = min(tid + i * PP_NT, npix - 1);
-      px[i].e0 = Eb[3 * k];
-      px[i].e1 = Eb[3 * k + 1];
-      px[i].e2 = Eb[3 * k + 2];
-      px[i].l = El[k];
-    }
-    double cost = lm_eval(S, S.c, Eb, El, npix, cs, ce, wm, true, px);
-    PP_T(7);  // (debug) LM set-up + first evaluation
-    for (int it = 0; it < RVS_LM_MAXIT; it++) {
-      lm_normal(S, Eb, istart, m, wm, cs, ce);
-      PP_T(8);  // (debug) normal equations
-      if (it == 0) {
-        // least_squares' gtol exit at the starting point (make_ccf.py:146-150,
-        // gtol = 1e-8 absolute): with |J^T rho' f|_inf below it TRF returns p0
-        // untouched -- what happens when the errors dwarf the flux.  The
-        // gradient with respect to the node values p is C^-T (E^T gw).
-        if (tid < 64) {
-          double g = 0;
-          if (tid < m)
-            for (int i = 0; i < m; i++) g = fma(Cinv[i * m + tid], S.bvec[i], g);
-          g = fabs(g);
-          if (!(g == g)) g = 1.0;  // NaN gradient: not an exit
-          for (int o = 32; o > 0; o >>= 1) g = fmax(g, __shfl_xor(g, o));
-          if (tid == 0 && g < 1e-8) S.stop = 1;
-        }
-        __syncthreads();
-        if (S.stop) break;
-      }
-      // damped step; retry with larger damping until the cost does not grow.
-      // The trial evaluation leaves its model values in wm: they are
-      // read by the NEXT iteration's lm_normal only (a retry re-solves the banded
-      // system in S), so an accepted trial needs no second evaluation -- one
-      // pass over the pixels less per iteration, same values.
-      bool accepted = false;
-      for (int tries = 0; tries < 40; tries++) {
-        if (tid < 64) lm_band_solve(S, m);
-        PP_T(9);  // (debug) band solve
-        const double cn =
-            lm_eval(S, S.cn, Eb, El, npix, cs, ce, wm, true, px);
-        PP_T(10);  // (debug) trial evaluation
-        if (cn <= cost) {  // accept (block-uniform decision)
-          accepted = true;
-          double mx = 0;
-          for (int i = 0; i < m; i++) mx = fmax(mx, fabs(S.dl[i]));
-          const double rel = (cost - cn) / fmax(cost, 1e-300);
-          __syncthreads();
-          if (tid == 0) {
-            for (int i = 0; i < m; i++) S.c[i] = S.cn[i];
-            S.lamd = fmax(S.lamd / 8, 1e-12);
-            // converged: the accepted step moved no coefficient (log flux) by
-            // 1e-9 or lowered the cost by less than 1e-12 of itself -- four orders
-            // inside least_squares' own ftol = xtol = 1e-8 (make_ccf.py:146-150)
-            if (mx < 1e-9 || rel < 1e-12) S.stop = 1;
-          }
-          cost = cn;
-          break;
-        }
-        __syncthreads();
-        if (tid == 0) {
-          S.lamd *= 4;
-          if (S.lamd > 1e12) S.stop = 1;
-        }
-        __syncthreads();
-        if (S.stop) break;
-      }
-      __syncthreads();
-      if (S.stop) break;
-      if (!accepted)  // (40 rejected trials: the weights of the kept point again)
-        cost = lm_eval(S, S.c, Eb, El, npix, cs, ce, wm, true, px);
-      PP_T(11);  // (debug) accept
-    }
-    __syncthreads();
+    lm_fit(S, Eb, El, Cinv, istart, m, npix, cs, ErrArray{ce}, wm PP_TPASS);
     if (pfit && tid < m) {
       // node values p = C c (C follows C^-1 in the Cinv buffer)
       const double *Cm = Cinv + m * m;
@@ -983,6 +1026,198 @@ extern "C" int rvs_ccf_preprocess(const double *lam, const double *spec,
                               Cinv, istart, nnode, bin_start, xind, rw, nfft, maxerr,
                               proc_spec, proc_ivar, sse, cont, pfit, status, nullptr,
                               nullptr, nullptr, stream);
+}
+
+// ---------------------------------------------------------------------------
+// CCF TEMPLATE rows: make_ccf.preprocess_model with get_continuum / fit_resid
+// (make_ccf.py:105-164, 167-221).  One block per model row (template x vsini), one
+// block per CU: the row and the model values of the last evaluation stay in LDS (2 x
+// ntp doubles); the error of a pixel is a function of its value and is never stored.
+//   median -> errors max(1e-5 m, 1e-2 median) -> binned-median start -> the soft-L1
+//   fit of ccf_preprocess_kernel (lm_fit) -> cont = max(cont, 1e-2 median(cont)) ->
+//   m / cont -> scipy interp1d (linear in ln lambda, 1 outside the row) onto the
+//   FFT grid.
+// f32row[r] != 0: the row holds float32 numbers (np.exp of a float32 array that no
+// vsini kernel touched, make_ccf.py:464-465): numpy then takes the medians, m * 1e-5
+// and, without continuum, interp1d's y_hi - y_lo in float32.
+// ---------------------------------------------------------------------------
+struct ErrModel {
+  const double *es;  // the caller's errors (get_continuum), or null:
+  double floor_;     // 1e-2 median(m)
+  bool f32;
+  __device__ __forceinline__ double operator()(int k, double s) const {
+    if (es) return es[k];
+    // (1e-2 * np.float32 is a float64 scalar; np.maximum casts it to the array's type)
+    if (f32) return (double)fmaxf(__fmul_rn((float)s, 1e-5f), (float)floor_);
+    return fmax(s * 1e-5, floor_);
+  }
+};
+typedef LMSharedT<CCF_MODEL_MAXNODE> LMSharedModel;
+// LDS of a block: two rows, the LM and the selection state, inside 159 KB
+#define CCF_MODEL_LDS (159 * 1024)
+static_assert(sizeof(double) * 2 * RVS_CCF_MODEL_MAX_NTP + sizeof(LMSharedModel) +
+                      sizeof(SelShared) <= CCF_MODEL_LDS,
+              "a model row of RVS_CCF_MODEL_MAX_NTP pixels does not fit the LDS");
+
+__global__ void __launch_bounds__(PP_NT)
+    ccf_model_kernel(const double *__restrict__ rows,
+                     const uint8_t *__restrict__ f32row,
+                     const double *__restrict__ erows, int ntp, int continuum,
+                     const double *__restrict__ Eb, const int32_t *__restrict__ El,
+                     const double *__restrict__ Cinv,
+                     const int32_t *__restrict__ istart, int nnode,
+                     const int32_t *__restrict__ bin_start,
+                     const double *__restrict__ lnlam,
+                     const double *__restrict__ logl,
+                     const int32_t *__restrict__ ihi, int npoints,
+                     double *__restrict__ model, double *__restrict__ cont_out,
+                     double *__restrict__ pfit, int32_t *__restrict__ status) {
+  extern __shared__ double sm[];
+  double *cs = sm;         // [ntp] the row
+  double *wm = cs + ntp;   // [ntp] model values of the last evaluation; then m / cont
+  __shared__ LMSharedModel S;
+  __shared__ SelShared Q;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const double *row = rows + (int64_t)b * ntp;
+  const bool f32 = f32row && f32row[b] != 0;
+  for (int k = tid; k < ntp; k += PP_NT) cs[k] = row[k];
+  __syncthreads();
+  const double *y = cs;   // what is interpolated onto the FFT grid
+  if (continuum) {
+    const int m = nnode;
+    {
+      double md = block_median(cs, ntp, false, Q);
+      if (f32) md = (double)(float)md;
+      if (tid == 0) {
+        S.medv = md;
+        double ms = md;
+        if (ms <= 0) {  // make_ccf.py:133-138
+          ms = fabs(ms);
+          if (ms == 0) ms = 1;
+          if (status) atomicOr(&status[b], RVS_ST_NONPOS_MEDIAN);
+        }
+        S.medspec = ms;
+      }
+      __syncthreads();
+    }
+    const ErrModel ce = {erows ? erows + (int64_t)b * ntp : nullptr, 1e-2 * S.medv,
+                         f32};
+    lm_binned_start(S, Q, cs, bin_start, m, f32);
+#ifdef RVS_PP_TIMING
+    unsigned long long t_prev = wall_clock64();
+#endif
+    lm_fit(S, Eb, El, Cinv, istart, m, ntp, cs, ce, wm PP_TPASS);
+    if (pfit && tid < m) {
+      const double *Cm = Cinv + m * m;   // node values p = C c
+      double s = 0;
+      for (int jj = 0; jj < m; jj++) s = fma(Cm[tid * m + jj], S.c[jj], s);
+      pfit[(int64_t)b * nnode + tid] = s;
+    }
+    // the continuum of the fit (get_continuum's return value) ...
+    for (int k = tid; k < ntp; k += PP_NT) {
+      const int l = El[k];
+      double s = Eb[3 * k] * S.c[l];
+      s = fma(Eb[3 * k + 1], S.c[l + 1], s);
+      s = fma(Eb[3 * k + 2], S.c[l + 2], s);
+      const double cont = exp(fmin(fmax(s, -100.0), 100.0));
+      wm[k] = cont;
+      if (cont_out) cont_out[(int64_t)b * ntp + k] = cont;
+    }
+    __syncthreads();
+    // ... floored at a hundredth of its median (make_ccf.py:197), divided out
+    const double cfloor = 1e-2 * block_median(wm, ntp, false, Q);
+    for (int k = tid; k < ntp; k += PP_NT) {
+      double cont = wm[k];
+      cont = (cfloor != cfloor) ? cfloor : fmax(cont, cfloor);
+      wm[k] = cs[k] / cont;
+    }
+    __syncthreads();
+    y = wm;
+  }
+  // scipy interp1d(np.log(lam), y, bounds_error=False, fill_value=1)(logl):
+  // slope = (y_hi - y_lo) / (x_hi - x_lo), y_lo + slope (x - x_lo); ihi < 0: outside
+  const bool d32 = f32 && !continuum;   // y is still the float32 row
+  for (int n = tid; n < npoints; n += PP_NT) {
+    const int hi = ihi[n];
+    double v = 1.0;
+    if (hi >= 1 && hi < ntp) {
+      const double ylo = y[hi - 1], yhi = y[hi], xlo = lnlam[hi - 1];
+      const double dy = d32 ? (double)__fsub_rn((float)yhi, (float)ylo) : yhi - ylo;
+      const double slope = dy / (lnlam[hi] - xlo);
+      v = slope * (logl[n] - xlo) + ylo;
+    }
+    model[(int64_t)b * npoints + n] = v;
+  }
+}
+
+// specs[inds] and np.exp of it in float32 (make_ccf.py:459-465): row b of the output
+// is row sel[b] of the library, exponentiated with numpy's float32 exp; a row number
+// outside the library gives a row of NaN
+__global__ void __launch_bounds__(256)
+    ccf_model_rows_kernel(const float *__restrict__ dats, int64_t ngrid,
+                          const int64_t *__restrict__ sel, int exp_flag, int ntp,
+                          double *__restrict__ rows) {
+  const int b = blockIdx.x;
+  const int64_t r = sel[b];
+  const bool ok = r >= 0 && r < ngrid;
+  const float *src = dats + (ok ? r : 0) * ntp;
+  for (int k = threadIdx.x; k < ntp; k += 256) {
+    double v = __builtin_nan("");
+    if (ok) v = exp_flag ? (double)np_expf(src[k]) : (double)src[k];
+    rows[(int64_t)b * ntp + k] = v;
+  }
+}
+
+extern "C" int rvs_ccf_model_rows(const float *dats, int64_t ngrid, const int64_t *sel,
+                                  int exp_flag, int ntp, int M, double *rows,
+                                  void *stream) {
+  if (!dats || !sel || !rows || ngrid < 1 || ntp < 1 || M < 1) return RVS_E_ARG;
+  hipLaunchKernelGGL(ccf_model_rows_kernel, dim3(M), dim3(256), 0, rvs_stream(stream),
+                     dats, ngrid, sel, exp_flag, ntp, rows);
+  RVS_LAUNCH_CHECK();
+  return 0;
+}
+
+// (csrc/ccf_fft.hip) rfft of the rows of `model` [M, nfft] and of their squares
+int ccf_model_rfft(const double *model, int nfft, int M, const double *twid,
+                   double *fft, double *fft2, hipStream_t st);
+
+extern "C" int rvs_ccf_models_build(const double *rows, const uint8_t *f32row,
+                                    const double *erows, int ntp, int M,
+                                    int continuum, const double *Eb,
+                                    const int32_t *El, const double *Cinv,
+                                    const int32_t *istart, int nnode,
+                                    const int32_t *bin_start, const double *lnlam,
+                                    const double *logl, const int32_t *ihi,
+                                    int npoints, const double *twid, double *model,
+                                    double *fft, double *fft2, double *cont,
+                                    double *pfit, int32_t *status, void *stream) {
+  if (ntp < 12 || ntp > RVS_CCF_MODEL_MAX_NTP || M < 1 || npoints < 2)
+    return RVS_E_ARG;
+  if (!rows || !lnlam || !logl || !ihi || !model) return RVS_E_ARG;
+  if (continuum && (nnode < 3 || nnode > CCF_MODEL_MAXNODE || !Eb || !El || !Cinv ||
+                    !istart || !bin_start))
+    return RVS_E_ARG;
+  if ((fft != nullptr) != (fft2 != nullptr)) return RVS_E_ARG;
+  if (fft) {   // the sizes rvs_ccf_xcorr takes
+    if (npoints < 64 || npoints > 16384 || (npoints & (npoints - 1)) || !twid)
+      return RVS_E_ARG;
+  }
+  const size_t shm = sizeof(double) * 2 * (size_t)ntp;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(
+        (const void *)ccf_model_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)(CCF_MODEL_LDS - sizeof(LMSharedModel) - sizeof(SelShared)));
+    (void)hipGetLastError();
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(ccf_model_kernel, dim3(M), dim3(PP_NT), shm, rvs_stream(stream),
+                     rows, f32row, erows, ntp, continuum, Eb, El, Cinv, istart, nnode,
+                     bin_start, lnlam, logl, ihi, npoints, model, cont, pfit, status);
+  RVS_LAUNCH_CHECK();
+  if (fft) return ccf_model_rfft(model, npoints, M, twid, fft, fft2, rvs_stream(stream));
+  return 0;
 }
 
 // ---------------------------------------------------------------------------

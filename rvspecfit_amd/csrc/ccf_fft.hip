@@ -445,20 +445,32 @@ __device__ __forceinline__ int fft_pos(int f, int log2n) {
   return pos;
 }
 
-// conj(rfft(x)) for x = proc_spec*proc_ivar (which 0) and proc_ivar (which 1)
+// conj(rfft(x)) for x = proc_spec*proc_ivar (which 0) and proc_ivar (which 1) into
+// work [B, 2, n2 + 1]; MODEL (a CCF template set, make_ccf.py:474-475): rfft(x) itself,
+// numpy's sign, for x = proc_spec (which 0 -> work [B, n2 + 1]) and its square (which 1
+// -> work2)
+template <bool MODEL>
 __global__ void __launch_bounds__(XC_NT)
     ccf_rfft_kernel(const double *__restrict__ proc_spec,
                     const double *__restrict__ proc_ivar, int nfft, int log2n,
-                    const double2 *__restrict__ tw, double2 *__restrict__ work) {
+                    const double2 *__restrict__ tw, double2 *__restrict__ work,
+                    double2 *__restrict__ work2) {
   extern __shared__ double2 fa[];
   const int b = blockIdx.x, which = blockIdx.y, tid = threadIdx.x;
   const int n2 = nfft >> 1;
   const double *ps = proc_spec + (int64_t)b * nfft;
-  const double *pi = proc_ivar + (int64_t)b * nfft;
+  const double *pi = MODEL ? nullptr : proc_ivar + (int64_t)b * nfft;
   xc_fill_twiddles<XC_NT>(fa, n2, tw);
   for (int n = tid; n < n2; n += XC_NT) {
     double x0, x1;
-    if (which == 0) {
+    if (MODEL) {
+      x0 = ps[2 * n];
+      x1 = ps[2 * n + 1];
+      if (which) {
+        x0 *= x0;
+        x1 *= x1;
+      }
+    } else if (which == 0) {
       x0 = ps[2 * n] * pi[2 * n];
       x1 = ps[2 * n + 1] * pi[2 * n + 1];
     } else {
@@ -468,7 +480,8 @@ __global__ void __launch_bounds__(XC_NT)
     fa[n] = make_double2(x0, x1);
   }
   fft_lds<-1, XC_NT>(fa, log2n, tw);
-  double2 *out = work + ((int64_t)b * 2 + which) * (n2 + 1);
+  double2 *out = MODEL ? (which ? work2 : work) + (int64_t)b * (n2 + 1)
+                       : work + ((int64_t)b * 2 + which) * (n2 + 1);
   for (int k = tid; k <= n2; k += XC_NT) {
     double2 X;
     if (k == 0 || k == n2) {
@@ -482,8 +495,34 @@ __global__ void __launch_bounds__(XC_NT)
       const double2 q = cmul(twid<-1>(tw, k, nfft), d);
       X = make_double2(0.5 * (e.x + q.y), 0.5 * (e.y - q.x));     // e/2 - (i/2) q
     }
-    out[k] = make_double2(X.x, -X.y);  // conjugate
+    out[k] = MODEL ? X : make_double2(X.x, -X.y);  // (data: the conjugate)
   }
+}
+
+int ccf_model_rfft(const double *model, int nfft, int M, const double *twid,
+                   double *fft, double *fft2, hipStream_t st) {
+  int log2n = 0;
+  while ((2 << log2n) < nfft) log2n++;
+  if ((2 << log2n) != nfft || nfft < 64 || nfft > 16384 || M < 1) return RVS_E_ARG;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void *)ccf_rfft_kernel<true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, XC_LDS_MAX);
+    (void)hipGetLastError();
+    attr_set = true;
+  }
+  for (int b0 = 0; b0 < M; b0 += 65535) {   // (grid.y carries `which`)
+    const int nb = (M - b0 < 65535) ? (M - b0) : 65535;
+    const int64_t o = (int64_t)b0 * ((nfft >> 1) + 1);
+    hipLaunchKernelGGL(ccf_rfft_kernel<true>, dim3(nb, 2), dim3(XC_NT),
+                       xc_lds_pair(nfft >> 1, 0).bytes, st,
+                       model + (int64_t)b0 * nfft, (const double *)nullptr, nfft, log2n,
+                       reinterpret_cast<const double2 *>(twid),
+                       reinterpret_cast<double2 *>(fft) + o,
+                       reinterpret_cast<double2 *>(fft2) + o);
+    RVS_LAUNCH_CHECK();
+  }
+  return 0;
 }
 
 #define XB_NT 512  // threads per block
@@ -1258,7 +1297,7 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
   const double2 *tw = reinterpret_cast<const double2 *>(twid_);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void *)ccf_rfft_kernel,
+    (void)hipFuncSetAttribute((const void *)ccf_rfft_kernel<false>,
                               hipFuncAttributeMaxDynamicSharedMemorySize,
                               XC_LDS_MAX);
     (void)hipFuncSetAttribute((const void *)ccf_xcorr_kernel,
@@ -1267,9 +1306,9 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
     (void)hipGetLastError();
     attr_set = true;
   }
-  hipLaunchKernelGGL(ccf_rfft_kernel, dim3(B, 2), dim3(XC_NT), shm1, st,
+  hipLaunchKernelGGL(ccf_rfft_kernel<false>, dim3(B, 2), dim3(XC_NT), shm1, st,
                      proc_spec, proc_ivar, nfft, log2n, tw,
-                     reinterpret_cast<double2 *>(work));
+                     reinterpret_cast<double2 *>(work), (double2 *)nullptr);
   RVS_LAUNCH_CHECK();
   const int G = xc_group(T, nfft);
   {

@@ -365,7 +365,8 @@ class ArmData:
         """Per-arm CCF tables (host-built once, see ccf_tables.py)."""
         cc = lib.ccf_set(config)
         maxvel, vgrid = ccf_tables.ccf_vel_grid(config)
-        key = (lib.name, id(lib), maxvel, len(vgrid), cc['continuum'])
+        key = (lib.name, id(lib), getattr(lib, 'ccf_version', 0), maxvel, len(vgrid),
+               cc['continuum'])
         if key in self._ccf:
             return self._ccf[key]
         dev = self.device

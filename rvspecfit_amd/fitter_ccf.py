@@ -19,6 +19,12 @@ class CCFCache:
     ccf2s = {}
     ccf_models = {}
 
+    @classmethod
+    def forget(cls, spec_setup):
+        """drop a setup's entries (its library got another set: add_ccf_set)"""
+        for d in (cls.ccf_info, cls.ccfs, cls.ccf2s, cls.ccf_models):
+            d.pop(spec_setup, None)
+
 
 def get_ccf_info(spec_setup, config):
     """fitter_ccf.get_ccf_info (fitter_ccf.py:21-59): (fft, fft2, models, info) of

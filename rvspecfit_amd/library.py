@@ -206,6 +206,7 @@ class TemplateLibrary:
             ptp = np.ptp(vec, axis=1)
             self.ptp = np.ascontiguousarray(ptp)
             self.ngrid = vec.shape[1]
+            self.vec = vec
             self.dats = _dev(d['dats'], torch.float32, device)
             self.idgrid = _dev(idgrid.ravel(), torch.int64, device)
             self.uvecs = _dev(np.concatenate(uvecs), torch.float64, device)
@@ -236,36 +237,61 @@ class TemplateLibrary:
         for pre in ('ccf_', 'ccfnc_'):
             if pre + 'fft' not in d:
                 continue
-            # the set is what its own ccfconf['continuum'] says it is
-            # (make_ccf.py:483-493), whatever prefix an older converter gave it
-            cont = bool(d[pre + 'continuum'])
-            if cont in self.ccf_sets:
+            cs = self._read_ccf_set(d, pre)
+            if cs['continuum'] in self.ccf_sets:
                 raise ValueError(
                     'setup %s: two CCF template sets with continuum=%s; '
                     'reconvert the artefacts with tools/convert_artefacts.py'
-                    % (name, cont))
-            fft = np.ascontiguousarray(d[pre + 'fft'], dtype=np.complex128)
-            fft2 = np.ascontiguousarray(d[pre + 'fft2'], dtype=np.complex128)
-            self.ccf_sets[cont] = dict(
-                T=fft.shape[0],
-                nfft=int(d[pre + 'npoints']),
-                fft=_dev(fft.view(np.float64), torch.float64, device),
-                fft2=_dev(fft2.view(np.float64), torch.float64, device),
-                mod=np.asarray(d[pre + 'mod']) if pre + 'mod' in d else None,
-                params=np.asarray(d[pre + 'params'], dtype=np.float64),
-                vsinis=np.asarray(d[pre + 'vsinis'], dtype=np.float64),
-                params_dev=_dev(d[pre + 'params'], torch.float64, device),
-                vsinis_dev=_dev(np.nan_to_num(np.asarray(d[pre + 'vsinis'],
-                                                         dtype=np.float64),
-                                              nan=0.0), torch.float64, device),
-                logl0=float(d[pre + 'logl0']), logl1=float(d[pre + 'logl1']),
-                npoints=int(d[pre + 'npoints']),
-                continuum=bool(d[pre + 'continuum']),
-                splinestep=float(d[pre + 'splinestep'])
-                if pre + 'splinestep' in d else None,
-                maxcontpts=int(d[pre + 'maxcontpts'])
-                if pre + 'maxcontpts' in d else 20)
+                    % (name, cs['continuum']))
+            self.ccf_sets[cs['continuum']] = cs
         self.ccf = self.ccf_sets.get(True)
+        self.ccf_version = 0   # counts add_ccf_set calls
+
+    def _read_ccf_set(self, d, pre):
+        """one CCF template set from the keys pre + ... of a converted artefact"""
+        device = self.device
+        # the set is what its own ccfconf['continuum'] says it is
+        # (make_ccf.py:483-493), whatever prefix an older converter gave it
+        fft = np.ascontiguousarray(d[pre + 'fft'], dtype=np.complex128)
+        fft2 = np.ascontiguousarray(d[pre + 'fft2'], dtype=np.complex128)
+        return dict(
+            T=fft.shape[0],
+            nfft=int(d[pre + 'npoints']),
+            fft=_dev(fft.view(np.float64), torch.float64, device),
+            fft2=_dev(fft2.view(np.float64), torch.float64, device),
+            mod=np.asarray(d[pre + 'mod']) if pre + 'mod' in d else None,
+            params=np.asarray(d[pre + 'params'], dtype=np.float64),
+            vsinis=np.asarray(d[pre + 'vsinis'], dtype=np.float64),
+            params_dev=_dev(d[pre + 'params'], torch.float64, device),
+            vsinis_dev=_dev(np.nan_to_num(np.asarray(d[pre + 'vsinis'],
+                                                     dtype=np.float64),
+                                          nan=0.0), torch.float64, device),
+            logl0=float(d[pre + 'logl0']), logl1=float(d[pre + 'logl1']),
+            npoints=int(d[pre + 'npoints']),
+            continuum=bool(d[pre + 'continuum']),
+            splinestep=float(d[pre + 'splinestep'])
+            if pre + 'splinestep' in d else None,
+            maxcontpts=int(d[pre + 'maxcontpts'])
+            if pre + 'maxcontpts' in d else 20)
+
+    def add_ccf_set(self, d):
+        """Attach the CCF template set(s) of `d` (make_ccf.build_ccf_set's dictionary,
+        or any dictionary in the converted artefact's keys), replacing the set of the
+        same kind; fitter_ccf.fit, pipeline.fit_batch and desi_fit use it from the
+        next call on (the tables batches keep per library follow ccf_version, and
+        what fitter_ccf.get_ccf_info has handed out for this setup is forgotten)."""
+        found = False
+        for pre in ('ccf_', 'ccfnc_'):
+            if pre + 'fft' in d:
+                cs = self._read_ccf_set(d, pre)
+                self.ccf_sets[cs['continuum']] = cs
+                found = True
+        if not found:
+            raise ValueError('add_ccf_set: no ccf_fft / ccfnc_fft in the dictionary')
+        self.ccf = self.ccf_sets.get(True)
+        self.ccf_version += 1
+        from . import fitter_ccf
+        fitter_ccf.CCFCache.forget(self.name)
 
     def ccf_set(self, config):
         """The CCF template set config['ccf_continuum_normalize'] selects

@@ -41,26 +41,30 @@ struct XcLds {
                  // c0 [nlag] (ws), c0 [2][nlag] (ws2: one row per template)
   int t1c;       // ws: T1c [XW_NT1C] double2, the twiddles of pass 1 and of the fold
   int ca;        // ws, RATIO: cA [nlag] doubles
+  int lt;        // ws: the lag table [XW_NLT] int32 (ccf_xcorr_ws_kernel)
   size_t bytes;  // of the launch
 };
 #define XW_NT1C 73   // 64 + 8 twiddles and one spare entry
+#define XW_NLT 256   // 64-block x end (position 0 / 63) x part (re / im) -> lag or -1
 #define XC_LDS_MAX (159 * 1024)   // dynamic LDS a block may ask for
 // ccf_xcorr_kernel; nlag = 0: ccf_rfft_kernel (the image and T1)
 __host__ __device__ constexpr XcLds xc_lds_pair(int n2, int nlag) {
   const int t1 = n2, c0 = t1 + XC_NTW(n2);
-  return {t1, c0, 0, 0, sizeof(double2) * (size_t)c0 + sizeof(double) * 2 * (size_t)nlag};
+  return {t1, c0, 0, 0, 0,
+          sizeof(double2) * (size_t)c0 + sizeof(double) * 2 * (size_t)nlag};
 }
-// ccf_xcorr_ws_kernel: two images; c0 is rounded up to whole double2
+// ccf_xcorr_ws_kernel: two images; c0 and cA are rounded up to whole double2
 __host__ __device__ constexpr XcLds xc_lds_ws(int n2, int nlag, bool ratio) {
   const int t1 = 2 * n2, c0 = t1 + XC_NTW(n2), t1c = c0 + ((nlag + 1) >> 1),
-            ca = t1c + XW_NT1C;
-  return {t1, c0, t1c, ca,
-          sizeof(double2) * (size_t)ca + (ratio ? sizeof(double) * (size_t)nlag : 0)};
+            ca = t1c + XW_NT1C, lt = ca + (ratio ? (nlag + 1) >> 1 : 0);
+  return {t1, c0, t1c, ca, lt,
+          sizeof(double2) * (size_t)lt + sizeof(int32_t) * (size_t)XW_NLT};
 }
 // ccf_xcorr_ws2_kernel: four images
 __host__ __device__ constexpr XcLds xc_lds_ws2(int n2, int nlag) {
   const int t1 = 4 * n2, c0 = t1 + XC_NTW(n2);
-  return {t1, c0, 0, 0, sizeof(double2) * (size_t)c0 + sizeof(double) * 2 * (size_t)nlag};
+  return {t1, c0, 0, 0, 0,
+          sizeof(double2) * (size_t)c0 + sizeof(double) * 2 * (size_t)nlag};
 }
 // every array of a layout lies behind the one before it and inside `bytes`
 // (nimg images, nrow rows of nlag doubles at c0), for every nlag a launch can carry
@@ -77,6 +81,8 @@ __host__ __device__ constexpr bool xc_lds_fits(const XcLds &L, int n2, int nimg,
     end = D2 * (L.t1c + 72);
     if (D2 * L.ca < end) return false;
     end = D2 * L.ca + (ratio ? D * (size_t)nlag : 0);
+    if (D2 * L.lt < end) return false;
+    end = D2 * L.lt + sizeof(int32_t) * (size_t)XW_NLT;
   }
   return end <= L.bytes && L.bytes <= XC_LDS_MAX;
 }
@@ -771,10 +777,21 @@ __global__ void __launch_bounds__(XB_NT)
 // the radix-8 passes, the lag read-back and the interpolation of template t on
 // image t & 1.  Operands per (spectrum, template): 131 KB instead of 270 KB through
 // L2 -> L1.  gfx950 has one s_barrier per workgroup: both roles execute the same
-// NBAR barriers per template (after pass 0, pass 1, the folded pass [or passes 2, 3],
-// the read-back); a producer's four pair batches fall into the first four intervals,
-// each batch requested one interval ahead (in flight across a barrier -- the barrier
-// does not wait for loads).  Same formulas per bin and per butterfly as
+// NBAR barriers per template.  Folded form (nfft 8192, the lags on positions 0 / 63 of
+// the image's 64-blocks): TWO -- (A) after pass 0, the only pass in which a wave reads
+// what another wrote; pass 1 and the folded pass of wave w stay inside
+// a[512 w .. 512 w + 511] and follow each other in the wave's own LDS order; the lane
+// that holds a 64-block's sums stores the block's lags to c0 (lag table lt[], built once
+// per block from lag_pos); (B) after those stores.  The interpolation of template t runs
+// behind (B), in front of pass 0 of t + 1, and c0 is rewritten only behind (A) of t + 1.
+// A producer's four pair batches fall two in front of each barrier: image (t + 1) & 1 is
+// complete at (B) of t, which is also the last barrier in front of which a consumer
+// read image (t - 1) & 1.  Other forms: a barrier after every pass and after the lag
+// read-back (five), one batch per interval.  Each batch is requested one batch ahead
+// (in flight across a barrier -- the barrier does not wait for loads).  Measured at
+// T = 76: four barriers 32.8 ms per step, three (no barrier between pass 1 and the
+// folded pass) 31.7, two 30.4-31.0.
+// Same formulas per bin and per butterfly as
 // ccf_xcorr_kernel (outputs equal to a few ulp: the compiler fuses the products of a
 // complex multiplication its own way in each kernel).  nfft = 8192, continuum mode,
 // nlag and nvel <= 512, any T (rvs_ccf_xcorr decides; RVS_XC_WS=0: the per-pair
@@ -821,14 +838,15 @@ __device__ __forceinline__ void xw_pass(double2 *a, const double2 *T1, int p, in
 }
 
 // LOG2N = 12 (nfft 8192: passes 8,8,8,8, the last two pruned / folded) or 11 (nfft
-// 4096: passes 8,8,8,4, nothing pruned).  NBAR barriers per template: 4 (12, folded) or 5.
+// 4096: passes 8,8,8,4, nothing pruned).  NBAR barriers per template: 2 (12, folded) or 5.
 // RATIO: the mode without continuum normalisation, -c0^2 / c1 at the lags
 // (fitter_ccf.py:204-207), is not linear in the two correlations: an iteration takes ONE
 // of them -- image 2t is F_t S*, image 2t + 1 is F2_t V* (a producer forms one product
-// per bin pair and requests half the operands), the read-back of image 2t parks c0 at
-// the lags, the read-back of 2t + 1 forms -c0^2 / c1 there (the lane that parked c0[l]
-// is the one that reads it) and only then the interpolation runs.  2 T iterations, the
-// same passes, barriers and formulas per bin as ccf_xcorr_kernel's two passes.
+// per bin pair and requests half the operands), the lag stores of image 2t park c0 at
+// the lags, those of 2t + 1 form -c0^2 / c1 there (the lane that parked c0[l] is the one
+// that reads it: the lag table or pre_pos gives a lag to the same lane in every
+// iteration) and only then the interpolation runs.  2 T iterations, the same passes,
+// barriers and formulas per bin as ccf_xcorr_kernel's two passes.
 template <int LOG2N, bool RATIO>
 __global__ void __launch_bounds__(XW_NT)
     ccf_xcorr_ws_kernel(const double2 *__restrict__ work,
@@ -853,6 +871,7 @@ __global__ void __launch_bounds__(XW_NT)
   // pass 1's 64 twiddles and the folded pass's 8, side by side (xw_pass)
   double2 *T1c = fa + lds.t1c;                             // [64 + 8]
   double *cA = reinterpret_cast<double *>(fa + lds.ca);    // RATIO: c0 at the lags [nlag]
+  int32_t *lt = reinterpret_cast<int32_t *>(fa + lds.lt);  // the lag table [XW_NLT]
   const int TI = RATIO ? 2 * T : T;   // image iterations
   const int b = blockIdx.x, tid = threadIdx.x;
   const bool producer = tid >= XW_HALF;
@@ -871,7 +890,18 @@ __global__ void __launch_bounds__(XW_NT)
     const unsigned m = pmask.g;
     bad = m != 0 && !((pos8 == 0 && m == 0x01u) || (pos8 == 7 && m == 0x80u));
   }
+  if (P12 && tid < XW_NLT) lt[tid] = -1;
   const bool fold = !__syncthreads_or(bad);
+  if (P12) {
+    // the folded pass's outputs ARE the lag values: lt[4 B + 2 e + part] is the lag that
+    // reads part (re / im) of position 0 (e = 0) or 63 (e = 1) of 64-block B, so the
+    // lane that holds the sum stores it to c0 itself
+    if (fold && tid < nlag) {
+      const int p = lag_pos[tid], e = (p >> 1) & 63;
+      if (e == 0 || e == 63) lt[(((p >> 7) & 63) << 2) + (e ? 2 : 0) + (p & 1)] = tid;
+    }
+    __syncthreads();
+  }
   const double2 *Sc = work + ((int64_t)b * 2) * (n2 + 1);
   const double2 *Vc = Sc + (n2 + 1);
   typedef int v4i_t __attribute__((ext_vector_type(4)));
@@ -951,7 +981,9 @@ __global__ void __launch_bounds__(XW_NT)
         dst[0] = make_double2(xk + xm, xk - xm);
       }
     };
-    const int nbar = (P12 && fold) ? 4 : 5;
+    // folded form: two barriers per template, two batches in front of each
+    const bool two = P12 && fold;
+    const int nbar = two ? 2 : 5;
     issue(0, 0, op[0]);
     if (NPP == 2) issue(0, 1, op[1]);
     for (int it = -1; it < TI; it++) {
@@ -975,8 +1007,8 @@ __global__ void __launch_bounds__(XW_NT)
             __syncthreads();
           }
         } else {
-          // one pair batch per interval, the next one requested first (in flight
-          // across the barrier)
+          // one pair batch per interval (folded form: two), the next one requested
+          // first (in flight across the barrier)
 #pragma unroll
           for (int u = 0; u < NPP; u++) {
             if (u + 1 < NPP)
@@ -984,10 +1016,10 @@ __global__ void __launch_bounds__(XW_NT)
             else if (tn + 1 < TI)
               issue(tn + 1, 0, op[(u + 1) & 1]);
             form(dst, u, op[u & 1], tn);
-            __syncthreads();
+            if (!two || (u & 1)) __syncthreads();
           }
         }
-        for (int q = NPP; q < nbar; q++) __syncthreads();
+        for (int q = two ? NPP / 2 : NPP; q < nbar; q++) __syncthreads();
       } else {
         for (int q = 0; q < nbar; q++) __syncthreads();
       }
@@ -1000,9 +1032,13 @@ __global__ void __launch_bounds__(XW_NT)
   const int pre_lo = ilo[tvx];
   const double pre_xg = vgrid[tvx];
   const double pre_x0 = lag_vel[pre_lo], pre_x1 = lag_vel[pre_lo + 1];
+  // the four lags of the lane's 64-block (folded pass), or -1
+  typedef int v4i32_t __attribute__((ext_vector_type(4)));
+  v4i32_t lag = {-1, -1, -1, -1};
+  if (P12) lag = reinterpret_cast<const v4i32_t *>(lt)[pt >> 3];
   for (int it = -1; it < TI; it++) {
     if (it < 0) {
-      const int nbar = (P12 && fold) ? 4 : 5;
+      const int nbar = (P12 && fold) ? 2 : 5;
       for (int q = 0; q < nbar; q++) __syncthreads();
       continue;
     }
@@ -1013,20 +1049,14 @@ __global__ void __launch_bounds__(XW_NT)
     if (pt < (n2 >> 3)) xw_pass<1, LOG2N>(a, T1, 0, pt);
     __syncthreads();
     if (pt < (n2 >> 3)) xw_pass<1, LOG2N>(a, T1, 1, pt, P12 ? T1c : nullptr);
-    __syncthreads();
-    if (!P12) {
-      // nfft 4096: a third radix-8 pass (M = 32) and the radix-4 pass (M = 4)
-      if (pt < (n2 >> 3)) xw_pass<1, LOG2N>(a, T1, 2, pt);
-      __syncthreads();
-      {
-        const int base = pt << 2;
-        double2 v0 = a[base], v1 = a[base + 1], v2 = a[base + 2], v3 = a[base + 3];
-        dft4<1>(v0, v1, v2, v3);
-        a[base] = v0, a[base + 1] = v1, a[base + 2] = v2, a[base + 3] = v3;
-      }
-      __syncthreads();
-    } else if (fold) {
-      // the last two passes as one (fft_lds): eight lanes per 64-block
+    if (P12 && fold) {
+      // pass 1 and the folded pass of wave w touch a[512 w .. 512 w + 511] only: the
+      // wave's own in-order LDS queue orders them, the compiler must not
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      // the last two passes as one (fft_lds): eight lanes per 64-block, whose lane 0
+      // stores the block's lags (RATIO: parks c0 in cA, then forms -c0^2 / c1 from it)
       const int s = pt & 7;
       const int B = pt >> 3;   // n2 / 64 = 64 blocks: one trip
       const unsigned m0 = pmask.b0 & 1u, m63 = pmask.b7 >> 7;
@@ -1044,70 +1074,94 @@ __global__ void __launch_bounds__(XW_NT)
           x += dpp_get<0x141, 0xf, 0xf>(x);   // row_half_mirror
           return x;
         };
+        auto put = [&](int l, double x) {
+          if (l < 0) return;
+          const double c = x * inv_n;
+          if (!RATIO)
+            c0[l] = c;
+          else if (it & 1)
+            c0[l] = -cA[l] * cA[l] / c;
+          else
+            cA[l] = c;
+        };
         if (m0) {
           x0.x = sum8(x0.x);
           x0.y = sum8(x0.y);
-          if (s == 0) a[B * 64] = x0;
+          if (s == 0) put(lag.x, x0.x), put(lag.y, x0.y);
         }
         if (m63) {
           x63.x = sum8(x63.x);
           x63.y = sum8(x63.y);
-          if (s == 0) a[B * 64 + 63] = x63;
+          if (s == 0) put(lag.z, x63.x), put(lag.w, x63.y);
         }
       }
       __syncthreads();
     } else {
-      {   // pass 2 (M = 64, Mp = 8): selected outputs only
-        const int blk = pt >> 3, r = pt & 7, base = (blk << 6) + r;
-        const unsigned mask = prune[blk];
-        if (mask != 0) {
-          double2 v[8];
-#pragma unroll
-          for (int j = 0; j < 8; j++) v[j] = a[base + 8 * j];
-          dft8<1>(v);
-          double2 wp[8];
-          wp[0] = make_double2(1.0, 0.0);
-          wp[1] = T1[r << (log2n + 1 - 6 - 1)];
-          wp[2] = cmul(wp[1], wp[1]);
-          wp[3] = cmul(wp[2], wp[1]);
-          wp[4] = cmul(wp[2], wp[2]);
-          wp[7] = cmul(wp[4], wp[3]);
-          wp[5] = cmul(wp[4], wp[1]);
-          wp[6] = cmul(wp[4], wp[2]);
-#pragma unroll
-          for (int q = 0; q < 8; q++)
-            if (mask & (1u << q))
-              a[base + 8 * q] = (q == 0) ? v[0] : cmul(v[q], wp[q]);
-        }
-      }
       __syncthreads();
-      {   // pass 3 (M = 8): no twiddles
-        const unsigned mask = pmask.g;
-        if (mask != 0) {
-          const int base = pt << 3;
-          double2 v[8];
-#pragma unroll
-          for (int j = 0; j < 8; j++) v[j] = a[base + j];
-          dft8<1>(v);
-#pragma unroll
-          for (int q = 0; q < 8; q++)
-            if (mask & (1u << q)) a[base + q] = v[q];
+      if (!P12) {
+        // nfft 4096: a third radix-8 pass (M = 32) and the radix-4 pass (M = 4)
+        if (pt < (n2 >> 3)) xw_pass<1, LOG2N>(a, T1, 2, pt);
+        __syncthreads();
+        {
+          const int base = pt << 2;
+          double2 v0 = a[base], v1 = a[base + 1], v2 = a[base + 2], v3 = a[base + 3];
+          dft4<1>(v0, v1, v2, v3);
+          a[base] = v0, a[base + 1] = v1, a[base + 2] = v2, a[base + 3] = v3;
         }
+        __syncthreads();
+      } else {
+        {   // pass 2 (M = 64, Mp = 8): selected outputs only
+          const int blk = pt >> 3, r = pt & 7, base = (blk << 6) + r;
+          const unsigned mask = prune[blk];
+          if (mask != 0) {
+            double2 v[8];
+  #pragma unroll
+            for (int j = 0; j < 8; j++) v[j] = a[base + 8 * j];
+            dft8<1>(v);
+            double2 wp[8];
+            wp[0] = make_double2(1.0, 0.0);
+            wp[1] = T1[r << (log2n + 1 - 6 - 1)];
+            wp[2] = cmul(wp[1], wp[1]);
+            wp[3] = cmul(wp[2], wp[1]);
+            wp[4] = cmul(wp[2], wp[2]);
+            wp[7] = cmul(wp[4], wp[3]);
+            wp[5] = cmul(wp[4], wp[1]);
+            wp[6] = cmul(wp[4], wp[2]);
+  #pragma unroll
+            for (int q = 0; q < 8; q++)
+              if (mask & (1u << q))
+                a[base + 8 * q] = (q == 0) ? v[0] : cmul(v[q], wp[q]);
+          }
+        }
+        __syncthreads();
+        {   // pass 3 (M = 8): no twiddles
+          const unsigned mask = pmask.g;
+          if (mask != 0) {
+            const int base = pt << 3;
+            double2 v[8];
+  #pragma unroll
+            for (int j = 0; j < 8; j++) v[j] = a[base + j];
+            dft8<1>(v);
+  #pragma unroll
+            for (int q = 0; q < 8; q++)
+              if (mask & (1u << q)) a[base + q] = v[q];
+          }
+        }
+        __syncthreads();
+      }
+      if (RATIO) {
+        if (pt < nlag) {
+          const double c = reinterpret_cast<const double *>(a)[pre_pos] * inv_n;
+          if (it & 1)
+            c0[pt] = -cA[pt] * cA[pt] / c;
+          else
+            cA[pt] = c;
+        }
+      } else if (pt < nlag) {
+        c0[pt] = reinterpret_cast<const double *>(a)[pre_pos] * inv_n;
       }
       __syncthreads();
     }
-    if (RATIO) {
-      if (pt < nlag) {
-        const double c = reinterpret_cast<const double *>(a)[pre_pos] * inv_n;
-        if (it & 1)
-          c0[pt] = -cA[pt] * cA[pt] / c;
-        else
-          cA[pt] = c;
-      }
-    } else if (pt < nlag) {
-      c0[pt] = reinterpret_cast<const double *>(a)[pre_pos] * inv_n;
-    }
-    __syncthreads();
     if ((!RATIO || (it & 1)) && pt < nvel) {
       const double sl = (c0[pre_lo + 1] - c0[pre_lo]) / (pre_x1 - pre_x0);
       const double val = sl * (pre_xg - pre_x0) + c0[pre_lo];

@@ -16,13 +16,32 @@
 // has seen as an upper bound (active sets only shrink) and refreshes that bound
 // every few rounds.  List entries beyond the live count are padded with a copy
 // of entry 0, so the objective kernels in between can run the full bound.
-// rvs_nm_run (below) runs the same rounds from C, with the bookkeeping between two
-// objective kernels in one kernel; the stand-alone entry points are its reference.
 //
 // The branch structure, constants (rho=1, chi=2, psi=0.5, sigma=0.5), stable
 // vertex ordering (NaN last) and the order of the floating-point operations
 // follow scipy/optimize/_optimize.py::_minimize_neldermead, the same as
 // tests/refmachines/neldermead_torch.py (which tests/ checks against scipy itself).
+//
+// A round exists in four forms, which leave the same state to the bit:
+//   stand-alone  nm_begin / nm_decide / nm_update_kernel: the entry points above
+//   one block    nm_glue_begin / decide / update_kernel: rvs_nm_run, the bookkeeping
+//                between two objective kernels (and their sum over the arms) in one
+//   rows + pack  nm_glue_*_rows_kernel + nm_glue_*_pack_kernel: the same on as many
+//                blocks as there are rows, the ordered compaction behind it
+//   one launch   nm_glue_spec_prep / spec_kernel: all four candidate points of a
+//                step evaluated together, one bookkeeping kernel per round
+// and every part of the step is stated once, for all of them:
+//   nm_case, nm_centroid, nm_point, nm_take   scipy's scalar decisions and points
+//   nm_with_N                    N as a compile-time constant (the simplex in registers)
+//   nm_may_step, nm_test_regs    flags and iteration count, termination test,
+//                                reflection point: does the simplex step next round
+//   nm_accept_regs               new point -> row N, order, store
+//   nm_decide_row, nm_update_row what decide and update do for one row; glue_*_row
+//                                add the value of the evaluation and the next test
+//   nm_compact_rows, nm_pad_tail the rows that go on, in order, listed and mapped
+// The forms differ in where a row's second value comes from, where the parked count
+// is added and where a row's point waits (registers, or its own row of X1 / X2).
+#include <type_traits>
 #include "common.h"
 #include "objective_sum.h"
 #include "nm_internal.h"
@@ -61,16 +80,176 @@ __device__ __forceinline__ int block_excl_scan(int flag, int *total,
   return off + pre;
 }
 
-// stable insertion sort of the N+1 vertices by f (NaN last), np.argsort order.
-// The simplex is pulled into registers first (N is a template parameter, all
-// loops unroll): sorting it in place in global memory is a chain of ~50
-// dependent loads/stores, which made the bookkeeping kernels latency-bound.
+// ---------------------------------------------------------------------------
+// vel_fit.ParamMapper.forward + the range / finiteness guard of chisq_func +
+// VSiniMapper.to_vsini + the Normal priors of chisq_func0 (vel_fit.py:95-254)
+// for J rows of the optimiser's parameter vectors.
+//   X [J, n]: (vel, [vsini], free stellar parameters in specParams order)
+//   src [ndim]: column of X feeding stellar parameter i, or -1 = fixed
+//   fixed [S, ndim], vsini_fixed [S] (used when vsini_col < 0, nullable = no
+//   rotation), prior_mean / prior_isig [S, ndim] (nullable; isig 0 = no prior)
+// out: job_spec[j] = list[j], vel, vsini (nullable), params [J, ndim],
+//      extra[j] = vsini penalty + priors, bad[j] (row answered with 1e30; its
+//      vel/params are replaced by vel 0 / the fixed+start values `safe`)
+// ---------------------------------------------------------------------------
+struct MapSrc {
+  int src[NM_MAXN];
+};
+
+// vel_fit.chisq_func's parameter mapping for ONE row: the optimiser's vector x of
+// simplex r -> (velocity, vsini, template parameters, prior penalty, bad flag) of job j
+struct MapP {
+  int n, ndim, vsini_col;
+  MapSrc M;
+  const double *fixed, *vsini_fixed, *safe, *prior_mean, *prior_isig;
+  double min_vel, max_vel, max_vsini;
+  int32_t *job_spec;
+  double *vel, *vsini, *params, *extra;
+  int32_t *bad;
+};
+
+// entry idx of a vector that lives in registers (a chain of selects; each entry
+// through a register first, or the compiler turns the chain into a load at a selected
+// offset and the vector into scratch memory: template_dev.h sel_dim)
+__device__ __forceinline__ double nm_pick(const double *x, int idx) {
+  double v = x[0];
+#pragma unroll
+  for (int i = 1; i < NM_MAXN; i++) {
+    double xi = x[i];
+    asm volatile("" : "+v"(xi));
+    v = (idx == i) ? xi : v;
+  }
+  return v;
+}
+
+// (x: the row in the caller's registers, NM_MAXN entries of which P.n count)
+__device__ __forceinline__ void map_row_regs(const MapP &P, int j, int r,
+                                             const double *x) {
+  const int ndim = P.ndim;
+  double v = x[0];
+  double pen = 0;
+  if (P.vsini) {
+    double vs;
+    if (P.vsini_col >= 0) {
+      const double v0 = nm_pick(x, P.vsini_col);
+      vs = fmin(fmax(v0, 0.0), P.max_vsini);  // np.clip
+      if (v0 < 0 || v0 > P.max_vsini) pen += (vs - v0) * (vs - v0);
+      if (v0 != v0) vs = v0;
+    } else {
+      vs = P.vsini_fixed[r];
+    }
+    P.vsini[j] = vs;
+  }
+  bool isbad = (v > P.max_vel) || (v < P.min_vel);
+  double p[NM_MAXN];
+#pragma unroll
+  for (int i = 0; i < NM_MAXN; i++) {   // (p[] in registers: static indices)
+    if (i >= ndim) break;
+    p[i] = (P.M.src[i] >= 0) ? nm_pick(x, P.M.src[i]) : P.fixed[(int64_t)r * ndim + i];
+    if (!(fabs(p[i]) <= 1.79e308)) isbad = true;
+  }
+  if (isbad) {
+    v = 0;
+#pragma unroll
+    for (int i = 0; i < NM_MAXN; i++)
+      if (i < ndim) p[i] = P.safe[(int64_t)r * ndim + i];
+  }
+  if (P.prior_mean)
+#pragma unroll
+    for (int i = 0; i < NM_MAXN; i++) {
+      if (i >= ndim) break;
+      const double d = (P.prior_mean[(int64_t)r * ndim + i] - p[i]) *
+                       P.prior_isig[(int64_t)r * ndim + i];
+      pen += d * d;
+    }
+  P.job_spec[j] = r;
+  P.vel[j] = v;
+#pragma unroll
+  for (int i = 0; i < NM_MAXN; i++)
+    if (i < ndim) P.params[(int64_t)j * ndim + i] = p[i];
+  P.extra[j] = pen;
+  P.bad[j] = isbad ? 1 : 0;
+}
+
+// row i < N of x (memory) <-> xr (registers: no indexing by a loop variable)
+__device__ __forceinline__ void nm_get_row(double *xr, const double *x, int N) {
+#pragma unroll
+  for (int i = 0; i < NM_MAXN; i++) xr[i] = (i < N) ? x[i] : 0.0;
+}
+__device__ __forceinline__ void nm_put_row(double *x, const double *xr, int N) {
+#pragma unroll
+  for (int i = 0; i < NM_MAXN; i++)
+    if (i < N) x[i] = xr[i];
+}
+
+// ---------------------------------------------------------------------------
+// scipy's step, every part once
+// ---------------------------------------------------------------------------
+
+// body(std::integral_constant<int, N>): the simplex of N + 1 vertices in registers
+// needs N at compile time (all loops unroll, all indices are static)
+template <typename BODY>
+__device__ __forceinline__ void nm_with_N(int N, BODY body) {
+  switch (N) {
+    case 1: body(std::integral_constant<int, 1>()); break;
+    case 2: body(std::integral_constant<int, 2>()); break;
+    case 3: body(std::integral_constant<int, 3>()); break;
+    case 4: body(std::integral_constant<int, 4>()); break;
+    case 5: body(std::integral_constant<int, 5>()); break;
+    case 6: body(std::integral_constant<int, 6>()); break;
+    case 7: body(std::integral_constant<int, 7>()); break;
+    default: body(std::integral_constant<int, 8>()); break;
+  }
+}
+
+// the case of a step from the value of the reflection point and the ordered values of
+// the simplex: 0 accept reflection, 1 expansion, 2 outside contraction, 3 inside
+__device__ __forceinline__ int nm_case(double fxr, double f0, double fn1, double fn) {
+  if (fxr < f0) return 1;
+  if (fxr < fn1) return 0;
+  if (fxr < fn) return 2;
+  return 3;
+}
+
+// one coordinate of the centroid of the N best vertices (v(k): that coordinate of
+// vertex k): the sum in vertex order, then / N
+template <typename V>
+__device__ __forceinline__ double nm_centroid(int N, V v) {
+  double xb = v(0);
+  for (int k = 1; k < N; k++) xb = xb + v(k);
+  return xb / N;
+}
+
+// one coordinate of the point of case c (0: the reflection point) from the centroid xb
+// and the worst vertex w, scipy's expressions
+__device__ __forceinline__ double nm_point(int c, double xb, double w) {
+  if (c == 0) return (1 + 1.0) * xb - 1.0 * w;
+  if (c == 1) return (1 + 1.0 * 2.0) * xb - 1.0 * 2.0 * w;
+  if (c == 2) return (1 + 0.5 * 1.0) * xb - 0.5 * 1.0 * w;
+  return (1 - 0.5) * xb + 0.5 * w;
+}
+
+// which point replaces the worst vertex (fxr: value of the reflection point, f2: of the
+// second point of case c, fn: the worst vertex's), or none: the simplex must shrink
+enum { NM_SHRINK, NM_TAKE_R, NM_TAKE_2 };
+__device__ __forceinline__ int nm_take(int c, double fxr, double f2, double fn) {
+  if (c == 0) return NM_TAKE_R;
+  if (c == 1) return (f2 < fxr) ? NM_TAKE_2 : NM_TAKE_R;
+  if (c == 2) return (f2 <= fxr) ? NM_TAKE_2 : NM_SHRINK;
+  return (f2 < fn) ? NM_TAKE_2 : NM_SHRINK;
+}
+
+// The simplex is pulled into registers (N is a template parameter, all loops unroll):
+// sorting it in place in global memory is a chain of ~50 dependent loads/stores, which
+// made the bookkeeping kernels latency-bound.
 template <int N>
 __device__ __forceinline__ void nm_load_regs(const double *__restrict__ gs,
                                              const double *__restrict__ gf,
-                                             double (&s)[N + 1][N], double (&f)[N + 1]) {
+                                             double (&s)[N + 1][N], double (&f)[N + 1],
+                                             int rows = N + 1) {
 #pragma unroll
   for (int a = 0; a <= N; a++) {
+    if (a >= rows) break;
     f[a] = gf[a];
 #pragma unroll
     for (int i = 0; i < N; i++) s[a][i] = gs[a * N + i];
@@ -89,6 +268,7 @@ __device__ __forceinline__ void nm_store_regs(double *gs, double *gf,
   }
 }
 
+// stable insertion sort of the N+1 vertices by f (NaN last), np.argsort order
 template <int N>
 __device__ __forceinline__ void nm_sort_regs(double (&s)[N + 1][N], double (&f)[N + 1]) {
 #pragma unroll
@@ -125,31 +305,54 @@ __device__ __forceinline__ void nm_sort_regs(double (&s)[N + 1][N], double (&f)[
   }
 }
 
+// the simplex at (gs, gf) ordered in place (after a shrink: all values are new)
+__device__ void nm_order(double *gs, double *gf, int N) {
+  nm_with_N(N, [&](auto n) {
+    constexpr int NN = decltype(n)::value;
+    double s[NN + 1][NN], f[NN + 1];
+    nm_load_regs<NN>(gs, gf, s, f);
+    nm_sort_regs<NN>(s, f);
+    nm_store_regs<NN>(gs, gf, s, f);
+  });
+}
+
+// The accepted point (src, fnew) becomes row N of the simplex at (gs, gf), the rows are
+// ordered and stored; s, f stay with the caller, so that the next round's test and
+// points come off the same registers -- the same operations on the same values as the
+// steps through memory (store row N; load, sort, store; load, test), two round trips
+// shorter.
 template <int N>
-__device__ void nm_order_t(double *gsim, double *gf) {
-  double s[N + 1][N], f[N + 1];
-  nm_load_regs<N>(gsim, gf, s, f);
+__device__ __forceinline__ void nm_accept_regs(double *gs, double *gf,
+                                               const double *__restrict__ src,
+                                               double fnew, double (&s)[N + 1][N],
+                                               double (&f)[N + 1]) {
+  nm_load_regs<N>(gs, gf, s, f, N);
+#pragma unroll
+  for (int i = 0; i < N; i++) s[N][i] = src[i];
+  f[N] = fnew;
   nm_sort_regs<N>(s, f);
-  nm_store_regs<N>(gsim, gf, s, f);
+  nm_store_regs<N>(gs, gf, s, f);
 }
 
-__device__ void nm_order(double *sim, double *f, int N) {
-  switch (N) {
-    case 1: nm_order_t<1>(sim, f); break;
-    case 2: nm_order_t<2>(sim, f); break;
-    case 3: nm_order_t<3>(sim, f); break;
-    case 4: nm_order_t<4>(sim, f); break;
-    case 5: nm_order_t<5>(sim, f); break;
-    case 6: nm_order_t<6>(sim, f); break;
-    case 7: nm_order_t<7>(sim, f); break;
-    default: nm_order_t<8>(sim, f); break;
+// May simplex r, after `nit` iterations, step in the coming round?  Not when it is
+// not active or a shrink is pending; at maxiter it stops (scipy: the while-condition
+// fails -> warnflag 2).
+__device__ __forceinline__ bool nm_may_step(int32_t *flags, int r, int nit,
+                                            int maxiter) {
+  const int fl = flags[r];
+  if ((fl & 5) != 1) return false;
+  if (nit >= maxiter) {
+    flags[r] = fl & ~1;
+    return false;
   }
+  return true;
 }
 
-// termination test and reflection point of one simplex, all loads up front
-// (N compile-time); returns 1 when converged
+// ... and does it?  scipy's termination test on the ordered simplex: converged
+// (success) -> flags, 0; else 1 and xr = its reflection point
 template <int N>
-__device__ __forceinline__ int nm_test_regs(const double (&s)[N + 1][N],
+__device__ __forceinline__ int nm_test_regs(int32_t *flags, int r,
+                                            const double (&s)[N + 1][N],
                                             const double (&f)[N + 1], double xatol,
                                             double fatol, double *xr) {
   double dx = 0, df = 0;
@@ -165,28 +368,130 @@ __device__ __forceinline__ int nm_test_regs(const double (&s)[N + 1][N],
     if (f[k] != f[k]) anynan = true;
   }
   // NaN propagates like np.max: a NaN difference never passes the test
-  if (!anynan && dx <= xatol && df <= fatol) return 1;
+  if (!anynan && dx <= xatol && df <= fatol) {
+    flags[r] = (flags[r] & ~1) | 2;
+    return 0;
+  }
+#pragma unroll
+  for (int i = 0; i < N; i++)
+    xr[i] = nm_point(0, nm_centroid(N, [&](int k) { return s[k][i]; }), s[N][i]);
+  return 1;
+}
+
+// the three other points a step can ask for (cases 1, 2, 3) -> xc
+template <int N>
+__device__ __forceinline__ void nm_other_points(const double (&s)[N + 1][N],
+                                                double (*xc)[NM_MAXN]) {
 #pragma unroll
   for (int i = 0; i < N; i++) {
-    double xb = s[0][i];
-#pragma unroll
-    for (int k = 1; k < N; k++) xb = xb + s[k][i];
-    xb = xb / N;
-    xr[i] = (1 + 1.0) * xb - 1.0 * s[N][i];
+    const double xb = nm_centroid(N, [&](int k) { return s[k][i]; });
+    xc[0][i] = nm_point(1, xb, s[N][i]);
+    xc[1][i] = nm_point(2, xb, s[N][i]);
+    xc[2][i] = nm_point(3, xb, s[N][i]);
   }
-  return 0;
 }
 
+// begin, one row: does simplex r step this round (xr = its reflection point)?  The
+// simplex is read only when its flags let it through.
+__device__ __forceinline__ int nm_begin_row(int N, const double *__restrict__ sim,
+                                            const double *__restrict__ fsim,
+                                            const int32_t *__restrict__ nit,
+                                            int32_t *flags, int r, int maxiter,
+                                            double xatol, double fatol, double *xr) {
+  if (!nm_may_step(flags, r, nit[r], maxiter)) return 0;
+  int go = 0;
+  nm_with_N(N, [&](auto n) {
+    constexpr int NN = decltype(n)::value;
+    double s[NN + 1][NN], f[NN + 1];
+    nm_load_regs<NN>(sim + (int64_t)r * (NN + 1) * NN, fsim + (int64_t)r * (NN + 1), s, f);
+    go = nm_test_regs<NN>(flags, r, s, f, xatol, fatol, xr);
+  });
+  return go;
+}
+
+// decide, one row: case c of the simplex at gs (memory: N at run time, one vertex at a
+// time) -> *case_j; the second point the case asks for -> x2 (registers: static
+// indices); returns 1 when there is one
+__device__ __forceinline__ int nm_decide_row(int N, const double *__restrict__ gs, int c,
+                                             int32_t *case_j, double *x2) {
+  *case_j = c;
+  if (c == 0) return 0;
+#pragma unroll
+  for (int i = 0; i < NM_MAXN; i++) {
+    if (i >= N) break;
+    x2[i] = nm_point(c, nm_centroid(N, [&](int k) { return gs[k * N + i]; }),
+                     gs[N * N + i]);
+  }
+  return 1;
+}
+
+// update, one row: the point that is taken (xr or x2, values fxr / f2; nfev as scipy
+// counts) accepted into the simplex at (gs, gf), one iteration more: returns the new
+// iteration count (>= 1; s, f = the ordered simplex), or 0 = the simplex must shrink
 template <int N>
-__device__ __forceinline__ int nm_begin_row(const double *__restrict__ gs,
-                                            const double *__restrict__ gf,
-                                            double xatol, double fatol,
-                                            double *xr) {
-  double s[N + 1][N], f[N + 1];
-  nm_load_regs<N>(gs, gf, s, f);
-  return nm_test_regs<N>(s, f, xatol, fatol, xr);
+__device__ __forceinline__ int nm_update_row(double *gs, double *gf, int32_t *nit_r,
+                                             int32_t *nfev_r, int c, double fxr,
+                                             double f2, double fn, const double *xr,
+                                             const double *x2, double (&s)[N + 1][N],
+                                             double (&f)[N + 1]) {
+  const int take = nm_take(c, fxr, f2, fn);
+  *nfev_r += (c == 0) ? 1 : 2;
+  if (take == NM_SHRINK) return 0;
+  const bool take2 = (take == NM_TAKE_2);
+  nm_accept_regs<N>(gs, gf, take2 ? x2 : xr, take2 ? f2 : fxr, s, f);
+  const int nit = *nit_r + 1;
+  *nit_r = nit;
+  return nit;
 }
 
+// The rows j < J that go on move, in order, to the front of (list, X) and are mapped
+// (P: nullable): row(j, r, x) says whether row j goes on, and if so leaves its simplex
+// and its point (registers).  pos_out[j] = the row's new position or -1 (nullable).
+// One block of NT threads, trips of NT rows; returns the count.  A row's new position is
+// at or before j: whatever row() reads of the rows of its trip and of later rows is
+// read before a position is written, provided the values are in registers by then.
+template <int NT, typename ROW>
+__device__ __forceinline__ int nm_compact_rows(const MapP *P, int N, int J, ROW row,
+                                               int32_t *list, double *X,
+                                               int32_t *pos_out,
+                                               int *sh /*[NT/64 + 1]*/) {
+  int base_out = 0;
+  for (int j0 = 0; j0 < J; j0 += NT) {
+    const int j = j0 + threadIdx.x;
+    int go = 0, r = 0;
+    double x[NM_MAXN] = {};
+    if (j < J) go = row(j, r, x);
+    int tot;
+    const int pos = base_out + block_excl_scan<NT>(go, &tot, sh);
+    if (pos_out && j < J) pos_out[j] = go ? pos : -1;
+    if (go) {
+      list[pos] = r;
+      nm_put_row(X + (int64_t)pos * N, x, N);
+      if (P) map_row_regs(*P, pos, r, x);
+    }
+    base_out += tot;
+  }
+  return base_out;
+}
+
+// entries [max(n, 1), jbound) of (list, X) <- a copy of entry 0 (simplex 0's best
+// vertex when the list is empty)
+__device__ __forceinline__ void nm_pad_tail(int n, int jbound, int N, int32_t *list,
+                                            double *X, const double *sim) {
+  if (n == 0 && threadIdx.x == 0) {
+    list[0] = 0;
+    for (int i = 0; i < N; i++) X[i] = sim[i];
+  }
+  __syncthreads();
+  for (int j = max(n, 1) + threadIdx.x; j < jbound; j += NM_NT) {
+    list[j] = list[0];
+    for (int i = 0; i < N; i++) X[(int64_t)j * N + i] = X[i];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The stand-alone round
+// ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(NM_NT)
     nm_begin_kernel(int S, int N, double xatol, double fatol, int maxiter,
                     const double *__restrict__ sim,
@@ -195,60 +500,21 @@ __global__ void __launch_bounds__(NM_NT)
                     int32_t *__restrict__ list1, double *__restrict__ X1,
                     int32_t *__restrict__ counts, int jbound) {
   __shared__ int sh[NM_NT / 64 + 1];
-  int base_out = 0;
-  for (int r0 = 0; r0 < S; r0 += NM_NT) {
-    const int r = r0 + threadIdx.x;
-    int go = 0;
-    double xr[NM_MAXN];
-    if (r < S && (flags[r] & 5) == 1) {  // active and no shrink pending
-      const double *s = sim + (int64_t)r * (N + 1) * N;
-      const double *f = fsim + (int64_t)r * (N + 1);
-      if (nit[r] >= maxiter) {
-        flags[r] &= ~1;  // scipy: while-condition fails -> warnflag 2
-      } else {
-        int conv = 0;
-        switch (N) {
-          case 1: conv = nm_begin_row<1>(s, f, xatol, fatol, xr); break;
-          case 2: conv = nm_begin_row<2>(s, f, xatol, fatol, xr); break;
-          case 3: conv = nm_begin_row<3>(s, f, xatol, fatol, xr); break;
-          case 4: conv = nm_begin_row<4>(s, f, xatol, fatol, xr); break;
-          case 5: conv = nm_begin_row<5>(s, f, xatol, fatol, xr); break;
-          case 6: conv = nm_begin_row<6>(s, f, xatol, fatol, xr); break;
-          case 7: conv = nm_begin_row<7>(s, f, xatol, fatol, xr); break;
-          default: conv = nm_begin_row<8>(s, f, xatol, fatol, xr); break;
-        }
-        if (conv)
-          flags[r] = (flags[r] & ~1) | 2;  // converged: success
-        else
-          go = 1;
-      }
-    }
-    int tot;
-    const int pos = base_out + block_excl_scan(go, &tot, sh);
-    if (go) {
-      list1[pos] = r;
-      for (int i = 0; i < N; i++) X1[(int64_t)pos * N + i] = xr[i];
-    }
-    base_out += tot;
-  }
+  const int n = nm_compact_rows<NM_NT>(
+      nullptr, N, S,
+      [&](int j, int &r, double *xr) {
+        r = j;
+        return nm_begin_row(N, sim, fsim, nit, flags, j, maxiter, xatol, fatol, xr);
+      },
+      list1, X1, nullptr, sh);
   __syncthreads();
   if (threadIdx.x == 0) {
-    counts[0] = base_out;
-    counts[3] = base_out;
+    counts[0] = n;
+    counts[3] = n;
   }
-  // pad the unused tail with a copy of entry 0 (or simplex 0's best vertex)
-  if (base_out == 0 && threadIdx.x == 0) {
-    list1[0] = 0;
-    for (int i = 0; i < N; i++) X1[i] = sim[i];
-  }
-  __syncthreads();
-  for (int j = max(base_out, 1) + threadIdx.x; j < jbound; j += NM_NT) {
-    list1[j] = list1[0];
-    for (int i = 0; i < N; i++) X1[(int64_t)j * N + i] = X1[i];
-  }
+  nm_pad_tail(n, jbound, N, list1, X1, sim);
 }
 
-// cases: 0 accept reflection, 1 expansion, 2 outside contraction, 3 inside
 __global__ void __launch_bounds__(NM_NT)
     nm_decide_kernel(int N, const double *__restrict__ sim,
                      const double *__restrict__ fsim,
@@ -259,63 +525,18 @@ __global__ void __launch_bounds__(NM_NT)
                      int jbound) {
   __shared__ int sh[NM_NT / 64 + 1];
   const int J = min(counts[0], jbound);
-  int base_out = 0;
-  for (int j0 = 0; j0 < J; j0 += NM_NT) {
-    const int j = j0 + threadIdx.x;
-    int go = 0;
-    double x2[NM_MAXN];
-    int r = 0;
-    if (j < J) {
-      r = list1[j];
-      const double *s = sim + (int64_t)r * (N + 1) * N;
-      const double *f = fsim + (int64_t)r * (N + 1);
-      const double fxr = F1[j];
-      int c;
-      if (fxr < f[0])
-        c = 1;
-      else if (fxr < f[N - 1])
-        c = 0;
-      else if (fxr < f[N])
-        c = 2;
-      else
-        c = 3;
-      cases[j] = c;
-      if (c != 0) {
-        go = 1;
-        for (int i = 0; i < N; i++) {
-          double xb = s[i];
-          for (int k = 1; k < N; k++) xb = xb + s[k * N + i];
-          xb = xb / N;
-          const double w = s[N * N + i];
-          if (c == 1)
-            x2[i] = (1 + 1.0 * 2.0) * xb - 1.0 * 2.0 * w;
-          else if (c == 2)
-            x2[i] = (1 + 0.5 * 1.0) * xb - 0.5 * 1.0 * w;
-          else
-            x2[i] = (1 - 0.5) * xb + 0.5 * w;
-        }
-      }
-    }
-    int tot;
-    const int pos = base_out + block_excl_scan(go, &tot, sh);
-    if (j < J) pos2[j] = go ? pos : -1;
-    if (go) {
-      list2[pos] = r;
-      for (int i = 0; i < N; i++) X2[(int64_t)pos * N + i] = x2[i];
-    }
-    base_out += tot;
-  }
+  const int n = nm_compact_rows<NM_NT>(
+      nullptr, N, J,
+      [&](int j, int &r, double *x2) {
+        r = list1[j];
+        const double *f = fsim + (int64_t)r * (N + 1);
+        return nm_decide_row(N, sim + (int64_t)r * (N + 1) * N,
+                             nm_case(F1[j], f[0], f[N - 1], f[N]), &cases[j], x2);
+      },
+      list2, X2, pos2, sh);
   __syncthreads();
-  if (threadIdx.x == 0) counts[1] = base_out;
-  if (base_out == 0 && threadIdx.x == 0) {
-    list2[0] = 0;
-    for (int i = 0; i < N; i++) X2[i] = sim[i];
-  }
-  __syncthreads();
-  for (int j = max(base_out, 1) + threadIdx.x; j < jbound; j += NM_NT) {
-    list2[j] = list2[0];
-    for (int i = 0; i < N; i++) X2[(int64_t)j * N + i] = X2[i];
-  }
+  if (threadIdx.x == 0) counts[1] = n;
+  nm_pad_tail(n, jbound, N, list2, X2, sim);
 }
 
 __global__ void __launch_bounds__(NM_NT)
@@ -331,49 +552,31 @@ __global__ void __launch_bounds__(NM_NT)
                      int32_t *__restrict__ counts, int jbound) {
   __shared__ int sh[NM_NT / 64 + 1];
   const int J = min(counts[0], jbound);
-  int base_out = 0;
+  int parked = 0;
   for (int j0 = 0; j0 < J; j0 += NM_NT) {
     const int j = j0 + threadIdx.x;
-    int go = 0, r = 0;
+    int go = 0;
     if (j < J) {
-      r = list1[j];
-      double *s = sim + (int64_t)r * (N + 1) * N;
-      double *f = fsim + (int64_t)r * (N + 1);
-      const int c = cases[j];
-      const double fxr = F1[j];
+      const int r = list1[j];
+      double *gf = fsim + (int64_t)r * (N + 1);
       const int p2 = pos2[j];
       const double f2 = (p2 >= 0) ? F2[p2] : __builtin_inf();
-      bool take2 = false, taker = false;
-      if (c == 0)
-        taker = true;
-      else if (c == 1) {
-        if (f2 < fxr)
-          take2 = true;
-        else
-          taker = true;
-      } else if (c == 2)
-        take2 = (f2 <= fxr);
-      else
-        take2 = (f2 < f[N]);
-      nfev[r] += (c == 0) ? 1 : 2;
-      if (take2 || taker) {
-        const double *src = take2 ? (X2 + (int64_t)p2 * N) : (X1 + (int64_t)j * N);
-        for (int i = 0; i < N; i++) s[N * N + i] = src[i];
-        f[N] = take2 ? f2 : fxr;
-        nm_order(s, f, N);
-        nit[r] += 1;
-      } else {
-        go = 1;  // shrink: parked (flag bit 2) until the host runs the shrink
-      }
+      nm_with_N(N, [&](auto n) {
+        constexpr int NN = decltype(n)::value;
+        double s[NN + 1][NN], f[NN + 1];
+        go = !nm_update_row<NN>(sim + (int64_t)r * (NN + 1) * NN, gf, &nit[r], &nfev[r],
+                                cases[j], F1[j], f2, gf[NN], X1 + (int64_t)j * NN,
+                                X2 + (int64_t)p2 * NN, s, f);
+      });
+      // shrink: parked (flag bit 2) until the host runs the shrink
+      if (go) flags[r] |= 4;
     }
     int tot;
-    const int pos = base_out + block_excl_scan(go, &tot, sh);
-    if (go) flags[r] |= 4;
-    (void)pos;
-    base_out += tot;
+    block_excl_scan(go, &tot, sh);
+    parked += tot;
   }
   __syncthreads();
-  if (threadIdx.x == 0) counts[4] += base_out;  // simplices waiting to shrink
+  if (threadIdx.x == 0) counts[4] += parked;  // simplices waiting to shrink
 }
 
 // list3 = simplices with a pending shrink (flag bit 2), counts[2] = how many
@@ -513,120 +716,16 @@ extern "C" int rvs_nm_shrink_store(int N, int k, double *sim, double *fsim,
 }
 
 // ---------------------------------------------------------------------------
-// vel_fit.ParamMapper.forward + the range / finiteness guard of chisq_func +
-// VSiniMapper.to_vsini + the Normal priors of chisq_func0 (vel_fit.py:95-254)
-// for J rows of the optimiser's parameter vectors.
-//   X [J, n]: (vel, [vsini], free stellar parameters in specParams order)
-//   src [ndim]: column of X feeding stellar parameter i, or -1 = fixed
-//   fixed [S, ndim], vsini_fixed [S] (used when vsini_col < 0, nullable = no
-//   rotation), prior_mean / prior_isig [S, ndim] (nullable; isig 0 = no prior)
-// out: job_spec[j] = list[j], vel, vsini (nullable), params [J, ndim],
-//      extra[j] = vsini penalty + priors, bad[j] (row answered with 1e30; its
-//      vel/params are replaced by vel 0 / the fixed+start values `safe`)
+// The parameter mapping and the objective around it as launches of their own
 // ---------------------------------------------------------------------------
-struct MapSrc {
-  int src[NM_MAXN];
-};
-
-// vel_fit.chisq_func's parameter mapping for ONE row: the optimiser's vector x of
-// simplex r -> (velocity, vsini, template parameters, prior penalty, bad flag) of job j
-struct MapP {
-  int n, ndim, vsini_col;
-  MapSrc M;
-  const double *fixed, *vsini_fixed, *safe, *prior_mean, *prior_isig;
-  double min_vel, max_vel, max_vsini;
-  int32_t *job_spec;
-  double *vel, *vsini, *params, *extra;
-  int32_t *bad;
-};
-
-// entry idx of a vector that lives in registers (a chain of selects; each entry
-// through a register first, or the compiler turns the chain into a load at a selected
-// offset and the vector into scratch memory: template_dev.h sel_dim)
-__device__ __forceinline__ double nm_pick(const double *x, int idx) {
-  double v = x[0];
-#pragma unroll
-  for (int i = 1; i < NM_MAXN; i++) {
-    double xi = x[i];
-    asm volatile("" : "+v"(xi));
-    v = (idx == i) ? xi : v;
-  }
-  return v;
-}
-
-// (x: the row in the caller's registers, NM_MAXN entries of which P.n count)
-__device__ __forceinline__ void map_row_regs(const MapP &P, int j, int r,
-                                             const double *x) {
-  const int ndim = P.ndim;
-  double v = x[0];
-  double pen = 0;
-  if (P.vsini) {
-    double vs;
-    if (P.vsini_col >= 0) {
-      const double v0 = nm_pick(x, P.vsini_col);
-      vs = fmin(fmax(v0, 0.0), P.max_vsini);  // np.clip
-      if (v0 < 0 || v0 > P.max_vsini) pen += (vs - v0) * (vs - v0);
-      if (v0 != v0) vs = v0;
-    } else {
-      vs = P.vsini_fixed[r];
-    }
-    P.vsini[j] = vs;
-  }
-  bool isbad = (v > P.max_vel) || (v < P.min_vel);
-  double p[NM_MAXN];
-#pragma unroll
-  for (int i = 0; i < NM_MAXN; i++) {   // (p[] in registers: static indices)
-    if (i >= ndim) break;
-    p[i] = (P.M.src[i] >= 0) ? nm_pick(x, P.M.src[i]) : P.fixed[(int64_t)r * ndim + i];
-    if (!(fabs(p[i]) <= 1.79e308)) isbad = true;
-  }
-  if (isbad) {
-    v = 0;
-#pragma unroll
-    for (int i = 0; i < NM_MAXN; i++)
-      if (i < ndim) p[i] = P.safe[(int64_t)r * ndim + i];
-  }
-  if (P.prior_mean)
-#pragma unroll
-    for (int i = 0; i < NM_MAXN; i++) {
-      if (i >= ndim) break;
-      const double d = (P.prior_mean[(int64_t)r * ndim + i] - p[i]) *
-                       P.prior_isig[(int64_t)r * ndim + i];
-      pen += d * d;
-    }
-  P.job_spec[j] = r;
-  P.vel[j] = v;
-#pragma unroll
-  for (int i = 0; i < NM_MAXN; i++)
-    if (i < ndim) P.params[(int64_t)j * ndim + i] = p[i];
-  P.extra[j] = pen;
-  P.bad[j] = isbad ? 1 : 0;
-}
-
-// row i < N of x (memory) <-> xr (registers: no indexing by a loop variable)
-__device__ __forceinline__ void nm_get_row(double *xr, const double *x, int N) {
-#pragma unroll
-  for (int i = 0; i < NM_MAXN; i++) xr[i] = (i < N) ? x[i] : 0.0;
-}
-__device__ __forceinline__ void nm_put_row(double *x, const double *xr, int N) {
-#pragma unroll
-  for (int i = 0; i < NM_MAXN; i++)
-    if (i < N) x[i] = xr[i];
-}
-
-__device__ __forceinline__ void map_row(const MapP &P, int j, int r,
-                                        const double *__restrict__ x) {
-  double xr[NM_MAXN];
-  nm_get_row(xr, x, P.n);
-  map_row_regs(P, j, r, xr);
-}
-
 __global__ void __launch_bounds__(256)
     proc_map_kernel(int J, const double *__restrict__ X,
                     const int32_t *__restrict__ list, MapP P) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= J) return;
-  map_row(P, j, list[j], X + (int64_t)j * P.n);
+  double xr[NM_MAXN];
+  nm_get_row(xr, X + (int64_t)j * P.n, P.n);
+  map_row_regs(P, j, list[j], xr);
 }
 
 __global__ void __launch_bounds__(256)
@@ -646,6 +745,29 @@ __global__ void __launch_bounds__(256)
     atomicOr(&spec_status[job_spec[j]], job_status[j]);
 }
 
+// the mapping's parameters as the kernels take them (o->n, o->ndim checked by the caller)
+static MapP map_params(const rvs_nm_objective *o) {
+  MapP P;
+  P.n = o->n, P.ndim = o->ndim, P.vsini_col = o->vsini_col;
+  for (int i = 0; i < NM_MAXN; i++) P.M.src[i] = (i < o->ndim) ? o->src[i] : -1;
+  P.fixed = o->fixed, P.vsini_fixed = o->vsini_fixed, P.safe = o->safe;
+  P.prior_mean = o->prior_mean, P.prior_isig = o->prior_isig;
+  P.min_vel = o->min_vel, P.max_vel = o->max_vel, P.max_vsini = o->max_vsini;
+  P.job_spec = o->job_spec, P.vel = o->vel, P.vsini = o->vsini, P.params = o->params;
+  P.extra = o->extra, P.bad = o->bad;
+  return P;
+}
+
+static int proc_map(int J, const double *X, const int32_t *list,
+                    const rvs_nm_objective *o, hipStream_t st) {
+  if (J < 1 || o->n < 1 || o->n > NM_MAXN || o->ndim < 1 || o->ndim > NM_MAXN)
+    return RVS_E_ARG;
+  hipLaunchKernelGGL(proc_map_kernel, dim3((J + 255) / 256), dim3(256), 0, st, J, X,
+                     list, map_params(o));
+  RVS_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int rvs_proc_map(int J, int n, int ndim, const double *X,
                             const int32_t *list, const int32_t *src,
                             int vsini_col, const double *fixed,
@@ -655,20 +777,15 @@ extern "C" int rvs_proc_map(int J, int n, int ndim, const double *X,
                             int32_t *job_spec, double *vel, double *vsini,
                             double *params, double *extra, int32_t *bad,
                             void *stream) {
-  if (J < 1 || n < 1 || n > NM_MAXN || ndim < 1 || ndim > NM_MAXN)
-    return RVS_E_ARG;
-  MapP P;
-  P.n = n, P.ndim = ndim, P.vsini_col = vsini_col;
-  for (int i = 0; i < NM_MAXN; i++) P.M.src[i] = (i < ndim) ? src[i] : -1;
-  P.fixed = fixed, P.vsini_fixed = vsini_fixed, P.safe = safe;
-  P.prior_mean = prior_mean, P.prior_isig = prior_isig;
-  P.min_vel = min_vel, P.max_vel = max_vel, P.max_vsini = max_vsini;
-  P.job_spec = job_spec, P.vel = vel, P.vsini = vsini, P.params = params;
-  P.extra = extra, P.bad = bad;
-  hipLaunchKernelGGL(proc_map_kernel, dim3((J + 255) / 256), dim3(256), 0,
-                     rvs_stream(stream), J, X, list, P);
-  RVS_LAUNCH_CHECK();
-  return 0;
+  rvs_nm_objective o = {};
+  o.n = n, o.ndim = ndim, o.vsini_col = vsini_col;
+  for (int i = 0; i < NM_MAXN && i < ndim; i++) o.src[i] = src[i];
+  o.fixed = fixed, o.vsini_fixed = vsini_fixed, o.safe = safe;
+  o.prior_mean = prior_mean, o.prior_isig = prior_isig;
+  o.min_vel = min_vel, o.max_vel = max_vel, o.max_vsini = max_vsini;
+  o.job_spec = job_spec, o.vel = vel, o.vsini = vsini, o.params = params;
+  o.extra = extra, o.bad = bad;
+  return proc_map(J, X, list, &o, rvs_stream(stream));
 }
 
 extern "C" int rvs_proc_finish(int J, const int32_t *counts, int cidx,
@@ -730,11 +847,7 @@ static int nm_objective_rows(const rvs_nm_objective *o, int J, const int32_t *li
 int rvs_internal_nm_eval(const rvs_nm_objective *o, const int32_t *list,
                          const double *X, int J, const int32_t *counts, int cidx,
                          double *F, hipStream_t st) {
-  int rc = rvs_proc_map(J, o->n, o->ndim, X, list, o->src, o->vsini_col,
-                        o->fixed, o->vsini_fixed, o->safe, o->prior_mean,
-                        o->prior_isig, o->min_vel, o->max_vel, o->max_vsini,
-                        o->job_spec, o->vel, o->vsini, o->params, o->extra,
-                        o->bad, st);
+  int rc = proc_map(J, X, list, o, st);
   if (rc) return rc;
   // rows behind the device count (simplices that finished since the host's last look,
   // simplices that need no second point this round) are not evaluated: a quarter of
@@ -793,177 +906,113 @@ __device__ __forceinline__ double glue_value(const NmGlue &G, int j) {
   return isbad ? 1e30 : tot + G.P.extra[j];
 }
 
-// nm_begin_kernel's test of simplex r: 1 = it steps this round (xr = reflection point)
 __device__ __forceinline__ int glue_begin_row(const NmGlue &G, int r, double *xr) {
-  int32_t *flags = G.m.flags;
+  return nm_begin_row(G.m.N, G.m.sim, G.m.fsim, G.m.nit, G.m.flags, r, G.maxiter,
+                      G.xatol, G.fatol, xr);
+}
+
+// the value of row j's evaluation -> F1[j], fxr, and the case of its simplex r (fn: the
+// worst vertex's value, for the update)
+__device__ __forceinline__ int glue_case_row(const NmGlue &G, int j, int r, double &fxr,
+                                             double &fn) {
   const int N = G.m.N;
-  if ((flags[r] & 5) != 1) return 0;  // not active, or a shrink pending
-  if (G.m.nit[r] >= G.maxiter) {
-    flags[r] &= ~1;  // scipy: while-condition fails -> warnflag 2
-    return 0;
-  }
-  const double *s = G.m.sim + (int64_t)r * (N + 1) * N;
   const double *f = G.m.fsim + (int64_t)r * (N + 1);
-  int conv = 0;
-  switch (N) {
-    case 1: conv = nm_begin_row<1>(s, f, G.xatol, G.fatol, xr); break;
-    case 2: conv = nm_begin_row<2>(s, f, G.xatol, G.fatol, xr); break;
-    case 3: conv = nm_begin_row<3>(s, f, G.xatol, G.fatol, xr); break;
-    case 4: conv = nm_begin_row<4>(s, f, G.xatol, G.fatol, xr); break;
-    case 5: conv = nm_begin_row<5>(s, f, G.xatol, G.fatol, xr); break;
-    case 6: conv = nm_begin_row<6>(s, f, G.xatol, G.fatol, xr); break;
-    case 7: conv = nm_begin_row<7>(s, f, G.xatol, G.fatol, xr); break;
-    default: conv = nm_begin_row<8>(s, f, G.xatol, G.fatol, xr); break;
-  }
-  if (conv) {
-    flags[r] = (flags[r] & ~1) | 2;  // converged: success
-    return 0;
-  }
-  return 1;
+  // (the simplex values requested ahead of the evaluation's chain of loads)
+  const double f0 = f[0], fn1 = f[N - 1];
+  fn = f[N];
+  fxr = glue_value(G, j);
+  G.m.F1[j] = fxr;
+  return nm_case(fxr, f0, fn1, fn);
 }
 
-// nm_update_kernel's accepted point + nm_order + nm_begin_kernel's test of simplex r on
-// ONE copy of the simplex in registers: the point becomes row N, the rows are ordered
-// and stored, and the next round's test and reflection point come off the same
-// registers -- the same operations on the same values as the three steps through
-// memory (store row N; load, sort, store; load, test), two round trips shorter.
+// decide row j: its simplex r, its value, its case (-> cases[j]); 1 = it asks for a
+// second point, x2
+__device__ __forceinline__ int glue_decide_row(const NmGlue &G, int j, int &r,
+                                               double *x2) {
+  const int N = G.m.N;
+  r = G.m.list1[j];
+  double fxr, fn;
+  const int c = glue_case_row(G, j, r, fxr, fn);
+  return nm_decide_row(N, G.m.sim + (int64_t)r * (N + 1) * N, c, &G.m.cases[j], x2);
+}
+
+// update row j of simplex r, case c, with the value f2 of its second point (row p2 of
+// X2; none: p2 < 0, f2 = inf): the step's point accepted, or the simplex parked for a
+// shrink (counted in *parked); then the next round's test of the simplex on the same
+// registers: 1 = it steps, xr = its reflection point (xc: its other points, nullable)
 template <int N>
-__device__ __forceinline__ int glue_accept_row_t(const NmGlue &G, int r, double *gs,
-                                                 double *gf,
-                                                 const double *__restrict__ src,
-                                                 double fnew, double *xr) {
+__device__ __forceinline__ int glue_update_row(const NmGlue &G, int j, int r, int c,
+                                               double fxr, double f2, double fn,
+                                               const double *X2, int p2, int *parked,
+                                               double *xr, double (*xc)[NM_MAXN]) {
   double s[N + 1][N], f[N + 1];
-#pragma unroll
-  for (int a = 0; a < N; a++) {
-    f[a] = gf[a];
-#pragma unroll
-    for (int i = 0; i < N; i++) s[a][i] = gs[a * N + i];
-  }
-#pragma unroll
-  for (int i = 0; i < N; i++) s[N][i] = src[i];
-  f[N] = fnew;
-  nm_sort_regs<N>(s, f);
-  nm_store_regs<N>(gs, gf, s, f);
-  const int nit = G.m.nit[r] + 1;
-  G.m.nit[r] = nit;
-  // (glue_begin_row's tests, in its order)
-  int32_t *flags = G.m.flags;
-  const int fl = flags[r];
-  if ((fl & 5) != 1) return 0;
-  if (nit >= G.maxiter) {
-    flags[r] = fl & ~1;
+  const int nit = nm_update_row<N>(G.m.sim + (int64_t)r * (N + 1) * N,
+                                   G.m.fsim + (int64_t)r * (N + 1), &G.m.nit[r],
+                                   &G.m.nfev[r], c, fxr, f2, fn, G.m.X1 + (int64_t)j * N,
+                                   X2 + (int64_t)p2 * N, s, f);
+  if (!nit) {
+    G.m.flags[r] |= 4;  // shrink: parked until the host runs the shrink
+    atomicAdd(parked, 1);
     return 0;
   }
-  if (nm_test_regs<N>(s, f, G.xatol, G.fatol, xr)) {
-    flags[r] = (fl & ~1) | 2;
-    return 0;
-  }
+  if (!nm_may_step(G.m.flags, r, nit, G.maxiter)) return 0;
+  if (!nm_test_regs<N>(G.m.flags, r, s, f, G.xatol, G.fatol, xr)) return 0;
+  if (xc) nm_other_points<N>(s, xc);
   return 1;
 }
 
-__device__ __forceinline__ int glue_accept_row(const NmGlue &G, int r, double *s,
-                                               double *f, const double *src,
-                                               double fnew, double *xr) {
-  switch (G.m.N) {
-    case 1: return glue_accept_row_t<1>(G, r, s, f, src, fnew, xr);
-    case 2: return glue_accept_row_t<2>(G, r, s, f, src, fnew, xr);
-    case 3: return glue_accept_row_t<3>(G, r, s, f, src, fnew, xr);
-    case 4: return glue_accept_row_t<4>(G, r, s, f, src, fnew, xr);
-    case 5: return glue_accept_row_t<5>(G, r, s, f, src, fnew, xr);
-    case 6: return glue_accept_row_t<6>(G, r, s, f, src, fnew, xr);
-    case 7: return glue_accept_row_t<7>(G, r, s, f, src, fnew, xr);
-    default: return glue_accept_row_t<8>(G, r, s, f, src, fnew, xr);
-  }
+// ... of a row whose decision waits in memory (cases, F1, pos2); f2_of(p2): the value of
+// its second point
+template <typename F2>
+__device__ __forceinline__ int glue_update_listed_row(const NmGlue &G, int j, int &r,
+                                                      F2 f2_of, int *parked,
+                                                      double *xr) {
+  const int N = G.m.N;
+  r = G.m.list1[j];
+  const int c = G.m.cases[j];
+  const double fxr = G.m.F1[j];
+  const int p2 = G.m.pos2[j];
+  // (requested ahead of the evaluation's chain of loads)
+  const double fn = G.m.fsim[(int64_t)r * (N + 1) + N];
+  const double f2 = (p2 >= 0) ? f2_of(p2) : __builtin_inf();
+  int go = 0;
+  nm_with_N(N, [&](auto n) {
+    go = glue_update_row<decltype(n)::value>(G, j, r, c, fxr, f2, fn, G.m.X2, p2, parked,
+                                             xr, nullptr);
+  });
+  return go;
 }
 
 __global__ void __launch_bounds__(NM_UNT) nm_glue_begin_kernel(NmGlue G) {
   __shared__ int sh[NM_UNT / 64 + 1];
-  const int S = G.m.S, N = G.m.N;
-  int base_out = 0;
-  for (int r0 = 0; r0 < S; r0 += NM_UNT) {
-    const int r = r0 + threadIdx.x;
-    double xr[NM_MAXN] = {};
-    const int go = (r < S) ? glue_begin_row(G, r, xr) : 0;
-    int tot;
-    const int pos = base_out + block_excl_scan<NM_UNT>(go, &tot, sh);
-    if (go) {
-      G.m.list1[pos] = r;
-      double *x = G.m.X1 + (int64_t)pos * N;
-      nm_put_row(x, xr, N);
-      map_row_regs(G.P, pos, r, xr);
-    }
-    base_out += tot;
-  }
+  const int n = nm_compact_rows<NM_UNT>(
+      &G.P, G.m.N, G.m.S,
+      [&](int j, int &r, double *xr) {
+        r = j;
+        return glue_begin_row(G, j, xr);
+      },
+      G.m.list1, G.m.X1, nullptr, sh);
   if (threadIdx.x == 0) {
-    G.m.counts[0] = base_out;
-    G.m.counts[3] = base_out;
+    G.m.counts[0] = n;
+    G.m.counts[3] = n;
   }
 }
 
+// (a row's own evaluation is read from job slot j: the slots this kernel rewrites for
+// the second evaluation lie at or before the rows already read)
 __global__ void __launch_bounds__(NM_NT) nm_glue_decide_kernel(NmGlue G, int jbound) {
   __shared__ int sh[NM_NT / 64 + 1];
-  const int N = G.m.N;
   const int J = min(G.m.counts[0], jbound);
-  int base_out = 0;
-  for (int j0 = 0; j0 < J; j0 += NM_NT) {
-    const int j = j0 + threadIdx.x;
-    int go = 0, r = 0;
-    double x2[NM_MAXN] = {};
-    if (j < J) {   // (nm_decide_kernel)
-      r = G.m.list1[j];
-      const double *s = G.m.sim + (int64_t)r * (N + 1) * N;
-      const double *f = G.m.fsim + (int64_t)r * (N + 1);
-      // (the simplex values requested ahead of the evaluation's chain of loads)
-      const double f0 = f[0], fn1 = f[N - 1], fn = f[N];
-      // (the row's own evaluation, read from job slot j: the slots this kernel
-      // rewrites for the second evaluation lie at or before the rows already read)
-      const double fxr = glue_value(G, j);
-      G.m.F1[j] = fxr;
-      int c;
-      if (fxr < f0)
-        c = 1;
-      else if (fxr < fn1)
-        c = 0;
-      else if (fxr < fn)
-        c = 2;
-      else
-        c = 3;
-      G.m.cases[j] = c;
-      if (c != 0) {
-        go = 1;
-#pragma unroll
-        for (int i = 0; i < NM_MAXN; i++) {   // (x2[] in registers: static indices)
-          if (i >= N) break;
-          double xb = s[i];
-          for (int k = 1; k < N; k++) xb = xb + s[k * N + i];
-          xb = xb / N;
-          const double w = s[N * N + i];
-          if (c == 1)
-            x2[i] = (1 + 1.0 * 2.0) * xb - 1.0 * 2.0 * w;
-          else if (c == 2)
-            x2[i] = (1 + 0.5 * 1.0) * xb - 0.5 * 1.0 * w;
-          else
-            x2[i] = (1 - 0.5) * xb + 0.5 * w;
-        }
-      }
-    }
-    int tot;
-    const int pos = base_out + block_excl_scan(go, &tot, sh);
-    if (j < J) G.m.pos2[j] = go ? pos : -1;
-    if (go) {
-      G.m.list2[pos] = r;
-      nm_put_row(G.m.X2 + (int64_t)pos * N, x2, N);
-      map_row_regs(G.P, pos, r, x2);
-    }
-    base_out += tot;
-  }
-  if (threadIdx.x == 0) G.m.counts[1] = base_out;
+  const int n = nm_compact_rows<NM_NT>(
+      &G.P, G.m.N, J,
+      [&](int j, int &r, double *x2) { return glue_decide_row(G, j, r, x2); },
+      G.m.list2, G.m.X2, G.m.pos2, sh);
+  if (threadIdx.x == 0) G.m.counts[1] = n;
 }
 
 __global__ void __launch_bounds__(NM_UNT) nm_glue_update_kernel(NmGlue G, int jbound) {
   __shared__ int sh[NM_UNT / 64 + 1];
   __shared__ int parked;
-  const int N = G.m.N;
   const int J = min(G.m.counts[0], jbound), J2 = min(G.m.counts[1], jbound);
   if (threadIdx.x == 0) parked = 0;
   // (all values of the second evaluation first: the rows' new slots below overwrite
@@ -971,56 +1020,17 @@ __global__ void __launch_bounds__(NM_UNT) nm_glue_update_kernel(NmGlue G, int jb
   // trip's packed positions)
   for (int p = threadIdx.x; p < J2; p += NM_UNT) G.m.F2[p] = glue_value(G, p);
   __syncthreads();
-  int base_out = 0;
-  for (int j0 = 0; j0 < J; j0 += NM_UNT) {
-    const int j = j0 + threadIdx.x;
-    int go = 0, r = 0;
-    double xr[NM_MAXN] = {};
-    if (j < J) {   // (nm_update_kernel)
-      r = G.m.list1[j];
-      double *s = G.m.sim + (int64_t)r * (N + 1) * N;
-      double *f = G.m.fsim + (int64_t)r * (N + 1);
-      const int c = G.m.cases[j];
-      const double fxr = G.m.F1[j];
-      const int p2 = G.m.pos2[j];
-      const double f2 = (p2 >= 0) ? G.m.F2[p2] : __builtin_inf();
-      bool take2 = false, taker = false;
-      if (c == 0)
-        taker = true;
-      else if (c == 1) {
-        if (f2 < fxr)
-          take2 = true;
-        else
-          taker = true;
-      } else if (c == 2)
-        take2 = (f2 <= fxr);
-      else
-        take2 = (f2 < f[N]);
-      G.m.nfev[r] += (c == 0) ? 1 : 2;
-      if (take2 || taker) {
-        const double *src = take2 ? (G.m.X2 + (int64_t)p2 * N)
-                                  : (G.m.X1 + (int64_t)j * N);
-        // ... and the next round's test of this simplex (nm_begin_kernel)
-        go = glue_accept_row(G, r, s, f, src, take2 ? f2 : fxr, xr);
-      } else {
-        G.m.flags[r] |= 4;  // shrink: parked until the host runs the shrink
-        atomicAdd(&parked, 1);
-      }
-    }
-    int tot;
-    const int pos = base_out + block_excl_scan<NM_UNT>(go, &tot, sh);
-    if (go) {   // pos <= j: rows of this trip were read above, later rows lie behind
-      G.m.list1[pos] = r;
-      double *x = G.m.X1 + (int64_t)pos * N;
-      nm_put_row(x, xr, N);
-      map_row_regs(G.P, pos, r, xr);
-    }
-    base_out += tot;
-  }
+  const int n = nm_compact_rows<NM_UNT>(
+      &G.P, G.m.N, J,
+      [&](int j, int &r, double *xr) {
+        return glue_update_listed_row(
+            G, j, r, [&](int p2) { return G.m.F2[p2]; }, &parked, xr);
+      },
+      G.m.list1, G.m.X1, nullptr, sh);
   __syncthreads();
   if (threadIdx.x == 0) {
-    G.m.counts[0] = base_out;
-    G.m.counts[3] = base_out;
+    G.m.counts[0] = n;
+    G.m.counts[3] = n;
     G.m.counts[4] += parked;  // simplices waiting to shrink
   }
 }
@@ -1039,21 +1049,6 @@ __global__ void __launch_bounds__(NM_UNT) nm_glue_update_kernel(NmGlue G, int jb
 // nm_spec_max).
 // ---------------------------------------------------------------------------
 #define NM_SNT 64
-template <int N>
-__device__ __forceinline__ void nm_other_points(const double (&s)[N + 1][N],
-                                                double (*xc)[NM_MAXN]) {
-#pragma unroll
-  for (int i = 0; i < N; i++) {   // (nm_decide_kernel's expressions)
-    double xb = s[0][i];
-#pragma unroll
-    for (int k = 1; k < N; k++) xb = xb + s[k][i];
-    xb = xb / N;
-    const double w = s[N][i];
-    xc[0][i] = (1 + 1.0 * 2.0) * xb - 1.0 * 2.0 * w;
-    xc[1][i] = (1 + 0.5 * 1.0) * xb - 0.5 * 1.0 * w;
-    xc[2][i] = (1 - 0.5) * xb + 0.5 * w;
-  }
-}
 
 // rows (q + 1) * J + pos of X1 and of the job tables <- candidate q of simplex r
 __device__ __forceinline__ void nm_put_candidates(const NmGlue &G, int J, int pos, int r,
@@ -1067,38 +1062,28 @@ __device__ __forceinline__ void nm_put_candidates(const NmGlue &G, int J, int po
   }
 }
 
-template <int N>
-__device__ __forceinline__ void glue_spec_prep_body(const NmGlue &G, int jbound) {
+__global__ void __launch_bounds__(NM_SNT) nm_glue_spec_prep_kernel(NmGlue G, int jbound) {
   const int J = min(G.m.counts[0], jbound);
   const int j = threadIdx.x;
-  if (j < J) {
-    const int r = G.m.list1[j];
-    double s[N + 1][N], f[N + 1];
-    nm_load_regs<N>(G.m.sim + (int64_t)r * (N + 1) * N, G.m.fsim + (int64_t)r * (N + 1),
-                    s, f);
-    double xc[3][NM_MAXN] = {};
-    nm_other_points<N>(s, xc);
-    nm_put_candidates(G, J, j, r, xc);
-  }
+  if (j < J)
+    nm_with_N(G.m.N, [&](auto n) {
+      constexpr int N = decltype(n)::value;
+      const int r = G.m.list1[j];
+      double s[N + 1][N], f[N + 1];
+      nm_load_regs<N>(G.m.sim + (int64_t)r * (N + 1) * N, G.m.fsim + (int64_t)r * (N + 1),
+                      s, f);
+      double xc[3][NM_MAXN] = {};
+      nm_other_points<N>(s, xc);
+      nm_put_candidates(G, J, j, r, xc);
+    });
   if (threadIdx.x == 0) G.m.counts[5] = 4 * J;
 }
 
-__global__ void __launch_bounds__(NM_SNT) nm_glue_spec_prep_kernel(NmGlue G, int jbound) {
-  switch (G.m.N) {
-    case 1: glue_spec_prep_body<1>(G, jbound); break;
-    case 2: glue_spec_prep_body<2>(G, jbound); break;
-    case 3: glue_spec_prep_body<3>(G, jbound); break;
-    case 4: glue_spec_prep_body<4>(G, jbound); break;
-    case 5: glue_spec_prep_body<5>(G, jbound); break;
-    case 6: glue_spec_prep_body<6>(G, jbound); break;
-    case 7: glue_spec_prep_body<7>(G, jbound); break;
-    default: glue_spec_prep_body<8>(G, jbound); break;
-  }
-}
-
-template <int N>
-__device__ __forceinline__ void glue_spec_body(const NmGlue &G, int jbound, int *sh,
-                                               int *parked) {
+__global__ void __launch_bounds__(NM_SNT) nm_glue_spec_kernel(NmGlue G, int jbound) {
+  __shared__ int sh[NM_SNT / 64 + 1];
+  __shared__ int parked;
+  if (threadIdx.x == 0) parked = 0;
+  __syncthreads();
   const int J = min(G.m.counts[0], jbound);
   const int j = threadIdx.x;
   int go = 0, r = 0;
@@ -1106,77 +1091,22 @@ __device__ __forceinline__ void glue_spec_body(const NmGlue &G, int jbound, int 
   double xc[3][NM_MAXN] = {};
   if (j < J) {
     r = G.m.list1[j];
-    double *gs = G.m.sim + (int64_t)r * (N + 1) * N;
-    double *gf = G.m.fsim + (int64_t)r * (N + 1);
-    const double f0 = gf[0], fn1 = gf[N - 1], fn = gf[N];
-    const double fxr = glue_value(G, j);   // (nm_decide_kernel)
-    G.m.F1[j] = fxr;
-    int c;
-    if (fxr < f0)
-      c = 1;
-    else if (fxr < fn1)
-      c = 0;
-    else if (fxr < fn)
-      c = 2;
-    else
-      c = 3;
+    double fxr, fn;
+    const int c = glue_case_row(G, j, r, fxr, fn);
     // the step's second point: candidate c of this row, or none
     const int p2 = (c == 0) ? -1 : c * J + j;
-    double f2 = __builtin_inf();
-    if (p2 >= 0) f2 = glue_value(G, p2);
-    bool take2 = false, taker = false;   // (nm_update_kernel)
-    if (c == 0)
-      taker = true;
-    else if (c == 1) {
-      if (f2 < fxr)
-        take2 = true;
-      else
-        taker = true;
-    } else if (c == 2)
-      take2 = (f2 <= fxr);
-    else
-      take2 = (f2 < fn);
-    G.m.nfev[r] += (c == 0) ? 1 : 2;
-    if (take2 || taker) {
-      const double *src = G.m.X1 + (int64_t)(take2 ? p2 : j) * N;
-      double s[N + 1][N], f[N + 1];
-#pragma unroll
-      for (int a = 0; a < N; a++) {
-        f[a] = gf[a];
-#pragma unroll
-        for (int i = 0; i < N; i++) s[a][i] = gs[a * N + i];
-      }
-#pragma unroll
-      for (int i = 0; i < N; i++) s[N][i] = src[i];
-      f[N] = take2 ? f2 : fxr;
-      nm_sort_regs<N>(s, f);
-      nm_store_regs<N>(gs, gf, s, f);
-      const int nit = G.m.nit[r] + 1;
-      G.m.nit[r] = nit;
-      // (glue_begin_row's tests, in its order)
-      int32_t *flags = G.m.flags;
-      const int fl = flags[r];
-      if ((fl & 5) == 1) {
-        if (nit >= G.maxiter) {
-          flags[r] = fl & ~1;
-        } else if (nm_test_regs<N>(s, f, G.xatol, G.fatol, xr)) {
-          flags[r] = (fl & ~1) | 2;
-        } else {
-          go = 1;
-          nm_other_points<N>(s, xc);
-        }
-      }
-    } else {
-      G.m.flags[r] |= 4;  // shrink: parked until the host runs the shrink
-      atomicAdd(parked, 1);
-    }
+    const double f2 = (p2 >= 0) ? glue_value(G, p2) : __builtin_inf();
+    nm_with_N(G.m.N, [&](auto n) {
+      go = glue_update_row<decltype(n)::value>(G, j, r, c, fxr, f2, fn, G.m.X1, p2,
+                                               &parked, xr, xc);
+    });
   }
   // (every row and value of this round has been read: the barriers of the scan)
   int tot;
   const int pos = block_excl_scan<NM_SNT>(go, &tot, sh);
   if (go) {
     G.m.list1[pos] = r;
-    nm_put_row(G.m.X1 + (int64_t)pos * N, xr, N);
+    nm_put_row(G.m.X1 + (int64_t)pos * G.m.N, xr, G.m.N);
     map_row_regs(G.P, pos, r, xr);
     nm_put_candidates(G, tot, pos, r, xc);
   }
@@ -1185,29 +1115,12 @@ __device__ __forceinline__ void glue_spec_body(const NmGlue &G, int jbound, int 
     G.m.counts[0] = tot;
     G.m.counts[3] = tot;
     G.m.counts[5] = 4 * tot;
-    G.m.counts[4] += *parked;  // simplices waiting to shrink
-  }
-}
-
-__global__ void __launch_bounds__(NM_SNT) nm_glue_spec_kernel(NmGlue G, int jbound) {
-  __shared__ int sh[NM_SNT / 64 + 1];
-  __shared__ int parked;
-  if (threadIdx.x == 0) parked = 0;
-  __syncthreads();
-  switch (G.m.N) {
-    case 1: glue_spec_body<1>(G, jbound, sh, &parked); break;
-    case 2: glue_spec_body<2>(G, jbound, sh, &parked); break;
-    case 3: glue_spec_body<3>(G, jbound, sh, &parked); break;
-    case 4: glue_spec_body<4>(G, jbound, sh, &parked); break;
-    case 5: glue_spec_body<5>(G, jbound, sh, &parked); break;
-    case 6: glue_spec_body<6>(G, jbound, sh, &parked); break;
-    case 7: glue_spec_body<7>(G, jbound, sh, &parked); break;
-    default: glue_spec_body<8>(G, jbound, sh, &parked); break;
+    G.m.counts[4] += parked;  // simplices waiting to shrink
   }
 }
 
 // ---------------------------------------------------------------------------
-// The two bookkeeping kernels above as TWO kernels each, for rounds of thousands of
+// The one-block bookkeeping kernels as TWO kernels each, for rounds of thousands of
 // rows: everything a row does for itself -- the value of its evaluation, its case,
 // the simplex update and ordering, the next round's test and point -- on as many
 // blocks as there are rows (`rows`), and the ordered compaction (lists in simplex
@@ -1216,99 +1129,43 @@ __global__ void __launch_bounds__(NM_SNT) nm_glue_spec_kernel(NmGlue G, int jbou
 // a fifth of a half's timeline, hidden only while the other half's objective kernel
 // runs.  Same operations per row, same order of the lists: the same state.  A row's
 // point waits in ITS OWN row of X1 / X2 (no other row reads that one) and its flag in
-// cases[]; the pack kernel reads a trip's rows into registers, waits for them, and
-// only then writes the packed positions (which lie at or before the rows read).
+// cases[] (non-zero: the row goes on).
 // ---------------------------------------------------------------------------
 #define NM_ROWS_NT 256
-__global__ void __launch_bounds__(NM_ROWS_NT)
-    nm_glue_decide_rows_kernel(NmGlue G, int jbound) {
+
+// the rows as the rows kernel left them, compacted: row j of `list_in` (null: j itself)
+// goes on when cases[j] is set, its point read back from row j of X
+__device__ __forceinline__ int glue_pack_rows(const NmGlue &G, int J,
+                                              const int32_t *list_in, int32_t *list_out,
+                                              double *X, int32_t *pos_out, int *sh) {
   const int N = G.m.N;
-  const int J = min(G.m.counts[0], jbound);
-  const int j = blockIdx.x * NM_ROWS_NT + threadIdx.x;
-  if (j >= J) return;
-  const int r = G.m.list1[j];
-  const double *s = G.m.sim + (int64_t)r * (N + 1) * N;
-  const double *f = G.m.fsim + (int64_t)r * (N + 1);
-  // (the simplex values requested ahead of the evaluation's chain of loads)
-  const double f0 = f[0], fn1 = f[N - 1], fn = f[N];
-  const double fxr = glue_value(G, j);
-  G.m.F1[j] = fxr;
-  int c;
-  if (fxr < f0)
-    c = 1;
-  else if (fxr < fn1)
-    c = 0;
-  else if (fxr < fn)
-    c = 2;
-  else
-    c = 3;
-  G.m.cases[j] = c;
-  if (c != 0) {
-    double *x2 = G.m.X2 + (int64_t)j * N;
-    for (int i = 0; i < N; i++) {
-      double xb = s[i];
-      for (int k = 1; k < N; k++) xb = xb + s[k * N + i];
-      xb = xb / N;
-      const double w = s[N * N + i];
-      if (c == 1)
-        x2[i] = (1 + 1.0 * 2.0) * xb - 1.0 * 2.0 * w;
-      else if (c == 2)
-        x2[i] = (1 + 0.5 * 1.0) * xb - 0.5 * 1.0 * w;
-      else
-        x2[i] = (1 - 0.5) * xb + 0.5 * w;
-    }
-  }
+  return nm_compact_rows<NM_NT>(
+      &G.P, N, J,
+      [&](int j, int &r, double *x) {
+        const int go = G.m.cases[j] != 0;
+        r = list_in ? list_in[j] : j;
+        if (go) nm_get_row(x, X + (int64_t)j * N, N);
+        // (a trip's rows are in registers before any thread writes a packed position)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        return go;
+      },
+      list_out, X, pos_out, sh);
 }
 
-// rows [0, J) with flag(j) set move, in order, to the front of (list, X): X row j -> row
-// pos, list[pos] = list_in[j] (j itself without a list); pos_out[j] = pos or -1
-// (nullable); returns the count
-template <typename FLAG>
-__device__ int nm_pack_rows(const NmGlue &G, int J, FLAG flag, const int32_t *list_in,
-                            int32_t *list_out, double *X, int32_t *pos_out, int *sh) {
-  const int N = G.m.N;
-  int base_out = 0;
-  for (int j0 = 0; j0 < J; j0 += NM_NT) {
-    const int j = j0 + threadIdx.x;
-    int go = 0, r = 0;
-    double xr[NM_MAXN] = {};
-    if (j < J) {
-      go = flag(j);
-      r = list_in ? list_in[j] : j;
-      if (go) nm_get_row(xr, X + (int64_t)j * N, N);
-    }
-    // (the rows are in registers before any thread writes a packed position)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int tot;
-    const int pos = base_out + block_excl_scan(go, &tot, sh);
-    if (pos_out && j < J) pos_out[j] = go ? pos : -1;
-    if (go) {
-      list_out[pos] = r;
-      nm_put_row(X + (int64_t)pos * N, xr, N);
-      map_row_regs(G.P, pos, r, xr);
-    }
-    base_out += tot;
-  }
-  return base_out;
-}
-
-// nm_glue_begin_kernel the same way (the start of a run and every return from a shrink
-// test all S simplices: ten trips of one block at 5000)
+// (the start of a run and every return from a shrink test all S simplices: ten trips
+// of one block at 5000)
 __global__ void __launch_bounds__(NM_ROWS_NT) nm_glue_begin_rows_kernel(NmGlue G) {
-  const int S = G.m.S, N = G.m.N;
   const int r = blockIdx.x * NM_ROWS_NT + threadIdx.x;
-  if (r >= S) return;
+  if (r >= G.m.S) return;
   double xr[NM_MAXN] = {};
   const int go = glue_begin_row(G, r, xr);
   G.m.cases[r] = go;   // (no round is in flight: the array is free)
-  if (go) nm_put_row(G.m.X1 + (int64_t)r * N, xr, N);
+  if (go) nm_put_row(G.m.X1 + (int64_t)r * G.m.N, xr, G.m.N);
 }
 
 __global__ void __launch_bounds__(NM_NT) nm_glue_begin_pack_kernel(NmGlue G) {
   __shared__ int sh[NM_NT / 64 + 1];
-  const int32_t *cases = G.m.cases;
-  const int n = nm_pack_rows(G, G.m.S, [=](int j) { return cases[j]; }, nullptr,
-                             G.m.list1, G.m.X1, nullptr, sh);
+  const int n = glue_pack_rows(G, G.m.S, nullptr, G.m.list1, G.m.X1, nullptr, sh);
   __syncthreads();
   if (threadIdx.x == 0) {
     G.m.counts[0] = n;
@@ -1316,65 +1173,46 @@ __global__ void __launch_bounds__(NM_NT) nm_glue_begin_pack_kernel(NmGlue G) {
   }
 }
 
+__global__ void __launch_bounds__(NM_ROWS_NT)
+    nm_glue_decide_rows_kernel(NmGlue G, int jbound) {
+  const int J = min(G.m.counts[0], jbound);
+  const int j = blockIdx.x * NM_ROWS_NT + threadIdx.x;
+  if (j >= J) return;
+  int r;
+  double x2[NM_MAXN] = {};
+  if (glue_decide_row(G, j, r, x2)) nm_put_row(G.m.X2 + (int64_t)j * G.m.N, x2, G.m.N);
+}
+
 __global__ void __launch_bounds__(NM_NT) nm_glue_decide_pack_kernel(NmGlue G, int jbound) {
   __shared__ int sh[NM_NT / 64 + 1];
   const int J = min(G.m.counts[0], jbound);
-  const int32_t *cases = G.m.cases;
-  const int n = nm_pack_rows(G, J, [=](int j) { return cases[j] != 0 ? 1 : 0; },
-                             G.m.list1, G.m.list2, G.m.X2, G.m.pos2, sh);
+  const int n = glue_pack_rows(G, J, G.m.list1, G.m.list2, G.m.X2, G.m.pos2, sh);
   if (threadIdx.x == 0) G.m.counts[1] = n;
 }
 
 __global__ void __launch_bounds__(NM_ROWS_NT)
     nm_glue_update_rows_kernel(NmGlue G, int jbound) {
-  const int N = G.m.N;
   const int J = min(G.m.counts[0], jbound);
   const int j = blockIdx.x * NM_ROWS_NT + threadIdx.x;
   if (j >= J) return;
-  const int r = G.m.list1[j];
-  double *s = G.m.sim + (int64_t)r * (N + 1) * N;
-  double *f = G.m.fsim + (int64_t)r * (N + 1);
-  const int c = G.m.cases[j];
-  const double fxr = G.m.F1[j];
-  const int p2 = G.m.pos2[j];
-  const double fn = f[N];   // (requested ahead of the evaluation's chain of loads)
-  double f2 = __builtin_inf();
-  if (p2 >= 0) {   // (this row's second point: nobody else's)
-    f2 = glue_value(G, p2);
-    G.m.F2[p2] = f2;
-  }
-  bool take2 = false, taker = false;
-  if (c == 0)
-    taker = true;
-  else if (c == 1) {
-    if (f2 < fxr)
-      take2 = true;
-    else
-      taker = true;
-  } else if (c == 2)
-    take2 = (f2 <= fxr);
-  else
-    take2 = (f2 < fn);
-  G.m.nfev[r] += (c == 0) ? 1 : 2;
-  int go = 0;
+  int r;
   double xr[NM_MAXN];
-  if (take2 || taker) {
-    const double *src = take2 ? (G.m.X2 + (int64_t)p2 * N) : (G.m.X1 + (int64_t)j * N);
-    go = glue_accept_row(G, r, s, f, src, take2 ? f2 : fxr, xr);
-  } else {
-    G.m.flags[r] |= 4;  // shrink: parked until the host runs the shrink
-    atomicAdd(&G.m.counts[4], 1);
-  }
+  const int go = glue_update_listed_row(
+      G, j, r,
+      [&](int p2) {   // (this row's second point: nobody else's)
+        const double f2 = glue_value(G, p2);
+        G.m.F2[p2] = f2;
+        return f2;
+      },
+      &G.m.counts[4], xr);
   G.m.cases[j] = go;   // (the case is used up: the flag of the pack kernel)
-  if (go) nm_put_row(G.m.X1 + (int64_t)j * N, xr, N);
+  if (go) nm_put_row(G.m.X1 + (int64_t)j * G.m.N, xr, G.m.N);
 }
 
 __global__ void __launch_bounds__(NM_NT) nm_glue_update_pack_kernel(NmGlue G, int jbound) {
   __shared__ int sh[NM_NT / 64 + 1];
   const int J = min(G.m.counts[0], jbound);
-  const int32_t *cases = G.m.cases;
-  const int n = nm_pack_rows(G, J, [=](int j) { return cases[j]; }, G.m.list1,
-                             G.m.list1, G.m.X1, nullptr, sh);
+  const int n = glue_pack_rows(G, J, G.m.list1, G.m.list1, G.m.X1, nullptr, sh);
   __syncthreads();
   if (threadIdx.x == 0) {
     G.m.counts[0] = n;
@@ -1393,14 +1231,7 @@ extern "C" int rvs_nm_run(const rvs_nm_state *m, const rvs_nm_objective *o,
   int32_t c[8];
   NmGlue G;
   G.m = *m;
-  MapP &P = G.P;
-  P.n = o->n, P.ndim = o->ndim, P.vsini_col = o->vsini_col;
-  for (int i = 0; i < NM_MAXN; i++) P.M.src[i] = (i < o->ndim) ? o->src[i] : -1;
-  P.fixed = o->fixed, P.vsini_fixed = o->vsini_fixed, P.safe = o->safe;
-  P.prior_mean = o->prior_mean, P.prior_isig = o->prior_isig;
-  P.min_vel = o->min_vel, P.max_vel = o->max_vel, P.max_vsini = o->max_vsini;
-  P.job_spec = o->job_spec, P.vel = o->vel, P.vsini = o->vsini, P.params = o->params;
-  P.extra = o->extra, P.bad = o->bad;
+  G.P = map_params(o);
   G.badchi = o->badchi, G.xatol = xatol, G.fatol = fatol, G.maxiter = maxiter;
   G.pen_scale = o->arms[0].pt.pen_scale;
   G.spec_status = o->status;

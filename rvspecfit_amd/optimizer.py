@@ -418,12 +418,15 @@ class DeviceNelderMead:
             objective.slots += int(st3[2])
             return self._result(sim, fs, int(st3[0]), stats)
 
-        def one_round(jb):
-            st = _lib.stream()
+        def begin(jb):
             rc = L.rvs_nm_begin(S, N, xatol, fatol, maxiter, _p(sim), _p(fs),
                                 _p(self.nit), _p(self.flags), _p(self.list1),
-                                _p(self.X1), _p(self.counts), jb, st)
+                                _p(self.X1), _p(self.counts), jb, _lib.stream())
             _lib.check(rc, 'rvs_nm_begin')
+
+        def one_round(jb):
+            st = _lib.stream()
+            begin(jb)
             objective.eval(self.list1, self.X1, jb, self.counts, 0, self.F1)
             rc = L.rvs_nm_decide(N, _p(sim), _p(fs), _p(self.list1),
                                  _p(self.F1), _p(self.cases), _p(self.pos2),
@@ -449,10 +452,7 @@ class DeviceNelderMead:
 
         jb = S
         rounds = 0
-        rc = L.rvs_nm_begin(S, N, xatol, fatol, maxiter, _p(sim), _p(fs),
-                            _p(self.nit), _p(self.flags), _p(self.list1),
-                            _p(self.X1), _p(self.counts), jb, _lib.stream())
-        _lib.check(rc, 'rvs_nm_begin')
+        begin(jb)
         while True:
             # host look: counts of the most recent begin (an upper bound of what
             # is active now), parked shrinks
@@ -460,11 +460,7 @@ class DeviceNelderMead:
             live, parked = int(c[0]), int(c[4])
             if parked > 0:
                 self._shrink(objective, sim, parked)
-                rc = L.rvs_nm_begin(S, N, xatol, fatol, maxiter, _p(sim), _p(fs),
-                                    _p(self.nit), _p(self.flags), _p(self.list1),
-                                    _p(self.X1), _p(self.counts), S,
-                                    _lib.stream())
-                _lib.check(rc, 'rvs_nm_begin')
+                begin(S)
                 continue
             if live == 0:
                 break

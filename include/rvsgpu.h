@@ -93,8 +93,10 @@ extern "C" {
  *  14: removed: rvs_nm_state.stop_below (and its padding word), options "xc_ws1",
  *      "nm_glue", "nm_bucket"
  *  15: rvs_ccf_models_build, rvs_ccf_model_rows (CCF template sets from model rows);
- *      status bit 0x200 = RVS_ST_NONPOS_MEDIAN */
-#define RVS_ABI_VERSION 15
+ *      status bit 0x200 = RVS_ST_NONPOS_MEDIAN
+ *  16: rvs_rebin_weights, rvs_rebin_apply, rvs_template_normalize (template libraries
+ *      from high-resolution models) */
+#define RVS_ABI_VERSION 16
 int rvs_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -965,6 +967,63 @@ typedef struct rvs_bfgs_state {
 int64_t rvs_bfgs_run_bytes(void);
 int rvs_bfgs_run(const rvs_bfgs_state *b, const rvs_nm_objective *o,
                  int sync_every, int64_t *stats, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Template libraries from high-resolution models; replaces rvs_make_interpol's
+ * per-model work: read_grid.make_rebinner (read_grid.py:360-466) without its sparse
+ * matrix, apply_rebinner between the photon conversions of
+ * make_interpol.extract_spectrum (make_interpol.py:152-154), and that function's
+ * continuum, logarithm, finite check and cast (:156-172, :367-368).
+ *
+ * The band.  Output pixel i (centre lam[i], half steps as read_grid.py:409-416, LSF
+ * sigma sigs[i] of :394-400) takes input pixels left[i] .. right[i] + 1: the segments
+ * left[i] .. right[i] of :423-441, i.e. searchsorted(lam0, lam[i] -/+ 5 sigs[i])
+ * (- 1 on the left) clamped to 0 and n0 - 2 -- found by the caller; the kernels clamp
+ * again and never read outside lam0 [n0], hr [., n0] or W [npix, K].
+ * W [npix, K] (row-major, K >= max_i right[i] - left[i] + 2): W[i, k] is the weight
+ * of input pixel left[i] + k -- coeff1 of segment k plus coeff2 of segment k - 1 of
+ * pix_integrator (:75-111), over leftstep + rightstep -- and 0 behind the window.
+ * The weight is the integral over the output pixel of the Gaussian-convolved linear
+ * interpolant; it is evaluated from the antiderivatives of Phi(u) and u Phi(u) with
+ * erfc in the tails (csrc/rebin.hip), not from the reference's expression.
+ * lam0 is the input grid AFTER the vacuum -> air conversion (:388-392, host work).
+ * npix <= 65535. */
+int rvs_rebin_weights(const double *lam0, int n0, const double *lam,
+                      const double *sigs, const int32_t *left, const int32_t *right,
+                      int npix, int K, double *W, void *stream);
+
+/* photons != 0 (extract_spectrum: photons in, per wavelength out):
+ *   out[t, i] = (1 / lam[i]) sum_k W[i, k] hr[t, left[i] + k] lam0[left[i] + k]
+ * photons == 0 (apply_rebinner alone; lam0 and lam are not read):
+ *   out[t, i] = sum_k W[i, k] hr[t, left[i] + k]
+ * for T models: hr [T, n0] with row stride hr_stride >= n0 ELEMENTS, float32
+ * (hr_f32 != 0; PHOENIX files) or float64; out float64 [T, npix]; sums in float64,
+ * each in ascending input pixel whatever T is (the same bits for any split of the
+ * models into calls).  T <= 32 * 65535 per call. */
+int rvs_rebin_apply(const void *hr, int hr_f32, int64_t hr_stride, int T, int n0,
+                    const double *lam0, const double *W, int K, const int32_t *left,
+                    const int32_t *right, const double *lam, int npix, int photons,
+                    double *out, void *stream);
+
+/* rows float64 [T, npix] (rvs_rebin_apply's out) -> out [T, npix], float32
+ * (float_bits 32) or float64 (64); one block per row.
+ * mode RVS_NORM_LINEAR_CONTINUUM: get_line_continuum (make_interpol.py:47-75) divided
+ *   out -- np.median of row[:npix // 2] and of row[npix // 2:], the straight line
+ *   through (lam1, log) and (lam2, log) evaluated and extrapolated at every lam[i],
+ *   exponentiated; lam1, lam2: the medians of the two halves of lam (host);
+ * mode RVS_NORM_MEDIAN: divided by np.median(row), lognorms[t] = its log;
+ * mode RVS_NORM_NONE.  lognorms [T] (nullable) is 0 in the other two modes.
+ * Then log when log_spec != 0.  status[t] = RVS_ST_NONFINITE when a value of the row
+ * is not finite (make_interpol.py:169-171 raises).  2 <= npix <= RVS_REBIN_MAX_NPIX,
+ * which is RVS_CCF_MODEL_MAX_NTP: what this writes rvs_ccf_models_build accepts. */
+#define RVS_REBIN_MAX_NPIX 9216
+#define RVS_NORM_NONE 0
+#define RVS_NORM_MEDIAN 1
+#define RVS_NORM_LINEAR_CONTINUUM 2
+int rvs_template_normalize(const double *rows, int T, int npix, const double *lam,
+                           int mode, double lam1, double lam2, int log_spec,
+                           int float_bits, void *out, double *lognorms,
+                           int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

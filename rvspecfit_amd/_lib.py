@@ -100,11 +100,14 @@ SIGNATURES = {
     'rvs_template_nn_arms': (I, [P, I, I, I, P, P]),
     'rvs_template_nn_arms_n': (I, [P, I, P, I, I, P, P]),
     'rvs_nn_outside': (I, [P, I, I, U, P, P, I, P, I, P, I, P, P]),
+    'rvs_rebin_weights': (I, [P, I, P, P, P, P, I, I, P, P]),
+    'rvs_rebin_apply': (I, [P, I, L, I, I, P, P, I, P, P, P, I, I, P, P]),
+    'rvs_template_normalize': (I, [P, I, I, P, I, D, D, I, I, P, P, P, P]),
 }
 
 _lib = None
 # RVS_ABI_VERSION of the include/rvsgpu.h these signatures mirror
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class RvsGpuError(RuntimeError):

@@ -311,6 +311,31 @@ class TemplateLibrary:
     def from_npz(cls, name, path, device='cuda'):
         return cls(name, np.load(path, allow_pickle=False), device=device)
 
+    @classmethod
+    def from_models(cls, name, lam_hr, models, vec, setupInfo,
+                    parnames=('teff', 'logg', 'feh', 'alpha'), air=False,
+                    resolution0=100000, normalize='linear_continuum', float_bits=32,
+                    log_parameters=(0, ), ccf=None, device='cuda'):
+        """A regular-grid library from high-resolution model spectra:
+        make_interpol.build_specs (rvs_make_interpol),
+        make_nd.regular_library (rvs_make_nd --regulargrid) and, with
+        ccf = dict(ccfconf=..., every=..., vsinis=...), make_ccf.build_ccf_set
+        (rvs_make_ccf) attached by add_ccf_set.  Arguments as build_specs.  With
+        float_bits = 32 the rows never leave the device.  float_bits = 64 only serves
+        the CCF set: build_ccf_set takes float64 rows from the host, so they make one
+        round trip, and the library itself keeps float32 rows either way."""
+        from . import make_ccf, make_interpol, make_nd
+        specs = make_interpol.build_specs(
+            lam_hr, models, vec, setupInfo, parnames=parnames, air=air,
+            resolution0=resolution0, normalize=normalize, float_bits=float_bits,
+            log_parameters=log_parameters, device=device)
+        lib = cls(name, make_nd.regular_library(specs), device=device)
+        if ccf is not None:
+            if float_bits != 32:     # build_ccf_set takes float64 rows from the host
+                specs = dict(specs, specs=specs['specs'].cpu().numpy())
+            lib.add_ccf_set(make_ccf.build_ccf_set(specs, **ccf))
+        return lib
+
     # -- A3 / A4 : template evaluation for a batch of parameter vectors ------
     def eval_batch(self, params, details=False, mapped=False):
         """params float64 [J, ndim] (device) -> templ [J, ntp], outside [J].

@@ -277,6 +277,33 @@ def make_interp_library_fast(setup, lam_left, lam_right, step, grid_kw=None,
                 parnames=PARNAMES, physical_vec=vec)
 
 
+def make_interp_library_convolved(setup, lam_left, lam_right, step, grid_kw=None,
+                                  resol=2000., hr_step=0.02, float_bits=32,
+                                  device='cuda', chunk=256):
+    """A synthetic library made the way a real one is: spectra_batch at high resolution
+    (hr_step Angstrom, no analytic line broadening), then the package's own
+    make_interpol.build_specs + make_nd.regular_library on the device -- convolution to
+    R = `resol`, integration over the output pixels, linear continuum, logarithm.  Same
+    dictionary as make_interp_library_fast (dats a device tensor); needs a GPU."""
+    import torch
+    from . import make_interpol, make_nd
+    u, vec = regular_grid(**(grid_kw or {}))
+    lam_hr = np.arange(lam_left * 0.99, lam_right * 1.01, hr_step)
+
+    def chunks():
+        for i0 in range(0, vec.shape[1], chunk):
+            v = [torch.as_tensor(vec[k, i0:i0 + chunk]).to(device) for k in range(4)]
+            yield spectra_batch(lam_hr, v[0], v[1], v[2], v[3], xp=torch)
+    S = make_interpol.build_specs(
+        lam_hr, chunks(), vec, (setup, lam_left, lam_right,
+                                make_interpol.Resolution(resol=resol), step, True),
+        parnames=PARNAMES, float_bits=float_bits, device=device)
+    lib = make_nd.regular_library(S)
+    return dict(setup=setup, lam=lib['lam'], dats=lib['dats'], vec=lib['vec'],
+                uvecs=[lib['uvec%d' % i] for i in range(4)], idgrid=lib['idgrid'],
+                log_step=True, log_ids=(0, ), parnames=PARNAMES, physical_vec=vec)
+
+
 def library_as_npz_dict(lib, ccf=None):
     """Flatten to the converted-artefact key set (tests/golden/lib_*.npz) that
     both library.TemplateLibrary and the oracle's Library read."""

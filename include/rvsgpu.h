@@ -42,6 +42,7 @@ extern "C" {
 #define RVS_ST_QUAD_ASSERT 0x80   /* parabola vertex outside its bracket (spec_fit.py:1014 assert)  */
 #define RVS_ST_ILLCOND 0x100      /* rvs_chisq_grid: normal matrix pivots span > 1e9 (long stretch of weightless pixels); re-evaluate the job with rvs_chisq_point */
 #define RVS_ST_NONPOS_MEDIAN 0x200 /* rvs_ccf_models_build: median of the model row <= 0 (make_ccf.py:133-138) */
+#define RVS_ST_RBF_NOTPD 0x400    /* rvs_rbf_factor: a pivot of the Cholesky factorisation is not positive (duplicate nodes: scipy's "Singular matrix") */
 
 /* library version / build probe (host).  RVS_ABI_VERSION changes whenever the
  * meaning of an argument, a status bit or a work-size formula changes; a caller
@@ -95,8 +96,11 @@ extern "C" {
  *  15: rvs_ccf_models_build, rvs_ccf_model_rows (CCF template sets from model rows);
  *      status bit 0x200 = RVS_ST_NONPOS_MEDIAN
  *  16: rvs_rebin_weights, rvs_rebin_apply, rvs_template_normalize (template libraries
- *      from high-resolution models) */
-#define RVS_ABI_VERSION 16
+ *      from high-resolution models)
+ *  17: rvs_rbf_work_size, rvs_rbf_factor, rvs_rbf_solve, rvs_rbf_eval (multiquadric
+ *      interpolation of template rows: regularize_grid); status bit 0x400 =
+ *      RVS_ST_RBF_NOTPD */
+#define RVS_ABI_VERSION 17
 int rvs_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -1024,6 +1028,44 @@ int rvs_template_normalize(const double *rows, int T, int npix, const double *la
                            int mode, double lam1, double lam2, int log_spec,
                            int float_bits, void *out, double *lognorms,
                            int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Filling the holes of a template grid; replaces the RBFInterpolator of
+ * regularize_grid.converter (regularize_grid.py:118-140) and, for
+ * kernel='multiquadric' (degree 0), scipy/interpolate/_rbfinterp.py:
+ * _build_system + _build_and_solve_system (factor, solve) and _chunk_evaluator (eval).
+ *
+ *   K[i,j] = -sqrt(|eps y_i - eps y_j|^2 + 1),   (K + diag(smoothing)) c + 1 lam = d,
+ *   1^T c = 0,   out[m,:] = sum_j -sqrt(|eps x_m - eps y_j|^2 + 1) c[j,:] + lam.
+ *
+ * y [N, ndim] nodes, d [N, S] values (float32 when d_f32 != 0, else float64; row
+ * stride d_stride >= S ELEMENTS), x [M, ndim] points, out [M, S] (float32 / float64 by
+ * float_bits; row stride out_stride >= S elements); smoothing [N] or NULL (zero).
+ * All arithmetic is float64.  `work`: rvs_rbf_work_size(N, S) DOUBLES, the caller's.
+ * rvs_rbf_factor fills its first part from the nodes alone; rvs_rbf_solve keeps the
+ * coefficients of ONE set of S columns behind it and rvs_rbf_eval reads them -- the
+ * columns are independent, so a caller short of memory factors once and walks d in
+ * column chunks of S with solve + eval per chunk.
+ * Route: blocked Cholesky of K + diag(smoothing) + a 1 1^T (a: the kernel of the nodes'
+ * bounding box, >= max |K_ij|), c and lam from the extra right-hand side 1
+ * (csrc/rbf.hip).  status (int32 [1], OR-ed into): RVS_ST_RBF_NOTPD when a pivot is
+ * not finite and above 8 N DBL_EPSILON a (coincident nodes), RVS_ST_NONFINITE for non-finite nodes,
+ * smoothing or values; the coefficients are then not to be used.
+ * Limits (RVS_E_ARG beyond, before any launch): 1 <= N <= RVS_RBF_MAX_N (the factor is
+ * N^2 doubles: 2 GiB there), 1 <= ndim <= 8, 1 <= S <= RVS_RBF_MAX_S,
+ * 1 <= M <= RVS_RBF_MAX_M, 0 < eps < 1e300.  rvs_rbf_work_size returns RVS_E_ARG. */
+#define RVS_RBF_MAX_N 16384
+#define RVS_RBF_MAX_S 1048576
+#define RVS_RBF_MAX_M 4194240
+int64_t rvs_rbf_work_size(int N, int S);
+int rvs_rbf_factor(const double *y, int N, int ndim, double eps,
+                   const double *smoothing, double *work, int32_t *status,
+                   void *stream);
+int rvs_rbf_solve(const void *d, int d_f32, int64_t d_stride, int N, int S,
+                  double *work, int32_t *status, void *stream);
+int rvs_rbf_eval(const double *x, int M, const double *y, int N, int ndim, double eps,
+                 const double *work, int S, int float_bits, void *out,
+                 int64_t out_stride, void *stream);
 
 #ifdef __cplusplus
 }

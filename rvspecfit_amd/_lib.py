@@ -103,11 +103,15 @@ SIGNATURES = {
     'rvs_rebin_weights': (I, [P, I, P, P, P, P, I, I, P, P]),
     'rvs_rebin_apply': (I, [P, I, L, I, I, P, P, I, P, P, P, I, I, P, P]),
     'rvs_template_normalize': (I, [P, I, I, P, I, D, D, I, I, P, P, P, P]),
+    'rvs_rbf_work_size': (L, [I, I]),
+    'rvs_rbf_factor': (I, [P, I, I, D, P, P, P, P]),
+    'rvs_rbf_solve': (I, [P, I, L, I, I, P, P, P]),
+    'rvs_rbf_eval': (I, [P, I, P, I, I, D, P, I, I, P, L, P]),
 }
 
 _lib = None
 # RVS_ABI_VERSION of the include/rvsgpu.h these signatures mirror
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class RvsGpuError(RuntimeError):
@@ -280,3 +284,4 @@ ST_ALLMASKED = 0x40
 ST_QUAD_ASSERT = 0x80
 ST_ILLCOND = 0x100
 ST_NONPOS_MEDIAN = 0x200
+ST_RBF_NOTPD = 0x400

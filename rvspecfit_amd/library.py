@@ -315,12 +315,17 @@ class TemplateLibrary:
     def from_models(cls, name, lam_hr, models, vec, setupInfo,
                     parnames=('teff', 'logg', 'feh', 'alpha'), air=False,
                     resolution0=100000, normalize='linear_continuum', float_bits=32,
-                    log_parameters=(0, ), ccf=None, device='cuda'):
+                    log_parameters=(0, ), ccf=None, regularize=None, device='cuda'):
         """A regular-grid library from high-resolution model spectra:
         make_interpol.build_specs (rvs_make_interpol),
         make_nd.regular_library (rvs_make_nd --regulargrid) and, with
         ccf = dict(ccfconf=..., every=..., vsinis=...), make_ccf.build_ccf_set
-        (rvs_make_ccf) attached by add_ccf_set.  Arguments as build_specs.  With
+        (rvs_make_ccf) attached by add_ccf_set.  Arguments as build_specs.
+        regularize = dict(smooth=..., min_feh=..., ..., step_alpha=...) (any subset, {}
+        for the reference's defaults) puts regularize_grid.regularize
+        (rvs_regularize_grid) between the first two: the holes of the model grid are
+        filled and the feh / alpha axes resampled before the library and the CCF set
+        are made.  With
         float_bits = 32 the rows never leave the device.  float_bits = 64 only serves
         the CCF set: build_ccf_set takes float64 rows from the host, so they make one
         round trip, and the library itself keeps float32 rows either way."""
@@ -329,6 +334,9 @@ class TemplateLibrary:
             lam_hr, models, vec, setupInfo, parnames=parnames, air=air,
             resolution0=resolution0, normalize=normalize, float_bits=float_bits,
             log_parameters=log_parameters, device=device)
+        if regularize is not None:
+            from . import regularize_grid
+            specs = regularize_grid.regularize(specs, **regularize)
         lib = cls(name, make_nd.regular_library(specs), device=device)
         if ccf is not None:
             if float_bits != 32:     # build_ccf_set takes float64 rows from the host

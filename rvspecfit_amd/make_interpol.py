@@ -267,12 +267,24 @@ def make_parser():
     p.add_argument('--nthreads', type=int, default=8, help='ignored')
     p.add_argument('--fixed_fwhm', action='store_true', default=False,
                    help='Keep the FWHM of the LSF constant rather than R')
+    p.add_argument('--regularize', action='store_true', default=False,
+                   help='Fill the gaps of the grid and resample its feh and alpha axes '
+                   '(rvs_regularize_grid) before the library is made')
+    for name, default, text in (('max_feh', 1.2, 'Max feh'), ('min_feh', -4, 'Min feh'),
+                                ('max_alpha', 1.2, 'Max alpha'),
+                                ('min_alpha', -.4, 'Min alpha'),
+                                ('step_feh', .25, 'step feh'),
+                                ('step_alpha', .2, 'step alpha'),
+                                ('smooth', 0., 'smoothing Parameter')):
+        p.add_argument('--' + name, type=float, default=default,
+                       help=text + ' (with --regularize)')
     return p
 
 
 def main(args=None):
-    """rvs_make_interpol + rvs_make_nd --regulargrid: writes <oprefix>/lib_<setup>.npz,
-    which TemplateLibrary.from_npz reads."""
+    """rvs_make_interpol (+ rvs_regularize_grid with --regularize) + rvs_make_nd
+    --regulargrid: writes <oprefix>/lib_<setup>.npz, which TemplateLibrary.from_npz
+    reads."""
     import os
     from . import fits_min, make_nd
     parser = make_parser()
@@ -302,6 +314,12 @@ def main(args=None):
                      args.log), parnames=parnames, air=args.air,
                     resolution0=args.resolution0, normalize=args.normalize,
                     float_bits=args.float_bits, log_parameters=log_parameters)
+    if args.regularize:
+        from . import regularize_grid
+        D = regularize_grid.regularize(
+            D, smooth=args.smooth, min_feh=args.min_feh, max_feh=args.max_feh,
+            step_feh=args.step_feh, min_alpha=args.min_alpha, max_alpha=args.max_alpha,
+            step_alpha=args.step_alpha)
     lib = make_nd.regular_library(D)
     lib['dats'] = lib['dats'].cpu().numpy()
     lib['revision'] = np.array(args.revision)

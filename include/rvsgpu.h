@@ -99,8 +99,10 @@ extern "C" {
  *      from high-resolution models)
  *  17: rvs_rbf_work_size, rvs_rbf_factor, rvs_rbf_solve, rvs_rbf_eval (multiquadric
  *      interpolation of template rows: regularize_grid); status bit 0x400 =
- *      RVS_ST_RBF_NOTPD */
-#define RVS_ABI_VERSION 17
+ *      RVS_ST_RBF_NOTPD
+ *  18: rvs_nn_train_work_size, rvs_nn_train_grad, rvs_nn_adam_step,
+ *      rvs_nn_train_epoch (training of the MLP rvs_template_nn evaluates) */
+#define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -1066,6 +1068,65 @@ int rvs_rbf_solve(const void *d, int d_f32, int64_t d_stride, int N, int S,
 int rvs_rbf_eval(const double *x, int M, const double *y, int N, int ndim, double eps,
                  const double *work, int S, int float_bits, void *out,
                  int64_t out_stride, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Training of the MLP that rvs_template_nn evaluates; replaces the optimiser loop of
+ * nn/train_interpolator.py:284-322 for NNInterpolator(withbn=False, SiLU)
+ * (nn/NNInterpolator.py:14-91): per batch  R = model(x) SD_0 + D_0,
+ * loss = mean|R - dat| / spread0, backward, torch.optim.Adam (betas 0.9 / 0.999,
+ * eps 1e-8, no weight decay).  float32 throughout (f32-input MFMA, exact products);
+ * every sum has a fixed order and no float atomics are used, so two runs from the same
+ * state give the same bits (csrc/nn_train.hip).
+ *
+ *   dats [T, npix] float32: training rows; x [T, ndim] float32: the Mapper's output
+ *   for them (nn/NNInterpolator.py:159-171); both stay where they are and are read by
+ *   row index (indices are clamped to [0, T)).
+ *   nlayer linear layers, dims int32 [nlayer + 1] (HOST; dims[0] = ndim, dims[nlayer] =
+ *   npix): SiLU behind every layer but the last.  W, b, dW, db, mW, mb, vW, vb: HOST
+ *   arrays of nlayer DEVICE pointers, W[l] [dims[l+1], dims[l]] row-major as
+ *   rvs_template_nn, the others of the same shapes (m*, v*: Adam's moments).
+ *   D0, SD0 float32 [npix] (train_interpolator.py:177-178), spread0 (:241).
+ *   work: rvs_nn_train_work_size(T, B, nlayer, dims) BYTES of device memory, 256-byte
+ *   aligned, the caller's (B: the largest batch it will be used with).
+ * Limits (RVS_E_ARG beyond, before any launch): 1 <= ndim <= 8, 2 <= nlayer <= 8,
+ * 1 <= hidden widths <= RVS_NN_TRAIN_MAX_WIDTH, 1 <= B <= RVS_NN_TRAIN_MAX_B,
+ * 1 <= npix <= RVS_NN_TRAIN_MAX_NPIX (RVS_REBIN_MAX_NPIX), T >= 1, spread0 > 0;
+ * rvs_nn_train_work_size returns RVS_E_ARG.
+ *
+ * rvs_nn_train_grad: forward and, when dW and db are not NULL, backward of ONE batch,
+ * the rows[0 .. nrows) (device int32) of dats / x; updates nothing.  loss (device
+ * double [1]) = mean|R - dat| / spread0; resid (nullable) float32 [nrows, npix] =
+ * R - dat; dW[l], db[l] = the gradients of loss (what autograd gives).  With dW == db ==
+ * NULL it is the evaluation loss of the rows (validation, train_interpolator.py:330-338).
+ *
+ * rvs_nn_adam_step: the update alone (torch/optim/adam.py: _single_tensor_adam) from
+ * given gradients; step >= 1 is the count the bias correction uses.
+ *
+ * rvs_nn_train_epoch: the steps of one epoch (train_interpolator.py:315-322) on
+ * `stream`, no host synchronisation: batch i is perm[i B .. min((i + 1) B, ntrain))
+ * (device int32; the last one short as DataLoader(drop_last=False), its loss normalised
+ * by its own size), step counts step0 + 1 ...  loss_accum (device double [1], ADDED
+ * to) += sum_i loss_i rows_i npix (lossAccum, :322); step_loss (nullable, device
+ * double [ceil(ntrain / B)]) = loss_i.  lr: the rate of this epoch. */
+#define RVS_NN_TRAIN_MAX_B 1024
+#define RVS_NN_TRAIN_MAX_WIDTH 1024
+#define RVS_NN_TRAIN_MAX_NPIX 9216
+int64_t rvs_nn_train_work_size(int T, int B, int nlayer, const int32_t *dims);
+int rvs_nn_train_grad(const float *dats, const float *x, int T, const int32_t *rows,
+                      int nrows, int nlayer, const int32_t *dims, const float *const *W,
+                      const float *const *b, const float *D0, const float *SD0,
+                      double spread0, float *const *dW, float *const *db, double *loss,
+                      float *resid, void *work, void *stream);
+int rvs_nn_adam_step(int nlayer, const int32_t *dims, float *const *W, float *const *b,
+                     const float *const *dW, const float *const *db, float *const *mW,
+                     float *const *mb, float *const *vW, float *const *vb, double lr,
+                     int step, void *stream);
+int rvs_nn_train_epoch(const float *dats, const float *x, int T, const int32_t *perm,
+                       int ntrain, int B, int nlayer, const int32_t *dims, float *const *W,
+                       float *const *b, float *const *mW, float *const *mb,
+                       float *const *vW, float *const *vb, const float *D0,
+                       const float *SD0, double spread0, double lr, int step0,
+                       double *loss_accum, double *step_loss, void *work, void *stream);
 
 #ifdef __cplusplus
 }

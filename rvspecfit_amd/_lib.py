@@ -107,11 +107,16 @@ SIGNATURES = {
     'rvs_rbf_factor': (I, [P, I, I, D, P, P, P, P]),
     'rvs_rbf_solve': (I, [P, I, L, I, I, P, P, P]),
     'rvs_rbf_eval': (I, [P, I, P, I, I, D, P, I, I, P, L, P]),
+    'rvs_nn_train_work_size': (L, [I, I, I, P]),
+    'rvs_nn_train_grad': (I, [P, P, I, P, I, I, P, P, P, P, P, D, P, P, P, P, P, P]),
+    'rvs_nn_adam_step': (I, [I, P, P, P, P, P, P, P, P, P, D, I, P]),
+    'rvs_nn_train_epoch': (I, [P, P, I, P, I, I, I, P, P, P, P, P, P, P, P, P, D, D, I,
+                               P, P, P, P]),
 }
 
 _lib = None
 # RVS_ABI_VERSION of the include/rvsgpu.h these signatures mirror
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class RvsGpuError(RuntimeError):

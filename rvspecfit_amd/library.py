@@ -315,8 +315,11 @@ class TemplateLibrary:
     def from_models(cls, name, lam_hr, models, vec, setupInfo,
                     parnames=('teff', 'logg', 'feh', 'alpha'), air=False,
                     resolution0=100000, normalize='linear_continuum', float_bits=32,
-                    log_parameters=(0, ), ccf=None, regularize=None, device='cuda'):
-        """A regular-grid library from high-resolution model spectra:
+                    log_parameters=(0, ), ccf=None, regularize=None, device='cuda',
+                    interpolation='regulargrid', nn_options=None):
+        """A library from high-resolution model spectra; interpolation = 'nn': the
+        MLP nn.train_interpolator.train makes of the rows (rvs_train_nn_interpolator;
+        nn_options: its keyword arguments), else a regular-grid library:
         make_interpol.build_specs (rvs_make_interpol),
         make_nd.regular_library (rvs_make_nd --regulargrid) and, with
         ccf = dict(ccfconf=..., every=..., vsinis=...), make_ccf.build_ccf_set
@@ -337,7 +340,15 @@ class TemplateLibrary:
         if regularize is not None:
             from . import regularize_grid
             specs = regularize_grid.regularize(specs, **regularize)
-        lib = cls(name, make_nd.regular_library(specs), device=device)
+        if interpolation == 'nn':
+            from .nn import train_interpolator
+            opts = dict(log_ids=tuple(log_parameters or ()), device=device)
+            opts.update(nn_options or {})
+            lib = cls(name, train_interpolator.train(specs, **opts), device=device)
+        elif interpolation == 'regulargrid':
+            lib = cls(name, make_nd.regular_library(specs), device=device)
+        else:
+            raise ValueError("interpolation is 'regulargrid' or 'nn'")
         if ccf is not None:
             if float_bits != 32:     # build_ccf_set takes float64 rows from the host
                 specs = dict(specs, specs=specs['specs'].cpu().numpy())

@@ -267,6 +267,9 @@ def make_parser():
     p.add_argument('--nthreads', type=int, default=8, help='ignored')
     p.add_argument('--fixed_fwhm', action='store_true', default=False,
                    help='Keep the FWHM of the LSF constant rather than R')
+    p.add_argument('--save_specs', action='store_true', default=False,
+                   help='also write specs_<setup>.npz, the rows '
+                   'rvspecfit_amd.nn.train_interpolator trains on')
     p.add_argument('--regularize', action='store_true', default=False,
                    help='Fill the gaps of the grid and resample its feh and alpha axes '
                    '(rvs_regularize_grid) before the library is made')
@@ -324,6 +327,12 @@ def main(args=None):
     lib['dats'] = lib['dats'].cpu().numpy()
     lib['revision'] = np.array(args.revision)
     os.makedirs(args.oprefix, exist_ok=True)
+    if args.save_specs:
+        np.savez(os.path.join(args.oprefix, 'specs_%s.npz' % args.setup),
+                 specs=torch.as_tensor(D['specs']).cpu().numpy(), vec=D['vec'], lam=D['lam'],
+                 parnames=np.array(D['parnames']), lognorms=D['lognorms'],
+                 log_step=np.array(D['log_step']), log_spec=np.array(D['log_spec']),
+                 log_ids=np.array(log_parameters, dtype=np.int64))
     fname = os.path.join(args.oprefix, 'lib_%s.npz' % args.setup)
     np.savez(fname, **lib)
     return fname

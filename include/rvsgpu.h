@@ -101,7 +101,11 @@ extern "C" {
  *      interpolation of template rows: regularize_grid); status bit 0x400 =
  *      RVS_ST_RBF_NOTPD
  *  18: rvs_nn_train_work_size, rvs_nn_train_grad, rvs_nn_adam_step,
- *      rvs_nn_train_epoch (training of the MLP rvs_template_nn evaluates) */
+ *      rvs_nn_train_epoch (training of the MLP rvs_template_nn evaluates)
+ *      (still 18: rvs_template_polylinear_grad, rvs_chisq_point_grad_work_size and
+ *      rvs_chisq_point_grad -- the objective's analytic gradient -- are additions;
+ *      no argument, status bit or work-size formula of an existing entry point
+ *      changed, so a caller built against 18 is served as before) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -167,6 +171,27 @@ int rvs_template_polylinear(const float *dats, int64_t ngrid, int ntp,
                             int exp_flag, const double *params, int B,
                             double *templ, double *outside, int32_t *cellinfo,
                             double *weights, void *stream);
+
+/* ... and its derivative with respect to the physical parameters.  Inside a cell
+ * GridInterp.__call__ (spec_inter.py:134-194) returns t = exp(sum_S w_S(p) L_S) with
+ * polylinear weights w_S of the mapped parameters (LogParamMapper.forward,
+ * read_grid.py:127-145), so  dt/dp_k = t * sum_S (dw_S/dp_k) L_S  -- a parameter in
+ * log_mask carries the factor 1/(p_k ln 10); without exp_flag the factor t is absent.
+ * templ  float64 [B, 1+ndim, ntp] out: row 0 the template (the bits of
+ *        rvs_template_polylinear, as are outside / cellinfo / weights), row 1+k
+ *        dt/dp_k per physical unit; the tangent rows are exactly 0 in the
+ *        nearest-neighbour modes (cellinfo mode 1 and 2), where the evaluator is
+ *        piecewise constant.  On a cell face the one-sided derivative of the cell
+ *        the search returns.
+ * Other arguments as rvs_template_polylinear. */
+int rvs_template_polylinear_grad(const float *dats, int64_t ngrid, int ntp,
+                                 const int64_t *idgrid, const double *uvecs,
+                                 const int32_t *lens, int ndim,
+                                 const double *vecs_s, const double *ptp,
+                                 uint32_t log_mask, int exp_flag,
+                                 const double *params, int B, double *templ,
+                                 double *outside, int32_t *cellinfo,
+                                 double *weights, void *stream);
 
 /* ------------------------------------------------------------------------
  * A3 on an irregular grid: Delaunay evaluator, replaces spec_inter.TriInterp
@@ -473,6 +498,40 @@ int rvs_chisq_point(const rvs_point_arm *arms, int narm, int npoly,
                     const int32_t *job_spec, const int32_t *job_templ, int J,
                     const double *vel, double badchi, void *scratch,
                     double *out, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------
+ * ... with its gradient: value and derivative of get_chisq (spec_fit.py:797-989;
+ * the marginalised chi^2 of get_chisq0, spec_fit.py:264-298) with respect to the
+ * job's velocity and the ntan parameters its template was differentiated by.
+ * One 256-thread block per (job, arm).
+ *   coef of every arm: [Tn, 1+ntan, ntp, 4] form-1 records -- row 0 the template,
+ *   row 1+k its tangent dt/dp_k (rvs_template_polylinear_grad through
+ *   rvs_vsini_convolve and rvs_spline_construct, which are linear in the rows).
+ *   The velocity tangent is S'(x) dx/dvel from the template's own record
+ *   (evalRV, spec_fit.py:403-405: x = lam sqrt((1-b)/(1+b)), b = vel/c).
+ * With ST = polys*m/e, A = ST ST^T, c = A^-1 ST D, r = D/e - c.ST the value is
+ * log det A + 2 sum log e + |r|^2, and for a tangent m' of the model
+ *   d chi^2 = sum_pix m'/e * ( 2 (m/e) polys^T A^-1 polys  -  2 r (c.polys) ),
+ * the first term being tr(A^-1 A'), the second c^T A' c - 2 c.v' of the normal
+ * equations with the residual formed explicitly.  A is factored once per block;
+ * every sum is folded in a fixed order (no atomics): repeated calls agree to the bit.
+ * polysT may be ANY basis of the continuum space; basis_const [narm] (host, or NULL)
+ * is added to the arm's value: 2 log|det R| when polysT holds the orthonormalised
+ * basis Q of polys^T = Q R (the gradient does not depend on the basis).
+ * grad [J, 1+ntan] out: {d/dvel, d/dp_0 ...} summed over the arms.  The penalty
+ * terms enter the value as in rvs_chisq_point and are not differentiated; an arm
+ * with a non finite penalty adds 1000*badchi and no gradient.  Where the
+ * factorisation fails: RVS_ST_CHOL_FALLBACK | RVS_ST_NONFINITE, value and gradient NaN.
+ * Restrictions (RVS_E_ARG otherwise): npoly <= 16, G <= 1, taps == NULL,
+ * fast_interp == 0, 0 <= ntan <= 6.
+ * scratch: rvs_chisq_point_grad_work_size(J, narm, ntan) bytes.
+ * ---------------------------------------------------------------------- */
+int64_t rvs_chisq_point_grad_work_size(int J, int narm, int ntan);
+int rvs_chisq_point_grad(const rvs_point_arm *arms, int narm, int npoly, int ntan,
+                         const int32_t *job_spec, const int32_t *job_templ, int J,
+                         const double *vel, double badchi,
+                         const double *basis_const, void *scratch, double *out,
+                         double *grad, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------
  * The same objective as ONE kernel per evaluation for regular-grid libraries:

@@ -25,6 +25,8 @@ SIGNATURES = {
     'rvs_option_get': (I, [ctypes.c_char_p, P]),
     'rvs_template_polylinear': (I, [P, L, I, P, P, P, I, P, P, U, I, P, I, P, P,
                                     P, P, P]),
+    'rvs_template_polylinear_grad': (I, [P, L, I, P, P, P, I, P, P, U, I, P, I, P,
+                                         P, P, P, P]),
     'rvs_template_tri': (I, [P, I, P, P, P, I, I, U, I, P, I, P, P, P, P, P]),
     'rvs_template_tri_buckets': (I, [P, I, P, P, P, I, I, U, I, P, P, I, P, P, P,
                                      P, P]),
@@ -55,6 +57,8 @@ SIGNATURES = {
     'rvs_chisq_continuum': (I, [P, P, P, P, P, I, I, I, P, P, P, P, P, P]),
     'rvs_chisq_point_work_size': (L, [I, I]),
     'rvs_chisq_point': (I, [P, I, I, P, P, I, P, D, P, P, P, P]),
+    'rvs_chisq_point_grad_work_size': (L, [I, I, I]),
+    'rvs_chisq_point_grad': (I, [P, I, I, I, P, P, I, P, D, P, P, P, P, P, P]),
     'rvs_nm_begin': (I, [I, I, D, D, I, P, P, P, P, P, P, P, I, P]),
     'rvs_nm_decide': (I, [I, P, P, P, P, P, P, P, P, P, I, P]),
     'rvs_nm_update': (I, [I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P]),

@@ -2143,6 +2143,313 @@ extern "C" int rvs_chisq_point(const rvs_point_arm *arms, int narm, int npoly,
 }
 
 // ---------------------------------------------------------------------------
+// The same objective with its gradient (include/rvsgpu.h, rvs_chisq_point_grad).
+// Layout as point_block_kernel: one 256-thread block per (job, arm), threads =
+// pixels.  Pass 1 accumulates A and v (P(P+1)/2 + P sums per lane, folded per wave
+// by DPP and across the four waves through LDS in a fixed order); EVERY wave then
+// factors the same matrix, so that the Cholesky factor sits in the registers of
+// all 256 lanes for pass 2.  Pass 2 forms per pixel the residual r, s = c.phi and
+// q = |L^-1 phi|^2 = phi^T A^-1 phi, i.e. the adjoint of the model value
+//     mbar = 2 (m/e^2) q - 2 r s / e
+// and accumulates |r|^2 and the 1 + NTAN products mbar * m'_k.  That is
+// tr(A^-1 A'_k) + c^T A'_k c - 2 c.v'_k without ever forming A'_k and v'_k: the
+// (P(P+1)/2 + P)(1 + K) sums of the tangent normal equations (1216 at P = 16, K = 7:
+// more than a lane's registers or a block's LDS slots per lane hold) become 2 + K,
+// and the residual enters explicitly, as in the value, instead of as a difference.
+// ---------------------------------------------------------------------------
+#define GRAD_MAXTAN 6   // the parameters of a regular-grid library (MAXDIM)
+template <int P>
+__global__ void __launch_bounds__(256)
+    point_grad_block_kernel(PointArms A, int ntan,
+                            const int32_t *__restrict__ job_spec,
+                            const int32_t *__restrict__ job_templ, int J,
+                            const double *__restrict__ vel,
+                            double *__restrict__ armchi,
+                            double *__restrict__ armgrad,
+                            int32_t *__restrict__ armst) {
+  constexpr int NT = P * (P + 1) / 2;
+  constexpr int NV = NT + P;
+  constexpr int NR = NV > 2 + GRAD_MAXTAN ? NV : 2 + GRAD_MAXTAN;
+  __shared__ double red[4][NR + 1];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int j = blockIdx.x;
+  const rvs_point_arm &T = A.a[blockIdx.y];
+  const int s = job_spec ? job_spec[j] : j;
+  const int t = job_templ ? job_templ[j] : j;
+  const ArmGrid AG = arm_grid(T, s);
+  const double bb = vel[j] / RVS_C_KMS;
+  const double f = sqrt((1.0 - bb) / (1.0 + bb));
+  // dx/dvel = lam * df/dvel,  d ln f / d beta = -1 / (1 - beta^2)
+  const double dfdv = -f / (RVS_C_KMS * (1.0 - bb * bb));
+  const double espec_sys = T.espec_sys;
+  const double sys2 = espec_sys * espec_sys;
+  const int npix = T.npix, K = 1 + ntan;
+  const double *sp = T.spec + (int64_t)s * npix;
+  const double *es = T.espec + (int64_t)s * npix;
+  const double4 *cf = reinterpret_cast<const double4 *>(T.coef) +
+                      (int64_t)t * K * T.ntp;
+  const double x0 = T.knots[0], xlast = T.knots[T.ntp - 1];
+  const double shift = T.log_step ? log(f) / log(T.knots[1] / x0) : 0.0;
+  const double lin_inv_step = T.log_step ? 0.0 : 1.0 / (T.knots[1] - x0);
+  double acc[NT];
+  double av[P];
+#pragma unroll
+  for (int i = 0; i < NT; i++) acc[i] = 0;
+#pragma unroll
+  for (int i = 0; i < P; i++) av[i] = 0;
+  for (int k = threadIdx.x; k < npix; k += 256) {
+    const double tv = point_tv(T, AG, cf, k, f, shift, x0, lin_inv_step);
+    double e = es[k];
+    if (espec_sys > 0) e = sqrt(sys2 + e * e);
+    const double ie = 1.0 / e;
+    const double te = tv * ie;
+    const double wt = te * te, u = te * (sp[k] * ie);
+    const double *pr = AG.polysT + (int64_t)k * P;
+    double pv[P], pw[P];
+#pragma unroll
+    for (int i = 0; i < P; i++) {
+      pv[i] = pr[i];
+      pw[i] = pv[i] * wt;
+    }
+#pragma unroll
+    for (int i = 0; i < P; i++) {
+      av[i] = fma(pv[i], u, av[i]);
+#pragma unroll
+      for (int jj = 0; jj <= i; jj++)
+        acc[TRI(i, jj)] = fma(pv[i], pw[jj], acc[TRI(i, jj)]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NT; i++) {
+    const double v = wave_sum_to63(acc[i]);
+    if (lane == 63) red[w][i] = v;
+  }
+#pragma unroll
+  for (int i = 0; i < P; i++) {
+    const double v = wave_sum_to63(av[i]);
+    if (lane == 63) red[w][NT + i] = v;
+  }
+  __syncthreads();
+  // every lane of every wave factors the same matrix (waves summed in order)
+#pragma unroll
+  for (int i = 0; i < NT; i++)
+    acc[i] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+#pragma unroll
+  for (int i = 0; i < P; i++)
+    av[i] = ((red[0][NT + i] + red[1][NT + i]) + red[2][NT + i]) +
+            red[3][NT + i];
+  bool ok = true;
+  double ldet = 0;
+  double idg[P];  // 1 / L_ii
+#pragma unroll
+  for (int i = 0; i < P; i++) {
+#pragma unroll
+    for (int jj = 0; jj <= i; jj++) {
+      double sum = acc[TRI(i, jj)];
+#pragma unroll
+      for (int q = 0; q < jj; q++) sum -= acc[TRI(i, q)] * acc[TRI(jj, q)];
+      if (jj == i) {
+        if (!(sum > 0)) ok = false;
+        const double d = sqrt(sum);
+        acc[TRI(i, i)] = d;
+        idg[i] = 1.0 / d;
+        ldet += log(d);
+      } else {
+        acc[TRI(i, jj)] = sum / acc[TRI(jj, jj)];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < P; i++) {
+    double sum = av[i];
+#pragma unroll
+    for (int q = 0; q < i; q++) sum -= acc[TRI(i, q)] * av[q];
+    av[i] = sum / acc[TRI(i, i)];
+  }
+#pragma unroll
+  for (int i = P - 1; i >= 0; i--) {
+    double sum = av[i];
+#pragma unroll
+    for (int q = i + 1; q < P; q++) sum -= acc[TRI(q, i)] * av[q];
+    av[i] = sum / acc[TRI(i, i)];
+  }
+  double rr = 0;
+  double gk[1 + GRAD_MAXTAN];
+#pragma unroll
+  for (int i = 0; i <= GRAD_MAXTAN; i++) gk[i] = 0;
+  for (int k = threadIdx.x; k < npix; k += 256) {
+    // the template and its velocity tangent from one record (point_tv's index)
+    const double x = AG.lam[k] * f;
+    int pos = T.log_step ? (int)(AG.pix[k] + shift)
+                         : (int)((x - x0) * lin_inv_step);
+    pos = min(max(pos, 0), T.ntp - 2);
+    const double dl = x - T.knots[pos];
+    const double4 c0 = cf[pos];
+    const double tv = fma(fma(fma(c0.w, dl, c0.z), dl, c0.y), dl, c0.x);
+    const double dtv = fma(dl, fma(3.0 * c0.w, dl, 2.0 * c0.z), c0.y);
+    double e = es[k];
+    if (espec_sys > 0) e = sqrt(sys2 + e * e);
+    const double ie = 1.0 / e;
+    const double *pr = AG.polysT + (int64_t)k * P;
+    double y[P];
+    double m = 0, q = 0;
+#pragma unroll
+    for (int i = 0; i < P; i++) {
+      const double ph = pr[i];
+      m = fma(av[i], ph, m);
+      double sum = ph;
+#pragma unroll
+      for (int qq = 0; qq < i; qq++) sum = fma(-acc[TRI(i, qq)], y[qq], sum);
+      y[i] = sum * idg[i];
+      q = fma(y[i], y[i], q);
+    }
+    const double r = sp[k] * ie - m * (tv * ie);
+    rr = fma(r, r, rr);
+    const double mbar = 2.0 * ie * ((tv * ie) * q - r * m);
+    gk[0] = fma(mbar, dtv * (AG.lam[k] * dfdv), gk[0]);
+#pragma unroll
+    for (int i = 1; i <= GRAD_MAXTAN; i++)
+      if (i < K) {
+        const double4 c = cf[(int64_t)i * T.ntp + pos];
+        gk[i] = fma(mbar, fma(fma(fma(c.w, dl, c.z), dl, c.y), dl, c.x), gk[i]);
+      }
+  }
+  __syncthreads();   // (red is read above by every wave)
+  {
+    const double v = wave_sum_to63(rr);
+    if (lane == 63) red[w][0] = v;
+  }
+#pragma unroll
+  for (int i = 0; i <= GRAD_MAXTAN; i++) {
+    const double v = wave_sum_to63(gk[i]);
+    if (lane == 63) red[w][1 + i] = v;
+  }
+  __syncthreads();
+  const int64_t o = (int64_t)blockIdx.y * J + j;
+  const double xa = AG.lam[0] * f, xb = AG.lam[npix - 1] * f;
+  const bool range = xa < x0 || xb < x0 || xa >= xlast || xb >= xlast;
+  rr = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+  const double lz = AG.wbase[2ll * T.S * npix + 2 * s];
+  double chi = 2.0 * ldet + 2.0 * lz + rr;
+  int st = 0;
+  if (range) {
+    st |= RVS_ST_SPLINE_RANGE;
+    chi = __builtin_nan("");
+  }
+  if (!ok) st |= RVS_ST_CHOL_FALLBACK;
+  if (!ok || !(fabs(chi) <= 1.79e308)) {
+    st |= RVS_ST_NONFINITE;
+    chi = __builtin_nan("");
+  }
+  if (threadIdx.x == 0) {
+    armchi[o] = chi;
+    armst[o] = st;
+  }
+  if (threadIdx.x < K) {
+    const int i = threadIdx.x;
+    const double g = ((red[0][1 + i] + red[1][1 + i]) + red[2][1 + i]) + red[3][1 + i];
+    armgrad[o * K + i] = (chi == chi) ? g : __builtin_nan("");
+  }
+}
+
+// arms summed in order; penalties of A11 (spec_fit.py:888-896) on the value only
+__global__ void point_grad_sum_kernel(PointArms A, int J, int K, double badchi,
+                                      double4 bconst,
+                                      const int32_t *__restrict__ job_spec,
+                                      const double *__restrict__ armchi,
+                                      const double *__restrict__ armgrad,
+                                      const int32_t *__restrict__ armst,
+                                      double *__restrict__ out,
+                                      double *__restrict__ grad,
+                                      int32_t *__restrict__ status) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= J) return;
+  if (A.a[0].pen_scale) badchi *= A.a[0].pen_scale[job_spec ? job_spec[j] : j];
+  const double bc[RVS_MAX_ARMS] = {bconst.x, bconst.y, bconst.z, bconst.w};
+  double tot = 0;
+  double g[1 + GRAD_MAXTAN];
+#pragma unroll
+  for (int i = 0; i <= GRAD_MAXTAN; i++) g[i] = 0;
+  int st = 0;
+#pragma unroll
+  for (int ia = 0; ia < RVS_MAX_ARMS; ia++) {
+    if (ia >= A.n) break;
+    const double *pp = A.a[ia].penalty;
+    const double pen = pp ? pp[j] : 0.0;
+    if (!(pen == pen) || isinf(pen)) {
+      tot += 1000.0 * badchi;
+      continue;
+    }
+    const int64_t o = (int64_t)ia * J + j;
+    tot += armchi[o] + bc[ia] + pen;
+    st |= armst[o];
+#pragma unroll
+    for (int i = 0; i <= GRAD_MAXTAN; i++)
+      if (i < K) g[i] += armgrad[o * K + i];
+  }
+  out[j] = tot;
+#pragma unroll
+  for (int i = 0; i <= GRAD_MAXTAN; i++)
+    if (i < K) grad[(int64_t)j * K + i] = g[i];
+  if (st) atomicOr(&status[j], st);
+}
+
+extern "C" int64_t rvs_chisq_point_grad_work_size(int J, int narm, int ntan) {
+  if (J < 1 || narm < 1 || ntan < 0 || ntan > GRAD_MAXTAN) return 0;
+  return (int64_t)narm * J *
+         (int64_t)((2 + ntan) * sizeof(double) + sizeof(int32_t));
+}
+
+extern "C" int rvs_chisq_point_grad(const rvs_point_arm *arms, int narm, int npoly,
+                                    int ntan, const int32_t *job_spec,
+                                    const int32_t *job_templ, int J,
+                                    const double *vel, double badchi,
+                                    const double *basis_const, void *scratch,
+                                    double *out, double *grad, int32_t *status,
+                                    void *stream) {
+  if (J < 1 || narm < 1 || narm > RVS_MAX_ARMS || !arms || !scratch ||
+      ntan < 0 || ntan > GRAD_MAXTAN)
+    return RVS_E_ARG;
+  static_assert(RVS_MAX_ARMS == 4, "basis constants travel as a double4");
+  PointArms A;
+  A.n = narm;
+  double bc[RVS_MAX_ARMS] = {0, 0, 0, 0};
+  for (int i = 0; i < narm; i++) {
+    A.a[i] = arms[i];
+    if (arms[i].npix < 1 || arms[i].ntp < 3 || arms[i].G > 1 || arms[i].taps ||
+        arms[i].fast_interp)
+      return RVS_E_ARG;
+    if (basis_const) bc[i] = basis_const[i];
+  }
+  for (int i = narm; i < RVS_MAX_ARMS; i++) A.a[i] = arms[0];
+  hipStream_t st = rvs_stream(stream);
+  const int K = 1 + ntan;
+  double *armchi = (double *)scratch;
+  double *armgrad = armchi + (int64_t)narm * J;
+  int32_t *armst = (int32_t *)(armgrad + (int64_t)narm * J * K);
+  dim3 grid(J, narm);
+#define RVS_CASE(PP)                                                           \
+  case PP:                                                                     \
+    hipLaunchKernelGGL(point_grad_block_kernel<PP>, grid, dim3(256), 0, st, A, \
+                       ntan, job_spec, job_templ, J, vel, armchi, armgrad,     \
+                       armst);                                                 \
+    break;
+  switch (npoly) {
+    RVS_CASE(1) RVS_CASE(2) RVS_CASE(3) RVS_CASE(4) RVS_CASE(5) RVS_CASE(6)
+    RVS_CASE(7) RVS_CASE(8) RVS_CASE(9) RVS_CASE(10) RVS_CASE(11) RVS_CASE(12)
+    RVS_CASE(13) RVS_CASE(14) RVS_CASE(15) RVS_CASE(16)
+    default:
+      return RVS_E_ARG;
+  }
+#undef RVS_CASE
+  hipLaunchKernelGGL(point_grad_sum_kernel, dim3((J + 255) / 256), dim3(256), 0,
+                     st, A, J, K, badchi, make_double4(bc[0], bc[1], bc[2], bc[3]),
+                     job_spec, armchi, armgrad, armst, out, grad, status);
+  RVS_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // A12: find_best tail (spec_fit.py:1072-1092).  One 256-thread block / group.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)

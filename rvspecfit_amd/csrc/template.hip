@@ -13,6 +13,11 @@
 // float32 rows of `dats`: consecutive lanes read consecutive pixels (coalesced
 // 4-B loads; rows are re-read by every spectrum sharing a cell and stay in L2 /
 // Infinity Cache).  Accumulation is float64 in vertex (itertools.product) order.
+// GRAD: `templ` is [B, 1 + ndim, ntp] -- behind the template row the ndim tangent
+// rows dt/dp_k = t * sum_v (dw_v/dp_k) L_v per PHYSICAL unit of p_k (the chain
+// through log10 of a log_mask parameter included), zero in the nearest-neighbour
+// modes; the template row is accumulated by the same statements either way.
+template <bool GRAD>
 __global__ void __launch_bounds__(256)
     polylinear_kernel(const float *__restrict__ dats, int64_t ngrid, int ntp,
                       const int64_t *__restrict__ idgrid,
@@ -31,7 +36,26 @@ __global__ void __launch_bounds__(256)
   int64_t *sh_id = PL.id;
   const int sh_nearest = PL.nearest;
   const double sh_dist = PL.dist;
-  double *out = templ + (int64_t)b * ntp;
+  double *out = templ + (int64_t)b * ntp * (GRAD ? 1 + nd : 1);
+  // dw_v/dp_d [d][v]: the weight's factor of dimension d replaced by -+1/(cell width)
+  __shared__ double sh_dw[GRAD ? (MAXDIM << MAXDIM) : 1];
+  if constexpr (GRAD) {
+    if (mode == 0) {
+      for (int i = tid; i < nd * nv; i += 256) {
+        const int d = i >> nd, v = i & (nv - 1);
+        const double *u = uvecs + sel_dim(G.uoff, d);
+        const int p = PL.pos[d];
+        double w = 1.0 / (u[p + 1] - u[p]);
+        if (G.log_mask & (1u << d))
+          w /= params[(int64_t)b * nd + d] * 2.302585092994046;
+        if (!((v >> (nd - 1 - d)) & 1)) w = -w;
+        for (int e = 0; e < nd; e++)
+          if (e != d) w *= ((v >> (nd - 1 - e)) & 1) ? PL.x[e] : (1 - PL.x[e]);
+        sh_dw[d * nv + v] = w;
+      }
+    }
+    __syncthreads();
+  }
   double mx = 0;
   bool anynan = false;
   if (mode == 0) {
@@ -41,6 +65,7 @@ __global__ void __launch_bounds__(256)
     const int n4 = ntp & ~3;
     for (int k = 4 * tid; k < n4; k += 4 * 256) {
       double a4[4] = {0, 0, 0, 0};
+      double g4[GRAD ? MAXDIM : 1][4] = {};
       for (int v = 0; v < nv; v++) {
         const f4u r = *reinterpret_cast<const f4u *>(dats + sh_id[v] * ntp + k);
         const double wv = sh_w[v];
@@ -48,17 +73,49 @@ __global__ void __launch_bounds__(256)
         a4[1] = fma(wv, (double)r.y, a4[1]);
         a4[2] = fma(wv, (double)r.z, a4[2]);
         a4[3] = fma(wv, (double)r.w, a4[3]);
+        if constexpr (GRAD) {
+#pragma unroll
+          for (int d = 0; d < MAXDIM; d++)
+            if (d < nd) {
+              const double dv = sh_dw[d * nv + v];
+              g4[d][0] = fma(dv, (double)r.x, g4[d][0]);
+              g4[d][1] = fma(dv, (double)r.y, g4[d][1]);
+              g4[d][2] = fma(dv, (double)r.z, g4[d][2]);
+              g4[d][3] = fma(dv, (double)r.w, g4[d][3]);
+            }
+        }
       }
 #pragma unroll
-      for (int q = 0; q < 4; q++) out[k + q] = exp_flag ? exp(a4[q]) : a4[q];
+      for (int q = 0; q < 4; q++) {
+        const double tq = exp_flag ? exp(a4[q]) : a4[q];
+        out[k + q] = tq;
+        if constexpr (GRAD) {
+#pragma unroll
+          for (int d = 0; d < MAXDIM; d++)
+            if (d < nd)
+              out[(int64_t)(1 + d) * ntp + k + q] = exp_flag ? tq * g4[d][q] : g4[d][q];
+        }
+      }
     }
     for (int k = n4 + tid; k < ntp; k += 256) {
       double acc = 0;
       for (int v = 0; v < nv; v++)
         acc = fma(sh_w[v], (double)dats[sh_id[v] * ntp + k], acc);
-      out[k] = exp_flag ? exp(acc) : acc;
+      const double tq = exp_flag ? exp(acc) : acc;
+      out[k] = tq;
+      if constexpr (GRAD) {
+        for (int d = 0; d < nd; d++) {
+          double g = 0;
+          for (int v = 0; v < nv; v++)
+            g = fma(sh_dw[d * nv + v], (double)dats[sh_id[v] * ntp + k], g);
+          out[(int64_t)(1 + d) * ntp + k] = exp_flag ? tq * g : g;
+        }
+      }
     }
   } else {
+    if constexpr (GRAD) {
+      for (int k = tid; k < nd * ntp; k += 256) out[ntp + k] = 0.0;
+    }
     // FF(self.dats[ret]) on a float32 row: numpy evaluates exp in float32
     const float *row = dats + (int64_t)sh_nearest * ntp;
     for (int k = tid; k < ntp; k += 256) {
@@ -98,7 +155,8 @@ __global__ void __launch_bounds__(256)
     weights[(int64_t)b * nv + tid] = (mode == 0) ? sh_w[tid] : 0.0;
 }
 
-extern "C" int rvs_template_polylinear(
+template <bool GRAD>
+static int polylinear_launch(
     const float *dats, int64_t ngrid, int ntp, const int64_t *idgrid,
     const double *uvecs, const int32_t *lens, int ndim, const double *vecs_s,
     const double *ptp, uint32_t log_mask, int exp_flag,
@@ -120,11 +178,34 @@ extern "C" int rvs_template_polylinear(
     G.gstride[d] = st;
     st *= lens[d];
   }
-  hipLaunchKernelGGL(polylinear_kernel, dim3(B), dim3(256), 0,
+  hipLaunchKernelGGL(polylinear_kernel<GRAD>, dim3(B), dim3(256), 0,
                      rvs_stream(stream), dats, ngrid, ntp, idgrid, uvecs, G,
                      vecs_s, exp_flag, params, templ, outside, cellinfo, weights);
   RVS_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int rvs_template_polylinear(
+    const float *dats, int64_t ngrid, int ntp, const int64_t *idgrid,
+    const double *uvecs, const int32_t *lens, int ndim, const double *vecs_s,
+    const double *ptp, uint32_t log_mask, int exp_flag,
+    const double *params, int B, double *templ, double *outside,
+    int32_t *cellinfo, double *weights, void *stream) {
+  return polylinear_launch<false>(dats, ngrid, ntp, idgrid, uvecs, lens, ndim,
+                                  vecs_s, ptp, log_mask, exp_flag, params, B,
+                                  templ, outside, cellinfo, weights, stream);
+}
+
+// spec_inter.py:134-194 differentiated: templ [B, 1 + ndim, ntp]
+extern "C" int rvs_template_polylinear_grad(
+    const float *dats, int64_t ngrid, int ntp, const int64_t *idgrid,
+    const double *uvecs, const int32_t *lens, int ndim, const double *vecs_s,
+    const double *ptp, uint32_t log_mask, int exp_flag,
+    const double *params, int B, double *templ, double *outside,
+    int32_t *cellinfo, double *weights, void *stream) {
+  return polylinear_launch<true>(dats, ngrid, ntp, idgrid, uvecs, lens, ndim,
+                                 vecs_s, ptp, log_mask, exp_flag, params, B,
+                                 templ, outside, cellinfo, weights, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -615,25 +615,39 @@ def _chunks(n, size):
 # --------------------------------------------------------------------------
 # template construction: A3/A4 -> A6 -> A7-construct
 # --------------------------------------------------------------------------
-def build_templates(lib, params, vsini=None, return_templ=False):
+def build_templates(lib, params, vsini=None, return_templ=False, tangents=False):
     """params [J, ndim] f64 device; vsini [J] f64 device or None.
-    Returns coef [J, ntp, 4], outside [J] (+ the broadened template)."""
+    Returns coef [J, ntp, 4], outside [J] (+ the broadened template).
+    tangents: the template AND its derivative with respect to each parameter,
+    coef [J, 1 + ndim, ntp, 4] (templ [J, 1 + ndim, ntp]) -- the broadening and the
+    spline construction are linear in the rows, so the tangent rows go through the
+    same two launches as rows of their own (vsini is held fixed)."""
     L = _lib.lib()
     J = params.shape[0]
-    templ, outside = lib.eval_batch(params)
+    R = 1
+    if tangents:
+        templ, outside = lib.eval_batch_grad(params)
+        R = 1 + lib.ndim
+    else:
+        templ, outside = lib.eval_batch(params)
     if vsini is not None:
         out = torch.empty_like(templ)
         vsini = vsini.to(torch.float64).contiguous()
-        rc = L.rvs_vsini_convolve(_lib.ptr(templ), _lib.ptr(vsini),
-                                  _lib.ptr(outside), lib.lnstep, 0.6, lib.ntp,
-                                  J, _lib.ptr(out), _lib.stream())
+        # (one vsini / outside flag per ROW of the launch)
+        vs_r = vsini if R == 1 else vsini.repeat_interleave(R)
+        out_r = outside if R == 1 else outside.repeat_interleave(R)
+        rc = L.rvs_vsini_convolve(_lib.ptr(templ), _lib.ptr(vs_r),
+                                  _lib.ptr(out_r), lib.lnstep, 0.6, lib.ntp,
+                                  J * R, _lib.ptr(out), _lib.stream())
         _lib.check(rc, 'rvs_vsini_convolve')
         templ = out
-    coef = torch.empty((J, lib.ntp, 4), dtype=torch.float64, device=lib.device)
+    shape = (J, lib.ntp, 4) if R == 1 else (J, R, lib.ntp, 4)
+    coef = torch.empty(shape, dtype=torch.float64, device=lib.device)
     # form 1: power-form records {y, b, c, d} consumed by the chi^2 kernels;
     # | 2: windowed solve, valid for the (log-)uniform grid of a library
-    rc = L.rvs_spline_construct(_lib.ptr(lib.knots), _lib.ptr(templ), lib.ntp, J,
-                                lib.spline_form, _lib.ptr(lib.spline_factors),
+    rc = L.rvs_spline_construct(_lib.ptr(lib.knots), _lib.ptr(templ), lib.ntp,
+                                J * R, lib.spline_form,
+                                _lib.ptr(lib.spline_factors),
                                 _lib.ptr(coef), _lib.stream())
     _lib.check(rc, 'rvs_spline_construct')
     if return_templ:
@@ -920,6 +934,81 @@ def chisq_point(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
                                _lib.ptr(status), _lib.stream())
         _lib.check(rc, 'rvs_chisq_point')
     return out, status
+
+
+def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False):
+    """ValueError naming what rvs_chisq_point_grad does not cover"""
+    if npoly > POINT_MAXP:
+        raise ValueError('the analytic gradient takes npoly <= %d, not %d'
+                         % (POINT_MAXP, npoly))
+    if fast_interp:
+        raise ValueError('the analytic gradient does not take fast_interp (the '
+                         'nearest-knot template has no velocity derivative)')
+    for ia, arm in enumerate(batch.arms):
+        if _arm_resol(arm, ia, resols) is not None:
+            raise ValueError('the analytic gradient does not take a resolution '
+                             'matrix (arm %s)' % arm.name)
+        if arm.G > 1:
+            raise ValueError('the analytic gradient does not take a grid set: arm '
+                             '%s has %d wavelength grids' % (arm.name, arm.G))
+        if libs[arm.name].kind != 'regulargrid':
+            raise ValueError('the analytic gradient needs regular-grid (polylinear) '
+                             'libraries, %s is a %s library'
+                             % (arm.name, libs[arm.name].kind))
+
+
+def chisq_point_grad(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
+                     job_spec=None, job_templ=None, espec_sys=0.0,
+                     outside_penalty=True, resols=None, fast_interp=False):
+    """chisq_point with the gradient (rvs_chisq_point_grad): coefs[ia] are the
+    [Tn, 1 + ndim, ntp, 4] records of build_templates(..., tangents=True).
+    Returns chisq [J] (the value of chisq_point, evaluated in the orthonormal
+    continuum basis), grad [J, 1 + ndim] = d chisq / d (vel, parameters) in
+    physical units, status int32 [J].  The outside penalty is piecewise and is
+    not differentiated.  What the kernel does not cover is refused, never
+    finite-differenced: npoly > 16, several wavelength grids per arm, a
+    resolution matrix, fast_interp, libraries that are not regular grids."""
+    import ctypes
+    check_grad_scope(batch, libs, npoly, resols, fast_interp)
+    narm = len(batch.arms)
+    L = _lib.lib()
+    dev = batch.device
+    vel = vel.to(device=dev, dtype=torch.float64).contiguous()
+    J = vel.shape[0]
+    ntan = coefs[0].shape[1] - 1
+    assert all(c.dim() == 4 and c.shape[1] == 1 + ntan for c in coefs)
+    out = torch.empty(J, dtype=torch.float64, device=dev)
+    grad = torch.empty((J, 1 + ntan), dtype=torch.float64, device=dev)
+    status = torch.zeros(J, dtype=torch.int32, device=dev)
+    nb = L.rvs_chisq_point_grad_work_size(J, narm, ntan)
+    scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
+    arr = (_lib.PointArm * narm)()
+    bconst = (ctypes.c_double * narm)()
+    keep = []
+    esys = _per_arm(espec_sys, narm)
+    for ia, arm in enumerate(batch.arms):
+        o = outsides[ia]
+        if job_templ is not None:
+            o = o[job_templ.long()]
+        pen = o * batch.badchi_jobs(job_spec) if outside_penalty else torch.where(
+            torch.isfinite(o), torch.zeros_like(o), o)
+        keep.append(fill_point_arm(arr[ia], arm, libs[arm.name], npoly, rbf,
+                                   esys[ia], None, coefs[ia], pen.contiguous()))
+        # the orthonormal basis of the same space (ArmData.basis_ortho): the value
+        # differs by the constant handed over beside it, the gradient not at all
+        qt, const = arm.basis_ortho(npoly, rbf)
+        arr[ia].polysT = qt.data_ptr()
+        bconst[ia] = const
+        keep.append(qt)
+    with _ktime('chisq_point_grad', J):
+        rc = L.rvs_chisq_point_grad(ctypes.addressof(arr), narm, npoly, ntan,
+                                    _lib.ptr(job_spec), _lib.ptr(job_templ), J,
+                                    _lib.ptr(vel), float(batch.badchi),
+                                    ctypes.addressof(bconst), _lib.ptr(scratch),
+                                    _lib.ptr(out), _lib.ptr(grad),
+                                    _lib.ptr(status), _lib.stream())
+        _lib.check(rc, 'rvs_chisq_point_grad')
+    return out, grad, status
 
 
 def fill_point_arm(p, arm, lib, npoly, rbf, espec_sys=0.0, resol=None, coef=None,

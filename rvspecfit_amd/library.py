@@ -398,6 +398,38 @@ class TemplateLibrary:
             return templ, outside, cell, wts
         return templ, outside
 
+    def eval_batch_grad(self, params, details=False):
+        """eval_batch with the derivative: templ [J, 1 + ndim, ntp] -- row 0 the
+        template (the bits of eval_batch), row 1 + k its derivative with respect
+        to physical parameter k (rvs_template_polylinear_grad; zero rows where
+        the evaluator answers with the nearest grid point) -- and outside [J].
+        Regular-grid libraries only."""
+        if self.kind != 'regulargrid':
+            raise ValueError('template tangents need a regular-grid (polylinear) '
+                             'library, %s is a %s library' % (self.name, self.kind))
+        L = _lib.lib()
+        J = params.shape[0]
+        params = params.to(torch.float64).contiguous()
+        templ = torch.empty((J, 1 + self.ndim, self.ntp), dtype=torch.float64,
+                            device=self.device)
+        outside = torch.empty(J, dtype=torch.float64, device=self.device)
+        nv = 1 << self.ndim
+        cell = wts = None
+        if details:
+            cell = torch.zeros((J, 2 + nv), dtype=torch.int32,
+                               device=self.device)
+            wts = torch.zeros((J, nv), dtype=torch.float64, device=self.device)
+        rc = L.rvs_template_polylinear_grad(
+            _lib.ptr(self.dats), self.ngrid, self.ntp, _lib.ptr(self.idgrid),
+            _lib.ptr(self.uvecs), _lib.ptr(self.lens), self.ndim,
+            _lib.ptr(self.vecs_s), _lib.ptr(self.ptp), self.log_mask,
+            self.exp_flag, _lib.ptr(params), J, _lib.ptr(templ),
+            _lib.ptr(outside), _lib.ptr(cell), _lib.ptr(wts), _lib.stream())
+        _lib.check(rc, 'rvs_template_polylinear_grad')
+        if details:
+            return templ, outside, cell, wts
+        return templ, outside
+
     def _tri_call(self, log_mask, params, J, templ, outside, sx, wts, stream):
         import ctypes
         L = _lib.lib()

@@ -486,6 +486,83 @@ def get_chisq(specdata, vel, atm_params, rot_params=None, resol_params=None,
     return ret
 
 
+def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
+                   config=None, outside_penalty=True, espec_systematic=None,
+                   resol_params=None, fast_interp=False):
+    """get_chisq (spec_fit.py:797-989) and its analytic gradient with respect to
+    (vel, *getSpecParams(setup)), in physical units: per km/s, per K, per dex.
+    vsini is held fixed.  The outside-grid penalty enters the value and is not
+    differentiated (it is piecewise); outside the grid the template is the
+    nearest grid point's, so the parameter derivatives are zero there.
+
+    One spectrum: returns (float, ndarray [1 + ndim]).  SpecBatch: vel [S],
+    atm_params [S, ndim] (or one tuple), rot_params None or vsini [S]; returns
+    device tensors [S] and [S, 1 + ndim].
+    Regular-grid libraries, npoly <= 16, one wavelength grid per setup, no
+    resolution matrix, no fast_interp: anything else raises ValueError."""
+    options = options or {}
+    npoly = options.get('npoly') or 5
+    rbf = options.get('rbf_continuum', True)
+    batch, is_batch = as_batch(specdata)
+    S, dev = batch.S, batch.device
+    resols = _resols(batch, resol_params)
+    libs = spec_inter.get_libs(batch.names, config)
+    ndim = libs[batch.names[0]].ndim
+    params = _params_tensor(atm_params, S, ndim, dev)
+    vsini = _vsini_tensor(rot_params, S, dev)
+    if isinstance(vel, torch.Tensor):
+        velt = vel.to(dev, torch.float64).reshape(S, 1)
+    else:
+        velt = torch.as_tensor(np.asarray(vel, dtype=np.float64)).to(dev)
+        velt = velt.reshape(-1, 1).expand(S, 1).contiguous()
+    vmin, vmax = float(velt.min().item()), float(velt.max().item())
+    _check_overlap_all(batch, libs, config, vmin, vmax)
+    if isinstance(espec_systematic, dict):
+        esys = [float(espec_systematic[n]) for n in batch.names]
+    else:
+        esys = float(espec_systematic) if espec_systematic is not None else 0.0
+    chisq, grad, status = _chisq_grad(batch, libs, None, velt[:, 0], params, vsini,
+                                      npoly, rbf, esys, outside_penalty, resols,
+                                      fast_interp)
+    if is_batch:
+        return chisq, grad
+    _raise_for_status(int(status[0].item()),
+                      f'velocity {vel}, atm parameters {atm_params}')
+    return float(chisq[0].item()), grad[0].cpu().numpy()
+
+
+def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
+                outside_penalty, resols, fast_interp):
+    # (the checks come first: nothing is built for a call that is refused)
+    engine.check_grad_scope(batch, libs, npoly, resols, fast_interp)
+    coefs, outs = [], []
+    for arm in batch.arms:
+        c, o = engine.build_templates(libs[arm.name], params, vsini, tangents=True)
+        coefs.append(c)
+        outs.append(o)
+    return engine.chisq_point_grad(batch, libs, coefs, outs, vel, npoly=npoly,
+                                   rbf=rbf, job_spec=js, espec_sys=esys,
+                                   outside_penalty=outside_penalty)
+
+
+def chisq_grad_jobs(batch, idx, vel, params, vsini, options, config,
+                    outside_penalty=True, espec_systematic=None, resol_params=None):
+    """chisq_jobs with the gradient: job j is spectrum idx[j] against its own
+    template (params[j], vsini[j]) at velocity vel[j] -- many points per spectrum
+    in one launch set (walker ensembles, HMC chains).
+    Returns chisq [J], grad [J, 1 + ndim] = d/d(vel, parameters), status [J]."""
+    options = options or {}
+    npoly = options.get('npoly') or 5
+    rbf = options.get('rbf_continuum', True)
+    libs = spec_inter.get_libs(batch.names, config)
+    params = params.contiguous()
+    esys = float(espec_systematic) if espec_systematic is not None else 0.0
+    resols = _resols(batch, resol_params)
+    js = idx.to(torch.int32).contiguous()
+    return _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
+                       outside_penalty, resols, False)
+
+
 # rows per launch set of the from-template objective (template buffers of
 # 3 arms x 32 768 rows x ~6000 px x 8 B = 4.7 GB)
 FROM_TEMPLATE_CHUNK = 32768

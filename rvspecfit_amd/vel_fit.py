@@ -359,6 +359,28 @@ def chisq_func0(pdict, args, outside_penalty=True):
     return chisq
 
 
+def chisq_func0_grad(pdict, args, outside_penalty=True):
+    """chisq_func0 and its analytic gradient with respect to (vel, *specParams), in
+    physical units: returns (float, ndarray [1 + ndim]).  The Normal priors add
+    2 (p - mu) / sigma^2 to their parameter's component.  The outside-grid penalty
+    is piecewise (a distance to the nearest grid point times a constant, switched
+    on at the grid's edge): it is part of the value and is NOT differentiated.
+    vsini (pdict['rot_params']) is held fixed."""
+    chisq, grad = spec_fit.get_chisq_grad(
+        args['specdata'], pdict['vel'], tuple(pdict['params']), pdict['rot_params'],
+        options=args['options'], config=args['config'],
+        outside_penalty=outside_penalty, resol_params=args.get('resolParams'))
+    grad = np.array(grad, dtype=np.float64)
+    if args.get('priors') is not None:
+        priors = args['priors']
+        for i, k in enumerate(args['paramMapper'].specParams):
+            if k in priors:
+                mu, sig = priors[k]
+                chisq += ((mu - pdict['params'][i]) / sig)**2
+                grad[1 + i] += 2.0 * (pdict['params'][i] - mu) / sig**2
+    return chisq, grad
+
+
 def chisq_func(p, args):
     """vel_fit.chisq_func (vel_fit.py:233-257): the function process minimises --
     1e30 outside [min_vel, max_vel] or at a non-finite parameter, else chisq_func0 +

@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""Value + gradient of the objective for J jobs: ONE spec_fit.chisq_grad_jobs call
+against the (2 + ndim) spec_fit.chisq_jobs calls of a forward difference (the point
+itself, then one call per displaced coordinate: velocity and the ndim parameters --
+what a caller without the gradient has to do, and what BFGS does per gradient).
+usage: grad_ab.py [--jobs J] [--spectra S] [--npoly P] [--rounds R] [--vsini]
+The workload is bench.py's (its synthetic DESI-shape polylinear libraries and
+spectra); the jobs are its truth parameters, jittered inside the grid, spread over the
+S spectra.  Both arms run alternately in one process, R rounds after a warm-up; one
+JSON line: median and minimum seconds of each arm, their ratio, and the largest
+difference between the analytic and the differenced gradient relative to
+max(|g_k|, 1e-6 |g|_inf) (a sanity figure: the difference is the forward
+difference's error)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--jobs', type=int, default=8192)
+    ap.add_argument('--spectra', type=int, default=512)
+    ap.add_argument('--npoly', type=int, default=10)
+    ap.add_argument('--rounds', type=int, default=7)
+    ap.add_argument('--vsini', action='store_true')
+    args = ap.parse_args()
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+    import bench
+    from rvspecfit_amd import _lib, engine, spec_fit, spec_inter
+    from rvspecfit_amd.library import TemplateLibrary
+    _lib.require_gpu()
+    dev = torch.device('cuda', 0)
+    S, J = args.spectra, args.jobs
+
+    def gpu_convolve(lam, templ, vsini):
+        t = torch.as_tensor(np.ascontiguousarray(templ)).to(dev)
+        v = torch.as_tensor(np.ascontiguousarray(vsini)).to(dev)
+        return engine.convolve_vsini(lam, t, v).cpu().numpy()
+
+    for name, d in bench.build_library_dicts(64, gpu_convolve).items():
+        spec_inter.register_library(TemplateLibrary(name, d, device=dev),
+                                    bench.CONFIG['template_lib'])
+    tp = bench.truth_params(S, seed=3)
+    batch = engine.SpecBatch([engine.ArmData(n, lam, sp, es, bad, device=dev)
+                              for n, lam, sp, es, bad in
+                              bench.make_spectra_device(tp, dev)])
+    cfg, opt = dict(bench.CONFIG), dict(bench.OPTIONS, npoly=args.npoly)
+    libs = spec_inter.get_libs(batch.names, cfg)
+    ndim = libs[batch.names[0]].ndim
+    g = torch.Generator(device=dev)
+    g.manual_seed(17)
+    idx = torch.arange(J, device=dev) % S
+    names = ['teff', 'logg', 'feh', 'alpha'][:ndim]
+    par = torch.stack([torch.as_tensor(np.asarray(tp[k], dtype=np.float64)).to(dev)[idx]
+                       for k in names], dim=1)
+    par = par * (1 + 1e-3 * (torch.rand(par.shape, device=dev, generator=g,
+                                        dtype=torch.float64) - 0.5))
+    vel = torch.as_tensor(np.asarray(tp['vel'], dtype=np.float64)).to(dev)[idx] + \
+        torch.rand(J, device=dev, generator=g, dtype=torch.float64)
+    vs = torch.full((J, ), 20.0, dtype=torch.float64, device=dev) if args.vsini \
+        else None
+    x = torch.cat([vel[:, None], par], dim=1)
+    h = 1.4901161193847656e-08 * torch.clamp(x.abs(), min=1.0)
+
+    def analytic():
+        return spec_fit.chisq_grad_jobs(batch, idx, vel, par, vs, opt, cfg)
+
+    def differenced():
+        f0, _ = spec_fit.chisq_jobs(batch, idx, vel, par, vs, opt, cfg)
+        cols = []
+        for k in range(1 + ndim):
+            y = x.clone()
+            y[:, k] += h[:, k]
+            fk, _ = spec_fit.chisq_jobs(batch, idx, y[:, 0].contiguous(),
+                                        y[:, 1:].contiguous(), vs, opt, cfg)
+            cols.append((fk - f0) / (y[:, k] - x[:, k]))
+        return f0, torch.stack(cols, dim=1)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    timed(analytic), timed(differenced)          # warm-up: tables, caches, clocks
+    ta, td = [], []
+    for _ in range(args.rounds):
+        t, (ca, ga, st) = timed(analytic)
+        ta.append(t)
+        t, (cd, gd) = timed(differenced)
+        td.append(t)
+    ok = (st == 0) & torch.isfinite(gd).all(dim=1)
+    scale = torch.maximum(ga.abs(), 1e-6 * ga.abs().max(dim=1, keepdim=True).values)
+    rel = ((ga - gd).abs() / scale)[ok]
+    print(json.dumps(dict(
+        jobs=J, spectra=S, npoly=args.npoly, ndim=ndim, vsini=bool(args.vsini),
+        rounds=args.rounds, chisq_jobs_calls=2 + ndim,
+        analytic_s_median=round(float(np.median(ta)), 6),
+        analytic_s_min=round(min(ta), 6),
+        differenced_s_median=round(float(np.median(td)), 6),
+        differenced_s_min=round(min(td), 6),
+        speedup_median=round(float(np.median(td) / np.median(ta)), 2),
+        jobs_ok=int(ok.sum()),
+        value_max_rel_diff=float(((ca - cd).abs() / cd.abs().clamp(min=1e3))[ok].max()),
+        grad_vs_forward_difference_max_rel=float(rel.max()) if rel.numel() else None)),
+        flush=True)
+
+
+if __name__ == '__main__':
+    main()

@@ -105,7 +105,8 @@ extern "C" {
  *      (still 18: rvs_template_polylinear_grad, rvs_chisq_point_grad_work_size and
  *      rvs_chisq_point_grad -- the objective's analytic gradient -- are additions;
  *      no argument, status bit or work-size formula of an existing entry point
- *      changed, so a caller built against 18 is served as before) */
+ *      changed, so a caller built against 18 is served as before; likewise
+ *      rvs_vsini_convolve_grad, the broadening with its vsini tangent row) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -247,6 +248,26 @@ int rvs_template_tri_buckets(const double *dats, int ntp, const int32_t *simplic
 int rvs_vsini_convolve(const double *templ, const double *vsini,
                        const double *outside, double lnstep, double eps,
                        int ntp, int B, double *out, void *stream);
+
+/* ... with the derivative of the taps (spec_fit.py:495-682 differentiated): job b
+ *     owns the R rows templ[b, 0..R-1] (a template and its parameter tangents), one
+ *     vsini[b] and one outside[b]; out is [B, R + 1, ntp].  Rows r < R are
+ *     templ[b, r] (*) w(vsini[b]), the bits rvs_vsini_convolve writes for those rows;
+ *     row R is templ[b, 0] (*) dw/dvsini per km/s, same 'same' zero padding and
+ *     summation order.  With Rv = vsini / (c lnstep) the un-normalised taps are
+ *     W_k = int Lambda(k - Rv x) K(x) dx; the boundary terms of Leibniz's rule cancel
+ *     (Lambda is continuous, K(+-1) = 0), so dW_k/dRv = -int_left x K + int_right x K
+ *     over the value's clipped limits, and with S = W_0 + 2 sum W_k the normalised
+ *     taps have dw/dRv = (W' - w S') / S.  w is C^1 across integer Rv.  The VALUE has
+ *     a kink at vsini = 0+ (W_0 = 1 - Rv E|x| for small Rv): in the copy cases
+ *     (vsini <= 0, NaN, Rv < 1e-9, non finite outside[b], more than 2048 one-sided
+ *     taps) rows r < R are copied and row R is exactly 0 -- the derivative of the
+ *     clamped function an optimiser sees, not the one-sided limit.
+ *     Sums folded in a fixed order, no atomics: repeated calls agree to the bit.
+ *     RVS_E_ARG for R < 1, B < 1, ntp < 1, out == templ, lnstep <= 0. */
+int rvs_vsini_convolve_grad(const double *templ, const double *vsini,
+                            const double *outside, double lnstep, double eps,
+                            int ntp, int R, int B, double *out, void *stream);
 
 /* ------------------------------------------------------------------------
  * A7  natural cubic spline through (knots, ys[b]); replaces `construct`
@@ -506,7 +527,8 @@ int rvs_chisq_point(const rvs_point_arm *arms, int narm, int npoly,
  * One 256-thread block per (job, arm).
  *   coef of every arm: [Tn, 1+ntan, ntp, 4] form-1 records -- row 0 the template,
  *   row 1+k its tangent dt/dp_k (rvs_template_polylinear_grad through
- *   rvs_vsini_convolve and rvs_spline_construct, which are linear in the rows).
+ *   rvs_vsini_convolve and rvs_spline_construct, which are linear in the rows; a
+ *   last row from rvs_vsini_convolve_grad makes vsini one more parameter).
  *   The velocity tangent is S'(x) dx/dvel from the template's own record
  *   (evalRV, spec_fit.py:403-405: x = lam sqrt((1-b)/(1+b)), b = vel/c).
  * With ST = polys*m/e, A = ST ST^T, c = A^-1 ST D, r = D/e - c.ST the value is

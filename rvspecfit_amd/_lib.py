@@ -31,6 +31,7 @@ SIGNATURES = {
     'rvs_template_tri_buckets': (I, [P, I, P, P, P, I, I, U, I, P, P, I, P, P, P,
                                      P, P]),
     'rvs_vsini_convolve': (I, [P, P, P, D, D, I, I, P, P]),
+    'rvs_vsini_convolve_grad': (I, [P, P, P, D, D, I, I, I, P, P]),
     'rvs_spline_factors': (I, [P, I, P, P]),
     'rvs_spline_factors_len': (ctypes.c_int64, [I]),
     'rvs_spline_construct': (I, [P, P, I, I, I, P, P, P]),

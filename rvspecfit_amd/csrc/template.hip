@@ -553,17 +553,54 @@ extern "C" int rvs_template_tri(const double *dats, int ntp,
 // ---------------------------------------------------------------------------
 #define VSINI_MAXTAP 2048  // one-sided taps kept in LDS
 
+// 'same' convolution with zero padding (scipy.signal.convolve mode='same') of one row
+// with the symmetric taps tab[|m|] * scale
+__device__ __forceinline__ void vsini_fir(const double *__restrict__ in,
+                                          double *__restrict__ o, const double *tab,
+                                          double scale, int kmax, int ntp, int tid) {
+  for (int i = tid; i < ntp; i += 256) {
+    double acc = 0;
+    // same summation order as a direct convolution: ascending input index
+    for (int m = -kmax; m <= kmax; m++) {
+      const int q = i + m;
+      if (q >= 0 && q < ntp) acc = fma(in[q], tab[m < 0 ? -m : m] * scale, acc);
+    }
+    o[i] = acc;
+  }
+}
+
+// One 256-thread block per output row.  GRAD = false: row b of `templ` with vsini[b].
+// GRAD = true: job b = blockIdx.x / (nrow + 1) owns nrow input rows and nrow + 1 output
+// rows; block r < nrow broadens row r with w(vsini[b]) by the statements of the value
+// path, block nrow writes templ[b, 0] (*) dw/dvsini.  With R = vsini / (c lnstep) the
+// un-normalised taps are W_k(R) = int Lambda(k - R x) K(x) dx over [-1, 1] (Lambda the
+// unit hat, K the limb-darkened profile).  Lambda is continuous and K(+-1) = 0, so the
+// Leibniz boundary terms cancel and
+//     dW_k/dR = -int_left x K dx + int_right x K dx
+// over the clipped limits of the value (left [k/R, (k+1)/R], right [(k-1)/R, k/R]):
+// rot_segment with slope -+1 and intercept 0.  The normalised taps w = W / S,
+// S = W_0 + 2 sum_{k>=1} W_k, have dw/dR = (W' - w S') / S, and d/dvsini = that
+// / (c lnstep).  The taps are C^1 across integer R (the tap that appears there enters
+// with weight 0).  At vsini = 0+ the value has a KINK (W_0 = 1 - R E|x| for small R):
+// the copy branches write a zero derivative row, the derivative of the clamped
+// function the optimiser sees (VSiniMapper), not a one-sided limit.
+template <bool GRAD>
 __global__ void __launch_bounds__(256)
     vsini_kernel(const double *__restrict__ templ,
                  const double *__restrict__ vsini,
                  const double *__restrict__ outside, double lnstep, double eps,
-                 int ntp, double *__restrict__ out,
+                 int ntp, int nrow, double *__restrict__ out,
                  int32_t *__restrict__ status) {
   __shared__ double wpos[VSINI_MAXTAP + 1];
+  __shared__ double dpos[GRAD ? VSINI_MAXTAP + 1 : 1];
   __shared__ double red[8];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const double *in = templ + (int64_t)b * ntp;
-  double *o = out + (int64_t)b * ntp;
+  const int tid = threadIdx.x;
+  const int b = GRAD ? blockIdx.x / (nrow + 1) : blockIdx.x;
+  const int row = GRAD ? blockIdx.x % (nrow + 1) : 0;
+  const bool drow = GRAD && row == nrow;   // (block-uniform)
+  const double *in = templ + (GRAD ? ((int64_t)b * nrow + (drow ? 0 : row)) * ntp
+                                   : (int64_t)b * ntp);
+  double *o = out + (int64_t)blockIdx.x * ntp;
   const double vs = vsini[b];
   const double R = (vs / RVS_C_KMS) / lnstep;
   bool copy = !(vs > 0) || (R < 1e-9);
@@ -580,7 +617,7 @@ __global__ void __launch_bounds__(256)
     }
   }
   if (copy) {
-    for (int k = tid; k < ntp; k += 256) o[k] = in[k];
+    for (int k = tid; k < ntp; k += 256) o[k] = drow ? 0.0 : in[k];
     return;
   }
   // taps k = 0..kmax (compute_vsini_kernel, spec_fit.py:565-625)
@@ -598,16 +635,31 @@ __global__ void __launch_bounds__(256)
   psum = block_sum<4>(psum, red);
   __syncthreads();
   const double inv = 1.0 / psum;
-  // 'same' convolution with zero padding (scipy.signal.convolve mode='same')
-  for (int i = tid; i < ntp; i += 256) {
-    double acc = 0;
-    // same summation order as a direct convolution: ascending input index
-    for (int m = -kmax; m <= kmax; m++) {
-      const int q = i + m;
-      if (q >= 0 && q < ntp) acc = fma(in[q], wpos[m < 0 ? -m : m] * inv, acc);
+  if constexpr (GRAD) {
+    if (drow) {
+      // W'_k over the same clipped legs, S' folded as S is
+      double dsum = 0;
+      for (int k = tid; k <= kmax; k += 256) {
+        double d = 0;
+        double lo = fmin(fmax(k / R, -1.0), 1.0), hi = fmin(fmax((k + 1) / R, -1.0), 1.0);
+        if (hi > lo) d += rot_segment(lo, hi, -1.0, 0.0, eps);
+        lo = fmin(fmax((k - 1) / R, -1.0), 1.0);
+        hi = fmin(fmax(k / R, -1.0), 1.0);
+        if (hi > lo) d += rot_segment(lo, hi, 1.0, 0.0, eps);
+        dpos[k] = d;
+        dsum += (k == 0) ? d : 2 * d;
+      }
+      dsum = block_sum<4>(dsum, red);
+      __syncthreads();
+      const double dscale = inv / (RVS_C_KMS * lnstep);
+      for (int k = tid; k <= kmax; k += 256)
+        dpos[k] = (dpos[k] - wpos[k] * inv * dsum) * dscale;
+      __syncthreads();
+      vsini_fir(in, o, dpos, 1.0, kmax, ntp, tid);
+      return;
     }
-    o[i] = acc;
   }
+  vsini_fir(in, o, wpos, inv, kmax, ntp, tid);
 }
 
 extern "C" int rvs_vsini_convolve(const double *templ, const double *vsini,
@@ -615,9 +667,23 @@ extern "C" int rvs_vsini_convolve(const double *templ, const double *vsini,
                                   double eps, int ntp, int B, double *out,
                                   void *stream) {
   if (B < 1 || ntp < 1 || templ == out || !(lnstep > 0)) return RVS_E_ARG;
-  hipLaunchKernelGGL(vsini_kernel, dim3(B), dim3(256), 0, rvs_stream(stream),
-                     templ, vsini, outside, lnstep, eps, ntp, out,
+  hipLaunchKernelGGL(vsini_kernel<false>, dim3(B), dim3(256), 0, rvs_stream(stream),
+                     templ, vsini, outside, lnstep, eps, ntp, 1, out,
                      (int32_t *)nullptr);
+  RVS_LAUNCH_CHECK();
+  return 0;
+}
+
+// spec_fit.py:495-682 differentiated: out [B, R + 1, ntp], row R = templ[b, 0] (*) dw/dvsini
+extern "C" int rvs_vsini_convolve_grad(const double *templ, const double *vsini,
+                                       const double *outside, double lnstep,
+                                       double eps, int ntp, int R, int B,
+                                       double *out, void *stream) {
+  if (R < 1 || B < 1 || ntp < 1 || templ == out || !(lnstep > 0)) return RVS_E_ARG;
+  if ((int64_t)B * (R + 1) > 0x7fffffffll) return RVS_E_ARG;
+  hipLaunchKernelGGL(vsini_kernel<true>, dim3((unsigned)((int64_t)B * (R + 1))),
+                     dim3(256), 0, rvs_stream(stream), templ, vsini, outside, lnstep,
+                     eps, ntp, R, out, (int32_t *)nullptr);
   RVS_LAUNCH_CHECK();
   return 0;
 }

@@ -615,22 +615,39 @@ def _chunks(n, size):
 # --------------------------------------------------------------------------
 # template construction: A3/A4 -> A6 -> A7-construct
 # --------------------------------------------------------------------------
-def build_templates(lib, params, vsini=None, return_templ=False, tangents=False):
+def build_templates(lib, params, vsini=None, return_templ=False, tangents=False,
+                    vsini_tangent=False):
     """params [J, ndim] f64 device; vsini [J] f64 device or None.
     Returns coef [J, ntp, 4], outside [J] (+ the broadened template).
     tangents: the template AND its derivative with respect to each parameter,
     coef [J, 1 + ndim, ntp, 4] (templ [J, 1 + ndim, ntp]) -- the broadening and the
     spline construction are linear in the rows, so the tangent rows go through the
-    same two launches as rows of their own (vsini is held fixed)."""
+    same two launches as rows of their own (vsini is held fixed).
+    vsini_tangent (with tangents): one more row, LAST, the derivative with respect
+    to vsini per km/s -- coef [J, 2 + ndim, ntp, 4]; the broadening is then one
+    rvs_vsini_convolve_grad launch, whose first 1 + ndim rows are the bits of the
+    call without it."""
     L = _lib.lib()
     J = params.shape[0]
     R = 1
+    if vsini_tangent and (vsini is None or not tangents):
+        raise ValueError('the vsini tangent needs a vsini and tangents=True')
     if tangents:
         templ, outside = lib.eval_batch_grad(params)
         R = 1 + lib.ndim
     else:
         templ, outside = lib.eval_batch(params)
-    if vsini is not None:
+    if vsini_tangent:
+        out = torch.empty((J, R + 1, lib.ntp), dtype=torch.float64, device=lib.device)
+        vsini = vsini.to(torch.float64).contiguous()
+        # (one vsini / outside flag per JOB of the launch)
+        rc = L.rvs_vsini_convolve_grad(_lib.ptr(templ), _lib.ptr(vsini),
+                                       _lib.ptr(outside), lib.lnstep, 0.6, lib.ntp,
+                                       R, J, _lib.ptr(out), _lib.stream())
+        _lib.check(rc, 'rvs_vsini_convolve_grad')
+        templ = out
+        R += 1
+    elif vsini is not None:
         out = torch.empty_like(templ)
         vsini = vsini.to(torch.float64).contiguous()
         # (one vsini / outside flag per ROW of the launch)
@@ -867,6 +884,8 @@ def chisq_grid(batch, libs, coefs, outsides, vels, npoly=5, rbf=True,
 # widest basis of rvs_chisq_point / rvs_chisq_grid (one lane keeps the packed
 # normal matrix); rvs_chisq_full takes 32
 POINT_MAXP = 16
+# most tangent rows of rvs_chisq_point_grad (GRAD_MAXTAN of csrc/chisq.hip)
+GRAD_MAXTAN = 6
 
 
 def _per_arm(v, n):
@@ -936,7 +955,8 @@ def chisq_point(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
     return out, status
 
 
-def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False):
+def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
+                     vsini_grad=False):
     """ValueError naming what rvs_chisq_point_grad does not cover"""
     if npoly > POINT_MAXP:
         raise ValueError('the analytic gradient takes npoly <= %d, not %d'
@@ -955,27 +975,33 @@ def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False):
             raise ValueError('the analytic gradient needs regular-grid (polylinear) '
                              'libraries, %s is a %s library'
                              % (arm.name, libs[arm.name].kind))
+        if vsini_grad and 1 + libs[arm.name].ndim > GRAD_MAXTAN:
+            raise ValueError('the analytic gradient takes at most %d tangents: vsini '
+                             'does not fit beside the ndim = %d parameters of %s'
+                             % (GRAD_MAXTAN, libs[arm.name].ndim, arm.name))
 
 
 def chisq_point_grad(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
                      job_spec=None, job_templ=None, espec_sys=0.0,
                      outside_penalty=True, resols=None, fast_interp=False):
     """chisq_point with the gradient (rvs_chisq_point_grad): coefs[ia] are the
-    [Tn, 1 + ndim, ntp, 4] records of build_templates(..., tangents=True).
+    [Tn, 1 + ntan, ntp, 4] records of build_templates(..., tangents=True), ntan =
+    ndim, or ndim + 1 with vsini_tangent=True (the vsini row last).
     Returns chisq [J] (the value of chisq_point, evaluated in the orthonormal
-    continuum basis), grad [J, 1 + ndim] = d chisq / d (vel, parameters) in
-    physical units, status int32 [J].  The outside penalty is piecewise and is
+    continuum basis), grad [J, 1 + ntan] = d chisq / d (vel, parameters[, vsini])
+    in physical units, status int32 [J].  The outside penalty is piecewise and is
     not differentiated.  What the kernel does not cover is refused, never
     finite-differenced: npoly > 16, several wavelength grids per arm, a
     resolution matrix, fast_interp, libraries that are not regular grids."""
     import ctypes
-    check_grad_scope(batch, libs, npoly, resols, fast_interp)
+    ntan = coefs[0].shape[1] - 1
+    check_grad_scope(batch, libs, npoly, resols, fast_interp,
+                     vsini_grad=ntan > libs[batch.arms[0].name].ndim)
     narm = len(batch.arms)
     L = _lib.lib()
     dev = batch.device
     vel = vel.to(device=dev, dtype=torch.float64).contiguous()
     J = vel.shape[0]
-    ntan = coefs[0].shape[1] - 1
     assert all(c.dim() == 4 and c.shape[1] == 1 + ntan for c in coefs)
     out = torch.empty(J, dtype=torch.float64, device=dev)
     grad = torch.empty((J, 1 + ntan), dtype=torch.float64, device=dev)

@@ -488,16 +488,20 @@ def get_chisq(specdata, vel, atm_params, rot_params=None, resol_params=None,
 
 def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
                    config=None, outside_penalty=True, espec_systematic=None,
-                   resol_params=None, fast_interp=False):
+                   resol_params=None, fast_interp=False, vsini_grad=False):
     """get_chisq (spec_fit.py:797-989) and its analytic gradient with respect to
     (vel, *getSpecParams(setup)), in physical units: per km/s, per K, per dex.
-    vsini is held fixed.  The outside-grid penalty enters the value and is not
+    vsini is held fixed unless vsini_grad: then the gradient has one more, LAST
+    component, d/dvsini per km/s (rot_params must be given; the other components
+    are the bits of the call without it; where the broadening is not applied --
+    vsini <= 0 -- it is 0, the derivative of the clamped function).  The
+    outside-grid penalty enters the value and is not
     differentiated (it is piecewise); outside the grid the template is the
     nearest grid point's, so the parameter derivatives are zero there.
 
     One spectrum: returns (float, ndarray [1 + ndim]).  SpecBatch: vel [S],
     atm_params [S, ndim] (or one tuple), rot_params None or vsini [S]; returns
-    device tensors [S] and [S, 1 + ndim].
+    device tensors [S] and [S, 1 + ndim] ([.., 2 + ndim] with vsini_grad).
     Regular-grid libraries, npoly <= 16, one wavelength grid per setup, no
     resolution matrix, no fast_interp: anything else raises ValueError."""
     options = options or {}
@@ -510,6 +514,9 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
     ndim = libs[batch.names[0]].ndim
     params = _params_tensor(atm_params, S, ndim, dev)
     vsini = _vsini_tensor(rot_params, S, dev)
+    if vsini_grad and vsini is None:
+        raise ValueError('vsini_grad=True needs rot_params: without rotation there '
+                         'is no vsini to differentiate by')
     if isinstance(vel, torch.Tensor):
         velt = vel.to(dev, torch.float64).reshape(S, 1)
     else:
@@ -523,7 +530,7 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
         esys = float(espec_systematic) if espec_systematic is not None else 0.0
     chisq, grad, status = _chisq_grad(batch, libs, None, velt[:, 0], params, vsini,
                                       npoly, rbf, esys, outside_penalty, resols,
-                                      fast_interp)
+                                      fast_interp, vsini_grad)
     if is_batch:
         return chisq, grad
     _raise_for_status(int(status[0].item()),
@@ -532,12 +539,13 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
 
 
 def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
-                outside_penalty, resols, fast_interp):
+                outside_penalty, resols, fast_interp, vsini_grad=False):
     # (the checks come first: nothing is built for a call that is refused)
-    engine.check_grad_scope(batch, libs, npoly, resols, fast_interp)
+    engine.check_grad_scope(batch, libs, npoly, resols, fast_interp, vsini_grad)
     coefs, outs = [], []
     for arm in batch.arms:
-        c, o = engine.build_templates(libs[arm.name], params, vsini, tangents=True)
+        c, o = engine.build_templates(libs[arm.name], params, vsini, tangents=True,
+                                      vsini_tangent=vsini_grad)
         coefs.append(c)
         outs.append(o)
     return engine.chisq_point_grad(batch, libs, coefs, outs, vel, npoly=npoly,
@@ -546,11 +554,16 @@ def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
 
 
 def chisq_grad_jobs(batch, idx, vel, params, vsini, options, config,
-                    outside_penalty=True, espec_systematic=None, resol_params=None):
+                    outside_penalty=True, espec_systematic=None, resol_params=None,
+                    vsini_grad=False):
     """chisq_jobs with the gradient: job j is spectrum idx[j] against its own
     template (params[j], vsini[j]) at velocity vel[j] -- many points per spectrum
     in one launch set (walker ensembles, HMC chains).
-    Returns chisq [J], grad [J, 1 + ndim] = d/d(vel, parameters), status [J]."""
+    Returns chisq [J], grad [J, 1 + ndim] = d/d(vel, parameters), status [J];
+    with vsini_grad (vsini must be given) grad is [J, 2 + ndim], d/dvsini last."""
+    if vsini_grad and vsini is None:
+        raise ValueError('vsini_grad=True needs vsini: without rotation there is no '
+                         'vsini to differentiate by')
     options = options or {}
     npoly = options.get('npoly') or 5
     rbf = options.get('rbf_continuum', True)
@@ -560,7 +573,7 @@ def chisq_grad_jobs(batch, idx, vel, params, vsini, options, config,
     resols = _resols(batch, resol_params)
     js = idx.to(torch.int32).contiguous()
     return _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
-                       outside_penalty, resols, False)
+                       outside_penalty, resols, False, vsini_grad)
 
 
 # rows per launch set of the from-template objective (template buffers of

@@ -359,17 +359,19 @@ def chisq_func0(pdict, args, outside_penalty=True):
     return chisq
 
 
-def chisq_func0_grad(pdict, args, outside_penalty=True):
+def chisq_func0_grad(pdict, args, outside_penalty=True, vsini_grad=False):
     """chisq_func0 and its analytic gradient with respect to (vel, *specParams), in
     physical units: returns (float, ndarray [1 + ndim]).  The Normal priors add
     2 (p - mu) / sigma^2 to their parameter's component.  The outside-grid penalty
     is piecewise (a distance to the nearest grid point times a constant, switched
     on at the grid's edge): it is part of the value and is NOT differentiated.
-    vsini (pdict['rot_params']) is held fixed."""
+    vsini (pdict['rot_params']) is held fixed unless vsini_grad: then the gradient is
+    [2 + ndim] with d/dvsini (per km/s) last, and pdict['rot_params'] must be set."""
     chisq, grad = spec_fit.get_chisq_grad(
         args['specdata'], pdict['vel'], tuple(pdict['params']), pdict['rot_params'],
         options=args['options'], config=args['config'],
-        outside_penalty=outside_penalty, resol_params=args.get('resolParams'))
+        outside_penalty=outside_penalty, resol_params=args.get('resolParams'),
+        vsini_grad=vsini_grad)
     grad = np.array(grad, dtype=np.float64)
     if args.get('priors') is not None:
         priors = args['priors']
@@ -390,6 +392,34 @@ def chisq_func(p, args):
             or (~np.isfinite(np.asarray(pdict['params'], dtype=float))).any()):
         return 1e30
     return chisq_func0(pdict, args) + pdict['penalty']
+
+
+def chisq_func_grad(p, args):
+    """chisq_func and its gradient with respect to the optimiser's own vector `p`, in
+    the order of paramMapper.get_fitted_params() (fixed parameters dropped): returns
+    (float, ndarray [len(p)]) -- the `fun` of scipy.optimize.minimize(..., jac=True).
+    The vsini component is the physical derivative where 0 < x < max_vsini; outside
+    that range VSiniMapper clamps, so the physical derivative is 0 and the penalty's
+    2 (x - clamp(x)) stands alone.  Priors as in chisq_func0_grad.  Where chisq_func
+    returns 1e30 (velocity out of bounds, non-finite parameter): (1e30, zeros)."""
+    mapper = args['paramMapper']
+    pdict = mapper.forward(p)
+    if (pdict['vel'] > args['max_vel'] or pdict['vel'] < args['min_vel']
+            or (~np.isfinite(np.asarray(pdict['params'], dtype=float))).any()):
+        return 1e30, np.zeros(len(p))
+    chisq, g0 = chisq_func0_grad(pdict, args, vsini_grad=mapper.fitVsini)
+    grad = []
+    for x, name in zip(p, mapper.get_fitted_params()):
+        if name == 'vel':
+            grad.append(g0[0])
+        elif name == 'vsini':
+            vsini = pdict['vsini']
+            inside = 0 < x < mapper.vsiniMapper.max_vsini
+            grad.append((g0[-1] if inside else 0.0) + 2.0 * (x - vsini))
+        else:
+            grad.append(g0[1 + list(mapper.specParams).index(name)])
+    assert len(grad) == len(p)
+    return chisq + pdict['penalty'], np.array(grad, dtype=np.float64)
 
 
 def hess_func(p, pdict, args):

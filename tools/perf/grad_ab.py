@@ -4,6 +4,9 @@ against the (2 + ndim) spec_fit.chisq_jobs calls of a forward difference (the po
 itself, then one call per displaced coordinate: velocity and the ndim parameters --
 what a caller without the gradient has to do, and what BFGS does per gradient).
 usage: grad_ab.py [--jobs J] [--spectra S] [--npoly P] [--rounds R] [--vsini]
+                  [--vsini-grad]
+--vsini-grad (implies --vsini): the analytic call carries the vsini tangent row
+(vsini_grad=True) and the forward difference displaces vsini too: 3 + ndim calls.
 The workload is bench.py's (its synthetic DESI-shape polylinear libraries and
 spectra); the jobs are its truth parameters, jittered inside the grid, spread over the
 S spectra.  Both arms run alternately in one process, R rounds after a warm-up; one
@@ -27,6 +30,7 @@ def main():
     ap.add_argument('--npoly', type=int, default=10)
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--vsini', action='store_true')
+    ap.add_argument('--vsini-grad', action='store_true')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
     import numpy as np
@@ -63,22 +67,25 @@ def main():
                                         dtype=torch.float64) - 0.5))
     vel = torch.as_tensor(np.asarray(tp['vel'], dtype=np.float64)).to(dev)[idx] + \
         torch.rand(J, device=dev, generator=g, dtype=torch.float64)
-    vs = torch.full((J, ), 20.0, dtype=torch.float64, device=dev) if args.vsini \
-        else None
-    x = torch.cat([vel[:, None], par], dim=1)
+    vg = args.vsini_grad
+    vs = torch.full((J, ), 20.0, dtype=torch.float64, device=dev) \
+        if args.vsini or vg else None
+    x = torch.cat([vel[:, None], par] + ([vs[:, None]] if vg else []), dim=1)
     h = 1.4901161193847656e-08 * torch.clamp(x.abs(), min=1.0)
 
     def analytic():
-        return spec_fit.chisq_grad_jobs(batch, idx, vel, par, vs, opt, cfg)
+        return spec_fit.chisq_grad_jobs(batch, idx, vel, par, vs, opt, cfg,
+                                        vsini_grad=vg)
 
     def differenced():
         f0, _ = spec_fit.chisq_jobs(batch, idx, vel, par, vs, opt, cfg)
         cols = []
-        for k in range(1 + ndim):
+        for k in range(x.shape[1]):
             y = x.clone()
             y[:, k] += h[:, k]
             fk, _ = spec_fit.chisq_jobs(batch, idx, y[:, 0].contiguous(),
-                                        y[:, 1:].contiguous(), vs, opt, cfg)
+                                        y[:, 1:1 + ndim].contiguous(),
+                                        y[:, -1].contiguous() if vg else vs, opt, cfg)
             cols.append((fk - f0) / (y[:, k] - x[:, k]))
         return f0, torch.stack(cols, dim=1)
 
@@ -100,8 +107,8 @@ def main():
     scale = torch.maximum(ga.abs(), 1e-6 * ga.abs().max(dim=1, keepdim=True).values)
     rel = ((ga - gd).abs() / scale)[ok]
     print(json.dumps(dict(
-        jobs=J, spectra=S, npoly=args.npoly, ndim=ndim, vsini=bool(args.vsini),
-        rounds=args.rounds, chisq_jobs_calls=2 + ndim,
+        jobs=J, spectra=S, npoly=args.npoly, ndim=ndim, vsini=vs is not None,
+        vsini_grad=vg, rounds=args.rounds, chisq_jobs_calls=1 + x.shape[1],
         analytic_s_median=round(float(np.median(ta)), 6),
         analytic_s_min=round(min(ta), 6),
         differenced_s_median=round(float(np.median(td)), 6),

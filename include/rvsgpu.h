@@ -106,7 +106,9 @@ extern "C" {
  *      rvs_chisq_point_grad -- the objective's analytic gradient -- are additions;
  *      no argument, status bit or work-size formula of an existing entry point
  *      changed, so a caller built against 18 is served as before; likewise
- *      rvs_vsini_convolve_grad, the broadening with its vsini tangent row) */
+ *      rvs_vsini_convolve_grad, the broadening with its vsini tangent row, and
+ *      rvs_template_tri_grad / rvs_template_tri_buckets_grad, the Delaunay
+ *      evaluator with its tangent rows) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -215,6 +217,26 @@ int rvs_template_tri(const double *dats, int ntp, const int32_t *simplices,
                      const double *params, int B, double *templ, double *outside,
                      int32_t *simplex, double *weights, void *stream);
 
+/* ... and its derivative with respect to the physical parameters.  Inside a simplex
+ * TriInterp.__call__ (spec_inter.py:11-59) returns t = exp(sum_i b_i L_i) with the
+ * barycentric coordinates b = T (q - r), b_ndim = 1 - sum_i b_i, of the mapped
+ * parameters q (LogParamMapper.forward, read_grid.py:127-145).  b is affine in q, so
+ * db_i/dp_k = T[i][k] s_k for i < ndim and db_ndim/dp_k = -sum_i T[i][k] s_k, with
+ * s_k = 1/(p_k ln 10) for a parameter in log_mask and 1 otherwise, and
+ * dt/dp_k = t * sum_i (db_i/dp_k) L_i; without exp_flag the factor t is absent.
+ * templ  float64 [B, 1+ndim, ntp] out: row 0 the template (the bits of
+ *        rvs_template_tri, as are outside / simplex / weights), row 1+k dt/dp_k per
+ *        physical unit.  No containing simplex (a non-finite mapped parameter
+ *        included): all 1+ndim rows NaN, NaN outside flag.  On a shared face the
+ *        one-sided derivative of the simplex the search returns.
+ * Other arguments as rvs_template_tri. */
+int rvs_template_tri_grad(const double *dats, int ntp, const int32_t *simplices,
+                          const double *transform, const double *extraflags,
+                          int nsimplex, int ndim, uint32_t log_mask, int exp_flag,
+                          const double *params, int B, double *templ,
+                          double *outside, int32_t *simplex, double *weights,
+                          void *stream);
+
 /* ... with find_simplex through a bucket grid instead of the exhaustive search (the
  * same answer: the lowest simplex id that passes scipy's inside test,
  * spec_inter.py:11-59 / Delaunay.find_simplex): cell c of a uniform grid over the
@@ -237,6 +259,18 @@ int rvs_template_tri_buckets(const double *dats, int ntp, const int32_t *simplic
                              const double *params, int B, double *templ,
                              double *outside, int32_t *simplex, double *weights,
                              void *stream);
+
+/* ... and rvs_template_tri_grad (spec_inter.py:11-59 differentiated) behind the same
+ * bucketed find_simplex: templ float64 [B, 1+ndim, ntp], every number that of
+ * rvs_template_tri_grad.  Other arguments as rvs_template_tri_buckets. */
+int rvs_template_tri_buckets_grad(const double *dats, int ntp,
+                                  const int32_t *simplices, const double *transform,
+                                  const double *extraflags, int nsimplex, int ndim,
+                                  uint32_t log_mask, int exp_flag,
+                                  const rvs_tri_buckets *buckets,
+                                  const double *params, int B, double *templ,
+                                  double *outside, int32_t *simplex, double *weights,
+                                  void *stream);
 
 /* ------------------------------------------------------------------------
  * A6  rotational broadening; replaces spec_fit.convolve_vsini /

@@ -30,6 +30,9 @@ SIGNATURES = {
     'rvs_template_tri': (I, [P, I, P, P, P, I, I, U, I, P, I, P, P, P, P, P]),
     'rvs_template_tri_buckets': (I, [P, I, P, P, P, I, I, U, I, P, P, I, P, P, P,
                                      P, P]),
+    'rvs_template_tri_grad': (I, [P, I, P, P, P, I, I, U, I, P, I, P, P, P, P, P]),
+    'rvs_template_tri_buckets_grad': (I, [P, I, P, P, P, I, I, U, I, P, P, I, P, P,
+                                          P, P, P]),
     'rvs_vsini_convolve': (I, [P, P, P, D, D, I, I, P, P]),
     'rvs_vsini_convolve_grad': (I, [P, P, P, D, D, I, I, I, P, P]),
     'rvs_spline_factors': (I, [P, I, P, P]),

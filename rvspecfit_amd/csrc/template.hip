@@ -224,6 +224,13 @@ extern "C" int rvs_template_polylinear_grad(
 //  tri_eval_kernel: b = T (p - r), spec = sum_i b_i dats[simplex_i] in vertex
 //    order with separately rounded products (numpy's (dats*b[:,None]).sum(0)),
 //    exp; outside = the same blend of `extraflags`; no simplex -> NaN.
+//    GRAD: `templ` is [B, 1 + nd, ntp] -- behind the template row the nd tangent
+//    rows dt/dp_k = t * sum_i (db_i/dp_k) L_i per PHYSICAL unit of p_k.  b = T (q - r)
+//    is affine in the mapped parameters q, so db_i/dp_k = T[i][k] s_k (i < nd) and
+//    db_nd/dp_k = -sum_i T[i][k] s_k, with s_k = 1 / (p_k ln 10) for a log_mask
+//    parameter and 1 otherwise: an (nd + 1) x nd table in LDS, filled once per block.
+//    A pixel's nd + 1 vertex values are read once and serve the value and all nd
+//    tangent sums; the template row is formed by the same operations either way.
 // ---------------------------------------------------------------------------
 #define TRI_MAXDIM 6
 
@@ -266,6 +273,7 @@ __global__ void __launch_bounds__(64)
   if (active && finite && found != 0x7fffffff) atomicMin(&simplex[b], found);
 }
 
+template <bool GRAD>
 __device__ __forceinline__ void
     tri_eval_body(const double *__restrict__ dats, int ntp,
                   const int32_t *__restrict__ simplices,
@@ -280,12 +288,14 @@ __device__ __forceinline__ void
   __shared__ double sh_b[TRI_MAXDIM + 1];
   __shared__ int sh_id[TRI_MAXDIM + 1];
   __shared__ double red_m[8];
+  // db_i/dp_k [i][k]
+  __shared__ double sh_db[GRAD ? (TRI_MAXDIM + 1) * TRI_MAXDIM : 1];
   const int b = blockIdx.x, tid = threadIdx.x;
   if (live && b >= live[0]) return;   // (rows nobody waits for: rvs_nm_run)
   const int sx = simplex[b];
-  double *out = templ + (int64_t)b * ntp;
+  double *out = templ + (int64_t)b * ntp * (GRAD ? 1 + nd : 1);
   if (sx == 0x7fffffff || sx < 0) {  // TriInterp returns nan (spec_inter.py:45-47)
-    for (int k = tid; k < ntp; k += 256) out[k] = __builtin_nan("");
+    for (int k = tid; k < ntp * (GRAD ? 1 + nd : 1); k += 256) out[k] = __builtin_nan("");
     if (tid == 0) outside[b] = __builtin_nan("");
     if (weights && tid <= nd) weights[(int64_t)b * (nd + 1) + tid] = 0.0;
     return;
@@ -307,15 +317,56 @@ __device__ __forceinline__ void
     sh_b[nd] = 1.0 - sum;
     for (int i = 0; i <= nd; i++) sh_id[i] = simplices[(int64_t)sx * (nd + 1) + i];
   }
+  if constexpr (GRAD) {
+    if (tid < nd) {   // column tid of the table
+      const double *T = transform + (int64_t)sx * (nd + 1) * nd;
+      double s = 1.0;
+      if ((log_mask >> tid) & 1u)
+        s = 1.0 / (params[(int64_t)b * nd + tid] * 2.302585092994046);
+      double sum = 0;
+      for (int i = 0; i < nd; i++) {
+        const double d = T[i * nd + tid] * s;
+        sh_db[i * TRI_MAXDIM + tid] = d;
+        sum += d;
+      }
+      sh_db[nd * TRI_MAXDIM + tid] = -sum;
+    }
+  }
   __syncthreads();
   double mx = 0;
   bool anynan = false;
   for (int k = tid; k < ntp; k += 256) {
-    double acc = __dmul_rn(dats[(int64_t)sh_id[0] * ntp + k], sh_b[0]);
-    for (int i = 1; i <= nd; i++)
-      acc = __dadd_rn(acc, __dmul_rn(dats[(int64_t)sh_id[i] * ntp + k], sh_b[i]));
+    double acc;
+    double g[GRAD ? TRI_MAXDIM : 1] = {};
+    if constexpr (GRAD) {
+      // (static indices: the vertex values and the tangent sums in registers)
+      double L[TRI_MAXDIM + 1];
+#pragma unroll
+      for (int i = 0; i <= TRI_MAXDIM; i++)
+        L[i] = (i <= nd) ? dats[(int64_t)sh_id[i] * ntp + k] : 0.0;
+      acc = __dmul_rn(L[0], sh_b[0]);
+#pragma unroll
+      for (int i = 1; i <= TRI_MAXDIM; i++)
+        if (i <= nd) acc = __dadd_rn(acc, __dmul_rn(L[i], sh_b[i]));
+#pragma unroll
+      for (int i = 0; i <= TRI_MAXDIM; i++)
+        if (i <= nd) {
+#pragma unroll
+          for (int d = 0; d < TRI_MAXDIM; d++)
+            if (d < nd) g[d] = fma(sh_db[i * TRI_MAXDIM + d], L[i], g[d]);
+        }
+    } else {
+      acc = __dmul_rn(dats[(int64_t)sh_id[0] * ntp + k], sh_b[0]);
+      for (int i = 1; i <= nd; i++)
+        acc = __dadd_rn(acc, __dmul_rn(dats[(int64_t)sh_id[i] * ntp + k], sh_b[i]));
+    }
     const double val = exp_flag ? exp(acc) : acc;
     out[k] = val;
+    if constexpr (GRAD) {
+#pragma unroll
+      for (int d = 0; d < TRI_MAXDIM; d++)
+        if (d < nd) out[(int64_t)(1 + d) * ntp + k] = exp_flag ? val * g[d] : g[d];
+    }
     if (!(val == val)) anynan = true;
     mx = fmax(mx, fabs(val));
   }
@@ -338,6 +389,7 @@ __device__ __forceinline__ void
   }
   if (weights && tid <= nd) weights[(int64_t)b * (nd + 1) + tid] = sh_b[tid];
 }
+template <bool GRAD>
 __global__ void __launch_bounds__(256)
     tri_eval_kernel(const double *__restrict__ dats, int ntp,
                     const int32_t *__restrict__ simplices,
@@ -349,8 +401,8 @@ __global__ void __launch_bounds__(256)
                     double *__restrict__ templ, double *__restrict__ outside,
                     double *__restrict__ weights,
                     const int32_t *__restrict__ live = nullptr) {
-  tri_eval_body(dats, ntp, simplices, transform, extraflags, nd, log_mask, exp_flag,
-                params, simplex, templ, outside, weights, live);
+  tri_eval_body<GRAD>(dats, ntp, simplices, transform, extraflags, nd, log_mask,
+                      exp_flag, params, simplex, templ, outside, weights, live);
 }
 
 // find_simplex through a uniform bucket grid over the (mapped) parameter space: a
@@ -437,7 +489,8 @@ __global__ void __launch_bounds__(64 * TRI_LOC_WAVES)
   tri_locate_bucket_body(transform, nd, log_mask, params, B, K, simplex, live);
 }
 
-extern "C" int rvs_template_tri_buckets(
+template <bool GRAD>
+static int tri_buckets_launch(
     const double *dats, int ntp, const int32_t *simplices, const double *transform,
     const double *extraflags, int nsimplex, int ndim, uint32_t log_mask,
     int exp_flag, const rvs_tri_buckets *buckets, const double *params, int B,
@@ -453,11 +506,34 @@ extern "C" int rvs_template_tri_buckets(
                      dim3((B + TRI_LOC_WAVES - 1) / TRI_LOC_WAVES),
                      dim3(64 * TRI_LOC_WAVES), 0, st, transform, ndim, log_mask, params,
                      B, *buckets, simplex, nullptr);
-  hipLaunchKernelGGL(tri_eval_kernel, dim3(B), dim3(256), 0, st, dats, ntp,
+  hipLaunchKernelGGL(tri_eval_kernel<GRAD>, dim3(B), dim3(256), 0, st, dats, ntp,
                      simplices, transform, extraflags, ndim, log_mask, exp_flag,
                      params, simplex, templ, outside, weights, nullptr);
   RVS_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int rvs_template_tri_buckets(
+    const double *dats, int ntp, const int32_t *simplices, const double *transform,
+    const double *extraflags, int nsimplex, int ndim, uint32_t log_mask,
+    int exp_flag, const rvs_tri_buckets *buckets, const double *params, int B,
+    double *templ, double *outside, int32_t *simplex, double *weights,
+    void *stream) {
+  return tri_buckets_launch<false>(dats, ntp, simplices, transform, extraflags,
+                                   nsimplex, ndim, log_mask, exp_flag, buckets, params,
+                                   B, templ, outside, simplex, weights, stream);
+}
+
+// spec_inter.py:11-59 differentiated: templ [B, 1 + ndim, ntp]
+extern "C" int rvs_template_tri_buckets_grad(
+    const double *dats, int ntp, const int32_t *simplices, const double *transform,
+    const double *extraflags, int nsimplex, int ndim, uint32_t log_mask,
+    int exp_flag, const rvs_tri_buckets *buckets, const double *params, int B,
+    double *templ, double *outside, int32_t *simplex, double *weights,
+    void *stream) {
+  return tri_buckets_launch<true>(dats, ntp, simplices, transform, extraflags,
+                                  nsimplex, ndim, log_mask, exp_flag, buckets, params,
+                                  B, templ, outside, simplex, weights, stream);
 }
 
 // the template rows of an optimiser round on Delaunay libraries (rvs_nm_run,
@@ -479,8 +555,9 @@ __global__ void __launch_bounds__(256)
     tri_eval_arms_kernel(TriArms A, int nd, const double *__restrict__ params,
                          const int32_t *__restrict__ live) {
   const rvs_nm_tri_arm &T = A.a[blockIdx.y];
-  tri_eval_body(T.dats, T.ntp, T.simplices, T.transform, T.extraflags, nd, T.log_mask,
-                T.exp_flag, params, T.simplex, T.templ, T.outside, nullptr, live);
+  tri_eval_body<false>(T.dats, T.ntp, T.simplices, T.transform, T.extraflags, nd,
+                       T.log_mask, T.exp_flag, params, T.simplex, T.templ, T.outside,
+                       nullptr, live);
 }
 
 int rvs_internal_template_tri_arms_n(const double *params, int B, const int32_t *live,
@@ -519,14 +596,12 @@ int rvs_internal_template_tri_arms_n(const double *params, int B, const int32_t 
   return 0;
 }
 
-extern "C" int rvs_template_tri(const double *dats, int ntp,
-                                const int32_t *simplices,
-                                const double *transform,
-                                const double *extraflags, int nsimplex, int ndim,
-                                uint32_t log_mask, int exp_flag,
-                                const double *params, int B, double *templ,
-                                double *outside, int32_t *simplex,
-                                double *weights, void *stream) {
+template <bool GRAD>
+static int tri_launch(const double *dats, int ntp, const int32_t *simplices,
+                      const double *transform, const double *extraflags,
+                      int nsimplex, int ndim, uint32_t log_mask, int exp_flag,
+                      const double *params, int B, double *templ, double *outside,
+                      int32_t *simplex, double *weights, void *stream) {
   if (ndim < 1 || ndim > TRI_MAXDIM || B < 1 || ntp < 1 || nsimplex < 1 ||
       !simplex)
     return RVS_E_ARG;
@@ -541,11 +616,38 @@ extern "C" int rvs_template_tri(const double *dats, int ntp,
   hipLaunchKernelGGL(tri_locate_kernel, dim3(groups, nslice), dim3(64), 0, st,
                      transform, nsimplex, ndim, log_mask, params, B, nslice,
                      simplex);
-  hipLaunchKernelGGL(tri_eval_kernel, dim3(B), dim3(256), 0, st, dats, ntp,
+  hipLaunchKernelGGL(tri_eval_kernel<GRAD>, dim3(B), dim3(256), 0, st, dats, ntp,
                      simplices, transform, extraflags, ndim, log_mask, exp_flag,
-                     params, simplex, templ, outside, weights);
+                     params, simplex, templ, outside, weights, nullptr);
   RVS_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int rvs_template_tri(const double *dats, int ntp,
+                                const int32_t *simplices,
+                                const double *transform,
+                                const double *extraflags, int nsimplex, int ndim,
+                                uint32_t log_mask, int exp_flag,
+                                const double *params, int B, double *templ,
+                                double *outside, int32_t *simplex,
+                                double *weights, void *stream) {
+  return tri_launch<false>(dats, ntp, simplices, transform, extraflags, nsimplex, ndim,
+                           log_mask, exp_flag, params, B, templ, outside, simplex,
+                           weights, stream);
+}
+
+// spec_inter.py:11-59 differentiated: templ [B, 1 + ndim, ntp]
+extern "C" int rvs_template_tri_grad(const double *dats, int ntp,
+                                     const int32_t *simplices,
+                                     const double *transform,
+                                     const double *extraflags, int nsimplex,
+                                     int ndim, uint32_t log_mask, int exp_flag,
+                                     const double *params, int B, double *templ,
+                                     double *outside, int32_t *simplex,
+                                     double *weights, void *stream) {
+  return tri_launch<true>(dats, ntp, simplices, transform, extraflags, nsimplex, ndim,
+                          log_mask, exp_flag, params, B, templ, outside, simplex,
+                          weights, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -971,9 +971,9 @@ def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
         if arm.G > 1:
             raise ValueError('the analytic gradient does not take a grid set: arm '
                              '%s has %d wavelength grids' % (arm.name, arm.G))
-        if libs[arm.name].kind != 'regulargrid':
+        if libs[arm.name].kind not in ('regulargrid', 'triangulation'):
             raise ValueError('the analytic gradient needs regular-grid (polylinear) '
-                             'libraries, %s is a %s library'
+                             'or Delaunay libraries, %s is a %s library'
                              % (arm.name, libs[arm.name].kind))
         if vsini_grad and 1 + libs[arm.name].ndim > GRAD_MAXTAN:
             raise ValueError('the analytic gradient takes at most %d tangents: vsini '
@@ -992,7 +992,8 @@ def chisq_point_grad(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
     in physical units, status int32 [J].  The outside penalty is piecewise and is
     not differentiated.  What the kernel does not cover is refused, never
     finite-differenced: npoly > 16, several wavelength grids per arm, a
-    resolution matrix, fast_interp, libraries that are not regular grids."""
+    resolution matrix, fast_interp, libraries that are neither regular grids nor
+    Delaunay triangulations (MLP libraries)."""
     import ctypes
     ntan = coefs[0].shape[1] - 1
     check_grad_scope(batch, libs, npoly, resols, fast_interp,

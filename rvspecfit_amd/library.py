@@ -401,18 +401,31 @@ class TemplateLibrary:
     def eval_batch_grad(self, params, details=False):
         """eval_batch with the derivative: templ [J, 1 + ndim, ntp] -- row 0 the
         template (the bits of eval_batch), row 1 + k its derivative with respect
-        to physical parameter k (rvs_template_polylinear_grad; zero rows where
-        the evaluator answers with the nearest grid point) -- and outside [J].
-        Regular-grid libraries only."""
-        if self.kind != 'regulargrid':
-            raise ValueError('template tangents need a regular-grid (polylinear) '
-                             'library, %s is a %s library' % (self.name, self.kind))
+        to physical parameter k -- and outside [J].  Regular-grid libraries
+        (rvs_template_polylinear_grad; zero rows where the evaluator answers with
+        the nearest grid point) and Delaunay libraries (rvs_template_tri_grad /
+        rvs_template_tri_buckets_grad; every row NaN where no simplex holds the
+        point); details=True adds what eval_batch adds for the library's kind."""
+        if self.kind not in ('regulargrid', 'triangulation'):
+            raise ValueError('template tangents need a regular-grid (polylinear) or '
+                             'a Delaunay library, %s is a %s library'
+                             % (self.name, self.kind))
         L = _lib.lib()
         J = params.shape[0]
         params = params.to(torch.float64).contiguous()
         templ = torch.empty((J, 1 + self.ndim, self.ntp), dtype=torch.float64,
                             device=self.device)
         outside = torch.empty(J, dtype=torch.float64, device=self.device)
+        if self.kind == 'triangulation':
+            sx = torch.empty(J, dtype=torch.int32, device=self.device)
+            wts = torch.zeros((J, self.ndim + 1), dtype=torch.float64,
+                              device=self.device) if details else None
+            rc = self._tri_call(self.log_mask, params, J, templ, outside, sx, wts,
+                                _lib.stream(), grad=True)
+            _lib.check(rc, 'rvs_template_tri_grad')
+            if details:
+                return templ, outside, sx, wts
+            return templ, outside
         nv = 1 << self.ndim
         cell = wts = None
         if details:
@@ -430,18 +443,21 @@ class TemplateLibrary:
             return templ, outside, cell, wts
         return templ, outside
 
-    def _tri_call(self, log_mask, params, J, templ, outside, sx, wts, stream):
+    def _tri_call(self, log_mask, params, J, templ, outside, sx, wts, stream,
+                  grad=False):
+        """grad: templ [J, 1 + ndim, ntp], the _grad entry points"""
         import ctypes
         L = _lib.lib()
         if self._tri_bk is not None and TRI_BUCKETS:
-            return L.rvs_template_tri_buckets(
+            return (L.rvs_template_tri_buckets_grad if grad
+                    else L.rvs_template_tri_buckets)(
                 _lib.ptr(self.dats), self.ntp, _lib.ptr(self.tri_simplices),
                 _lib.ptr(self.tri_transform), _lib.ptr(self.tri_extraflags),
                 self.tri_nsimplex, self.ndim, log_mask, self.exp_flag,
                 ctypes.addressof(self._tri_bk), _lib.ptr(params), J,
                 _lib.ptr(templ), _lib.ptr(outside), _lib.ptr(sx), _lib.ptr(wts),
                 stream)
-        return L.rvs_template_tri(
+        return (L.rvs_template_tri_grad if grad else L.rvs_template_tri)(
             _lib.ptr(self.dats), self.ntp, _lib.ptr(self.tri_simplices),
             _lib.ptr(self.tri_transform), _lib.ptr(self.tri_extraflags),
             self.tri_nsimplex, self.ndim, log_mask, self.exp_flag,

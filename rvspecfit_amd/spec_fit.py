@@ -502,8 +502,10 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
     One spectrum: returns (float, ndarray [1 + ndim]).  SpecBatch: vel [S],
     atm_params [S, ndim] (or one tuple), rot_params None or vsini [S]; returns
     device tensors [S] and [S, 1 + ndim] ([.., 2 + ndim] with vsini_grad).
-    Regular-grid libraries, npoly <= 16, one wavelength grid per setup, no
-    resolution matrix, no fast_interp: anything else raises ValueError."""
+    Regular-grid and Delaunay libraries, npoly <= 16, one wavelength grid per
+    setup, no resolution matrix, no fast_interp: anything else (an MLP library
+    included) raises ValueError.  On a Delaunay library a point that no simplex
+    holds has the value's penalty and a zero gradient."""
     options = options or {}
     npoly = options.get('npoly') or 5
     rbf = options.get('rbf_continuum', True)

@@ -4,10 +4,12 @@ against the (2 + ndim) spec_fit.chisq_jobs calls of a forward difference (the po
 itself, then one call per displaced coordinate: velocity and the ndim parameters --
 what a caller without the gradient has to do, and what BFGS does per gradient).
 usage: grad_ab.py [--jobs J] [--spectra S] [--npoly P] [--rounds R] [--vsini]
-                  [--vsini-grad]
+                  [--vsini-grad] [--evaluator polylinear|tri]
+--evaluator tri: bench.py's Delaunay library (the same grid nodes triangulated, its
+`--evaluator tri`): rvs_template_tri_buckets_grad in front of the same chain.
 --vsini-grad (implies --vsini): the analytic call carries the vsini tangent row
 (vsini_grad=True) and the forward difference displaces vsini too: 3 + ndim calls.
-The workload is bench.py's (its synthetic DESI-shape polylinear libraries and
+The workload is bench.py's (its synthetic DESI-shape libraries and
 spectra); the jobs are its truth parameters, jittered inside the grid, spread over the
 S spectra.  Both arms run alternately in one process, R rounds after a warm-up; one
 JSON line: median and minimum seconds of each arm, their ratio, and the largest
@@ -31,6 +33,7 @@ def main():
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--vsini', action='store_true')
     ap.add_argument('--vsini-grad', action='store_true')
+    ap.add_argument('--evaluator', choices=['polylinear', 'tri'], default='polylinear')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
     import numpy as np
@@ -47,6 +50,7 @@ def main():
         v = torch.as_tensor(np.ascontiguousarray(vsini)).to(dev)
         return engine.convolve_vsini(lam, t, v).cpu().numpy()
 
+    bench.EVALUATOR = args.evaluator
     for name, d in bench.build_library_dicts(64, gpu_convolve).items():
         spec_inter.register_library(TemplateLibrary(name, d, device=dev),
                                     bench.CONFIG['template_lib'])
@@ -107,7 +111,8 @@ def main():
     scale = torch.maximum(ga.abs(), 1e-6 * ga.abs().max(dim=1, keepdim=True).values)
     rel = ((ga - gd).abs() / scale)[ok]
     print(json.dumps(dict(
-        jobs=J, spectra=S, npoly=args.npoly, ndim=ndim, vsini=vs is not None,
+        jobs=J, spectra=S, npoly=args.npoly, ndim=ndim, evaluator=args.evaluator,
+        vsini=vs is not None,
         vsini_grad=vg, rounds=args.rounds, chisq_jobs_calls=1 + x.shape[1],
         analytic_s_median=round(float(np.median(ta)), 6),
         analytic_s_min=round(min(ta), 6),

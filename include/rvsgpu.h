@@ -711,6 +711,30 @@ int rvs_bfgs_result(void *h, double *x, double *fun, int32_t *nit,
                     int64_t *rounds);
 void rvs_bfgs_end(void *h);
 
+/* The same runs around an objective that returns its gradient: scipy's
+ * minimize(fun, x0, method='BFGS', jac=True, options={'hess_inv0': ...}), where
+ * MemoizeJac calls `fun` once per new x and ScalarFunction hands out the value and
+ * the gradient of that call.  Every pending request is ONE row per run, and its
+ * reply is the row F[r, 0 .. n] = (f, df/dx_0 .. df/dx_{n-1}):
+ *     h = rvs_bfgs_begin_jac(...)                     arguments of rvs_bfgs_begin
+ *     while ((rows = rvs_bfgs_pending(h, idx, X, cap)) > 0) {     cap >= S suffices
+ *         F[r, :] = (objective, gradient)(spectrum idx[r], point X[r, :])
+ *         rvs_bfgs_feed_jac(h, F [rows, 1 + n], rows);
+ *     }
+ *     rvs_bfgs_result_jac(h, x, fun, nit, nfev, njev, status, hess_inv, &rounds);
+ *     rvs_bfgs_end(h);
+ * nfev / njev are scipy's: values and gradients ScalarFunction handed out (both
+ * count an x once; the objective itself ran once per x).  rvs_bfgs_feed on a handle
+ * of rvs_bfgs_begin_jac, rvs_bfgs_feed_jac on one of rvs_bfgs_begin, a row count
+ * other than the pending one and a NULL array: RVS_E_ARG. */
+void *rvs_bfgs_begin_jac(int S, int n, const double *x0, const double *hess_inv0,
+                         double gtol, double c1, double c2, double xrtol,
+                         int maxiter);
+int rvs_bfgs_feed_jac(void *h, const double *F, int64_t nrows);
+int rvs_bfgs_result_jac(void *h, double *x, double *fun, int32_t *nit,
+                        int32_t *nfev, int32_t *njev, int32_t *status,
+                        double *hess_inv, int64_t *rounds);
+
 /* ------------------------------------------------------------------------
  * The tables that depend only on a wavelength grid, for G grids at once (one per
  * arm on the fast path; one per SPECTRUM for SDSS-style objects): built on the
@@ -1088,6 +1112,100 @@ typedef struct rvs_bfgs_state {
 int64_t rvs_bfgs_run_bytes(void);
 int rvs_bfgs_run(const rvs_bfgs_state *b, const rvs_nm_objective *o,
                  int sync_every, int64_t *stats, void *stream);
+
+/* ------------------------------------------------------------------------
+ * The second minimiser on the analytic gradient: scipy's
+ * minimize(vel_fit.chisq_func_grad, x, method='BFGS', jac=True, hess_inv0=...) for S
+ * spectra, the rounds on the device.
+ *
+ * rvs_proc_finish_grad is to vel_fit.chisq_func_grad what rvs_proc_finish is to
+ * chisq_func: from the gradient chain's chi [J] and grad [J, 1 + ntan] -- ordered
+ * (vel, stellar parameters in library order, vsini last when it is fitted: ntan =
+ * ndim or ndim + 1) -- and what rvs_proc_map wrote for the rows X [J, n], it forms
+ * F [J, 1 + n]: F[j, 0] = bad ? 1e30 : chi + extra as rvs_proc_finish does, then the
+ * derivative by every column of X: the velocity's copied; a fitted parameter's taken
+ * through src (HOST [ndim], as for rvs_proc_map), plus 2 (p - mean) isig^2 where
+ * prior_isig is not 0; the vsini column's (d/dvsini if 0 < x < max_vsini, else 0)
+ * + 2 (x - clamp(x, 0, max_vsini)).  A bad row is (1e30, zeros).  Status bits of the
+ * live rows are OR-ed into spec_status[job_spec[j]] as by rvs_proc_finish.
+ * RVS_E_ARG: a NULL array, n > 8, ndim > 6, ntan != ndim + (vsini_col >= 0), a src
+ * entry that is 0, vsini_col or >= n, columns of X without a source. */
+int rvs_proc_finish_grad(int J, int n, int ndim, int ntan, const int32_t *counts,
+                         int cidx, const double *chi, const double *grad,
+                         const double *X, const double *params, const double *extra,
+                         const int32_t *bad, const int32_t *job_spec,
+                         const int32_t *job_status, const int32_t *src,
+                         int vsini_col, const double *prior_mean,
+                         const double *prior_isig, double max_vsini, double *F,
+                         int32_t *spec_status, void *stream);
+
+/* One arm of the gradient chain: its template library -- tri == 0: a regular grid,
+ * the arguments of rvs_template_polylinear_grad (dats float32; lens, ptp HOST arrays);
+ * tri != 0: a Delaunay library, the arguments of rvs_template_tri_buckets_grad
+ * (buckets.cell_start != NULL) or rvs_template_tri_grad (dats float64) -- the knots and
+ * rvs_spline_factors of its template grid, and the caller's row buffers for `cap` rows
+ * with K = 1 + ntan template rows each:
+ *   templ   [cap, K, ntp]     the evaluator's rows (1 + ndim per job)
+ *   templ2  [cap, K, ntp]     the broadened rows (vsini_mode != 0)
+ *   coef    [cap, K, ntp, 4]  form-1 spline records: rvs_point_arm.coef of the arm
+ *   outside, penalty [cap]    penalty: rvs_point_arm.penalty of the arm
+ *   simplex int32 [cap]       (Delaunay)
+ *   vs_rows, out_rows [cap (1 + ndim)]  (vsini_mode == 1: vsini / outside per row) */
+typedef struct rvs_grad_arm {
+  const void *dats;
+  const int64_t *idgrid;
+  const double *uvecs, *vecs_s;
+  const int32_t *lens;
+  const double *ptp;
+  const double *transform, *extraflags;
+  const int32_t *simplices;
+  const double *knots, *factors;
+  double *templ, *templ2, *coef, *outside, *penalty, *vs_rows, *out_rows;
+  int32_t *simplex;
+  rvs_tri_buckets buckets;
+  int64_t ngrid;
+  double lnstep;
+  int32_t tri, nsimplex, ntp, exp_flag, spline_form;
+  uint32_t log_mask;
+} rvs_grad_arm;
+
+/* The chain for the rows of a round: arms / point / basis_const are HOST arrays [narm];
+ * `point` are the descriptors rvs_chisq_point_grad takes (polysT the orthonormalised
+ * basis, basis_const its log-determinant constant, coef / penalty the arm's buffers
+ * above); pen_scale as rvs_point_arm.pen_scale (device [S] or NULL).
+ *   vsini_mode  0 no rotation; 1 vsini fixed (rvs_vsini_convolve over the 1 + ndim
+ *               rows); 2 vsini fitted (rvs_vsini_convolve_grad, ntan = ndim + 1)
+ *   point_work  rvs_chisq_point_grad_work_size(cap, narm, ntan) bytes
+ *   chi [cap], grad [cap, 1 + ntan]   the chain's results of a chunk
+ *   njev [S]    out: gradients handed out per run (scipy's njev)
+ * rvs_grad_chain_work_size: bytes of all of these buffers together, for choosing cap
+ * (ntp HOST [narm]); 0 for arguments out of range. */
+typedef struct rvs_grad_chain {
+  const rvs_grad_arm *arms;
+  const rvs_point_arm *point;
+  const double *basis_const;
+  const double *pen_scale;
+  void *point_work;
+  double *chi, *grad;
+  int32_t *njev;
+  int32_t narm, ntan, cap, vsini_mode;
+} rvs_grad_chain;
+int64_t rvs_grad_chain_work_size(int cap, int narm, int ntan, const int32_t *ntp,
+                                 int vsini_mode);
+
+/* rvs_bfgs_run with the machine of rvs_bfgs_begin_jac: a run asks for ONE row per
+ * request and reads (f, grad f) = F[row, 0 .. n]; a round is advance -> scan -> emit
+ * (the kernels of rvs_bfgs_run) -> per chunk of g->cap rows rvs_proc_map, the gradient
+ * chain (per arm the template rows and their tangents, the broadening, the spline
+ * records; rvs_chisq_point_grad over all arms) and rvs_proc_finish_grad, with no
+ * interpreter in between; the host looks at the counters as rvs_bfgs_run does.
+ * `b` as for rvs_bfgs_run (its buffers at their sizes there; b->cap is not read);
+ * `o`: the mapping's tables and row buffers (capacity >= g->cap rows), narm, npoly,
+ * badchi, status; o->arms / nn / tri / chi / scratch are not read.
+ * n = o->n <= 8, ndim <= 6, S <= 24 g->cap.  stats as for rvs_bfgs_run. */
+int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                      const rvs_grad_chain *g, int sync_every, int64_t *stats,
+                      void *stream);
 
 /* ------------------------------------------------------------------------
  * Template libraries from high-resolution models; replaces rvs_make_interpol's

@@ -78,8 +78,15 @@ SIGNATURES = {
     'rvs_bfgs_feed': (I, [P, P, L]),
     'rvs_bfgs_result': (I, [P, P, P, P, P, P, P, P]),
     'rvs_bfgs_end': (None, [P]),
+    'rvs_bfgs_begin_jac': (P, [I, I, P, P, D, D, D, D, I]),
+    'rvs_bfgs_feed_jac': (I, [P, P, L]),
+    'rvs_bfgs_result_jac': (I, [P, P, P, P, P, P, P, P, P]),
     'rvs_bfgs_run_bytes': (L, []),
     'rvs_bfgs_run': (I, [P, P, I, P, P]),
+    'rvs_proc_finish_grad': (I, [I, I, I, I, P, I, P, P, P, P, P, P, P, P, P, I, P, P,
+                                 D, P, P, P]),
+    'rvs_grad_chain_work_size': (L, [I, I, I, P, I]),
+    'rvs_bfgs_run_grad': (I, [P, P, P, I, P, P]),
     'rvs_objective_max_ntp': (I, [I]),
     'rvs_objective_resol_ok': (I, [I, I, I, I]),
     'rvs_objective_work_size': (L, [I, I]),
@@ -233,6 +240,27 @@ class NmTriArm(ctypes.Structure):
                  'simplex')] + [('buckets', TriBuckets)] + [
                     (k, ctypes.c_int32) for k in ('ntp', 'nsimplex', 'exp_flag')] + [
                     ('log_mask', ctypes.c_uint32)]
+
+
+class GradArm(ctypes.Structure):
+    """rvs_grad_arm of include/rvsgpu.h"""
+    _fields_ = [(k, ctypes.c_void_p) for k in
+                ('dats', 'idgrid', 'uvecs', 'vecs_s', 'lens', 'ptp', 'transform',
+                 'extraflags', 'simplices', 'knots', 'factors', 'templ', 'templ2',
+                 'coef', 'outside', 'penalty', 'vs_rows', 'out_rows', 'simplex')] + [
+                    ('buckets', TriBuckets), ('ngrid', ctypes.c_int64),
+                    ('lnstep', ctypes.c_double)] + [
+                    (k, ctypes.c_int32) for k in
+                    ('tri', 'nsimplex', 'ntp', 'exp_flag', 'spline_form')] + [
+                    ('log_mask', ctypes.c_uint32)]
+
+
+class GradChain(ctypes.Structure):
+    """rvs_grad_chain of include/rvsgpu.h"""
+    _fields_ = [(k, ctypes.c_void_p) for k in
+                ('arms', 'point', 'basis_const', 'pen_scale', 'point_work', 'chi',
+                 'grad', 'njev')] + [(k, ctypes.c_int32) for k in
+                                     ('narm', 'ntan', 'cap', 'vsini_mode')]
 
 
 class PointArm(ctypes.Structure):

@@ -21,11 +21,14 @@ import numpy as np
 
 
 def minimize_lockstep_native(func, x0, hess_inv0=None, max_rows=None, gtol=1e-5,
-                             c1=1e-4, c2=0.9, xrtol=0, maxiter=None):
+                             c1=1e-4, c2=0.9, xrtol=0, maxiter=None, jac=False):
     """minimize_lockstep with the per-spectrum state machines in C++
     (csrc/bfgs_host.cpp, rvs_bfgs_*): the same algorithm, scalar arithmetic in
     index order, so it follows the Python/scipy iterates to rounding rather than
-    to the bit; the host cost per request drops from ~20 us to ~0.1 us."""
+    to the bit; the host cost per request drops from ~20 us to ~0.1 us.
+    jac=True: scipy's minimize(..., jac=True) -- func(idx [J], X [J, n]) returns
+    [J, 1 + n], the value and its gradient (rvs_bfgs_*_jac: one row per request,
+    no differences); the result then carries njev."""
     import ctypes
     from . import _lib
     L = _lib.lib()
@@ -37,8 +40,9 @@ def minimize_lockstep_native(func, x0, hess_inv0=None, max_rows=None, gtol=1e-5,
     def p(a):
         return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
-    h = L.rvs_bfgs_begin(S, n, p(x0), p(H0), float(gtol), float(c1), float(c2),
-                         float(xrtol), int(maxiter or 0))
+    begin = L.rvs_bfgs_begin_jac if jac else L.rvs_bfgs_begin
+    h = begin(S, n, p(x0), p(H0), float(gtol), float(c1), float(c2),
+              float(xrtol), int(maxiter or 0))
     if not h:
         raise ValueError('rvs_bfgs_begin: bad arguments (n <= 16)')
     h = ctypes.c_void_p(h)
@@ -61,7 +65,13 @@ def minimize_lockstep_native(func, x0, hess_inv0=None, max_rows=None, gtol=1e-5,
                                dtype=np.float64)
                     for a in range(0, rows, max_rows)])
             F = np.ascontiguousarray(F)
-            _lib.check(L.rvs_bfgs_feed(h, p(F), rows), 'rvs_bfgs_feed')
+            if jac:
+                if F.shape != (rows, n + 1):
+                    raise ValueError('jac=True: the objective returns [rows, 1 + n]'
+                                     ', not %s' % (F.shape, ))
+                _lib.check(L.rvs_bfgs_feed_jac(h, p(F), rows), 'rvs_bfgs_feed_jac')
+            else:
+                _lib.check(L.rvs_bfgs_feed(h, p(F), rows), 'rvs_bfgs_feed')
         x = np.empty((S, n))
         fun = np.empty(S)
         nit = np.empty(S, dtype=np.int32)
@@ -69,23 +79,39 @@ def minimize_lockstep_native(func, x0, hess_inv0=None, max_rows=None, gtol=1e-5,
         status = np.empty(S, dtype=np.int32)
         Hk = np.empty((S, n, n))
         rounds = ctypes.c_int64(0)
-        _lib.check(L.rvs_bfgs_result(h, p(x), p(fun), p(nit), p(nfev), p(status),
-                                     p(Hk), ctypes.byref(rounds)),
-                   'rvs_bfgs_result')
+        if jac:
+            njev = np.empty(S, dtype=np.int32)
+            _lib.check(L.rvs_bfgs_result_jac(h, p(x), p(fun), p(nit), p(nfev),
+                                             p(njev), p(status), p(Hk),
+                                             ctypes.byref(rounds)),
+                       'rvs_bfgs_result_jac')
+        else:
+            _lib.check(L.rvs_bfgs_result(h, p(x), p(fun), p(nit), p(nfev),
+                                         p(status), p(Hk), ctypes.byref(rounds)),
+                       'rvs_bfgs_result')
     finally:
         L.rvs_bfgs_end(h)
-    return dict(x=x, fun=fun, nit=nit.astype(np.int64),
-                nfev=nfev.astype(np.int64), status=status.astype(np.int64),
-                hess_inv=list(Hk), rounds=int(rounds.value))
+    ret = dict(x=x, fun=fun, nit=nit.astype(np.int64),
+               nfev=nfev.astype(np.int64), status=status.astype(np.int64),
+               hess_inv=list(Hk), rounds=int(rounds.value))
+    if jac:
+        ret['njev'] = njev.astype(np.int64)
+    return ret
 
 
 def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.9,
-                             xrtol=0, maxiter=None, sync_every=4):
+                             xrtol=0, maxiter=None, sync_every=4, jac=False,
+                             chain=None, cap=None):
     """The runs on the device (csrc/bfgs_dev.hip, rvs_bfgs_run) around an
     optimizer.ProcessObjective whose rounds the library drives (pobj.native):
     x0 [S, n] device tensor, hess_inv0 [n, n] array.  Returns
     device tensors x [S, n], fun, nit, nfev, status [S] and the statistics of the
-    run (rounds, objective calls, rows launched)."""
+    run (rounds, objective calls, rows launched).
+    jac=True: scipy's jac=True on the analytic gradient (rvs_bfgs_run_grad): the
+    objective is the gradient chain of an optimizer.GradChain (`chain`, or one
+    built here with `cap` rows per chunk -- by default as many as
+    optimizer.GRAD_CHAIN_BUDGET holds); the result then carries njev.  Libraries
+    and options the gradient does not cover raise ValueError."""
     import ctypes
     import torch
     from . import _lib
@@ -94,6 +120,9 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     S, n = x0.shape
     if n != pobj.n or S != pobj.S:
         raise ValueError('minimize_lockstep_device: x0 does not fit the objective')
+    if jac and chain is None:
+        from . import optimizer
+        chain = optimizer.GradChain(pobj, cap=cap)
     f64 = dict(dtype=torch.float64, device=dev)
     i32 = dict(dtype=torch.int32, device=dev)
     rows = S * (n + 1)
@@ -116,13 +145,28 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     b.S, b.n, b.cap, b.maxiter = S, n, int(pobj.cap), int(maxiter or 0)
     o = pobj.native_desc()
     st3 = (ctypes.c_int64 * 3)()
-    _lib.check(L.rvs_bfgs_run(ctypes.addressof(b), ctypes.addressof(o),
-                              int(sync_every), st3, _lib.stream()),
-               'rvs_bfgs_run')
+    if jac:
+        g = chain.desc()
+        _lib.check(L.rvs_bfgs_run_grad(ctypes.addressof(b), ctypes.addressof(o),
+                                       ctypes.addressof(g), int(sync_every), st3,
+                                       _lib.stream()),
+                   'rvs_bfgs_run_grad')
+    else:
+        _lib.check(L.rvs_bfgs_run(ctypes.addressof(b), ctypes.addressof(o),
+                                  int(sync_every), st3, _lib.stream()),
+                   'rvs_bfgs_run')
     pobj.calls += int(st3[1])
     nfev = keep['nfev'].long()
-    pobj.jobs += int(nfev.sum().item())
     pobj.slots += int(st3[2])
-    return dict(x=keep['x'], fun=keep['fun'], nit=keep['nit'].long(), nfev=nfev,
-                status=keep['status'].long(), rounds=int(st3[0]),
-                calls=int(st3[1]), rows_launched=int(st3[2]))
+    ret = dict(x=keep['x'], fun=keep['fun'], nit=keep['nit'].long(), nfev=nfev,
+               status=keep['status'].long(), rounds=int(st3[0]),
+               calls=int(st3[1]), rows_launched=int(st3[2]))
+    if jac:
+        ret['njev'] = chain.njev.long().clone()
+        # rows the chain evaluated (one per distinct x of a run, the value-only
+        # points of the line_search_wolfe2 fall-back included): what GradChain.rows
+        # counts on the host path
+        pobj.jobs += int(st3[2])
+    else:
+        pobj.jobs += int(nfev.sum().item())
+    return ret

@@ -61,6 +61,24 @@ __global__ void __launch_bounds__(BF_NT) bfgs_advance_kernel(BfgsDev D, int firs
   D.nreq[s] = r.done ? 0 : r.nrows;
 }
 
+// jac mode (rvs_bfgs_run_grad): the second instantiation of the machine.  A run's one
+// row was answered with (f, grad f) = F[row, 0 .. n]
+__global__ void __launch_bounds__(BF_NT) bfgs_advance_jac_kernel(BfgsDev D, int first) {
+  const int s = blockIdx.x * BF_NT + threadIdx.x;
+  if (s >= D.S) return;
+  Run &r = D.runs[s];
+  if (first) {
+    rvs_bfgs::init_jac(r, D.n, D.x0 + (int64_t)s * D.n, D.H0, D.gtol, D.c1, D.c2,
+                       D.xrtol, D.maxiter);
+  } else {
+    if (r.done) return;
+    const double *f = D.F + (int64_t)D.off[s] * (D.n + 1);
+    for (int q = 0; q <= D.n; q++) r.vals[q] = f[q];
+  }
+  rvs_bfgs::advance_jac(r);
+  D.nreq[s] = r.done ? 0 : r.nrows;
+}
+
 __global__ void __launch_bounds__(BF_SCAN_NT) bfgs_scan_kernel(BfgsDev D) {
   __shared__ int wsum[BF_SCAN_NT / 64];
   __shared__ int carry[2];
@@ -122,6 +140,11 @@ __global__ void __launch_bounds__(BF_NT)
   status[s] = r.done ? r.status : -1;
   if (hess_inv)
     for (int i = 0; i < n * n; i++) hess_inv[(int64_t)s * n * n + i] = r.Hk[i];
+}
+
+__global__ void __launch_bounds__(256) bfgs_njev_kernel(BfgsDev D, int32_t *njev) {
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s < D.S) njev[s] = D.runs[s].ngev;
 }
 
 }  // namespace
@@ -187,6 +210,78 @@ extern "C" int rvs_bfgs_run(const rvs_bfgs_state *b, const rvs_nm_objective *o,
   }
   hipLaunchKernelGGL(bfgs_result_kernel, agrid, dim3(BF_NT), 0, st, D, b->x, b->fun,
                      b->hess_inv, b->nit, b->nfev, b->status);
+  RVS_LAUNCH_CHECK();
+  if (hipStreamSynchronize(st) != hipSuccess) return RVS_E_LAUNCH;
+  if (stats) {
+    stats[0] = rounds;
+    stats[1] = calls;
+    stats[2] = jobs;
+  }
+  return 0;
+}
+
+extern "C" int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                                 const rvs_grad_chain *g, int sync_every,
+                                 int64_t *stats, void *stream) {
+  if (!b || !o || !g || b->S < 1 || b->n < 1 || b->n > 8 || b->n != o->n ||
+      sync_every < 1 || !b->runs || !b->x0 || !b->x || !b->fun || !b->nit ||
+      !b->nfev || !b->status || !b->nreq || !b->off || !b->list || !b->X || !b->F ||
+      !b->counts || !g->njev || !rvs_internal_grad_chain_ok(g, o))
+    return RVS_E_ARG;
+  const int S = b->S, n = b->n, cap = g->cap;
+  const int64_t maxrows = S;   // one row per live run
+  if ((maxrows + cap - 1) / cap > BF_NCHUNK) return RVS_E_ARG;
+  hipStream_t st = rvs_stream(stream);
+  BfgsDev D;
+  D.runs = static_cast<Run *>(b->runs);
+  D.S = S, D.n = n, D.cap = cap;
+  D.x0 = b->x0, D.H0 = b->hess_inv0;
+  D.gtol = b->gtol, D.c1 = b->c1, D.c2 = b->c2, D.xrtol = b->xrtol;
+  D.maxiter = b->maxiter;
+  D.nreq = b->nreq, D.off = b->off, D.list = b->list, D.counts = b->counts;
+  D.X = b->X, D.F = b->F;
+  const dim3 agrid((S + BF_NT - 1) / BF_NT);
+  const dim3 egrid((int)(((int64_t)S * (n + 1) + 255) / 256));
+  auto step = [&](int first) {
+    hipLaunchKernelGGL(bfgs_advance_jac_kernel, agrid, dim3(BF_NT), 0, st, D, first);
+    hipLaunchKernelGGL(bfgs_scan_kernel, dim3(1), dim3(BF_SCAN_NT), 0, st, D);
+    hipLaunchKernelGGL(bfgs_emit_kernel, egrid, dim3(256), 0, st, D);
+  };
+  step(1);
+  RVS_LAUNCH_CHECK();
+  int64_t rounds = 0, calls = 0, jobs = 0;
+  int32_t c[BF_NCHUNK + 8];
+  while (true) {
+    if (hipMemcpyAsync(c, b->counts, sizeof(int32_t) * (BF_NCHUNK + 2),
+                       hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return RVS_E_LAUNCH;
+    const int64_t total = c[BF_NCHUNK], live = c[BF_NCHUNK + 1];
+    if (total == 0) break;
+    // (the policy of rvs_bfgs_run; behind the look every live run asks for at most
+    // its one row)
+    const int window = (total > 4096) ? 1 : sync_every;
+    for (int r = 0; r < window; r++) {
+      int64_t bound = (r == 0) ? total : live;
+      if (bound > maxrows) bound = maxrows;
+      for (int64_t a = 0, ch = 0; a < bound; a += cap, ch++) {
+        const int J = (int)((bound - a < cap) ? bound - a : cap);
+        int rc = rvs_internal_grad_chain_eval(o, g, b->list + a, b->X + a * n, J,
+                                              b->counts, (int)ch,
+                                              b->F + a * (n + 1), st);
+        if (rc) return rc;
+        calls++;
+        jobs += J;
+      }
+      step(0);
+      RVS_LAUNCH_CHECK();
+      rounds++;
+    }
+  }
+  hipLaunchKernelGGL(bfgs_result_kernel, agrid, dim3(BF_NT), 0, st, D, b->x, b->fun,
+                     b->hess_inv, b->nit, b->nfev, b->status);
+  hipLaunchKernelGGL(bfgs_njev_kernel, dim3((S + 255) / 256), dim3(256), 0, st, D,
+                     g->njev);
   RVS_LAUNCH_CHECK();
   if (hipStreamSynchronize(st) != hipSuccess) return RVS_E_LAUNCH;
   if (stats) {

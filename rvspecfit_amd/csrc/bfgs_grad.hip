@@ -1,0 +1,250 @@
+// bfgs_grad.hip -- the optimiser's (f, grad f) from the analytic-gradient chain: what
+// vel_fit.chisq_func_grad is to one vector, for the rows of a round of rvs_bfgs_run_grad
+// (bfgs_dev.hip).
+//
+//   rvs_proc_map            X [J, n] -> vel, vsini, params, prior / vsini penalty, bad
+//   per arm                 rvs_template_polylinear_grad | rvs_template_tri(_buckets)_grad
+//                           rvs_vsini_convolve_grad (vsini fitted) | rvs_vsini_convolve
+//                           over the 1 + ndim rows (vsini fixed) | nothing
+//                           rvs_spline_construct of the (1 + ntan) J rows
+//                           the outside penalty of the rows
+//   rvs_chisq_point_grad    all arms: chi [J], grad [J, 1 + ntan] = d/d(vel, parameters
+//                           in library order[, vsini])
+//   rvs_proc_finish_grad    F [J, 1 + n] = (chisq_func, its gradient in X's columns)
+//
+// The chain is engine.build_templates(tangents=True, vsini_tangent=...) +
+// engine.chisq_point_grad: the same entry points with the same arguments, called from
+// C on one stream, so a row has the bits spec_fit.chisq_grad_jobs gives it.
+#include "common.h"
+#include "nm_internal.h"
+
+namespace {
+
+struct FinP {
+  int n, ndim, ntan, vsini_col;
+  int src[8];
+  const double *prior_mean, *prior_isig;
+  double max_vsini;
+};
+
+__global__ void __launch_bounds__(256)
+    proc_finish_grad_kernel(int J, const int32_t *__restrict__ counts, int cidx, FinP P,
+                            const double *__restrict__ chi,
+                            const double *__restrict__ grad,
+                            const double *__restrict__ X,
+                            const double *__restrict__ params,
+                            const double *__restrict__ extra,
+                            const int32_t *__restrict__ bad,
+                            const int32_t *__restrict__ job_spec,
+                            const int32_t *__restrict__ job_status,
+                            double *__restrict__ F, int32_t *__restrict__ spec_status) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= J) return;
+  const int n = P.n, K = 1 + P.ntan;
+  double *f = F + (int64_t)j * (n + 1);
+  const int isbad = bad[j];
+  f[0] = isbad ? 1e30 : chi[j] + extra[j];
+  if (isbad) {
+    for (int c = 0; c < n; c++) f[1 + c] = 0.0;
+    return;
+  }
+  const double *g = grad + (int64_t)j * K;
+  const int r = job_spec[j];
+  f[1] = g[0];   // column 0 of X is the velocity
+  for (int i = 0; i < P.ndim; i++) {
+    const int c = P.src[i];
+    if (c < 0) continue;   // fixed: no column
+    double v = g[1 + i];
+    if (P.prior_mean) {
+      const double is = P.prior_isig[(int64_t)r * P.ndim + i];
+      if (is != 0)
+        v += 2.0 * (params[(int64_t)j * P.ndim + i] -
+                    P.prior_mean[(int64_t)r * P.ndim + i]) * is * is;
+    }
+    f[1 + c] = v;
+  }
+  if (P.vsini_col >= 0) {
+    // VSiniMapper clamps: inside (0, max_vsini) the physical derivative, outside 0;
+    // the penalty (x - clamp(x))^2 adds 2 (x - clamp(x))
+    const double x = X[(int64_t)j * n + P.vsini_col];
+    const double cl = fmin(fmax(x, 0.0), P.max_vsini);
+    const bool inside = (0 < x) && (x < P.max_vsini);
+    f[1 + P.vsini_col] = (inside ? g[P.ntan] : 0.0) + 2.0 * (x - cl);
+  }
+  const int live = counts ? counts[cidx] : J;
+  if (j < live && job_status[j]) atomicOr(&spec_status[r], job_status[j]);
+}
+
+// penalty[j] = outside[j] * (badchi of the job's spectrum): engine.chisq_point_grad's
+// `o * batch.badchi_jobs(job_spec)`
+__global__ void __launch_bounds__(256)
+    grad_penalty_kernel(int J, const double *__restrict__ outside,
+                        const double *__restrict__ pen_scale,
+                        const int32_t *__restrict__ job_spec, double badchi,
+                        double *__restrict__ pen) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= J) return;
+  const double b = pen_scale ? pen_scale[job_spec[j]] * badchi : badchi;
+  pen[j] = outside[j] * b;
+}
+
+// one vsini / outside flag per ROW of rvs_vsini_convolve over the R rows of a job
+__global__ void __launch_bounds__(256)
+    grad_repeat_kernel(int J, int R, const double *__restrict__ vsini,
+                       const double *__restrict__ outside, double *__restrict__ vs_rows,
+                       double *__restrict__ out_rows) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= J * R) return;
+  vs_rows[t] = vsini[t / R];
+  out_rows[t] = outside[t / R];
+}
+
+int chain_ok(const rvs_grad_chain *g, const rvs_nm_objective *o) {
+  if (!g || !o || !g->arms || !g->point || !g->point_work || !g->chi || !g->grad ||
+      g->narm < 1 || g->narm > RVS_MAX_ARMS || g->narm != o->narm || g->cap < 1 ||
+      g->vsini_mode < 0 || g->vsini_mode > 2 || o->ndim < 1 || o->ndim > 6 ||
+      o->n < 1 || o->n > 8)
+    return 0;
+  if (g->ntan != o->ndim + (g->vsini_mode == 2 ? 1 : 0) || g->ntan > 6) return 0;
+  if ((g->vsini_mode == 2) != (o->vsini_col >= 0)) return 0;
+  if ((g->vsini_mode != 0) != (o->vsini != nullptr)) return 0;
+  if (!o->vel || !o->params || !o->extra || !o->bad || !o->job_spec || !o->jstatus ||
+      !o->status || !o->fixed || !o->safe)
+    return 0;
+  for (int a = 0; a < g->narm; a++) {
+    const rvs_grad_arm &A = g->arms[a];
+    if (!A.dats || !A.knots || !A.templ || !A.coef || !A.outside || !A.penalty ||
+        A.ntp < 3 || A.ntp != g->point[a].ntp || !(A.lnstep > 0))
+      return 0;
+    if (g->point[a].coef != A.coef || g->point[a].penalty != A.penalty) return 0;
+    if (A.tri ? (!A.transform || !A.extraflags || !A.simplices || !A.simplex ||
+                 A.nsimplex < 1)
+              : (!A.idgrid || !A.uvecs || !A.vecs_s || !A.lens || !A.ptp || A.ngrid < 1))
+      return 0;
+    if (g->vsini_mode != 0 && !A.templ2) return 0;
+    if (g->vsini_mode == 1 && (!A.vs_rows || !A.out_rows)) return 0;
+  }
+  return 1;
+}
+
+}  // namespace
+
+extern "C" int rvs_proc_finish_grad(int J, int n, int ndim, int ntan,
+                                    const int32_t *counts, int cidx, const double *chi,
+                                    const double *grad, const double *X,
+                                    const double *params, const double *extra,
+                                    const int32_t *bad, const int32_t *job_spec,
+                                    const int32_t *job_status, const int32_t *src,
+                                    int vsini_col, const double *prior_mean,
+                                    const double *prior_isig, double max_vsini,
+                                    double *F, int32_t *spec_status, void *stream) {
+  if (J < 1 || n < 1 || n > 8 || ndim < 1 || ndim > 6 || !src || !chi || !grad || !X ||
+      !params || !extra || !bad || !job_spec || !job_status || !F || !spec_status ||
+      vsini_col >= n || (prior_mean && !prior_isig))
+    return RVS_E_ARG;
+  if (ntan != ndim + (vsini_col >= 0 ? 1 : 0)) return RVS_E_ARG;
+  FinP P;
+  P.n = n, P.ndim = ndim, P.ntan = ntan, P.vsini_col = vsini_col;
+  int ncol = 1 + (vsini_col >= 0 ? 1 : 0);
+  for (int i = 0; i < 8; i++) {
+    P.src[i] = (i < ndim) ? src[i] : -1;
+    if (P.src[i] >= n || P.src[i] == 0 || (P.src[i] >= 0 && P.src[i] == vsini_col))
+      return RVS_E_ARG;
+    if (P.src[i] > 0) ncol++;
+  }
+  if (ncol != n) return RVS_E_ARG;   // every column of X has exactly one source
+  P.prior_mean = prior_mean, P.prior_isig = prior_isig;
+  P.max_vsini = max_vsini;
+  hipLaunchKernelGGL(proc_finish_grad_kernel, dim3((J + 255) / 256), dim3(256), 0,
+                     rvs_stream(stream), J, counts, cidx, P, chi, grad, X, params, extra,
+                     bad, job_spec, job_status, F, spec_status);
+  RVS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int64_t rvs_grad_chain_work_size(int cap, int narm, int ntan,
+                                            const int32_t *ntp, int vsini_mode) {
+  if (cap < 1 || narm < 1 || narm > RVS_MAX_ARMS || ntan < 1 || ntan > 6 || !ntp ||
+      vsini_mode < 0 || vsini_mode > 2)
+    return 0;
+  const int64_t K = 1 + ntan;
+  int64_t b = rvs_chisq_point_grad_work_size(cap, narm, ntan);
+  b += (int64_t)cap * (1 + K) * sizeof(double);   // chi, grad
+  for (int a = 0; a < narm; a++) {
+    if (ntp[a] < 3) return 0;
+    const int64_t rows = (int64_t)cap * K * ntp[a] * sizeof(double);
+    b += rows * (vsini_mode ? 2 : 1);   // templ (+ templ2)
+    b += rows * 4;                      // coef
+    b += (int64_t)cap * (2 * sizeof(double) + sizeof(int32_t));   // outside, penalty, simplex
+    if (vsini_mode == 1) b += (int64_t)cap * K * 2 * sizeof(double);   // vs_rows, out_rows
+  }
+  return b;
+}
+
+int rvs_internal_grad_chain_ok(const rvs_grad_chain *g, const rvs_nm_objective *o) {
+  return chain_ok(g, o);
+}
+
+int rvs_internal_grad_chain_eval(const rvs_nm_objective *o, const rvs_grad_chain *g,
+                                 const int32_t *list, const double *X, int J,
+                                 const int32_t *counts, int cidx, double *F,
+                                 hipStream_t st) {
+  if (J < 1 || J > g->cap) return RVS_E_ARG;
+  const int ndim = o->ndim, ntan = g->ntan;
+  int rc = rvs_proc_map(J, o->n, ndim, X, list, o->src, o->vsini_col, o->fixed,
+                        o->vsini_fixed, o->safe, o->prior_mean, o->prior_isig,
+                        o->min_vel, o->max_vel, o->max_vsini, o->job_spec, o->vel,
+                        o->vsini, o->params, o->extra, o->bad, st);
+  if (rc) return rc;
+  const int R = 1 + ndim;
+  for (int a = 0; a < g->narm; a++) {
+    const rvs_grad_arm &A = g->arms[a];
+    if (!A.tri)
+      rc = rvs_template_polylinear_grad(
+          static_cast<const float *>(A.dats), A.ngrid, A.ntp, A.idgrid, A.uvecs, A.lens,
+          ndim, A.vecs_s, A.ptp, A.log_mask, A.exp_flag, o->params, J, A.templ,
+          A.outside, nullptr, nullptr, st);
+    else if (A.buckets.cell_start)
+      rc = rvs_template_tri_buckets_grad(
+          static_cast<const double *>(A.dats), A.ntp, A.simplices, A.transform,
+          A.extraflags, A.nsimplex, ndim, A.log_mask, A.exp_flag, &A.buckets, o->params,
+          J, A.templ, A.outside, A.simplex, nullptr, st);
+    else
+      rc = rvs_template_tri_grad(static_cast<const double *>(A.dats), A.ntp,
+                                 A.simplices, A.transform, A.extraflags, A.nsimplex,
+                                 ndim, A.log_mask, A.exp_flag, o->params, J, A.templ,
+                                 A.outside, A.simplex, nullptr, st);
+    if (rc) return rc;
+    const double *rows = A.templ;
+    if (g->vsini_mode == 2) {   // R rows in, R + 1 out: the vsini tangent last
+      rc = rvs_vsini_convolve_grad(A.templ, o->vsini, A.outside, A.lnstep, 0.6, A.ntp, R,
+                                   J, A.templ2, st);
+      if (rc) return rc;
+      rows = A.templ2;
+    } else if (g->vsini_mode == 1) {
+      hipLaunchKernelGGL(grad_repeat_kernel, dim3((J * R + 255) / 256), dim3(256), 0, st,
+                         J, R, o->vsini, A.outside, A.vs_rows, A.out_rows);
+      RVS_LAUNCH_CHECK();
+      rc = rvs_vsini_convolve(A.templ, A.vs_rows, A.out_rows, A.lnstep, 0.6, A.ntp,
+                              J * R, A.templ2, st);
+      if (rc) return rc;
+      rows = A.templ2;
+    }
+    rc = rvs_spline_construct(A.knots, rows, A.ntp, J * (1 + ntan), A.spline_form,
+                              A.factors, A.coef, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(grad_penalty_kernel, dim3((J + 255) / 256), dim3(256), 0, st, J,
+                       A.outside, g->pen_scale, o->job_spec, o->badchi, A.penalty);
+    RVS_LAUNCH_CHECK();
+  }
+  if (hipMemsetAsync(o->jstatus, 0, sizeof(int32_t) * J, st) != hipSuccess)
+    return RVS_E_LAUNCH;
+  rc = rvs_chisq_point_grad(g->point, g->narm, o->npoly, ntan, o->job_spec, nullptr, J,
+                            o->vel, o->badchi, g->basis_const, g->point_work, g->chi,
+                            g->grad, o->jstatus, st);
+  if (rc) return rc;
+  return rvs_proc_finish_grad(J, o->n, ndim, ntan, counts, cidx, g->chi, g->grad, X,
+                              o->params, o->extra, o->bad, o->job_spec, o->jstatus,
+                              o->src, o->vsini_col, o->prior_mean, o->prior_isig,
+                              o->max_vsini, F, o->status, st);
+}

@@ -30,7 +30,53 @@ struct Driver {
   std::vector<Run> runs;
   std::vector<int> order;  // spectra with a pending request, ascending
   int64_t rounds = 0;
+  bool jac = false;  // rvs_bfgs_begin_jac: replies are (f, grad f), advance_jac()
 };
+
+Driver *begin(bool jac, int S, int n, const double *x0, const double *hess_inv0,
+              double gtol, double c1, double c2, double xrtol, int maxiter) {
+  if (S < 1 || n < 1 || n > MAXN || !x0) return nullptr;
+  Driver *d = new Driver;
+  d->S = S;
+  d->n = n;
+  d->jac = jac;
+  d->runs.resize(S);
+  for (int s = 0; s < S; s++) {
+    Run &r = d->runs[s];
+    // runs to the first request (f and g at x0)
+    if (jac) {
+      rvs_bfgs::init_jac(r, n, x0 + (int64_t)s * n, hess_inv0, gtol, c1, c2, xrtol,
+                         maxiter);
+      rvs_bfgs::advance_jac(r);
+    } else {
+      rvs_bfgs::init(r, n, x0 + (int64_t)s * n, hess_inv0, gtol, c1, c2, xrtol,
+                     maxiter);
+      rvs_bfgs::advance(r);
+    }
+  }
+  return d;
+}
+
+int result(Driver *d, double *x, double *fun, int32_t *nit, int32_t *nfev,
+           int32_t *njev, int32_t *status, double *hess_inv, int64_t *rounds) {
+  if (!d || !x || !fun || !nit || !nfev || !status) return RVS_E_ARG;
+  const int n = d->n;
+  for (int s = 0; s < d->S; s++)
+    if (!d->runs[s].done) return RVS_E_ARG;
+  for (int s = 0; s < d->S; s++) {
+    const Run &r = d->runs[s];
+    std::memcpy(x + (int64_t)s * n, r.xk, sizeof(double) * n);
+    fun[s] = r.fval;
+    nit[s] = r.nit;
+    nfev[s] = r.nfev;
+    if (njev) njev[s] = r.ngev;
+    status[s] = r.status;
+    if (hess_inv)
+      std::memcpy(hess_inv + (int64_t)s * n * n, r.Hk, sizeof(double) * n * n);
+  }
+  if (rounds) *rounds = d->rounds;
+  return 0;
+}
 
 }  // namespace
 
@@ -39,18 +85,13 @@ extern "C" {
 void *rvs_bfgs_begin(int S, int n, const double *x0, const double *hess_inv0,
                      double gtol, double c1, double c2, double xrtol,
                      int maxiter) {
-  if (S < 1 || n < 1 || n > MAXN || !x0) return nullptr;
-  Driver *d = new Driver;
-  d->S = S;
-  d->n = n;
-  d->runs.resize(S);
-  for (int s = 0; s < S; s++) {
-    Run &r = d->runs[s];
-    rvs_bfgs::init(r, n, x0 + (int64_t)s * n, hess_inv0, gtol, c1, c2, xrtol,
-                   maxiter);
-    rvs_bfgs::advance(r);  // runs to the first request (f and g at x0)
-  }
-  return d;
+  return begin(false, S, n, x0, hess_inv0, gtol, c1, c2, xrtol, maxiter);
+}
+
+void *rvs_bfgs_begin_jac(int S, int n, const double *x0, const double *hess_inv0,
+                         double gtol, double c1, double c2, double xrtol,
+                         int maxiter) {
+  return begin(true, S, n, x0, hess_inv0, gtol, c1, c2, xrtol, maxiter);
 }
 
 int64_t rvs_bfgs_pending(void *h, int64_t *idx, double *X, int64_t cap_rows) {
@@ -75,7 +116,7 @@ int64_t rvs_bfgs_pending(void *h, int64_t *idx, double *X, int64_t cap_rows) {
 
 int rvs_bfgs_feed(void *h, const double *F, int64_t nrows) {
   Driver *d = static_cast<Driver *>(h);
-  if (!d) return RVS_E_ARG;
+  if (!d || d->jac || !F) return RVS_E_ARG;
   int64_t at = 0;
   for (int s : d->order) {
     Run &r = d->runs[s];
@@ -91,25 +132,35 @@ int rvs_bfgs_feed(void *h, const double *F, int64_t nrows) {
   return 0;
 }
 
+int rvs_bfgs_feed_jac(void *h, const double *F, int64_t nrows) {
+  Driver *d = static_cast<Driver *>(h);
+  if (!d || !d->jac || !F || nrows != (int64_t)d->order.size()) return RVS_E_ARG;
+  const int n = d->n;
+  int64_t at = 0;
+  for (int s : d->order) {
+    Run &r = d->runs[s];   // (one row per run: r.nrows == 1)
+    for (int q = 0; q <= n; q++) r.vals[q] = F[at * (n + 1) + q];
+    at += 1;
+    rvs_bfgs::advance_jac(r);
+  }
+  d->rounds += 1;
+  d->order.clear();
+  return 0;
+}
+
 int rvs_bfgs_result(void *h, double *x, double *fun, int32_t *nit,
                     int32_t *nfev, int32_t *status, double *hess_inv,
                     int64_t *rounds) {
-  Driver *d = static_cast<Driver *>(h);
-  if (!d) return RVS_E_ARG;
-  const int n = d->n;
-  for (int s = 0; s < d->S; s++) {
-    const Run &r = d->runs[s];
-    if (!r.done) return RVS_E_ARG;
-    std::memcpy(x + (int64_t)s * n, r.xk, sizeof(double) * n);
-    fun[s] = r.fval;
-    nit[s] = r.nit;
-    nfev[s] = r.nfev;
-    status[s] = r.status;
-    if (hess_inv)
-      std::memcpy(hess_inv + (int64_t)s * n * n, r.Hk, sizeof(double) * n * n);
-  }
-  if (rounds) *rounds = d->rounds;
-  return 0;
+  return result(static_cast<Driver *>(h), x, fun, nit, nfev, nullptr, status,
+                hess_inv, rounds);
+}
+
+int rvs_bfgs_result_jac(void *h, double *x, double *fun, int32_t *nit,
+                        int32_t *nfev, int32_t *njev, int32_t *status,
+                        double *hess_inv, int64_t *rounds) {
+  if (!njev) return RVS_E_ARG;
+  return result(static_cast<Driver *>(h), x, fun, nit, nfev, njev, status,
+                hess_inv, rounds);
 }
 
 void rvs_bfgs_end(void *h) {

@@ -200,7 +200,10 @@ class ProcessObjective:
     def native_desc(self):
         """rvs_nm_objective: this objective for the C round driver"""
         o = _lib.NmObjective()
-        o.arms = ctypes.addressof(self.oarr)
+        # (the chain form has no one-kernel descriptors: rvs_bfgs_run_grad, which
+        # reads the mapping alone, is its only caller there)
+        oarr = getattr(self, 'oarr', None)
+        o.arms = None if oarr is None else ctypes.addressof(oarr)
         for k, t in (('fixed', self.fixed), ('vsini_fixed', self.vsini_fixed),
                      ('safe', self.safe), ('prior_mean', self.prior_mean),
                      ('prior_isig', self.prior_isig), ('vel', self.vel),
@@ -331,6 +334,174 @@ class ProcessObjective:
                 _p(self.job_spec), None, J, _p(self.vel), self.badchi,
                 _p(self.scratch), _p(self.chi), _p(self.jstatus), st)
             _lib.check(rc, 'rvs_chisq_point')
+
+
+# bytes the row buffers of a GradChain may take (template rows, their tangents and the
+# spline records of `cap` rows per arm: 48 (1 + ntan) ntp bytes per row and arm, 2.7 MB
+# at ntan = 6 and 8000 template pixels); a round with more rows runs in chunks
+GRAD_CHAIN_BUDGET = 4 << 30
+
+
+class GradChain:
+    """chisq_func_grad for the rows of a round: the rvs_grad_chain of
+    rvs_bfgs_run_grad around a ProcessObjective (whose mapping tables and row
+    buffers it uses), and the same evaluation driven from Python (`rows`)."""
+
+    def __init__(self, pobj, cap=None, budget=None):
+        L = _lib.lib()
+        batch, libs = pobj.batch, pobj.libs
+        fit = pobj.vsini_col >= 0
+        # (refused before anything is built; nothing falls back to differences)
+        engine.check_grad_scope(batch, libs, pobj.npoly, pobj.resols, False,
+                                vsini_grad=fit)
+        self.pobj = pobj
+        dev = pobj.dev
+        narm = len(batch.arms)
+        self.ntan = pobj.ndim + (1 if fit else 0)
+        self.vsini_mode = 2 if fit else (1 if pobj.has_vsini else 0)
+        ntps = [libs[a.name].ntp for a in batch.arms]
+        cap = self.choose_cap(pobj.S, ntps, self.ntan, self.vsini_mode, cap=cap,
+                              budget=budget, row_capacity=pobj.cap)
+        ntp = (ctypes.c_int32 * narm)(*ntps)
+        size = lambda c: L.rvs_grad_chain_work_size(  # noqa: E731
+            c, narm, self.ntan, ntp, self.vsini_mode)
+        self.cap = cap
+        self.nbytes = int(size(cap))
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        K, R = 1 + self.ntan, 1 + pobj.ndim
+        self.arms = (_lib.GradArm * narm)()
+        self.point = (_lib.PointArm * narm)()
+        self.bconst = (ctypes.c_double * narm)()
+        self._keep = []
+        for ia, arm in enumerate(batch.arms):
+            lib = libs[arm.name]
+            b = dict(templ=torch.empty((cap, K, lib.ntp), **f64),
+                     templ2=torch.empty((cap, K, lib.ntp), **f64)
+                     if self.vsini_mode else None,
+                     coef=torch.empty((cap, K, lib.ntp, 4), **f64),
+                     outside=torch.empty(cap, **f64), penalty=torch.empty(cap, **f64),
+                     simplex=torch.empty(cap, **i32),
+                     vs_rows=torch.empty(cap * R, **f64)
+                     if self.vsini_mode == 1 else None,
+                     out_rows=torch.empty(cap * R, **f64)
+                     if self.vsini_mode == 1 else None)
+            a = self.arms[ia]
+            for k, t in b.items():
+                setattr(a, k, None if t is None else t.data_ptr())
+            a.dats, a.knots = lib.dats.data_ptr(), lib.knots.data_ptr()
+            a.factors = None if lib.spline_factors is None else \
+                lib.spline_factors.data_ptr()
+            a.spline_form, a.lnstep = lib.spline_form, lib.lnstep
+            a.ntp, a.exp_flag, a.log_mask = lib.ntp, lib.exp_flag, lib.log_mask
+            if lib.kind == 'triangulation':
+                from . import library
+                a.tri, a.nsimplex = 1, lib.tri_nsimplex
+                a.transform = lib.tri_transform.data_ptr()
+                a.extraflags = lib.tri_extraflags.data_ptr()
+                a.simplices = lib.tri_simplices.data_ptr()
+                # (the search TemplateLibrary._tri_call chooses)
+                if lib._tri_bk is not None and library.TRI_BUCKETS:
+                    a.buckets = lib._tri_bk
+            else:
+                a.tri, a.ngrid = 0, lib.ngrid
+                a.idgrid, a.uvecs = lib.idgrid.data_ptr(), lib.uvecs.data_ptr()
+                a.vecs_s = lib.vecs_s.data_ptr()
+                a.lens, a.ptp = lib.lens.ctypes.data, lib.ptp.ctypes.data
+            self._keep.append(b)
+            self._keep.append(engine.fill_point_arm(
+                self.point[ia], arm, lib, pobj.npoly, pobj.rbf, 0.0, None, b['coef'],
+                b['penalty']))
+            # the orthonormal basis of the same space, as engine.chisq_point_grad
+            qt, const = arm.basis_ortho(pobj.npoly, pobj.rbf)
+            self.point[ia].polysT = qt.data_ptr()
+            self.bconst[ia] = const
+            self._keep.append(qt)
+        nb = L.rvs_chisq_point_grad_work_size(cap, narm, self.ntan)
+        self.point_work = torch.empty((nb + 7) // 8, **f64)
+        self.chi = torch.empty(cap, **f64)
+        self.grad = torch.empty((cap, K), **f64)
+        self.njev = torch.zeros(pobj.S, **i32)
+
+    MAX_CHUNKS = 24     # the chunk counters of the scan kernel (bfgs_dev.hip)
+
+    @staticmethod
+    def choose_cap(S, ntps, ntan, vsini_mode, cap=None, budget=None,
+                   row_capacity=None):
+        """rows per chunk for S runs on arms of ntps template pixels: `cap`, or the
+        most whose buffers (rvs_grad_chain_work_size) stay inside `budget`
+        (GRAD_CHAIN_BUDGET).  ValueError where MAX_CHUNKS chunks of that many rows
+        do not hold one row per run: at the default budget, three arms of 8000
+        template pixels and ntan = 6 that is beyond ~12 000 spectra per call."""
+        L = _lib.lib()
+        narm = len(ntps)
+        ntp = (ctypes.c_int32 * narm)(*ntps)
+        if cap is None:
+            budget = GRAD_CHAIN_BUDGET if budget is None else budget
+            one = L.rvs_grad_chain_work_size(1, narm, ntan, ntp, vsini_mode)
+            if one <= 0:
+                raise ValueError('GradChain: %d arms / %d tangents are outside '
+                                 'rvs_grad_chain_work_size' % (narm, ntan))
+            cap = max(1, min(S, int(budget // one)))
+        cap = int(cap if row_capacity is None else min(cap, row_capacity))
+        if cap < 1 or (S + cap - 1) // cap > GradChain.MAX_CHUNKS:
+            raise ValueError(
+                'second_minimizer_jac: the gradient chain holds %d rows per chunk '
+                '(optimizer.GRAD_CHAIN_BUDGET = %d bytes) and a round at most %d '
+                'chunks: %d spectra do not fit one call; pass them in smaller batches'
+                % (cap, GRAD_CHAIN_BUDGET if budget is None else budget,
+                   GradChain.MAX_CHUNKS, S))
+        return cap
+
+    def desc(self):
+        g = _lib.GradChain()
+        g.arms, g.point = ctypes.addressof(self.arms), ctypes.addressof(self.point)
+        g.basis_const = ctypes.addressof(self.bconst)
+        ps = self.pobj.batch.pen_scale
+        g.pen_scale = None if ps is None else ps.data_ptr()
+        g.point_work = self.point_work.data_ptr()
+        g.chi, g.grad = self.chi.data_ptr(), self.grad.data_ptr()
+        g.njev = self.njev.data_ptr()
+        g.narm, g.ntan = len(self.arms), self.ntan
+        g.cap, g.vsini_mode = self.cap, self.vsini_mode
+        return g
+
+    def rows(self, idx, X):
+        """(chisq_func, its gradient) of the rows X [J, n] of spectra idx [J]: numpy
+        in, numpy [J, 1 + n] out -- rvs_proc_map, spec_fit.chisq_grad_jobs' launches
+        and rvs_proc_finish_grad, driven from Python.  The objective of
+        bfgs.minimize_lockstep_native(jac=True), and what rvs_bfgs_run_grad's rounds
+        are held against."""
+        from . import spec_fit
+        p, L = self.pobj, _lib.lib()
+        dev = p.dev
+        idx_t = torch.as_tensor(idx, dtype=torch.int32).to(dev).contiguous()
+        X_t = torch.as_tensor(X, dtype=torch.float64).to(dev).contiguous()
+        J = X_t.shape[0]
+        F = torch.empty((J, p.n + 1), dtype=torch.float64, device=dev)
+        st = _lib.stream()
+        for a in range(0, J, p.cap):
+            n = min(J, a + p.cap) - a
+            rc = L.rvs_proc_map(n, p.n, p.ndim, _p(X_t[a:]), _p(idx_t[a:]), p.src,
+                                p.vsini_col, _p(p.fixed), _p(p.vsini_fixed),
+                                _p(p.safe), _p(p.prior_mean), _p(p.prior_isig),
+                                p.min_vel, p.max_vel, p.max_vsini, _p(p.job_spec),
+                                _p(p.vel), _p(p.vsini), _p(p.params), _p(p.extra),
+                                _p(p.bad), st)
+            _lib.check(rc, 'rvs_proc_map')
+            chi, grad, status = spec_fit._chisq_grad(
+                p.batch, p.libs, p.job_spec[:n], p.vel[:n], p.params[:n],
+                None if p.vsini is None else p.vsini[:n], p.npoly, p.rbf, 0.0, True,
+                p.resols, False, p.vsini_col >= 0)
+            rc = L.rvs_proc_finish_grad(
+                n, p.n, p.ndim, self.ntan, None, 0, _p(chi), _p(grad.contiguous()),
+                _p(X_t[a:]), _p(p.params), _p(p.extra), _p(p.bad), _p(p.job_spec),
+                _p(status), p.src, p.vsini_col, _p(p.prior_mean), _p(p.prior_isig),
+                p.max_vsini, _p(F[a:]), _p(p.status), st)
+            _lib.check(rc, 'rvs_proc_finish_grad')
+            p.calls += 1
+            p.jobs += n
+        return F.cpu().numpy()
 
 
 # False: the rounds of a fused objective are driven from Python (one_round below,

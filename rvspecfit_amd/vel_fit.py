@@ -887,6 +887,24 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
         if fitVsini:
             vsiniMapper = VSiniMapper(max_vsini)
     tm = timers if timers is not None else {}
+    # config['second_minimizer_jac']: the BFGS polish on the analytic gradient
+    # (rvs_bfgs_run_grad).  What the gradient does not cover is refused here, before
+    # anything is built: nothing falls back to differences
+    bfgs_jac = bool(config.get('second_minimizer')
+                    and config.get('second_minimizer_jac'))
+    if bfgs_jac:
+        engine.check_grad_scope(batch, spec_inter.get_libs(batch.names, config),
+                                options.get('npoly') or 5,
+                                spec_fit._resols(batch, resolParams),
+                                bool(options.get('fast_interp')),
+                                vsini_grad=fitVsini)
+        # (and the batch must fit the chain's chunks: known here, not after the
+        # simplex stage)
+        _libs = spec_inter.get_libs(batch.names, config)
+        optimizer.GradChain.choose_cap(
+            S, [_libs[a.name].ntp for a in batch.arms],
+            len(names) + (1 if fitVsini else 0),
+            2 if fitVsini else (1 if 'vsini' in pd0 else 0))
 
     def _tick(k, t0):
         # (stage clocks only when somebody asked for them: the device-wide
@@ -960,7 +978,30 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
         from . import bfgs
         t0 = time.time()
         hess_inv0 = get_hess_inv(mapper.get_fitted_params())
-        if BFGS_ON_DEVICE and optimizer.NATIVE_ROUNDS and pobj.native:
+        if bfgs_jac:
+            # scipy's jac=True on vel_fit.chisq_func_grad: the gradient chain as the
+            # objective, its rounds inside the library (RVS_BFGS_ON_DEVICE=0: the
+            # same machine on the host around the same chain driven from Python)
+            jobs_before = pobj.jobs
+            slots_before = pobj.slots
+            chain = optimizer.GradChain(pobj)
+            if BFGS_ON_DEVICE:
+                br = bfgs.minimize_lockstep_device(pobj, x, hess_inv0=hess_inv0,
+                                                   jac=True, chain=chain)
+                x = br['x']
+                br = {k_: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v)
+                      for k_, v in br.items()}
+            else:
+                br = bfgs.minimize_lockstep_native(chain.rows, x.cpu().numpy(),
+                                                   hess_inv0=hess_inv0, jac=True)
+                x = torch.as_tensor(br['x']).to(dev)
+            obj.status |= pobj.status
+            obj.nfev += pobj.jobs - jobs_before
+            slots += pobj.slots - slots_before
+            bfgs_info = dict(nit=br['nit'], nfev=br['nfev'], njev=br['njev'],
+                             status=br['status'], rounds=br['rounds'],
+                             device=BFGS_ON_DEVICE, jac=True)
+        elif BFGS_ON_DEVICE and optimizer.NATIVE_ROUNDS and pobj.native:
             # the rounds inside the library (rvs_bfgs_run), on the objective the
             # simplex stage ran on
             jobs_before = pobj.jobs

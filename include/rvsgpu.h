@@ -108,7 +108,8 @@ extern "C" {
  *      changed, so a caller built against 18 is served as before; likewise
  *      rvs_vsini_convolve_grad, the broadening with its vsini tangent row, and
  *      rvs_template_tri_grad / rvs_template_tri_buckets_grad, the Delaunay
- *      evaluator with its tangent rows) */
+ *      evaluator with its tangent rows; and rvs_chisq_point_fisher_work_size /
+ *      rvs_chisq_point_fisher, the Fisher matrix of the marginalised fit) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -588,6 +589,36 @@ int rvs_chisq_point_grad(const rvs_point_arm *arms, int narm, int npoly, int nta
                          const double *vel, double badchi,
                          const double *basis_const, void *scratch, double *out,
                          double *grad, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------
+ * ... and with the Fisher matrix of the fit: the expected information of the Gaussian
+ * likelihood in (velocity, the ntan parameters), marginalised over the continuum
+ * coefficients -- the Gauss-Newton part of the Hessian of 0.5 * (-2 log L), the
+ * quantity vel_fit.hess_func differences, so that its inverse is a covariance.
+ * Arguments, restrictions, value, gradient and status bits are those of
+ * rvs_chisq_point_grad (the same two passes in the same block: out and grad carry the
+ * same bits); a third pass forms, per arm, with s = c.polys the fitted continuum,
+ * J_ki = s_k m'_ki / e_k the whitened model's Jacobian and y = L^-1 polys (A = L L^T),
+ *   F_il = sum_k J_ki J_kl - sum_p B_pi B_pl,   B_pi = sum_k y_p(k) (m_k/e_k) J_ki,
+ * the Schur complement of the joint Fisher matrix of (parameters, continuum).  Tangent
+ * 0 is the velocity tangent, tangent i >= 1 row i of coef.  It is positive
+ * semi-definite up to rounding and exactly symmetric (each entry is formed once and
+ * written to both halves); every sum is folded in a fixed order (no atomics).  The
+ * penalty terms and log det A are not part of it.
+ * fisher [J, 1+ntan, 1+ntan] out: summed over the arms in arm order; an arm with a non
+ * finite penalty adds nothing; where an arm's value is NaN its matrix is NaN.
+ * fisher == NULL: RVS_E_ARG.
+ * scratch: rvs_chisq_point_fisher_work_size(J, narm, ntan) bytes =
+ * narm * J * ((2 + ntan + (1 + ntan)^2) * 8 + 4); 0 for what is refused (J < 1,
+ * narm < 1, ntan outside 0..6).
+ * ---------------------------------------------------------------------- */
+int64_t rvs_chisq_point_fisher_work_size(int J, int narm, int ntan);
+int rvs_chisq_point_fisher(const rvs_point_arm *arms, int narm, int npoly, int ntan,
+                           const int32_t *job_spec, const int32_t *job_templ, int J,
+                           const double *vel, double badchi,
+                           const double *basis_const, void *scratch, double *out,
+                           double *grad, double *fisher, int32_t *status,
+                           void *stream);
 
 /* ------------------------------------------------------------------------
  * The same objective as ONE kernel per evaluation for regular-grid libraries:

@@ -63,6 +63,8 @@ SIGNATURES = {
     'rvs_chisq_point': (I, [P, I, I, P, P, I, P, D, P, P, P, P]),
     'rvs_chisq_point_grad_work_size': (L, [I, I, I]),
     'rvs_chisq_point_grad': (I, [P, I, I, I, P, P, I, P, D, P, P, P, P, P, P]),
+    'rvs_chisq_point_fisher_work_size': (L, [I, I, I]),
+    'rvs_chisq_point_fisher': (I, [P, I, I, I, P, P, I, P, D, P, P, P, P, P, P, P]),
     'rvs_nm_begin': (I, [I, I, D, D, I, P, P, P, P, P, P, P, I, P]),
     'rvs_nm_decide': (I, [I, P, P, P, P, P, P, P, P, P, I, P]),
     'rvs_nm_update': (I, [I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P]),

@@ -2156,20 +2156,37 @@ extern "C" int rvs_chisq_point(const rvs_point_arm *arms, int narm, int npoly,
 // (P(P+1)/2 + P)(1 + K) sums of the tangent normal equations (1216 at P = 16, K = 7:
 // more than a lane's registers or a block's LDS slots per lane hold) become 2 + K,
 // and the residual enters explicitly, as in the value, instead of as a difference.
+//
+// The Fisher matrix of the same fit (rvs_chisq_point_fisher) is a third pass behind
+// the same two, in the same block: point_grad_block<P, true>.  With J_ki = s_k m'_ki /
+// e_k (s = c.phi, the fitted continuum) and the orthonormal rows U = L^-1 ST,
+//     F_il = sum_k J_ki J_kl - sum_p B_pi B_pl,   B_pi = sum_k y_p(k) (m_k / e_k) J_ki,
+// y = L^-1 phi the forward substitution of pass 2.  The P K + K (K + 1) / 2 sums (140
+// at P = 16, K = 7) do not fit beside L in a lane's registers, so the pass loops over
+// the tangents: for tangent i the P sums B_.i and the K - i sums G_il, l >= i, with y
+// recomputed -- K times the multiply-adds of pass 2 on a path that runs once per
+// spectrum.  Sums are folded as everywhere here (DPP per wave, the four waves in order
+// through LDS); F_il is formed once and written to both halves.
 // ---------------------------------------------------------------------------
 #define GRAD_MAXTAN 6   // the parameters of a regular-grid library (MAXDIM)
-template <int P>
-__global__ void __launch_bounds__(256)
-    point_grad_block_kernel(PointArms A, int ntan,
-                            const int32_t *__restrict__ job_spec,
-                            const int32_t *__restrict__ job_templ, int J,
-                            const double *__restrict__ vel,
-                            double *__restrict__ armchi,
-                            double *__restrict__ armgrad,
-                            int32_t *__restrict__ armst) {
+// rows of L that stay in registers in point_fisher_block_kernel<16> (the others are read
+// from LDS); chosen from the compiler's resource report: 14 and 12 leave scratch, 8 none
+#define FISHER_LROWS_P16 8
+template <int P, bool FISHER>
+__device__ __forceinline__ void
+    point_grad_block(const PointArms &A, int ntan,
+                     const int32_t *__restrict__ job_spec,
+                     const int32_t *__restrict__ job_templ, int J,
+                     const double *__restrict__ vel,
+                     double *__restrict__ armchi,
+                     double *__restrict__ armgrad,
+                     double *__restrict__ armfisher,
+                     int32_t *__restrict__ armst) {
   constexpr int NT = P * (P + 1) / 2;
   constexpr int NV = NT + P;
-  constexpr int NR = NV > 2 + GRAD_MAXTAN ? NV : 2 + GRAD_MAXTAN;
+  constexpr int KM = 1 + GRAD_MAXTAN;
+  constexpr int NG = FISHER && P + KM > 1 + KM ? P + KM : 1 + KM;
+  constexpr int NR = NV > NG ? NV : NG;
   __shared__ double red[4][NR + 1];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int j = blockIdx.x;
@@ -2273,6 +2290,21 @@ __global__ void __launch_bounds__(256)
     for (int q = i + 1; q < P; q++) sum -= acc[TRI(q, i)] * av[q];
     av[i] = sum / acc[TRI(i, i)];
   }
+  // With the Fisher pass at P = 16, L, the job's scalars and the sums of a tangent do
+  // not all fit a lane's registers: the last rows of L then live in LDS, every lane
+  // reading the same address (the same numbers, so pass 2 gives the same bits)
+  constexpr int PL = FISHER && P > 15 ? FISHER_LROWS_P16 : P;
+  __shared__ double lsh[PL < P ? NT : 1];
+  if constexpr (PL < P) {
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int q = TRI(PL, 0); q < NT; q++) lsh[q] = acc[q];
+    }
+    __syncthreads();
+  }
+  auto lmat = [&](int p, int qq) {
+    return p < PL ? acc[TRI(p, qq)] : lsh[TRI(p, qq)];
+  };
   double rr = 0;
   double gk[1 + GRAD_MAXTAN];
 #pragma unroll
@@ -2299,7 +2331,7 @@ __global__ void __launch_bounds__(256)
       m = fma(av[i], ph, m);
       double sum = ph;
 #pragma unroll
-      for (int qq = 0; qq < i; qq++) sum = fma(-acc[TRI(i, qq)], y[qq], sum);
+      for (int qq = 0; qq < i; qq++) sum = fma(-lmat(i, qq), y[qq], sum);
       y[i] = sum * idg[i];
       q = fma(y[i], y[i], q);
     }
@@ -2350,6 +2382,122 @@ __global__ void __launch_bounds__(256)
     const double g = ((red[0][1 + i] + red[1][1 + i]) + red[2][1 + i]) + red[3][1 + i];
     armgrad[o * K + i] = (chi == chi) ? g : __builtin_nan("");
   }
+  if constexpr (FISHER) {
+    __shared__ double bsh[KM][P];
+    __shared__ double gsh[KM][KM];
+    for (int i = 0; i < K; i++) {
+      double bp[P], gl[KM];   // B_.i and G_i,i+d
+#pragma unroll
+      for (int p = 0; p < P; p++) bp[p] = 0;
+#pragma unroll
+      for (int d = 0; d < KM; d++) gl[d] = 0;
+      for (int k = threadIdx.x; k < npix; k += 256) {
+        const double x = AG.lam[k] * f;
+        int pos = T.log_step ? (int)(AG.pix[k] + shift)
+                             : (int)((x - x0) * lin_inv_step);
+        pos = min(max(pos, 0), T.ntp - 2);
+        const double dl = x - T.knots[pos];
+        const double4 c0 = cf[pos];
+        const double tv = fma(fma(fma(c0.w, dl, c0.z), dl, c0.y), dl, c0.x);
+        double e = es[k];
+        if (espec_sys > 0) e = sqrt(sys2 + e * e);
+        const double ie = 1.0 / e;
+        const double *pr = AG.polysT + (int64_t)k * P;
+        double y[P];
+        double m = 0;
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+          const double ph = pr[p];
+          m = fma(av[p], ph, m);
+          double sum = ph;
+#pragma unroll
+          for (int qq = 0; qq < p; qq++)
+            sum = fma(-lmat(p, qq), y[qq], sum);
+          y[p] = sum * idg[p];
+        }
+        const double se = m * ie;   // J_kl = se * m'_kl
+        double ti;
+        if (i == 0) {
+          ti = fma(dl, fma(3.0 * c0.w, dl, 2.0 * c0.z), c0.y) * (AG.lam[k] * dfdv);
+        } else {
+          const double4 c = cf[(int64_t)i * T.ntp + pos];
+          ti = fma(fma(fma(c.w, dl, c.z), dl, c.y), dl, c.x);
+        }
+        const double ji = se * ti;
+        const double z = (tv * ie) * ji;
+#pragma unroll
+        for (int p = 0; p < P; p++) bp[p] = fma(y[p], z, bp[p]);
+        gl[0] = fma(ji, ji, gl[0]);
+#pragma unroll
+        for (int d = 1; d < KM; d++)
+          if (i + d < K) {
+            const double4 c = cf[(int64_t)(i + d) * T.ntp + pos];
+            const double tl = fma(fma(fma(c.w, dl, c.z), dl, c.y), dl, c.x);
+            gl[d] = fma(ji, se * tl, gl[d]);
+          }
+      }
+      __syncthreads();   // (red: the sums of the pass before are read)
+#pragma unroll
+      for (int p = 0; p < P; p++) {
+        const double v = wave_sum_to63(bp[p]);
+        if (lane == 63) red[w][p] = v;
+      }
+#pragma unroll
+      for (int d = 0; d < KM; d++) {
+        const double v = wave_sum_to63(gl[d]);
+        if (lane == 63) red[w][P + d] = v;
+      }
+      __syncthreads();
+      if (threadIdx.x < P + KM) {
+        const int q = threadIdx.x;
+        const double v = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+        if (q < P)
+          bsh[i][q] = v;
+        else if (i + q - P < K)
+          gsh[i][i + q - P] = v;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < KM * KM) {
+      const int i = threadIdx.x / KM, l = threadIdx.x % KM;
+      if (i <= l && l < K) {
+        double bb2 = 0;
+#pragma unroll
+        for (int p = 0; p < P; p++) bb2 = fma(bsh[i][p], bsh[l][p], bb2);
+        const double v = (chi == chi) ? gsh[i][l] - bb2 : __builtin_nan("");
+        double *fo = armfisher + o * K * K;
+        fo[i * K + l] = v;
+        fo[l * K + i] = v;
+      }
+    }
+  }
+}
+
+template <int P>
+__global__ void __launch_bounds__(256)
+    point_grad_block_kernel(PointArms A, int ntan,
+                            const int32_t *__restrict__ job_spec,
+                            const int32_t *__restrict__ job_templ, int J,
+                            const double *__restrict__ vel,
+                            double *__restrict__ armchi,
+                            double *__restrict__ armgrad,
+                            int32_t *__restrict__ armst) {
+  point_grad_block<P, false>(A, ntan, job_spec, job_templ, J, vel, armchi, armgrad,
+                             nullptr, armst);
+}
+
+template <int P>
+__global__ void __launch_bounds__(256)
+    point_fisher_block_kernel(PointArms A, int ntan,
+                              const int32_t *__restrict__ job_spec,
+                              const int32_t *__restrict__ job_templ, int J,
+                              const double *__restrict__ vel,
+                              double *__restrict__ armchi,
+                              double *__restrict__ armgrad,
+                              double *__restrict__ armfisher,
+                              int32_t *__restrict__ armst) {
+  point_grad_block<P, true>(A, ntan, job_spec, job_templ, J, vel, armchi, armgrad,
+                            armfisher, armst);
 }
 
 // arms summed in order; penalties of A11 (spec_fit.py:888-896) on the value only
@@ -2394,19 +2542,51 @@ __global__ void point_grad_sum_kernel(PointArms A, int J, int K, double badchi,
   if (st) atomicOr(&status[j], st);
 }
 
-extern "C" int64_t rvs_chisq_point_grad_work_size(int J, int narm, int ntan) {
-  if (J < 1 || narm < 1 || ntan < 0 || ntan > GRAD_MAXTAN) return 0;
-  return (int64_t)narm * J *
-         (int64_t)((2 + ntan) * sizeof(double) + sizeof(int32_t));
+// the arms' Fisher matrices summed in order: the arms point_grad_sum_kernel skips add
+// nothing; one thread per (job, entry)
+__global__ void point_fisher_sum_kernel(PointArms A, int J, int K,
+                                        const double *__restrict__ armfisher,
+                                        double *__restrict__ fisher) {
+  const int64_t KK = (int64_t)K * K;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= J * KK) return;
+  const int64_t j = idx / KK;
+  double tot = 0;
+#pragma unroll
+  for (int ia = 0; ia < RVS_MAX_ARMS; ia++) {
+    if (ia >= A.n) break;
+    const double *pp = A.a[ia].penalty;
+    const double pen = pp ? pp[j] : 0.0;
+    if (!(pen == pen) || isinf(pen)) continue;
+    tot += armfisher[(int64_t)ia * J * KK + idx];
+  }
+  fisher[idx] = tot;
 }
 
-extern "C" int rvs_chisq_point_grad(const rvs_point_arm *arms, int narm, int npoly,
-                                    int ntan, const int32_t *job_spec,
-                                    const int32_t *job_templ, int J,
-                                    const double *vel, double badchi,
-                                    const double *basis_const, void *scratch,
-                                    double *out, double *grad, int32_t *status,
-                                    void *stream) {
+// scratch of the gradient call, and of the Fisher call when `fisher`
+static int64_t point_grad_work(int J, int narm, int ntan, bool fisher) {
+  if (J < 1 || narm < 1 || ntan < 0 || ntan > GRAD_MAXTAN) return 0;
+  const int K = 1 + ntan;
+  return (int64_t)narm * J *
+         (int64_t)((1 + K + (fisher ? K * K : 0)) * sizeof(double) +
+                   sizeof(int32_t));
+}
+
+extern "C" int64_t rvs_chisq_point_grad_work_size(int J, int narm, int ntan) {
+  return point_grad_work(J, narm, ntan, false);
+}
+
+extern "C" int64_t rvs_chisq_point_fisher_work_size(int J, int narm, int ntan) {
+  return point_grad_work(J, narm, ntan, true);
+}
+
+// rvs_chisq_point_grad, and rvs_chisq_point_fisher where `fisher` is given
+static int point_grad_launch(const rvs_point_arm *arms, int narm, int npoly,
+                             int ntan, const int32_t *job_spec,
+                             const int32_t *job_templ, int J, const double *vel,
+                             double badchi, const double *basis_const,
+                             void *scratch, double *out, double *grad,
+                             double *fisher, int32_t *status, void *stream) {
   if (J < 1 || narm < 1 || narm > RVS_MAX_ARMS || !arms || !scratch ||
       ntan < 0 || ntan > GRAD_MAXTAN)
     return RVS_E_ARG;
@@ -2426,13 +2606,20 @@ extern "C" int rvs_chisq_point_grad(const rvs_point_arm *arms, int narm, int npo
   const int K = 1 + ntan;
   double *armchi = (double *)scratch;
   double *armgrad = armchi + (int64_t)narm * J;
-  int32_t *armst = (int32_t *)(armgrad + (int64_t)narm * J * K);
+  double *armfisher = armgrad + (int64_t)narm * J * K;
+  int32_t *armst =
+      (int32_t *)(armfisher + (fisher ? (int64_t)narm * J * K * K : 0));
   dim3 grid(J, narm);
 #define RVS_CASE(PP)                                                           \
   case PP:                                                                     \
-    hipLaunchKernelGGL(point_grad_block_kernel<PP>, grid, dim3(256), 0, st, A, \
-                       ntan, job_spec, job_templ, J, vel, armchi, armgrad,     \
-                       armst);                                                 \
+    if (fisher)                                                                \
+      hipLaunchKernelGGL(point_fisher_block_kernel<PP>, grid, dim3(256), 0,    \
+                         st, A, ntan, job_spec, job_templ, J, vel, armchi,     \
+                         armgrad, armfisher, armst);                           \
+    else                                                                       \
+      hipLaunchKernelGGL(point_grad_block_kernel<PP>, grid, dim3(256), 0, st,  \
+                         A, ntan, job_spec, job_templ, J, vel, armchi,         \
+                         armgrad, armst);                                      \
     break;
   switch (npoly) {
     RVS_CASE(1) RVS_CASE(2) RVS_CASE(3) RVS_CASE(4) RVS_CASE(5) RVS_CASE(6)
@@ -2445,8 +2632,38 @@ extern "C" int rvs_chisq_point_grad(const rvs_point_arm *arms, int narm, int npo
   hipLaunchKernelGGL(point_grad_sum_kernel, dim3((J + 255) / 256), dim3(256), 0,
                      st, A, J, K, badchi, make_double4(bc[0], bc[1], bc[2], bc[3]),
                      job_spec, armchi, armgrad, armst, out, grad, status);
+  if (fisher) {
+    const int64_t n = (int64_t)J * K * K;
+    hipLaunchKernelGGL(point_fisher_sum_kernel, dim3((unsigned)((n + 255) / 256)),
+                       dim3(256), 0, st, A, J, K, armfisher, fisher);
+  }
   RVS_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int rvs_chisq_point_grad(const rvs_point_arm *arms, int narm, int npoly,
+                                    int ntan, const int32_t *job_spec,
+                                    const int32_t *job_templ, int J,
+                                    const double *vel, double badchi,
+                                    const double *basis_const, void *scratch,
+                                    double *out, double *grad, int32_t *status,
+                                    void *stream) {
+  return point_grad_launch(arms, narm, npoly, ntan, job_spec, job_templ, J, vel,
+                           badchi, basis_const, scratch, out, grad, nullptr,
+                           status, stream);
+}
+
+extern "C" int rvs_chisq_point_fisher(const rvs_point_arm *arms, int narm,
+                                      int npoly, int ntan, const int32_t *job_spec,
+                                      const int32_t *job_templ, int J,
+                                      const double *vel, double badchi,
+                                      const double *basis_const, void *scratch,
+                                      double *out, double *grad, double *fisher,
+                                      int32_t *status, void *stream) {
+  if (!fisher) return RVS_E_ARG;
+  return point_grad_launch(arms, narm, npoly, ntan, job_spec, job_templ, J, vel,
+                           badchi, basis_const, scratch, out, grad, fisher, status,
+                           stream);
 }
 
 // ---------------------------------------------------------------------------

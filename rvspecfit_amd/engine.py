@@ -994,6 +994,29 @@ def chisq_point_grad(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
     finite-differenced: npoly > 16, several wavelength grids per arm, a
     resolution matrix, fast_interp, libraries that are neither regular grids nor
     Delaunay triangulations (MLP libraries)."""
+    return _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
+                             job_templ, espec_sys, outside_penalty, resols,
+                             fast_interp, False)
+
+
+def chisq_point_fisher(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
+                       job_spec=None, job_templ=None, espec_sys=0.0,
+                       outside_penalty=True, resols=None, fast_interp=False):
+    """chisq_point_grad with the Fisher matrix of the fit (rvs_chisq_point_fisher): the
+    arguments and the scope of chisq_point_grad.  Returns chisq [J], grad [J, 1 + ntan]
+    (the bits of chisq_point_grad), fisher [J, 1 + ntan, 1 + ntan] over (vel,
+    parameters[, vsini]) in physical units, status int32 [J].  fisher is the expected
+    information of the likelihood marginalised over the continuum, the Gauss-Newton
+    part of the Hessian of 0.5 chisq: exactly symmetric, positive semi-definite up to
+    rounding; the penalties and log det A are not part of it."""
+    return _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
+                             job_templ, espec_sys, outside_penalty, resols,
+                             fast_interp, True)
+
+
+def _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
+                      job_templ, espec_sys, outside_penalty, resols, fast_interp,
+                      want_fisher):
     import ctypes
     ntan = coefs[0].shape[1] - 1
     check_grad_scope(batch, libs, npoly, resols, fast_interp,
@@ -1007,7 +1030,12 @@ def chisq_point_grad(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
     out = torch.empty(J, dtype=torch.float64, device=dev)
     grad = torch.empty((J, 1 + ntan), dtype=torch.float64, device=dev)
     status = torch.zeros(J, dtype=torch.int32, device=dev)
-    nb = L.rvs_chisq_point_grad_work_size(J, narm, ntan)
+    fisher = None
+    if want_fisher:
+        fisher = torch.empty((J, 1 + ntan, 1 + ntan), dtype=torch.float64, device=dev)
+        nb = L.rvs_chisq_point_fisher_work_size(J, narm, ntan)
+    else:
+        nb = L.rvs_chisq_point_grad_work_size(J, narm, ntan)
     scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
     arr = (_lib.PointArm * narm)()
     bconst = (ctypes.c_double * narm)()
@@ -1027,13 +1055,17 @@ def chisq_point_grad(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
         arr[ia].polysT = qt.data_ptr()
         bconst[ia] = const
         keep.append(qt)
+    head = (ctypes.addressof(arr), narm, npoly, ntan, _lib.ptr(job_spec),
+            _lib.ptr(job_templ), J, _lib.ptr(vel), float(batch.badchi),
+            ctypes.addressof(bconst), _lib.ptr(scratch), _lib.ptr(out), _lib.ptr(grad))
+    if want_fisher:
+        with _ktime('chisq_point_fisher', J):
+            rc = L.rvs_chisq_point_fisher(*head, _lib.ptr(fisher), _lib.ptr(status),
+                                          _lib.stream())
+            _lib.check(rc, 'rvs_chisq_point_fisher')
+        return out, grad, fisher, status
     with _ktime('chisq_point_grad', J):
-        rc = L.rvs_chisq_point_grad(ctypes.addressof(arr), narm, npoly, ntan,
-                                    _lib.ptr(job_spec), _lib.ptr(job_templ), J,
-                                    _lib.ptr(vel), float(batch.badchi),
-                                    ctypes.addressof(bconst), _lib.ptr(scratch),
-                                    _lib.ptr(out), _lib.ptr(grad),
-                                    _lib.ptr(status), _lib.stream())
+        rc = L.rvs_chisq_point_grad(*head, _lib.ptr(status), _lib.stream())
         _lib.check(rc, 'rvs_chisq_point_grad')
     return out, grad, status
 

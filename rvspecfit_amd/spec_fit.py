@@ -506,6 +506,15 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
     setup, no resolution matrix, no fast_interp: anything else (an MLP library
     included) raises ValueError.  On a Delaunay library a point that no simplex
     holds has the value's penalty and a zero gradient."""
+    return _get_chisq_grad(specdata, vel, atm_params, rot_params, options, config,
+                           outside_penalty, espec_systematic, resol_params, fast_interp,
+                           vsini_grad, False)
+
+
+def _get_chisq_grad(specdata, vel, atm_params, rot_params, options, config,
+                    outside_penalty, espec_systematic, resol_params, fast_interp,
+                    vsini_grad, fisher):
+    # get_chisq_grad, and get_chisq_fisher where `fisher`
     options = options or {}
     npoly = options.get('npoly') or 5
     rbf = options.get('rbf_continuum', True)
@@ -530,18 +539,37 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
         esys = [float(espec_systematic[n]) for n in batch.names]
     else:
         esys = float(espec_systematic) if espec_systematic is not None else 0.0
-    chisq, grad, status = _chisq_grad(batch, libs, None, velt[:, 0], params, vsini,
-                                      npoly, rbf, esys, outside_penalty, resols,
-                                      fast_interp, vsini_grad)
+    res = _chisq_grad(batch, libs, None, velt[:, 0], params, vsini, npoly, rbf, esys,
+                      outside_penalty, resols, fast_interp, vsini_grad, fisher)
     if is_batch:
-        return chisq, grad
-    _raise_for_status(int(status[0].item()),
+        return res[:-1]
+    _raise_for_status(int(res[-1][0].item()),
                       f'velocity {vel}, atm parameters {atm_params}')
-    return float(chisq[0].item()), grad[0].cpu().numpy()
+    return (float(res[0][0].item()), ) + tuple(r[0].cpu().numpy() for r in res[1:-1])
+
+
+def get_chisq_fisher(specdata, vel, atm_params, rot_params=None, options=None,
+                     config=None, outside_penalty=True, espec_systematic=None,
+                     resol_params=None, fast_interp=False, vsini_grad=False):
+    """get_chisq_grad with the Fisher matrix of the fit over (vel,
+    *getSpecParams(setup)[, vsini]) in physical units: the expected information of the
+    likelihood marginalised over the continuum coefficients, i.e. the Gauss-Newton part
+    of the Hessian of 0.5 chi^2 (the function vel_fit.hess_func differences), so that
+    its inverse is a covariance.  Unlike that Hessian it is positive semi-definite at
+    any point, not only at an exact optimum.  The outside penalty and log det A are not
+    part of it; outside the grid the parameter rows and columns are zero.
+
+    One spectrum: returns (float, ndarray [K], ndarray [K, K]), K = 1 + ndim (2 + ndim
+    with vsini_grad).  SpecBatch: device tensors [S], [S, K], [S, K, K].  Value and
+    gradient are the bits of get_chisq_grad; arguments and scope are its own (anything
+    else raises ValueError)."""
+    return _get_chisq_grad(specdata, vel, atm_params, rot_params, options, config,
+                           outside_penalty, espec_systematic, resol_params, fast_interp,
+                           vsini_grad, True)
 
 
 def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
-                outside_penalty, resols, fast_interp, vsini_grad=False):
+                outside_penalty, resols, fast_interp, vsini_grad=False, fisher=False):
     # (the checks come first: nothing is built for a call that is refused)
     engine.check_grad_scope(batch, libs, npoly, resols, fast_interp, vsini_grad)
     coefs, outs = [], []
@@ -550,9 +578,20 @@ def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
                                       vsini_tangent=vsini_grad)
         coefs.append(c)
         outs.append(o)
-    return engine.chisq_point_grad(batch, libs, coefs, outs, vel, npoly=npoly,
-                                   rbf=rbf, job_spec=js, espec_sys=esys,
-                                   outside_penalty=outside_penalty)
+    call = engine.chisq_point_fisher if fisher else engine.chisq_point_grad
+    return call(batch, libs, coefs, outs, vel, npoly=npoly, rbf=rbf, job_spec=js,
+                espec_sys=esys, outside_penalty=outside_penalty)
+
+
+def chisq_fisher_jobs(batch, idx, vel, params, vsini, options, config,
+                      outside_penalty=True, espec_systematic=None, resol_params=None,
+                      vsini_grad=False):
+    """chisq_grad_jobs with the Fisher matrix (get_chisq_fisher) of every job.
+    Returns chisq [J], grad [J, K], fisher [J, K, K], status [J]; K = 1 + ndim, or
+    2 + ndim with vsini_grad (vsini last)."""
+    return _chisq_grad_jobs(batch, idx, vel, params, vsini, options, config,
+                            outside_penalty, espec_systematic, resol_params,
+                            vsini_grad, True)
 
 
 def chisq_grad_jobs(batch, idx, vel, params, vsini, options, config,
@@ -563,6 +602,13 @@ def chisq_grad_jobs(batch, idx, vel, params, vsini, options, config,
     in one launch set (walker ensembles, HMC chains).
     Returns chisq [J], grad [J, 1 + ndim] = d/d(vel, parameters), status [J];
     with vsini_grad (vsini must be given) grad is [J, 2 + ndim], d/dvsini last."""
+    return _chisq_grad_jobs(batch, idx, vel, params, vsini, options, config,
+                            outside_penalty, espec_systematic, resol_params,
+                            vsini_grad, False)
+
+
+def _chisq_grad_jobs(batch, idx, vel, params, vsini, options, config, outside_penalty,
+                     espec_systematic, resol_params, vsini_grad, fisher):
     if vsini_grad and vsini is None:
         raise ValueError('vsini_grad=True needs vsini: without rotation there is no '
                          'vsini to differentiate by')
@@ -575,7 +621,7 @@ def chisq_grad_jobs(batch, idx, vel, params, vsini, options, config,
     resols = _resols(batch, resol_params)
     js = idx.to(torch.int32).contiguous()
     return _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
-                       outside_penalty, resols, False, vsini_grad)
+                       outside_penalty, resols, False, vsini_grad, fisher)
 
 
 # rows per launch set of the from-template objective (template buffers of

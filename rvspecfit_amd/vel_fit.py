@@ -672,6 +672,97 @@ def param_uncertainties(specdata, vel, atm_params, vsini=None, options=None,
                 bad_hessian=bool(bad[0]))
 
 
+def _uncertainties_from_fisher(F, names, stellar, prior_isig2=None, fixParam=()):
+    """The host part of fisher_uncertainties on plain numpy: F [S, K, K] over `names`
+    (K = len(names)), `stellar` the names among them that are stellar parameters,
+    prior_isig2 {name: 1 / sigma^2, scalar or [S]}, fixParam the names to drop.
+    Both inverses go through _uncertainties_from_hessians (the reference's rule and its
+    diagonal fallback) after the symmetric scaling diag(F)^-1/2 F diag(F)^-1/2: K beside
+    dex gives condition numbers of 1e8 ... 1e10 unscaled.  A zero row (a parameter the
+    model does not depend on: a point outside the grid) keeps its scale 1, makes the
+    matrix singular and takes the fallback: an infinite error, bad_fisher, no
+    exception."""
+    F = np.array(F, dtype=np.float64)
+    S = F.shape[0]
+    assert F.shape[1:] == (len(names), len(names))
+    for k, v in (prior_isig2 or {}).items():
+        if k in names:
+            i = list(names).index(k)
+            F[:, i, i] += np.broadcast_to(np.asarray(v, dtype=np.float64), (S, ))
+    keep = [i for i, k in enumerate(names) if k not in fixParam]
+    names = [names[i] for i in keep]
+    F = F[:, keep][:, :, keep]
+
+    def scaled_inverse(M):
+        d = np.diagonal(M, axis1=1, axis2=2)
+        with np.errstate(all='ignore'):
+            sc = np.where(d > 0, 1. / np.sqrt(np.where(d > 0, d, 1.)), 1.)
+        err, inv, bad = _uncertainties_from_hessians(M * sc[:, :, None] * sc[:, None, :])
+        return err * sc, inv * sc[:, :, None] * sc[:, None, :], bad
+
+    err, covar, bad = scaled_inverse(F)
+    ist = [i for i, k in enumerate(names) if k in stellar]
+    perr, pcovar, pbad = scaled_inverse(F[:, ist][:, :, ist])
+    nan = np.full(S, np.nan)
+    return dict(names=names, fisher=F, covar=covar,
+                err={k: err[:, i] for i, k in enumerate(names)},
+                vel_err=err[:, names.index('vel')] if 'vel' in names else nan,
+                param_err={names[i]: perr[:, n] for n, i in enumerate(ist)},
+                param_covar=pcovar, bad_fisher=bad | pbad)
+
+
+def fisher_uncertainties(specdata, vel, atm_params, vsini=None, options=None,
+                         config=None, priors=None, fixParam=None, vsini_grad=False):
+    """Uncertainties from the Fisher matrix of the continuum-marginalised fit
+    (spec_fit.get_chisq_fisher) at the given point: one deterministic call instead of the
+    33+ objective evaluations of param_uncertainties, and positive semi-definite at any
+    point, where the finite-difference Hessian holds only at an exact optimum.
+    names = ['vel'] + the stellar parameters not in fixParam (+ ['vsini'] with
+    vsini_grad, which needs vsini).  Normal priors {name: (mean, sigma)} add 1 / sigma^2
+    to their diagonal entry.  Returns a dict:
+      names, fisher [n, n], covar [n, n] = fisher^-1 (joint: every error is
+      marginalised over the other names), err {name: sigma}, vel_err,
+      param_err {name: sigma} / param_covar: the stellar block inverted on its own, i.e.
+      with velocity and vsini held -- the reference's definition (vel_fit.py:699-725),
+      comparable with param_uncertainties and process,
+      bad_fisher: an inverse that could not be formed or gave a non-finite error.
+    One spectrum (list of SpecData; atm_params a dict or a sequence in the
+    interpolator's order): floats and arrays as listed; a SpecBatch: the same with a
+    leading S axis.  The scope is get_chisq_grad's (ValueError otherwise)."""
+    batch, is_batch = as_batch(specdata)
+    dev, S = batch.device, batch.S
+    stellar = list(spec_inter.getSpecParams(batch.names[0], config))
+    if isinstance(atm_params, dict):
+        atm_params = [atm_params[k] for k in stellar]
+    pt = torch.as_tensor(np.asarray(
+        atm_params.cpu() if isinstance(atm_params, torch.Tensor) else atm_params,
+        dtype=np.float64)).to(dev).reshape(-1, len(stellar))
+    pt = pt.expand(S, len(stellar)).contiguous()
+    velt = _as_param_tensors(dict(vel=vel), S, dev)['vel']
+    vs = None
+    if vsini is not None:
+        vs = _as_param_tensors(dict(vsini=vsini), S, dev)['vsini']
+    _, _, F = spec_fit.get_chisq_fisher(batch, velt, pt, vs, options=options,
+                                        config=config, vsini_grad=vsini_grad)
+    names = ['vel'] + stellar + (['vsini'] if vsini_grad else [])
+    isig2 = {}
+    for k, (_, sg) in (priors or {}).items():
+        sg = sg.cpu().numpy() if isinstance(sg, torch.Tensor) else np.asarray(sg)
+        isig2[k] = 1. / np.asarray(sg, dtype=np.float64)**2
+    res = _uncertainties_from_fisher(F.cpu().numpy(), names, stellar, isig2,
+                                     list(fixParam) if fixParam is not None else [])
+    if is_batch:
+        return res
+
+    def one(v):
+        if isinstance(v, dict):
+            return {k: one(x) for k, x in v.items()}
+        if isinstance(v, list):
+            return v
+        return v[0] if v[0].ndim else v[0].item()
+    return one(res)
+
+
 # A SpecBatch of at least PROCESS_SPLIT_MIN spectra is fitted as two interleaved
 # halves by two host threads on two HIP streams: the optimiser's rounds run in C
 # (rvs_nm_run, no interpreter lock), so while one half is in the latency-bound
@@ -906,6 +997,20 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
             len(names) + (1 if fitVsini else 0),
             2 if fitVsini else (1 if 'vsini' in pd0 else 0))
 
+    # config['fisher_uncertainties']: the joint covariance of (vel, parameters[, vsini])
+    # from the Fisher matrix at the returned optimum, beside the Hessian's products.
+    # The scope is the gradient's and is checked here, before anything is built
+    fisher_unc = bool(config.get('fisher_uncertainties'))
+    if fisher_unc:
+        try:
+            engine.check_grad_scope(batch, spec_inter.get_libs(batch.names, config),
+                                    options.get('npoly') or 5,
+                                    spec_fit._resols(batch, resolParams),
+                                    bool(options.get('fast_interp')),
+                                    vsini_grad=fitVsini)
+        except ValueError as e:
+            raise ValueError("config['fisher_uncertainties']: %s" % e) from None
+
     def _tick(k, t0):
         # (stage clocks only when somebody asked for them: the device-wide
         # synchronisation they need would make the two halves of a split batch wait
@@ -1097,6 +1202,17 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
         ret['logl'] = -0.5 * ret['chisq']
         ret['chisq_array'] = [float(_) for _ in outp['chisq_array'][0]]
         ret['npix_array'] = [int(_) for _ in outp['npix_array'][0]]
+    if fisher_unc:
+        t0 = time.time()
+        fu = fisher_uncertainties(batch if is_batch else specdata, best_vel, bparams,
+                                  bvsini, options=options, config=config,
+                                  priors=priors, fixParam=fixParam, vsini_grad=fitVsini)
+        ret['covar_fisher'] = fu['covar']
+        ret['names_fisher'] = fu['names']
+        ret['vel_err_fisher'] = torch.as_tensor(fu['vel_err']).to(dev) if is_batch \
+            else fu['vel_err']
+        ret['param_err_fisher'] = fu['param_err']
+        _tick('fisher', t0)
     ret['nm_vel'] = nm_vel if is_batch else float(nm_vel[0].item())
     ret['nm_nit'] = nit if is_batch else int(nit[0].item())
     ret['nm_nfev'] = nfev if is_batch else int(nfev[0].item())

@@ -805,7 +805,15 @@ int rvs_ccf_tables_build(const double *lam, const int32_t *npix_g, int G, int np
  * chisq [G, Np, Nv] (velocity fastest); vels + g*vel_stride -> [Nv];
  * nvel (nullable int32 [G]) = number of valid velocities of group g.
  * res [G, 8] = best_chi, best_vel, vel_err, kurtosis, skewness, i1 (vel idx),
- *              i2 (template idx), spare;   probs [G, Nv] (nullable)
+ *              i2 (template idx), sum_i exp(-(chisq[i2, i] - best_chi) / 2);
+ * probs [G, Nv] (nullable); entries from nvel[g] on are 0 and are never read
+ * from chisq or vels.  status (nullable int32 [G], OR-ed into) gets
+ * RVS_ST_QUAD_ASSERT where the reference's assert would have fired.
+ * A group with nvel[g] < 1 (a refinement window that closed) reads neither
+ * chisq nor vels: best_chi = +inf, best_vel = vel_err = kurtosis = skewness =
+ * NaN, i1 = i2 = -1, res[7] = 0, probs[g, :] = 0, status untouched (vel_fit's
+ * `lost` mask overwrites the same four numbers with NaN).
+ * RVS_E_ARG for G, Np or Nv < 1.
  * ---------------------------------------------------------------------- */
 int rvs_grid_moments(const double *chisq, const double *vels,
                      int64_t vel_stride, const int32_t *nvel, int G, int Np,

@@ -2749,6 +2749,25 @@ __global__ void __launch_bounds__(256)
       bnan = on;
     }
   }
+  if (nv < 1) {
+    // empty group (a refinement window that closed): no element was visited,
+    // bkey is still its initial value and indexes nothing
+    if (probs)
+      for (int i = tid; i < Nv; i += 256) probs[(int64_t)g * Nv + i] = 0;
+    if (tid == 0) {
+      const double qnan = __builtin_nan("");
+      double *r = res + (int64_t)g * 8;
+      r[0] = __builtin_inf();
+      r[1] = qnan;
+      r[2] = qnan;
+      r[3] = qnan;
+      r[4] = qnan;
+      r[5] = -1;
+      r[6] = -1;
+      r[7] = 0;
+    }
+    return;
+  }
   const int i1 = (int)(bkey / Np), i2 = (int)(bkey % Np);
   const double *col = c + (int64_t)i2 * Nv;
   double psum = 0;

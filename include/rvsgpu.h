@@ -109,7 +109,11 @@ extern "C" {
  *      rvs_vsini_convolve_grad, the broadening with its vsini tangent row, and
  *      rvs_template_tri_grad / rvs_template_tri_buckets_grad, the Delaunay
  *      evaluator with its tangent rows; and rvs_chisq_point_fisher_work_size /
- *      rvs_chisq_point_fisher, the Fisher matrix of the marginalised fit) */
+ *      rvs_chisq_point_fisher, the Fisher matrix of the marginalised fit; and
+ *      rvs_template_nn_grad, the MLP evaluator with its tangent rows, with
+ *      rvs_grad_arm.tri == 2 -- until now one of the non-zero values that meant
+ *      Delaunay; the tree's callers write 1 for that -- naming an MLP arm of the
+ *      gradient chain) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -969,6 +973,43 @@ int rvs_template_nn(const double *params, int B, int ndim, uint32_t log_mask,
                     const int32_t *dims, float *act0, float *act1,
                     double *templ, void *stream);
 
+/* rvs_template_nn with the derivative of the template by every physical parameter, in
+ * forward mode: templ [B, 1 + ndim, ntp] (ntp = dims[nlayer]), row 0 the template,
+ * row 1 + k d template / d p_k.  Arguments as rvs_template_nn; act1 holds
+ * B (1 + ndim) rows of the widest layer (the last hidden layer's rows: the hidden stack
+ * is one launch, so no second image is needed); act0 is not used and may be any
+ * non-NULL pointer.
+ *   Input.   Mapper.forward is x_d = (f32(q_d) - M_d) / S_d, q_d = log10(p_d) for a
+ *            parameter in log_mask, else p_d.  The float32 casts are taken as the
+ *            identity: dx_d / dp_k = delta_dk s_k / S_k, s_k = 1 / (p_k ln 10) under
+ *            the logarithm and 1 otherwise, at the float64 p_k.  The tangent of
+ *            parameter k enters the network as the one-hot e_k (the first layer's
+ *            tangent is column k of W[0]); s_k / S_k is applied in float64 by the
+ *            last epilogue, so no float32 value is scaled by it.
+ *   Hidden.  z = W a + b, sigma = 1 / (1 + expf(-z)), a+ = z sigma:
+ *            adot+ = sigma (1 + z (1 - sigma)) (W adot) -- the same product without
+ *            the bias, times the SiLU derivative at the VALUE row's z of the column.
+ *   Last.    y = W a + b, ydot_k = W adot_k.  Row 0: t = exp(clip(y, -300, 300)) in
+ *            float64; row 1 + k: t ydot_k s_k / S_k, and exactly 0 where |y| > 300
+ *            (the clip is flat there).
+ *   A job whose mapped parameters are not all finite (NaN, a non-positive value under
+ *   the logarithm) has NaN in all 1 + ndim rows, as rvs_template_tri_grad has.
+ * Row 0 carries the bits of rvs_template_nn for the same arguments (finite jobs): the
+ * value row goes through the same products in the same order.  The tangents are
+ * float32 arithmetic: exact to float32 rounding, not to float64's.  No float atomics:
+ * two calls give the same bits.  The rows of a job lie in one block tile of either
+ * kernel (csrc/nn.hip); the call's HBM traffic beyond the weights is the float32 rows
+ * of the last hidden layer and the B (1 + ndim) ntp doubles it writes.
+ * Scope (RVS_E_ARG beyond, before any launch): the networks of rvs_template_nn's
+ * fused hidden stack -- 3 <= nlayer <= 7, every hidden width <= 256 and, from the
+ * second layer's input on, a multiple of 32 (the last layer's input excepted) --
+ * with ndim <= 6 and B (1 + ndim) < 2^28. */
+int rvs_template_nn_grad(const double *params, int B, int ndim, uint32_t log_mask,
+                         const double *M, const double *S, int nlayer,
+                         const float *const *W, const float *const *b,
+                         const int32_t *dims, float *act0, float *act1,
+                         double *templ /* [B, 1 + ndim, ntp] */, void *stream);
+
 /* Outside flag of an NN library; replaces OutsideInterpolator.__call__
  * (nn/RVSInterpolator.py:63-71) as SpecInterpolator.outsideFlag calls it on the
  * Mapper-transformed point (spec_inter.py:257-272, nn/NNInterpolator.py:159-171):
@@ -1180,8 +1221,18 @@ int rvs_proc_finish_grad(int J, int n, int ndim, int ntan, const int32_t *counts
 
 /* One arm of the gradient chain: its template library -- tri == 0: a regular grid,
  * the arguments of rvs_template_polylinear_grad (dats float32; lens, ptp HOST arrays);
- * tri != 0: a Delaunay library, the arguments of rvs_template_tri_buckets_grad
- * (buckets.cell_start != NULL) or rvs_template_tri_grad (dats float64) -- the knots and
+ * tri == 1: a Delaunay library, the arguments of rvs_template_tri_buckets_grad
+ * (buckets.cell_start != NULL) or rvs_template_tri_grad (dats float64); tri == 2: an
+ * MLP library -- dats points to a HOST rvs_nm_nn_arm with the arguments of
+ * rvs_template_nn_grad and rvs_nn_outside, whose act1 holds cap (1 + ndim) rows of the
+ * widest layer (float32; the caller's, NOT counted by rvs_grad_chain_work_size, whose
+ * formula is unchanged; act0 any non-NULL pointer) and whose templ / outside are
+ * not read (the rows go to this struct's).  xeqs == NULL: no hull, outside is zeroed for
+ * every job -- a job with a non-finite mapped parameter then has NaN rows and a clean
+ * flag, and its chi^2 is whatever rvs_chisq_point_grad makes of NaN rows (status
+ * RVS_ST_NONFINITE), as on the value path; with a hull rvs_nn_outside answers NaN and
+ * the job takes the penalty.  (Any other non-zero tri means Delaunay, as before 2 had
+ * a meaning of its own.) -- the knots and
  * rvs_spline_factors of its template grid, and the caller's row buffers for `cap` rows
  * with K = 1 + ntan template rows each:
  *   templ   [cap, K, ntp]     the evaluator's rows (1 + ndim per job)

@@ -114,6 +114,7 @@ SIGNATURES = {
     'rvs_ccf_models_build': (I, [P, P, P, I, I, I, P, P, P, P, I, P, P, P, P, I, P,
                                  P, P, P, P, P, P, P]),
     'rvs_template_nn': (I, [P, I, I, U, P, P, I, P, P, P, P, P, P, P]),
+    'rvs_template_nn_grad': (I, [P, I, I, U, P, P, I, P, P, P, P, P, P, P]),
     'rvs_template_nn_arms': (I, [P, I, I, I, P, P]),
     'rvs_template_nn_arms_n': (I, [P, I, P, I, I, P, P]),
     'rvs_nn_outside': (I, [P, I, I, U, P, P, I, P, I, P, I, P, P]),

@@ -4,6 +4,7 @@
 //
 //   rvs_proc_map            X [J, n] -> vel, vsini, params, prior / vsini penalty, bad
 //   per arm                 rvs_template_polylinear_grad | rvs_template_tri(_buckets)_grad
+//                           | rvs_template_nn_grad + rvs_nn_outside
 //                           rvs_vsini_convolve_grad (vsini fitted) | rvs_vsini_convolve
 //                           over the 1 + ndim rows (vsini fixed) | nothing
 //                           rvs_spline_construct of the (1 + ntan) J rows
@@ -117,9 +118,16 @@ int chain_ok(const rvs_grad_chain *g, const rvs_nm_objective *o) {
         A.ntp < 3 || A.ntp != g->point[a].ntp || !(A.lnstep > 0))
       return 0;
     if (g->point[a].coef != A.coef || g->point[a].penalty != A.penalty) return 0;
-    if (A.tri ? (!A.transform || !A.extraflags || !A.simplices || !A.simplex ||
-                 A.nsimplex < 1)
-              : (!A.idgrid || !A.uvecs || !A.vecs_s || !A.lens || !A.ptp || A.ngrid < 1))
+    if (A.tri == 2) {   // an MLP library: dats is a HOST rvs_nm_nn_arm
+      const rvs_nm_nn_arm *N = static_cast<const rvs_nm_nn_arm *>(A.dats);
+      if (!N->M || !N->S || !N->W || !N->b || !N->dims || !N->act0 || !N->act1 ||
+          N->nlayer < 3 || N->dims[0] != o->ndim || N->dims[N->nlayer] != A.ntp ||
+          (N->xeqs ? (!N->yeqs || N->nfx < 1 || N->nfy < 1) : (N->nfx || N->nfy)))
+        return 0;
+    } else if (A.tri ? (!A.transform || !A.extraflags || !A.simplices || !A.simplex ||
+                        A.nsimplex < 1)
+                     : (!A.idgrid || !A.uvecs || !A.vecs_s || !A.lens || !A.ptp ||
+                        A.ngrid < 1))
       return 0;
     if (g->vsini_mode != 0 && !A.templ2) return 0;
     if (g->vsini_mode == 1 && (!A.vs_rows || !A.out_rows)) return 0;
@@ -199,7 +207,17 @@ int rvs_internal_grad_chain_eval(const rvs_nm_objective *o, const rvs_grad_chain
   const int R = 1 + ndim;
   for (int a = 0; a < g->narm; a++) {
     const rvs_grad_arm &A = g->arms[a];
-    if (!A.tri)
+    if (A.tri == 2) {
+      const rvs_nm_nn_arm *N = static_cast<const rvs_nm_nn_arm *>(A.dats);
+      rc = rvs_template_nn_grad(o->params, J, ndim, N->log_mask, N->M, N->S, N->nlayer,
+                                N->W, N->b, N->dims, N->act0, N->act1, A.templ, st);
+      if (rc) return rc;
+      // (xeqs == NULL: nfx = nfy = 0, the flags are zeroed on the stream -- also
+      // those of a job whose rows are NaN: include/rvsgpu.h, rvs_grad_arm)
+      rc = rvs_nn_outside(N->xeqs ? o->params : nullptr, J, ndim, N->log_mask, N->M,
+                          N->S, N->xeqs ? 0 : 1, N->xeqs, N->nfx, N->yeqs, N->nfy,
+                          A.outside, st);
+    } else if (!A.tri)
       rc = rvs_template_polylinear_grad(
           static_cast<const float *>(A.dats), A.ngrid, A.ntp, A.idgrid, A.uvecs, A.lens,
           ndim, A.vecs_s, A.ptp, A.log_mask, A.exp_flag, o->params, J, A.templ,

@@ -173,12 +173,24 @@ __device__ __forceinline__ void exp_clip300_n(double (&y)[NE]) {
 // (bx, nbx: this block's index among the nbx blocks that walk the tiles of ONE
 // matrix product: the whole grid of nn_linear_kernel, one y-slice of the grid of
 // nn_linear_group_kernel)
-template <bool BIG, bool KVEC, bool FINAL>
+//
+// GRAD (rvs_template_nn_grad, FINAL only): the rows are jobs of R = 1 + ndim rows
+// each -- the value row and one tangent row per parameter -- stored densely, and a
+// tile takes RT = (BM / R) R of them (whole jobs; the BM - RT rows of the tile's tail
+// are computed on clamped addresses and stored nowhere), so that the epilogue finds
+// the value row's y of its column inside the block: see the epilogue below.
+struct NNGradIn {
+  const double *params, *M, *S;   // [B, ndim], [ndim], [ndim]
+  int ndim;
+  uint32_t log_mask;
+};
+template <bool BIG, bool KVEC, bool FINAL, bool GRAD = false>
 __device__ __forceinline__ void
     nn_linear_body(const float *__restrict__ X, const float *__restrict__ W,
                    const float *__restrict__ bias, int Bn, int K, int N,
                    float *__restrict__ yout32, double *__restrict__ yout64,
-                   const int bx, const int nbx) {
+                   const int bx, const int nbx, const NNGradIn *gi = nullptr) {
+  static_assert(!GRAD || FINAL, "tangent rows: the last layer only");
   constexpr int BM = BIG ? NN_BM : 32;
   constexpr int TI = BIG ? 2 : 1, TJ = BIG ? 2 : 1;   // MFMA tiles per wave
   __shared__ __attribute__((aligned(16))) float lds[2][(BM + NN_BN) * NN_LDK];
@@ -191,10 +203,53 @@ __device__ __forceinline__ void
   // 0.12 of that layer's 0.33 ms (measured with the stores compiled out) and did
   // not move under any arrangement tried: one tile per block, persistent blocks,
   // next-tile prefetch ahead of the stores, staggered block starts.
-  const int ntr = (Bn + BM - 1) / BM, ntc = (N + NN_BN - 1) / NN_BN;
-  int row0 = (bx % ntr) * BM, col0 = (bx / ntr) * NN_BN;
+  int gR = 1;
+  if constexpr (GRAD) gR = gi->ndim + 1;
+  const int RT = GRAD ? (BM / gR) * gR : BM;   // rows a tile takes
+  const int ntr = (Bn + RT - 1) / RT, ntc = (N + NN_BN - 1) / NN_BN;
+  int row0 = (bx % ntr) * RT, col0 = (bx / ntr) * NN_BN;
+  // GRAD: per tile row, 8 (job of the tile) + (row of the job), and the float64
+  // factor of the row's epilogue (grad_scale below)
+  int *rowjk = nullptr;
+  double *rowsc = nullptr;
+  if constexpr (GRAD) {
+    __shared__ int rowjk_s[BM];
+    __shared__ double rowsc_s[BM];
+    rowjk = rowjk_s;
+    rowsc = rowsc_s;
+    if (tid < BM) rowjk[tid] = 8 * (tid / gR) + tid % gR;
+  }
   bool first = true;
   for (int tile = bx; tile < ntr * ntc; tile += nbx) {
+  if constexpr (GRAD) {
+    // Row 1 + k of a job is t ydot_k s_k / S_k, s_k = 1 / (p_k ln 10) under the
+    // logarithm, else 1, at the float64 p_k; row 0 has the factor 1.  A job whose
+    // mapped parameters (as nn_map_kernel forms them) are not all finite has NaN
+    // in every row.
+    if (tid < BM) {
+      double s = 0.0;
+      const int g = row0 + tid;
+      if (tid < RT && g < Bn) {
+        const int job = g / gR, k = g - job * gR, nd = gi->ndim;
+        bool bad = false;
+        for (int d = 0; d < nd; d++) {
+          float y = (float)gi->params[(int64_t)job * nd + d];
+          if (gi->log_mask & (1u << d)) y = (float)log10((double)y);
+          const float x = (float)(((double)y - gi->M[d]) / gi->S[d]);
+          bad = bad || !(fabsf(x) <= 3.402823466e38f);
+        }
+        s = 1.0;
+        if (k > 0) {
+          const int d = k - 1;
+          if (gi->log_mask & (1u << d))
+            s = 1.0 / (gi->params[(int64_t)job * nd + d] * 2.302585092994045684);
+          s = s / gi->S[d];
+        }
+        if (bad) s = __builtin_nan("");
+      }
+      rowsc[tid] = s;
+    }
+  }
   f32x16 acc[TI][TJ];
 #pragma unroll
   for (int i = 0; i < TI; i++)
@@ -286,7 +341,7 @@ __device__ __forceinline__ void
   const int erow0 = row0, ecol0 = col0;
   if (tile + nbx < ntr * ntc) {
     const int nt = tile + nbx;
-    row0 = (nt % ntr) * BM;
+    row0 = (nt % ntr) * RT;
     col0 = (nt / ntr) * NN_BN;
     fetch(0);
   }
@@ -320,10 +375,65 @@ __device__ __forceinline__ void
       }
     }
   };
+  (void)emit;
+  if constexpr (GRAD) {
+    // The value rows' y = acc + bias go through LDS (the staging image: every read
+    // of it lies behind the slab loop's last barrier), one float per (job of the
+    // tile, column); then every element takes the y of its job and column:
+    //   row 0      t = exp(clip(y, +-300)) in float64: the arithmetic of emit above
+    //   row 1 + k  t ydot_k s_k / S_k with ydot_k = acc (no bias), in float64;
+    //              exactly 0 where |y| > 300 (the clip is flat there)
+    // (up to BM / 2 jobs of a tile, at ndim = 1: the image runs over BOTH staging
+    // buffers, which are one array)
+    static_assert((BM / 2) * NN_BN <= 2 * (BM + NN_BN) * NN_LDK,
+                  "the value rows' y of a tile fit the staging image");
+    float *yv = reinterpret_cast<float *>(lds);   // [BM / gR][NN_BN]
+#pragma unroll
+    for (int tj = 0; tj < TJ; tj++) {
+      const int cl = wc * WCOLS + tj * 32 + (lane & 31);
+      const float bv = bias[min(ecol0 + cl, N - 1)];
+#pragma unroll
+      for (int ti = 0; ti < TI; ti++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int rt = wr * WROWS + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          const int jk = rowjk[rt];
+          if ((jk & 7) == 0 && rt < RT) yv[(jk >> 3) * NN_BN + cl] = acc[ti][tj][r] + bv;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int tj = 0; tj < TJ; tj++) {
+      const int cl = wc * WCOLS + tj * 32 + (lane & 31);
+      const int col = ecol0 + cl;
+      const bool cok = col < N;
+#pragma unroll
+      for (int ti = 0; ti < TI; ti++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int rt = wr * WROWS + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          if (rt >= RT) continue;   // the tile's padding
+          const int jk = rowjk[rt];
+          const float y = yv[(jk >> 3) * NN_BN + cl];
+          double v = (double)y;
+          const bool flat = v > 300.0 || v < -300.0;
+          v = fmin(fmax(v, -300.0), 300.0);
+          const double e = exp_clip300(v);
+          const double s = rowsc[rt];
+          double o = e;
+          if (jk & 7) o = flat ? 0.0 : e * (double)acc[ti][tj][r] * s;
+          if (s != s) o = s;
+          const int row = erow0 + rt;
+          if (cok && row < Bn) yout64[(int64_t)row * N + col] = o;
+        }
+    }
+    __syncthreads();   // (the next tile's first slab goes to the same LDS)
+  } else {
   if (erow0 + BM <= Bn && ecol0 + NN_BN <= N)
     emit(std::true_type{});
   else
     emit(std::false_type{});
+  }
   }   // tiles
 }
 
@@ -614,6 +724,15 @@ __global__ void __launch_bounds__(256, BIG ? NN_MINB_BIG : 4)
                                    blockIdx.x, gridDim.x);
 }
 
+template <bool BIG, bool KVEC>
+__global__ void __launch_bounds__(256, BIG ? NN_MINB_BIG : 4)
+    nn_linear_grad_kernel(const float *__restrict__ X, const float *__restrict__ W,
+                          const float *__restrict__ bias, int Bn, int K, int N,
+                          NNGradIn G, double *__restrict__ yout64) {
+  nn_linear_body<BIG, KVEC, true, true>(X, W, bias, Bn, K, N, nullptr, yout64,
+                                        blockIdx.x, gridDim.x, &G);
+}
+
 // The last layers of several arms' MLPs (same input rows, same K; own weights
 // and widths) in ONE launch: grid.y = arm.  An optimiser round evaluates a few
 // hundred rows per arm -- one wave of blocks per launch -- and three dependent
@@ -672,20 +791,45 @@ struct NNHidden {
   int nl;
 };
 
+//
+// GRAD (rvs_template_nn_grad): forward mode.  A job is R = 1 + ndim rows of the
+// block's 32 -- the value row and, per parameter k, the tangent row that starts as
+// the one-hot e_k at the network's input (the factor s_k / S_k of Mapper.forward's
+// derivative is applied in float64 by the last layer's epilogue) -- so a block owns
+// 32 / R jobs and RT = (32 / R) R output rows; the rows behind them are the start of
+// one more job, computed and stored nowhere.  A tangent goes through a layer as the
+// same product without the bias, times the SiLU derivative
+//   sigma (1 + z (1 - sigma)),  sigma = 1 / (1 + expf(-z))
+// at the VALUE row's pre-activation z of the same column.  The MFMA leaves that z in
+// another lane's registers: it goes through the layer's OUTPUT image in LDS (nobody
+// reads that image before the layer's last barrier; a wave writes and reads its own
+// 32 columns only), then the image gets the activations.  A value row takes the
+// arithmetic of the value kernel operation by operation (an accumulator element
+// depends on its own row of the A operand alone): its bits are rvs_template_nn's.
+// rk[32]: row of the job (0 = value) per block row.
+template <bool GRAD>
 __device__ __forceinline__ void
     nn_hidden_body(const double *__restrict__ params, int Bn, int ndim,
                    uint32_t log_mask, const double *__restrict__ M,
                    const double *__restrict__ S, const NNHidden &H,
                    float *__restrict__ yout, float (*act)[32 * NH_LD],
-                   float *xin) {
+                   float *xin, int *rk = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int row0 = blockIdx.x * 32;
+  const int gR = GRAD ? ndim + 1 : 1;
+  const int RT = (32 / gR) * gR;                  // output rows of a block
+  const int row0 = blockIdx.x * RT;
+  const int nrow = Bn * gR;                       // (Bn: jobs)
+  (void)nrow;
+  if constexpr (GRAD) {
+    if (tid < 32) rk[tid] = tid % gR;
+  }
   // Mapper.forward of the block's 32 rows
   if (tid < 32 * 8) {
     const int r = tid >> 3, d = tid & 7;
     float v = 0.f;
     if (d < ndim) {
-      const int gr = min(row0 + r, Bn - 1);
+      const int gr = GRAD ? min(blockIdx.x * (32 / gR) + r / gR, Bn - 1)
+                          : min(row0 + r, Bn - 1);
       float y = (float)params[(int64_t)gr * ndim + d];
       if (log_mask & (1u << d)) y = (float)log10((double)y);
       v = (float)(((double)y - M[d]) / S[d]);
@@ -706,7 +850,19 @@ __device__ __forceinline__ void
       float y = bv;
 #pragma unroll
       for (int d = 0; d < 8; d++) y = fmaf(w[d], xin[r * 8 + d], y);
-      act[1][r * NH_LD + c] = c < N ? y / (1.0f + expf(-y)) : 0.f;
+      float a = y / (1.0f + expf(-y));
+      if constexpr (GRAD) {
+        // the tangent of parameter k at the input is e_k: W e_k is column k of W[0]
+        const int k = rk[r];
+        if (k > 0) {
+          float wk = 0.f;
+#pragma unroll
+          for (int d = 0; d < 8; d++) wk = (d == k - 1) ? w[d] : wk;
+          const float sg = 1.0f / (1.0f + expf(-y));
+          a = sg * (1.0f + y * (1.0f - sg)) * wk;
+        }
+      }
+      act[1][r * NH_LD + c] = c < N ? a : 0.f;
     }
   }
   __syncthreads();
@@ -747,7 +903,42 @@ __device__ __forceinline__ void
           acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q][e], cb0[q][e], acc, 0, 0, 0);
     }
     const bool last = (l == H.nl - 1);
-    {
+    if constexpr (GRAD) {
+      const int col = col0 + (lane & 31);
+      const bool cok = col < N;
+      const float bv = H.b[l][cok ? col : 0];
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (rk[row] == 0) outp[row * NH_LD + col] = acc[r] + bv;
+      }
+      __syncthreads();
+      float av[16];
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int k = rk[row];
+        const float y = acc[r] + bv;
+        float a = y / (1.0f + expf(-y));
+        if (k > 0) {
+          const float z = outp[(row - k) * NH_LD + col];
+          const float sg = 1.0f / (1.0f + expf(-z));
+          a = sg * (1.0f + z * (1.0f - sg)) * acc[r];
+        }
+        av[r] = cok ? a : 0.f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (last) {
+          if (cok && row < RT && row0 + row < nrow)
+            yout[(int64_t)(row0 + row) * N + col] = av[r];
+        } else {
+          outp[row * NH_LD + col] = av[r];
+        }
+      }
+    } else {
       const int col = col0 + (lane & 31);
       const bool cok = col < N;
       const float bv = H.b[l][cok ? col : 0];
@@ -774,7 +965,19 @@ __global__ void __launch_bounds__(512, 2)
                      float *__restrict__ yout) {
   __shared__ __attribute__((aligned(16))) float act[2][32 * NH_LD];
   __shared__ float xin[32 * 8];
-  nn_hidden_body(params, Bn, ndim, log_mask, M, S, H, yout, act, xin);
+  nn_hidden_body<false>(params, Bn, ndim, log_mask, M, S, H, yout, act, xin);
+}
+
+// ... of the B jobs of rvs_template_nn_grad: yout [B (1 + ndim), width]
+__global__ void __launch_bounds__(512, 2)
+    nn_hidden_grad_kernel(const double *__restrict__ params, int B, int ndim,
+                          uint32_t log_mask, const double *__restrict__ M,
+                          const double *__restrict__ S, NNHidden H,
+                          float *__restrict__ yout) {
+  __shared__ __attribute__((aligned(16))) float act[2][32 * NH_LD];
+  __shared__ float xin[32 * 8];
+  __shared__ int rk[32];
+  nn_hidden_body<true>(params, B, ndim, log_mask, M, S, H, yout, act, xin, rk);
 }
 
 // the hidden stacks of several arms in one launch (grid.y = arm)
@@ -793,8 +996,8 @@ __global__ void __launch_bounds__(512, 2)
   if (live) Bn = min(Bn, live[0]);
   if ((int)blockIdx.x * 32 >= Bn) return;
   const int a = blockIdx.y;
-  nn_hidden_body(params, Bn, ndim, G.log_mask[a], G.M[a], G.S[a], G.H[a],
-                 G.yout[a], act, xin);
+  nn_hidden_body<false>(params, Bn, ndim, G.log_mask[a], G.M[a], G.S[a], G.H[a],
+                        G.yout[a], act, xin);
 }
 
 extern "C" int rvs_template_nn(const double *params, int B, int ndim,
@@ -878,6 +1081,60 @@ extern "C" int rvs_template_nn(const double *params, int B, int ndim,
     cur = nxt;
     nxt = t;
   }
+  return 0;
+}
+
+// rvs_template_nn with its tangent rows: include/rvsgpu.h.  Two launches: the
+// hidden stack in forward mode (nn_hidden_grad_kernel), then the last layer with
+// the float64 epilogue of all 1 + ndim rows of a job (nn_linear_grad_kernel) --
+// 128-row tiles from NN_BIG_MIN tiles up, like the value path, else 32-row tiles.
+extern "C" int rvs_template_nn_grad(const double *params, int B, int ndim,
+                                    uint32_t log_mask, const double *M,
+                                    const double *S, int nlayer,
+                                    const float *const *W, const float *const *b,
+                                    const int32_t *dims, float *act0, float *act1,
+                                    double *templ, void *stream) {
+  if (B < 1 || ndim < 1 || ndim > 6 || nlayer < 3 || nlayer - 1 > NH_MAXL ||
+      !params || !M || !S || !W || !b || !dims || !act0 || !act1 || !templ ||
+      dims[0] != ndim || dims[nlayer] < 1)
+    return RVS_E_ARG;
+  for (int l = 0; l < nlayer - 1; l++)
+    if (dims[l + 1] < 1 || dims[l + 1] > 256 || (l > 0 && (dims[l] & 31)))
+      return RVS_E_ARG;
+  for (int l = 0; l < nlayer; l++)
+    if (!W[l] || !b[l]) return RVS_E_ARG;
+  const int R = 1 + ndim;
+  if ((int64_t)B * R > 0x7fffffff / 8) return RVS_E_ARG;
+  hipStream_t st = rvs_stream(stream);
+  NNHidden H;
+  H.nl = nlayer - 1;
+  for (int l = 0; l < H.nl; l++) {
+    H.W[l] = W[l];
+    H.b[l] = b[l];
+  }
+  for (int l = 0; l <= H.nl; l++) H.dims[l] = dims[l];
+  const int jt32 = 32 / R, jt128 = NN_BM / R;   // jobs of a tile
+  hipLaunchKernelGGL(nn_hidden_grad_kernel, dim3((B + jt32 - 1) / jt32), dim3(512), 0,
+                     st, params, B, ndim, log_mask, M, S, H, act1);
+  RVS_LAUNCH_CHECK();
+  const int K = dims[nlayer - 1], N = dims[nlayer];
+  const int64_t ntc = (N + NN_BN - 1) / NN_BN;
+  const bool big = ntc * ((B + jt128 - 1) / jt128) >= NN_BIG_MIN;
+  const int64_t ntile = ntc * (big ? (B + jt128 - 1) / jt128 : (B + jt32 - 1) / jt32);
+  const int64_t nres = 256ll * (big ? NN_MINB_BIG : 4);
+  const dim3 grid((unsigned)(ntile < nres ? ntile : nres));
+  NNGradIn G;
+  G.params = params, G.M = M, G.S = S, G.ndim = ndim, G.log_mask = log_mask;
+  const bool kv = (K & 3) == 0;
+#define NN_LAUNCH_G(BG, KV)                                                     \
+  hipLaunchKernelGGL((nn_linear_grad_kernel<BG, KV>), grid, dim3(256), 0, st,    \
+                     act1, W[nlayer - 1], b[nlayer - 1], B * R, K, N, G, templ)
+  if (big && kv) NN_LAUNCH_G(true, true);
+  else if (big) NN_LAUNCH_G(true, false);
+  else if (kv) NN_LAUNCH_G(false, true);
+  else NN_LAUNCH_G(false, false);
+#undef NN_LAUNCH_G
+  RVS_LAUNCH_CHECK();
   return 0;
 }
 

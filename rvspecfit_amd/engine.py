@@ -956,8 +956,12 @@ def chisq_point(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
 
 
 def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
-                     vsini_grad=False):
-    """ValueError naming what rvs_chisq_point_grad does not cover"""
+                     vsini_grad=False, nn_gradient=False):
+    """ValueError naming what rvs_chisq_point_grad does not cover.  nn_gradient
+    (config['nn_gradient'] of the callers): MLP libraries are admitted -- their
+    tangent rows (rvs_template_nn_grad) are float32 arithmetic, which a caller has to
+    ask for; without it they are refused like any other kind without tangents."""
+    kinds = ('regulargrid', 'triangulation') + (('nn', ) if nn_gradient else ())
     if npoly > POINT_MAXP:
         raise ValueError('the analytic gradient takes npoly <= %d, not %d'
                          % (POINT_MAXP, npoly))
@@ -971,7 +975,7 @@ def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
         if arm.G > 1:
             raise ValueError('the analytic gradient does not take a grid set: arm '
                              '%s has %d wavelength grids' % (arm.name, arm.G))
-        if libs[arm.name].kind not in ('regulargrid', 'triangulation'):
+        if libs[arm.name].kind not in kinds:
             raise ValueError('the analytic gradient needs regular-grid (polylinear) '
                              'or Delaunay libraries, %s is a %s library'
                              % (arm.name, libs[arm.name].kind))
@@ -983,7 +987,8 @@ def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
 
 def chisq_point_grad(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
                      job_spec=None, job_templ=None, espec_sys=0.0,
-                     outside_penalty=True, resols=None, fast_interp=False):
+                     outside_penalty=True, resols=None, fast_interp=False,
+                     nn_gradient=False):
     """chisq_point with the gradient (rvs_chisq_point_grad): coefs[ia] are the
     [Tn, 1 + ntan, ntp, 4] records of build_templates(..., tangents=True), ntan =
     ndim, or ndim + 1 with vsini_tangent=True (the vsini row last).
@@ -993,15 +998,16 @@ def chisq_point_grad(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
     not differentiated.  What the kernel does not cover is refused, never
     finite-differenced: npoly > 16, several wavelength grids per arm, a
     resolution matrix, fast_interp, libraries that are neither regular grids nor
-    Delaunay triangulations (MLP libraries)."""
+    Delaunay triangulations (MLP libraries, unless nn_gradient: check_grad_scope)."""
     return _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
                              job_templ, espec_sys, outside_penalty, resols,
-                             fast_interp, False)
+                             fast_interp, False, nn_gradient)
 
 
 def chisq_point_fisher(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
                        job_spec=None, job_templ=None, espec_sys=0.0,
-                       outside_penalty=True, resols=None, fast_interp=False):
+                       outside_penalty=True, resols=None, fast_interp=False,
+                       nn_gradient=False):
     """chisq_point_grad with the Fisher matrix of the fit (rvs_chisq_point_fisher): the
     arguments and the scope of chisq_point_grad.  Returns chisq [J], grad [J, 1 + ntan]
     (the bits of chisq_point_grad), fisher [J, 1 + ntan, 1 + ntan] over (vel,
@@ -1011,16 +1017,17 @@ def chisq_point_fisher(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
     rounding; the penalties and log det A are not part of it."""
     return _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
                              job_templ, espec_sys, outside_penalty, resols,
-                             fast_interp, True)
+                             fast_interp, True, nn_gradient)
 
 
 def _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
                       job_templ, espec_sys, outside_penalty, resols, fast_interp,
-                      want_fisher):
+                      want_fisher, nn_gradient=False):
     import ctypes
     ntan = coefs[0].shape[1] - 1
     check_grad_scope(batch, libs, npoly, resols, fast_interp,
-                     vsini_grad=ntan > libs[batch.arms[0].name].ndim)
+                     vsini_grad=ntan > libs[batch.arms[0].name].ndim,
+                     nn_gradient=nn_gradient)
     narm = len(batch.arms)
     L = _lib.lib()
     dev = batch.device

@@ -405,14 +405,22 @@ class TemplateLibrary:
         (rvs_template_polylinear_grad; zero rows where the evaluator answers with
         the nearest grid point) and Delaunay libraries (rvs_template_tri_grad /
         rvs_template_tri_buckets_grad; every row NaN where no simplex holds the
-        point); details=True adds what eval_batch adds for the library's kind."""
-        if self.kind not in ('regulargrid', 'triangulation'):
-            raise ValueError('template tangents need a regular-grid (polylinear) or '
-                             'a Delaunay library, %s is a %s library'
+        point); details=True adds what eval_batch adds for the library's kind.
+        MLP libraries (rvs_template_nn_grad: forward mode through the network, the
+        tangent rows in float32 arithmetic -- exact to float32 rounding; every row
+        NaN where a mapped parameter is not finite; outside as eval_batch gives it,
+        not differentiated; no details)."""
+        if self.kind not in ('regulargrid', 'triangulation', 'nn'):
+            raise ValueError('template tangents need a regular-grid (polylinear), '
+                             'a Delaunay or an MLP library, %s is a %s library'
                              % (self.name, self.kind))
         L = _lib.lib()
         J = params.shape[0]
         params = params.to(torch.float64).contiguous()
+        if self.kind == 'nn':
+            if details:
+                raise ValueError('eval_batch_grad: an MLP library has no details')
+            return self._eval_nn_grad(params)
         templ = torch.empty((J, 1 + self.ndim, self.ntp), dtype=torch.float64,
                             device=self.device)
         outside = torch.empty(J, dtype=torch.float64, device=self.device)
@@ -532,6 +540,49 @@ class TemplateLibrary:
         _lib.check(rc, 'rvs_template_nn')
         outside.copy_(self._nn_outside(params, mapped))
         return templ, outside
+
+    def check_nn_grad_scope(self):
+        """ValueError naming what rvs_template_nn_grad does not take of this MLP
+        (the entry point's own check answers RVS_E_ARG)"""
+        d = [int(_) for _ in self.nn_dims]
+        nl = len(d) - 1
+        why = None
+        if self.ndim > 6:
+            why = 'ndim = %d > 6' % self.ndim
+        elif nl < 3 or nl - 1 > 6:
+            why = '%d layers (3 to 7)' % nl
+        elif max(d[1:nl]) > 256:
+            why = 'a hidden width of %d > 256' % max(d[1:nl])
+        elif any(w % 32 for w in d[1:nl - 1]):
+            why = 'hidden widths %s: every one but the last a multiple of 32' \
+                % (d[1:nl], )
+        if why is not None:
+            raise ValueError('the tangent rows of an MLP library (rvs_template_nn_grad'
+                             ') take the networks of the fused hidden stack; %s has %s'
+                             % (self.name, why))
+
+    def _eval_nn_grad(self, params):
+        import ctypes
+        self.check_nn_grad_scope()
+        L = _lib.lib()
+        J, R = params.shape[0], 1 + self.ndim
+        nl = len(self.nn_W)
+        templ = torch.empty((J, R, self.ntp), dtype=torch.float64, device=self.device)
+        # (act1: the rows of the last hidden layer; act0 is not used by the entry point)
+        a1 = torch.empty((J * R, self.nn_width()), dtype=torch.float32,
+                         device=self.device)
+        a0 = a1[:1]
+        Wp = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in self.nn_W])
+        bp = (ctypes.c_void_p * nl)(*[b.data_ptr() for b in self.nn_b])
+        from . import engine
+        with engine._ktime('template_nn_grad', J):
+            rc = L.rvs_template_nn_grad(
+                _lib.ptr(params), J, self.ndim, self.log_mask, _lib.ptr(self.nn_M),
+                _lib.ptr(self.nn_S), nl, ctypes.cast(Wp, ctypes.c_void_p),
+                ctypes.cast(bp, ctypes.c_void_p), _lib.ptr(self.nn_dims),
+                _lib.ptr(a0), _lib.ptr(a1), _lib.ptr(templ), _lib.stream())
+        _lib.check(rc, 'rvs_template_nn_grad')
+        return templ, self._nn_outside(params)
 
     def hull_device(self):
         """(xeqs, yeqs) facet equations of the two convex hulls on the device,

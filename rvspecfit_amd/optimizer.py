@@ -78,6 +78,8 @@ class ProcessObjective:
         self.min_vel, self.max_vel = float(config['min_vel']), float(
             config['max_vel'])
         self.max_vsini = float(config['max_vsini'])
+        # (MLP libraries in the gradient chain are opt-in: engine.check_grad_scope)
+        self.nn_gradient = bool(config.get('nn_gradient'))
         cap = S
         self.cap = cap
         self.job_spec = torch.zeros(cap, **i32)
@@ -353,7 +355,8 @@ class GradChain:
         fit = pobj.vsini_col >= 0
         # (refused before anything is built; nothing falls back to differences)
         engine.check_grad_scope(batch, libs, pobj.npoly, pobj.resols, False,
-                                vsini_grad=fit)
+                                vsini_grad=fit,
+                                nn_gradient=getattr(pobj, 'nn_gradient', False))
         self.pobj = pobj
         dev = pobj.dev
         narm = len(batch.arms)
@@ -389,12 +392,43 @@ class GradChain:
             a = self.arms[ia]
             for k, t in b.items():
                 setattr(a, k, None if t is None else t.data_ptr())
-            a.dats, a.knots = lib.dats.data_ptr(), lib.knots.data_ptr()
+            a.knots = lib.knots.data_ptr()
+            if lib.kind != 'nn':
+                a.dats = lib.dats.data_ptr()
             a.factors = None if lib.spline_factors is None else \
                 lib.spline_factors.data_ptr()
             a.spline_form, a.lnstep = lib.spline_form, lib.lnstep
-            a.ntp, a.exp_flag, a.log_mask = lib.ntp, lib.exp_flag, lib.log_mask
-            if lib.kind == 'triangulation':
+            a.ntp, a.log_mask = lib.ntp, lib.log_mask
+            a.exp_flag = getattr(lib, 'exp_flag', 1)
+            if lib.kind == 'nn':
+                # tri == 2: dats is a HOST rvs_nm_nn_arm; its activation buffer
+                # (act1: cap (1 + ndim) float32 rows of the widest layer; act0 is
+                # not used) is this object's, outside rvs_grad_chain_work_size
+                lib.check_nn_grad_scope()
+                n = _lib.NmNNArm()
+                nl = len(lib.nn_W)
+                Wp = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in lib.nn_W])
+                bp = (ctypes.c_void_p * nl)(*[x.data_ptr() for x in lib.nn_b])
+                b['a1'] = torch.empty((cap * R, lib.nn_width()),
+                                      dtype=torch.float32, device=dev)
+                b['a0'] = b['a1'][:1]
+                n.M, n.S = lib.nn_M.data_ptr(), lib.nn_S.data_ptr()
+                n.W = ctypes.cast(Wp, ctypes.c_void_p)
+                n.b = ctypes.cast(bp, ctypes.c_void_p)
+                n.dims = lib.nn_dims.ctypes.data
+                n.act0, n.act1 = b['a0'].data_ptr(), b['a1'].data_ptr()
+                n.templ = n.outside = None
+                hull = lib.hull_device()
+                if hull is None:
+                    n.xeqs = n.yeqs = None
+                    n.nfx = n.nfy = 0
+                else:
+                    n.xeqs, n.yeqs = hull[0].data_ptr(), hull[1].data_ptr()
+                    n.nfx, n.nfy = hull[0].shape[0], hull[1].shape[0]
+                n.nlayer, n.log_mask = nl, lib.log_mask
+                a.tri, a.dats = 2, ctypes.addressof(n)
+                self._keep += [n, Wp, bp, hull]
+            elif lib.kind == 'triangulation':
                 from . import library
                 a.tri, a.nsimplex = 1, lib.tri_nsimplex
                 a.transform = lib.tri_transform.data_ptr()
@@ -492,7 +526,8 @@ class GradChain:
             chi, grad, status = spec_fit._chisq_grad(
                 p.batch, p.libs, p.job_spec[:n], p.vel[:n], p.params[:n],
                 None if p.vsini is None else p.vsini[:n], p.npoly, p.rbf, 0.0, True,
-                p.resols, False, p.vsini_col >= 0)
+                p.resols, False, p.vsini_col >= 0,
+                nn_gradient=getattr(p, 'nn_gradient', False))
             rc = L.rvs_proc_finish_grad(
                 n, p.n, p.ndim, self.ntan, None, 0, _p(chi), _p(grad.contiguous()),
                 _p(X_t[a:]), _p(p.params), _p(p.extra), _p(p.bad), _p(p.job_spec),

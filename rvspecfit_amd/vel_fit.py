@@ -988,7 +988,8 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
                                 options.get('npoly') or 5,
                                 spec_fit._resols(batch, resolParams),
                                 bool(options.get('fast_interp')),
-                                vsini_grad=fitVsini)
+                                vsini_grad=fitVsini,
+                                nn_gradient=bool(config.get('nn_gradient')))
         # (and the batch must fit the chain's chunks: known here, not after the
         # simplex stage)
         _libs = spec_inter.get_libs(batch.names, config)
@@ -1007,7 +1008,8 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
                                     options.get('npoly') or 5,
                                     spec_fit._resols(batch, resolParams),
                                     bool(options.get('fast_interp')),
-                                    vsini_grad=fitVsini)
+                                    vsini_grad=fitVsini,
+                                    nn_gradient=bool(config.get('nn_gradient')))
         except ValueError as e:
             raise ValueError("config['fisher_uncertainties']: %s" % e) from None
 

@@ -113,7 +113,10 @@ extern "C" {
  *      rvs_template_nn_grad, the MLP evaluator with its tangent rows, with
  *      rvs_grad_arm.tri == 2 -- until now one of the non-zero values that meant
  *      Delaunay; the tree's callers write 1 for that -- naming an MLP arm of the
- *      gradient chain) */
+ *      gradient chain; and the Levenberg-Marquardt polish: rvs_proc_finish_fisher,
+ *      rvs_fisher_chain_work_size, rvs_lm_begin / _pending / _feed / _result / _end,
+ *      rvs_lm_run_bytes and rvs_lm_run with the new structs rvs_fisher_chain and
+ *      rvs_lm_state -- rvs_grad_chain and every other struct keep their layout) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -1296,6 +1299,97 @@ int64_t rvs_grad_chain_work_size(int cap, int narm, int ntan, const int32_t *ntp
 int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective *o,
                       const rvs_grad_chain *g, int sync_every, int64_t *stats,
                       void *stream);
+
+/* ------------------------------------------------------------------------
+ * The second minimiser as Levenberg-Marquardt on the Fisher matrix
+ * (config['second_minimizer_lm']): Nielsen's damping with Marquardt's diagonal scaling
+ * on (value, gradient, Gauss-Newton Hessian) rows, for S spectra.
+ *
+ * rvs_proc_finish_fisher is rvs_proc_finish_grad (its arguments, checks, value, gradient
+ * and status handling: the same statements, the same bits) with the chain's
+ * fisher [J, K, K], K = 1 + ntan, ordered (vel, library parameters, vsini last), and
+ * forms F [J, 1 + n + n (n + 1) / 2] = (f, grad f over X's columns, H: the lower
+ * triangle row-major over X's columns), H the Gauss-Newton Hessian of chisq_func in the
+ * optimiser's coordinates: H_ab = 2 fisher[row of a, row of b] (the matrix is in the
+ * 0.5 chi^2 convention); fixed parameters have no row or column; + 2 isig^2 on the
+ * diagonal of a parameter with a prior; the vsini row and column are the matrix's where
+ * 0 < x < max_vsini, else 0, with + 2 on its diagonal where x is outside
+ * [0, max_vsini] (the clamp penalty's second derivative).  log det A and the outside
+ * penalties add nothing.  A bad row is (1e30, zeros, zeros).  One thread per row, no
+ * float atomics.  RVS_E_ARG as rvs_proc_finish_grad, and for fisher == NULL. */
+int rvs_proc_finish_fisher(int J, int n, int ndim, int ntan, const int32_t *counts,
+                           int cidx, const double *chi, const double *grad,
+                           const double *fisher, const double *X, const double *params,
+                           const double *extra, const int32_t *bad,
+                           const int32_t *job_spec, const int32_t *job_status,
+                           const int32_t *src, int vsini_col, const double *prior_mean,
+                           const double *prior_isig, double max_vsini, double *F,
+                           int32_t *spec_status, void *stream);
+
+/* What the Fisher form of the gradient chain needs beside an rvs_grad_chain (which is
+ * unchanged; its point_work is not used by this form):
+ *   fisher_work  rvs_chisq_point_fisher_work_size(cap, narm, ntan) bytes
+ *   fisher       [cap, 1 + ntan, 1 + ntan]
+ * rvs_fisher_chain_work_size: rvs_grad_chain_work_size plus these two; 0 for arguments
+ * out of range. */
+typedef struct rvs_fisher_chain {
+  void *fisher_work;
+  double *fisher;
+} rvs_fisher_chain;
+int64_t rvs_fisher_chain_work_size(int cap, int narm, int ntan, const int32_t *ntp,
+                                   int vsini_mode);
+
+/* The machine on the host (csrc/lm_machine.h, one source with rvs_lm_run), shaped like
+ * the rvs_bfgs_*_jac family: begin -> { pending -> the caller's objective -> feed } ->
+ * result -> end.  A request is ONE row per live run; its reply is a row of
+ * rvs_proc_finish_fisher, F [rows, 1 + n + n (n + 1) / 2].
+ *   begin    x0 [S, n], n <= 8; gtol: ends where max |g_i| <= gtol (scipy BFGS's
+ *            test); xtol, tau, mu_max <= 0: 1e-10, 1e-3, 1e16; maxiter <= 0: 200 n.
+ *            NULL for bad arguments
+ *   pending  idx [cap_rows], X [cap_rows, n] out; returns the rows (0: all runs ended),
+ *            -1 for a NULL argument, -2 where cap_rows is too small
+ *   feed     nrows must be what pending returned
+ *   result   x [S, n], fun [S], grad [S, n], hess [S, n, n] (nullable: H at x), mu [S],
+ *            nit, nfev (rows), status [S] (0 converged, 1 maxiter, 2 no decrease can be
+ *            found / a bad first row), rounds (nullable); RVS_E_ARG while runs live */
+void *rvs_lm_begin(int S, int n, const double *x0, double gtol, double xtol, double tau,
+                   double mu_max, int maxiter);
+int64_t rvs_lm_pending(void *h, int64_t *idx, double *X, int64_t cap_rows);
+int rvs_lm_feed(void *h, const double *F, int64_t nrows);
+int rvs_lm_result(void *h, double *x, double *fun, double *grad, double *hess,
+                  double *mu, int32_t *nit, int32_t *nfev, int32_t *status,
+                  int64_t *rounds);
+void rvs_lm_end(void *h);
+
+/* The same runs with their rounds on the device: a round is advance (one thread per
+ * run: the scaled Cholesky factor and the two triangular solves) -> scan -> emit (the
+ * kernels of rvs_bfgs_run_grad) -> per chunk of g->cap rows the gradient chain with
+ * rvs_chisq_point_fisher and rvs_proc_finish_fisher as its last two calls; the host
+ * looks at the counters as rvs_bfgs_run does.
+ *   runs      S * rvs_lm_run_bytes() bytes of device memory (8-byte aligned)
+ *   x0 [S, n] start points (device)
+ *   x, grad [S, n], fun, mu [S], hess [S, n, n] (nullable), nit / nfev / status [S]:
+ *             results, as rvs_lm_result's
+ *   nreq, off, list [S]; X [S, n]; F [S, 1 + n + n (n + 1) / 2]; counts [32]: work
+ *             arrays (list zero-filled by the caller)
+ *   gtol, xtol, tau, mu_max, maxiter as for rvs_lm_begin
+ * `o`, `g` as for rvs_bfgs_run_grad (g->njev is not written), `fc` the Fisher buffers
+ * for g->cap rows.  n = o->n <= 8, ndim <= 6, S <= 24 g->cap.  stats as for
+ * rvs_bfgs_run. */
+typedef struct rvs_lm_state {
+  void *runs;
+  const double *x0;
+  double *x, *fun, *grad, *hess, *mu;
+  int32_t *nit, *nfev, *status;
+  int32_t *nreq, *off, *list, *counts;
+  double *X, *F;
+  double gtol, xtol, tau, mu_max;
+  int32_t S, n, maxiter, reserved_;
+} rvs_lm_state;
+int64_t rvs_lm_run_bytes(void);
+int rvs_lm_run(const rvs_lm_state *b, const rvs_nm_objective *o,
+               const rvs_grad_chain *g, const rvs_fisher_chain *fc, int sync_every,
+               int64_t *stats, void *stream);
 
 /* ------------------------------------------------------------------------
  * Template libraries from high-resolution models; replaces rvs_make_interpol's

@@ -89,6 +89,16 @@ SIGNATURES = {
                                  D, P, P, P]),
     'rvs_grad_chain_work_size': (L, [I, I, I, P, I]),
     'rvs_bfgs_run_grad': (I, [P, P, P, I, P, P]),
+    'rvs_proc_finish_fisher': (I, [I, I, I, I, P, I, P, P, P, P, P, P, P, P, P, P, I, P,
+                                   P, D, P, P, P]),
+    'rvs_fisher_chain_work_size': (L, [I, I, I, P, I]),
+    'rvs_lm_begin': (P, [I, I, P, D, D, D, D, I]),
+    'rvs_lm_pending': (L, [P, P, P, L]),
+    'rvs_lm_feed': (I, [P, P, L]),
+    'rvs_lm_result': (I, [P, P, P, P, P, P, P, P, P, P]),
+    'rvs_lm_end': (None, [P]),
+    'rvs_lm_run_bytes': (L, []),
+    'rvs_lm_run': (I, [P, P, P, P, I, P, P]),
     'rvs_objective_max_ntp': (I, [I]),
     'rvs_objective_resol_ok': (I, [I, I, I, I]),
     'rvs_objective_work_size': (L, [I, I]),
@@ -264,6 +274,21 @@ class GradChain(ctypes.Structure):
                 ('arms', 'point', 'basis_const', 'pen_scale', 'point_work', 'chi',
                  'grad', 'njev')] + [(k, ctypes.c_int32) for k in
                                      ('narm', 'ntan', 'cap', 'vsini_mode')]
+
+
+class FisherChain(ctypes.Structure):
+    """rvs_fisher_chain of include/rvsgpu.h"""
+    _fields_ = [('fisher_work', ctypes.c_void_p), ('fisher', ctypes.c_void_p)]
+
+
+class LmState(ctypes.Structure):
+    """rvs_lm_state of include/rvsgpu.h"""
+    _fields_ = [(k, ctypes.c_void_p) for k in
+                ('runs', 'x0', 'x', 'fun', 'grad', 'hess', 'mu', 'nit', 'nfev',
+                 'status', 'nreq', 'off', 'list', 'counts', 'X', 'F')] + [
+                    (k, ctypes.c_double) for k in
+                    ('gtol', 'xtol', 'tau', 'mu_max')] + [
+                    (k, ctypes.c_int32) for k in ('S', 'n', 'maxiter', 'reserved_')]
 
 
 class PointArm(ctypes.Structure):

@@ -6,9 +6,9 @@
 // bfgs_host.cpp -- live in HBM, one thread per spectrum advances its run to the next
 // request, and a round is
 //   bfgs_advance_kernel  values of the last request -> run -> rows it needs next
-//   bfgs_scan_kernel     exclusive scan of the row counts: every run's first row,
+//   rounds_scan_kernel   exclusive scan of the row counts: every run's first row,
 //                        the rows of each launch chunk, the number of live runs
-//   bfgs_emit_kernel     the requested points into one list (spectrum order)
+//   rounds_emit_kernel   the requested points into one list (spectrum order)
 //   <objective>          rvs_proc_map -> objective kernel -> rvs_proc_finish per chunk
 //                        of `cap` rows (nm.hip: the objective of rvs_nm_run)
 // with the counts on the device: the host looks (a 128-byte copy) every round while
@@ -30,8 +30,14 @@ using rvs_bfgs::Run;
 // against 64 runs per block (16: 0.085 / 0.224; tools/perf/ab_libs3.sh)
 #define BF_NT 4
 #endif
-#define BF_SCAN_NT 1024
-#define BF_NCHUNK 24    // counts[0 .. 24): rows of chunk c; [24] rows; [25] live runs
+
+namespace {
+
+__device__ inline const double *rounds_request_rows(const Run &r) { return r.rows; }
+
+}  // namespace
+
+#include "rounds_dev.h"   // the scan and the emit of a round (shared with lm_dev.hip)
 
 namespace {
 
@@ -77,53 +83,6 @@ __global__ void __launch_bounds__(BF_NT) bfgs_advance_jac_kernel(BfgsDev D, int 
   }
   rvs_bfgs::advance_jac(r);
   D.nreq[s] = r.done ? 0 : r.nrows;
-}
-
-__global__ void __launch_bounds__(BF_SCAN_NT) bfgs_scan_kernel(BfgsDev D) {
-  __shared__ int wsum[BF_SCAN_NT / 64];
-  __shared__ int carry[2];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (tid == 0) carry[0] = carry[1] = 0;
-  __syncthreads();
-  for (int s0 = 0; s0 < D.S; s0 += BF_SCAN_NT) {
-    const int s = s0 + tid;
-    const int nr = (s < D.S) ? D.nreq[s] : 0;
-    int v = nr;   // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(v, o, 64);
-      if (lane >= o) v += t;
-    }
-    if (lane == 63) wsum[w] = v;
-    const int alive = wave_sum_i(nr > 0 ? 1 : 0);
-    __syncthreads();
-    int base = carry[0];
-    for (int i = 0; i < w; i++) base += wsum[i];
-    if (s < D.S) D.off[s] = base + v - nr;
-    __syncthreads();
-    if (lane == 0 && alive) atomicAdd(&carry[1], alive);
-    if (tid == BF_SCAN_NT - 1) carry[0] = base + v;
-    __syncthreads();
-  }
-  if (tid < BF_NCHUNK) {
-    const int rest = carry[0] - tid * D.cap;
-    D.counts[tid] = rest < 0 ? 0 : (rest > D.cap ? D.cap : rest);
-  }
-  if (tid == 0) {
-    D.counts[BF_NCHUNK] = carry[0];
-    D.counts[BF_NCHUNK + 1] = carry[1];
-  }
-}
-
-__global__ void __launch_bounds__(256) bfgs_emit_kernel(BfgsDev D) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int per = D.n + 1;
-  const int s = t / per, q = t - s * per;
-  if (s >= D.S || q >= D.nreq[s]) return;
-  const int j = D.off[s] + q, n = D.n;
-  D.list[j] = s;
-  const double *src = D.runs[s].rows + q * n;
-  for (int i = 0; i < n; i++) D.X[(int64_t)j * n + i] = src[i];
 }
 
 __global__ void __launch_bounds__(BF_NT)
@@ -174,8 +133,8 @@ extern "C" int rvs_bfgs_run(const rvs_bfgs_state *b, const rvs_nm_objective *o,
   const dim3 egrid((int)((maxrows + 255) / 256));
   auto step = [&](int first) {
     hipLaunchKernelGGL(bfgs_advance_kernel, agrid, dim3(BF_NT), 0, st, D, first);
-    hipLaunchKernelGGL(bfgs_scan_kernel, dim3(1), dim3(BF_SCAN_NT), 0, st, D);
-    hipLaunchKernelGGL(bfgs_emit_kernel, egrid, dim3(256), 0, st, D);
+    hipLaunchKernelGGL(rounds_scan_kernel<BfgsDev>, dim3(1), dim3(BF_SCAN_NT), 0, st, D);
+    hipLaunchKernelGGL(rounds_emit_kernel<BfgsDev>, egrid, dim3(256), 0, st, D);
   };
   step(1);
   RVS_LAUNCH_CHECK();
@@ -244,8 +203,8 @@ extern "C" int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective
   const dim3 egrid((int)(((int64_t)S * (n + 1) + 255) / 256));
   auto step = [&](int first) {
     hipLaunchKernelGGL(bfgs_advance_jac_kernel, agrid, dim3(BF_NT), 0, st, D, first);
-    hipLaunchKernelGGL(bfgs_scan_kernel, dim3(1), dim3(BF_SCAN_NT), 0, st, D);
-    hipLaunchKernelGGL(bfgs_emit_kernel, egrid, dim3(256), 0, st, D);
+    hipLaunchKernelGGL(rounds_scan_kernel<BfgsDev>, dim3(1), dim3(BF_SCAN_NT), 0, st, D);
+    hipLaunchKernelGGL(rounds_emit_kernel<BfgsDev>, egrid, dim3(256), 0, st, D);
   };
   step(1);
   RVS_LAUNCH_CHECK();

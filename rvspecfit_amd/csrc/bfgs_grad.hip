@@ -12,6 +12,11 @@
 //   rvs_chisq_point_grad    all arms: chi [J], grad [J, 1 + ntan] = d/d(vel, parameters
 //                           in library order[, vsini])
 //   rvs_proc_finish_grad    F [J, 1 + n] = (chisq_func, its gradient in X's columns)
+// and the Fisher form of the last two calls, for the rows of a round of rvs_lm_run
+// (lm_dev.hip):
+//   rvs_chisq_point_fisher  chi, grad and fisher [J, 1 + ntan, 1 + ntan]
+//   rvs_proc_finish_fisher  F [J, 1 + n + n (n + 1) / 2] = (chisq_func, its gradient, the
+//                           lower triangle of its Gauss-Newton Hessian in X's columns)
 //
 // The chain is engine.build_templates(tangents=True, vsini_tangent=...) +
 // engine.chisq_point_grad: the same entry points with the same arguments, called from
@@ -24,29 +29,34 @@ namespace {
 struct FinP {
   int n, ndim, ntan, vsini_col;
   int src[8];
+  int tan[8];   // column of X -> its row of grad / fisher (the inverse of src)
   const double *prior_mean, *prior_isig;
   double max_vsini;
 };
 
+// one row of rvs_proc_finish_grad (FISHER = false) or rvs_proc_finish_fisher: the value
+// and the gradient are the same statements for both, the Fisher form appends the packed
+// Hessian behind them
+template <bool FISHER>
 __global__ void __launch_bounds__(256)
-    proc_finish_grad_kernel(int J, const int32_t *__restrict__ counts, int cidx, FinP P,
-                            const double *__restrict__ chi,
-                            const double *__restrict__ grad,
-                            const double *__restrict__ X,
-                            const double *__restrict__ params,
-                            const double *__restrict__ extra,
-                            const int32_t *__restrict__ bad,
-                            const int32_t *__restrict__ job_spec,
-                            const int32_t *__restrict__ job_status,
-                            double *__restrict__ F, int32_t *__restrict__ spec_status) {
+    proc_finish_kernel(int J, const int32_t *__restrict__ counts, int cidx, FinP P,
+                       const double *__restrict__ chi, const double *__restrict__ grad,
+                       const double *__restrict__ fisher, const double *__restrict__ X,
+                       const double *__restrict__ params,
+                       const double *__restrict__ extra,
+                       const int32_t *__restrict__ bad,
+                       const int32_t *__restrict__ job_spec,
+                       const int32_t *__restrict__ job_status,
+                       double *__restrict__ F, int32_t *__restrict__ spec_status) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= J) return;
   const int n = P.n, K = 1 + P.ntan;
-  double *f = F + (int64_t)j * (n + 1);
+  const int width = FISHER ? 1 + n + n * (n + 1) / 2 : n + 1;
+  double *f = F + (int64_t)j * width;
   const int isbad = bad[j];
   f[0] = isbad ? 1e30 : chi[j] + extra[j];
   if (isbad) {
-    for (int c = 0; c < n; c++) f[1 + c] = 0.0;
+    for (int c = 1; c < width; c++) f[c] = 0.0;
     return;
   }
   const double *g = grad + (int64_t)j * K;
@@ -64,13 +74,37 @@ __global__ void __launch_bounds__(256)
     }
     f[1 + c] = v;
   }
+  bool inside = true, beyond = false;
   if (P.vsini_col >= 0) {
     // VSiniMapper clamps: inside (0, max_vsini) the physical derivative, outside 0;
     // the penalty (x - clamp(x))^2 adds 2 (x - clamp(x))
     const double x = X[(int64_t)j * n + P.vsini_col];
     const double cl = fmin(fmax(x, 0.0), P.max_vsini);
-    const bool inside = (0 < x) && (x < P.max_vsini);
+    inside = (0 < x) && (x < P.max_vsini);
+    beyond = (x < 0) || (x > P.max_vsini);
     f[1 + P.vsini_col] = (inside ? g[P.ntan] : 0.0) + 2.0 * (x - cl);
+  }
+  if (FISHER) {
+    // H_ab = 2 fisher[tan a, tan b] (the matrix is in the 0.5 chi^2 convention); the
+    // vsini row and column where the mapper does not clamp, else 0; on the diagonal the
+    // second derivatives of a prior, 2 isig^2, and of the clamp penalty, 2
+    const double *fm = fisher + (int64_t)j * K * K;
+    double *h = f + 1 + n;
+    for (int a = 0; a < n; a++)
+      for (int b = 0; b <= a; b++) {
+        double v = 2.0 * fm[P.tan[a] * K + P.tan[b]];
+        if ((a == P.vsini_col || b == P.vsini_col) && !inside) v = 0.0;
+        if (a == b) {
+          const int i = P.tan[a] - 1;
+          if (a == P.vsini_col) {
+            if (beyond) v += 2.0;
+          } else if (i >= 0 && P.prior_mean) {
+            const double is = P.prior_isig[(int64_t)r * P.ndim + i];
+            if (is != 0) v += 2.0 * (is * is);
+          }
+        }
+        h[a * (a + 1) / 2 + b] = v;
+      }
   }
   const int live = counts ? counts[cidx] : J;
   if (j < live && job_status[j]) atomicOr(&spec_status[r], job_status[j]);
@@ -137,6 +171,52 @@ int chain_ok(const rvs_grad_chain *g, const rvs_nm_objective *o) {
 
 }  // namespace
 
+namespace {
+
+// the argument checks and the launch of both forms (fisher == NULL: the gradient's)
+int proc_finish(bool want_fisher, int J, int n, int ndim, int ntan,
+                const int32_t *counts, int cidx, const double *chi, const double *grad,
+                const double *fisher, const double *X, const double *params,
+                const double *extra, const int32_t *bad, const int32_t *job_spec,
+                const int32_t *job_status, const int32_t *src, int vsini_col,
+                const double *prior_mean, const double *prior_isig, double max_vsini,
+                double *F, int32_t *spec_status, void *stream) {
+  if (J < 1 || n < 1 || n > 8 || ndim < 1 || ndim > 6 || !src || !chi || !grad || !X ||
+      !params || !extra || !bad || !job_spec || !job_status || !F || !spec_status ||
+      vsini_col >= n || (prior_mean && !prior_isig) || (want_fisher && !fisher))
+    return RVS_E_ARG;
+  if (ntan != ndim + (vsini_col >= 0 ? 1 : 0)) return RVS_E_ARG;
+  FinP P;
+  P.n = n, P.ndim = ndim, P.ntan = ntan, P.vsini_col = vsini_col;
+  int ncol = 1 + (vsini_col >= 0 ? 1 : 0);
+  for (int i = 0; i < 8; i++) P.tan[i] = 0;
+  for (int i = 0; i < 8; i++) {
+    P.src[i] = (i < ndim) ? src[i] : -1;
+    if (P.src[i] >= n || P.src[i] == 0 || (P.src[i] >= 0 && P.src[i] == vsini_col))
+      return RVS_E_ARG;
+    if (P.src[i] > 0) {
+      ncol++;
+      P.tan[P.src[i]] = 1 + i;
+    }
+  }
+  if (ncol != n) return RVS_E_ARG;   // every column of X has exactly one source
+  if (vsini_col >= 0) P.tan[vsini_col] = ntan;
+  P.prior_mean = prior_mean, P.prior_isig = prior_isig;
+  P.max_vsini = max_vsini;
+  if (want_fisher)
+    hipLaunchKernelGGL(proc_finish_kernel<true>, dim3((J + 255) / 256), dim3(256), 0,
+                       rvs_stream(stream), J, counts, cidx, P, chi, grad, fisher, X,
+                       params, extra, bad, job_spec, job_status, F, spec_status);
+  else
+    hipLaunchKernelGGL(proc_finish_kernel<false>, dim3((J + 255) / 256), dim3(256), 0,
+                       rvs_stream(stream), J, counts, cidx, P, chi, grad, fisher, X,
+                       params, extra, bad, job_spec, job_status, F, spec_status);
+  RVS_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace
+
 extern "C" int rvs_proc_finish_grad(int J, int n, int ndim, int ntan,
                                     const int32_t *counts, int cidx, const double *chi,
                                     const double *grad, const double *X,
@@ -146,28 +226,24 @@ extern "C" int rvs_proc_finish_grad(int J, int n, int ndim, int ntan,
                                     int vsini_col, const double *prior_mean,
                                     const double *prior_isig, double max_vsini,
                                     double *F, int32_t *spec_status, void *stream) {
-  if (J < 1 || n < 1 || n > 8 || ndim < 1 || ndim > 6 || !src || !chi || !grad || !X ||
-      !params || !extra || !bad || !job_spec || !job_status || !F || !spec_status ||
-      vsini_col >= n || (prior_mean && !prior_isig))
-    return RVS_E_ARG;
-  if (ntan != ndim + (vsini_col >= 0 ? 1 : 0)) return RVS_E_ARG;
-  FinP P;
-  P.n = n, P.ndim = ndim, P.ntan = ntan, P.vsini_col = vsini_col;
-  int ncol = 1 + (vsini_col >= 0 ? 1 : 0);
-  for (int i = 0; i < 8; i++) {
-    P.src[i] = (i < ndim) ? src[i] : -1;
-    if (P.src[i] >= n || P.src[i] == 0 || (P.src[i] >= 0 && P.src[i] == vsini_col))
-      return RVS_E_ARG;
-    if (P.src[i] > 0) ncol++;
-  }
-  if (ncol != n) return RVS_E_ARG;   // every column of X has exactly one source
-  P.prior_mean = prior_mean, P.prior_isig = prior_isig;
-  P.max_vsini = max_vsini;
-  hipLaunchKernelGGL(proc_finish_grad_kernel, dim3((J + 255) / 256), dim3(256), 0,
-                     rvs_stream(stream), J, counts, cidx, P, chi, grad, X, params, extra,
-                     bad, job_spec, job_status, F, spec_status);
-  RVS_LAUNCH_CHECK();
-  return 0;
+  return proc_finish(false, J, n, ndim, ntan, counts, cidx, chi, grad, nullptr, X,
+                     params, extra, bad, job_spec, job_status, src, vsini_col,
+                     prior_mean, prior_isig, max_vsini, F, spec_status, stream);
+}
+
+extern "C" int rvs_proc_finish_fisher(int J, int n, int ndim, int ntan,
+                                      const int32_t *counts, int cidx,
+                                      const double *chi, const double *grad,
+                                      const double *fisher, const double *X,
+                                      const double *params, const double *extra,
+                                      const int32_t *bad, const int32_t *job_spec,
+                                      const int32_t *job_status, const int32_t *src,
+                                      int vsini_col, const double *prior_mean,
+                                      const double *prior_isig, double max_vsini,
+                                      double *F, int32_t *spec_status, void *stream) {
+  return proc_finish(true, J, n, ndim, ntan, counts, cidx, chi, grad, fisher, X, params,
+                     extra, bad, job_spec, job_status, src, vsini_col, prior_mean,
+                     prior_isig, max_vsini, F, spec_status, stream);
 }
 
 extern "C" int64_t rvs_grad_chain_work_size(int cap, int narm, int ntan,
@@ -189,6 +265,15 @@ extern "C" int64_t rvs_grad_chain_work_size(int cap, int narm, int ntan,
   return b;
 }
 
+extern "C" int64_t rvs_fisher_chain_work_size(int cap, int narm, int ntan,
+                                              const int32_t *ntp, int vsini_mode) {
+  const int64_t b = rvs_grad_chain_work_size(cap, narm, ntan, ntp, vsini_mode);
+  if (b <= 0) return 0;
+  const int64_t K = 1 + ntan;
+  return b + rvs_chisq_point_fisher_work_size(cap, narm, ntan) +
+         (int64_t)cap * K * K * sizeof(double);
+}
+
 int rvs_internal_grad_chain_ok(const rvs_grad_chain *g, const rvs_nm_objective *o) {
   return chain_ok(g, o);
 }
@@ -196,8 +281,9 @@ int rvs_internal_grad_chain_ok(const rvs_grad_chain *g, const rvs_nm_objective *
 int rvs_internal_grad_chain_eval(const rvs_nm_objective *o, const rvs_grad_chain *g,
                                  const int32_t *list, const double *X, int J,
                                  const int32_t *counts, int cidx, double *F,
-                                 hipStream_t st) {
-  if (J < 1 || J > g->cap) return RVS_E_ARG;
+                                 hipStream_t st, const rvs_fisher_chain *fc) {
+  if (J < 1 || J > g->cap || (fc && (!fc->fisher_work || !fc->fisher)))
+    return RVS_E_ARG;
   const int ndim = o->ndim, ntan = g->ntan;
   int rc = rvs_proc_map(J, o->n, ndim, X, list, o->src, o->vsini_col, o->fixed,
                         o->vsini_fixed, o->safe, o->prior_mean, o->prior_isig,
@@ -257,6 +343,17 @@ int rvs_internal_grad_chain_eval(const rvs_nm_objective *o, const rvs_grad_chain
   }
   if (hipMemsetAsync(o->jstatus, 0, sizeof(int32_t) * J, st) != hipSuccess)
     return RVS_E_LAUNCH;
+  if (fc) {   // the Fisher form of the last two calls
+    rc = rvs_chisq_point_fisher(g->point, g->narm, o->npoly, ntan, o->job_spec, nullptr,
+                                J, o->vel, o->badchi, g->basis_const, fc->fisher_work,
+                                g->chi, g->grad, fc->fisher, o->jstatus, st);
+    if (rc) return rc;
+    return rvs_proc_finish_fisher(J, o->n, ndim, ntan, counts, cidx, g->chi, g->grad,
+                                  fc->fisher, X, o->params, o->extra, o->bad,
+                                  o->job_spec, o->jstatus, o->src, o->vsini_col,
+                                  o->prior_mean, o->prior_isig, o->max_vsini, F,
+                                  o->status, st);
+  }
   rc = rvs_chisq_point_grad(g->point, g->narm, o->npoly, ntan, o->job_spec, nullptr, J,
                             o->vel, o->badchi, g->basis_const, g->point_work, g->chi,
                             g->grad, o->jstatus, st);

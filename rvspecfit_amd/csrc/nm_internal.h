@@ -16,9 +16,12 @@ __attribute__((visibility("hidden"))) int rvs_internal_nm_eval(
     const int32_t *counts, int cidx, double *F, hipStream_t st);
 
 // bfgs_grad.hip: (f, grad f) of the rows (list, X) through the gradient chain `g`:
-// F [J, 1 + n], J <= g->cap; _ok: the descriptors fit each other (checked once per run)
+// F [J, 1 + n], J <= g->cap; _ok: the descriptors fit each other (checked once per run).
+// fc != NULL: the Fisher form of the last two calls (rvs_chisq_point_fisher,
+// rvs_proc_finish_fisher), F [J, 1 + n + n (n + 1) / 2]
 __attribute__((visibility("hidden"))) int rvs_internal_grad_chain_ok(
     const rvs_grad_chain *g, const rvs_nm_objective *o);
 __attribute__((visibility("hidden"))) int rvs_internal_grad_chain_eval(
     const rvs_nm_objective *o, const rvs_grad_chain *g, const int32_t *list,
-    const double *X, int J, const int32_t *counts, int cidx, double *F, hipStream_t st);
+    const double *X, int J, const int32_t *counts, int cidx, double *F, hipStream_t st,
+    const rvs_fisher_chain *fc = nullptr);

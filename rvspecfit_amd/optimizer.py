@@ -347,9 +347,13 @@ GRAD_CHAIN_BUDGET = 4 << 30
 class GradChain:
     """chisq_func_grad for the rows of a round: the rvs_grad_chain of
     rvs_bfgs_run_grad around a ProcessObjective (whose mapping tables and row
-    buffers it uses), and the same evaluation driven from Python (`rows`)."""
+    buffers it uses), and the same evaluation driven from Python (`rows`).
+    fisher=True: the Fisher form of the chain (rvs_lm_run: rvs_chisq_point_fisher and
+    rvs_proc_finish_fisher as its last two calls) -- `rows` then returns
+    [rows, 1 + n + n (n + 1) / 2] = (f, gradient, lower triangle of the Gauss-Newton
+    Hessian), and the Fisher buffers are counted inside the same budget."""
 
-    def __init__(self, pobj, cap=None, budget=None):
+    def __init__(self, pobj, cap=None, budget=None, fisher=False):
         L = _lib.lib()
         batch, libs = pobj.batch, pobj.libs
         fit = pobj.vsini_col >= 0
@@ -358,15 +362,18 @@ class GradChain:
                                 vsini_grad=fit,
                                 nn_gradient=getattr(pobj, 'nn_gradient', False))
         self.pobj = pobj
+        self.fisher = bool(fisher)
         dev = pobj.dev
         narm = len(batch.arms)
         self.ntan = pobj.ndim + (1 if fit else 0)
         self.vsini_mode = 2 if fit else (1 if pobj.has_vsini else 0)
         ntps = [libs[a.name].ntp for a in batch.arms]
         cap = self.choose_cap(pobj.S, ntps, self.ntan, self.vsini_mode, cap=cap,
-                              budget=budget, row_capacity=pobj.cap)
+                              budget=budget, row_capacity=pobj.cap, fisher=self.fisher)
         ntp = (ctypes.c_int32 * narm)(*ntps)
-        size = lambda c: L.rvs_grad_chain_work_size(  # noqa: E731
+        work_size = L.rvs_fisher_chain_work_size if self.fisher else \
+            L.rvs_grad_chain_work_size
+        size = lambda c: work_size(  # noqa: E731
             c, narm, self.ntan, ntp, self.vsini_mode)
         self.cap = cap
         self.nbytes = int(size(cap))
@@ -456,34 +463,43 @@ class GradChain:
         self.chi = torch.empty(cap, **f64)
         self.grad = torch.empty((cap, K), **f64)
         self.njev = torch.zeros(pobj.S, **i32)
+        if self.fisher:
+            nb = L.rvs_chisq_point_fisher_work_size(cap, narm, self.ntan)
+            self.fisher_work = torch.empty((nb + 7) // 8, **f64)
+            self.fisher_buf = torch.empty((cap, K, K), **f64)
 
     MAX_CHUNKS = 24     # the chunk counters of the scan kernel (bfgs_dev.hip)
 
     @staticmethod
     def choose_cap(S, ntps, ntan, vsini_mode, cap=None, budget=None,
-                   row_capacity=None):
+                   row_capacity=None, fisher=False):
         """rows per chunk for S runs on arms of ntps template pixels: `cap`, or the
         most whose buffers (rvs_grad_chain_work_size) stay inside `budget`
         (GRAD_CHAIN_BUDGET).  ValueError where MAX_CHUNKS chunks of that many rows
         do not hold one row per run: at the default budget, three arms of 8000
-        template pixels and ntan = 6 that is beyond ~12 000 spectra per call."""
+        template pixels and ntan = 6 that is beyond ~12 000 spectra per call.
+        fisher: the chain of second_minimizer_lm, whose Fisher scratch and matrices
+        (rvs_fisher_chain_work_size) count inside the same budget."""
         L = _lib.lib()
+        key = 'second_minimizer_lm' if fisher else 'second_minimizer_jac'
+        work_size = L.rvs_fisher_chain_work_size if fisher else \
+            L.rvs_grad_chain_work_size
         narm = len(ntps)
         ntp = (ctypes.c_int32 * narm)(*ntps)
         if cap is None:
             budget = GRAD_CHAIN_BUDGET if budget is None else budget
-            one = L.rvs_grad_chain_work_size(1, narm, ntan, ntp, vsini_mode)
+            one = work_size(1, narm, ntan, ntp, vsini_mode)
             if one <= 0:
-                raise ValueError('GradChain: %d arms / %d tangents are outside '
-                                 'rvs_grad_chain_work_size' % (narm, ntan))
+                raise ValueError('%s: GradChain: %d arms / %d tangents are outside '
+                                 'rvs_grad_chain_work_size' % (key, narm, ntan))
             cap = max(1, min(S, int(budget // one)))
         cap = int(cap if row_capacity is None else min(cap, row_capacity))
         if cap < 1 or (S + cap - 1) // cap > GradChain.MAX_CHUNKS:
             raise ValueError(
-                'second_minimizer_jac: the gradient chain holds %d rows per chunk '
+                '%s: the gradient chain holds %d rows per chunk '
                 '(optimizer.GRAD_CHAIN_BUDGET = %d bytes) and a round at most %d '
                 'chunks: %d spectra do not fit one call; pass them in smaller batches'
-                % (cap, GRAD_CHAIN_BUDGET if budget is None else budget,
+                % (key, cap, GRAD_CHAIN_BUDGET if budget is None else budget,
                    GradChain.MAX_CHUNKS, S))
         return cap
 
@@ -500,19 +516,29 @@ class GradChain:
         g.cap, g.vsini_mode = self.cap, self.vsini_mode
         return g
 
+    def fisher_desc(self):
+        """rvs_fisher_chain: the Fisher buffers of a chain built with fisher=True"""
+        fc = _lib.FisherChain()
+        fc.fisher_work = self.fisher_work.data_ptr()
+        fc.fisher = self.fisher_buf.data_ptr()
+        return fc
+
     def rows(self, idx, X):
         """(chisq_func, its gradient) of the rows X [J, n] of spectra idx [J]: numpy
         in, numpy [J, 1 + n] out -- rvs_proc_map, spec_fit.chisq_grad_jobs' launches
         and rvs_proc_finish_grad, driven from Python.  The objective of
         bfgs.minimize_lockstep_native(jac=True), and what rvs_bfgs_run_grad's rounds
-        are held against."""
+        are held against.  With fisher=True: [J, 1 + n + n (n + 1) / 2] through
+        rvs_chisq_point_fisher and rvs_proc_finish_fisher, the objective of
+        lm.minimize_lockstep_native and what rvs_lm_run's rounds are held against."""
         from . import spec_fit
         p, L = self.pobj, _lib.lib()
         dev = p.dev
         idx_t = torch.as_tensor(idx, dtype=torch.int32).to(dev).contiguous()
         X_t = torch.as_tensor(X, dtype=torch.float64).to(dev).contiguous()
         J = X_t.shape[0]
-        F = torch.empty((J, p.n + 1), dtype=torch.float64, device=dev)
+        width = p.n + 1 + (p.n * (p.n + 1) // 2 if self.fisher else 0)
+        F = torch.empty((J, width), dtype=torch.float64, device=dev)
         st = _lib.stream()
         for a in range(0, J, p.cap):
             n = min(J, a + p.cap) - a
@@ -523,17 +549,22 @@ class GradChain:
                                 _p(p.vel), _p(p.vsini), _p(p.params), _p(p.extra),
                                 _p(p.bad), st)
             _lib.check(rc, 'rvs_proc_map')
-            chi, grad, status = spec_fit._chisq_grad(
+            res = spec_fit._chisq_grad(
                 p.batch, p.libs, p.job_spec[:n], p.vel[:n], p.params[:n],
                 None if p.vsini is None else p.vsini[:n], p.npoly, p.rbf, 0.0, True,
-                p.resols, False, p.vsini_col >= 0,
+                p.resols, False, p.vsini_col >= 0, self.fisher,
                 nn_gradient=getattr(p, 'nn_gradient', False))
-            rc = L.rvs_proc_finish_grad(
-                n, p.n, p.ndim, self.ntan, None, 0, _p(chi), _p(grad.contiguous()),
-                _p(X_t[a:]), _p(p.params), _p(p.extra), _p(p.bad), _p(p.job_spec),
-                _p(status), p.src, p.vsini_col, _p(p.prior_mean), _p(p.prior_isig),
-                p.max_vsini, _p(F[a:]), _p(p.status), st)
-            _lib.check(rc, 'rvs_proc_finish_grad')
+            chi, grad, status = res[0], res[1], res[-1]
+            tail = (_p(X_t[a:]), _p(p.params), _p(p.extra), _p(p.bad), _p(p.job_spec),
+                    _p(status), p.src, p.vsini_col, _p(p.prior_mean), _p(p.prior_isig),
+                    p.max_vsini, _p(F[a:]), _p(p.status), st)
+            head = (n, p.n, p.ndim, self.ntan, None, 0, _p(chi), _p(grad.contiguous()))
+            if self.fisher:
+                rc = L.rvs_proc_finish_fisher(*head, _p(res[2].contiguous()), *tail)
+                _lib.check(rc, 'rvs_proc_finish_fisher')
+            else:
+                rc = L.rvs_proc_finish_grad(*head, *tail)
+                _lib.check(rc, 'rvs_proc_finish_grad')
             p.calls += 1
             p.jobs += n
         return F.cpu().numpy()

@@ -408,6 +408,11 @@ def chisq_func_grad(p, args):
             or (~np.isfinite(np.asarray(pdict['params'], dtype=float))).any()):
         return 1e30, np.zeros(len(p))
     chisq, g0 = chisq_func0_grad(pdict, args, vsini_grad=mapper.fitVsini)
+    return chisq + pdict['penalty'], _optimiser_grad(p, mapper, pdict, g0)
+
+
+def _optimiser_grad(p, mapper, pdict, g0):
+    # the gradient over (vel, *specParams[, vsini]) in the optimiser's own columns
     grad = []
     for x, name in zip(p, mapper.get_fitted_params()):
         if name == 'vel':
@@ -419,7 +424,55 @@ def chisq_func_grad(p, args):
         else:
             grad.append(g0[1 + list(mapper.specParams).index(name)])
     assert len(grad) == len(p)
-    return chisq + pdict['penalty'], np.array(grad, dtype=np.float64)
+    return np.array(grad, dtype=np.float64)
+
+
+def chisq_func_fisher(p, args):
+    """chisq_func_grad with the Gauss-Newton Hessian of chisq_func in the optimiser's
+    own vector: returns (float, ndarray [n], ndarray [n, n]), n = len(p) -- the public
+    form of a row of optimizer.GradChain(fisher=True) and what the Levenberg-Marquardt
+    polish (config['second_minimizer_lm']) steps on.  Value and gradient are
+    chisq_func_grad's.  H_ab = 2 F_ab with F the Fisher matrix of
+    spec_fit.get_chisq_fisher (which is in the 0.5 chi^2 convention) over the fitted
+    parameters; fixed parameters have no row or column; a Normal prior adds 2 / sigma^2
+    to its parameter's diagonal; the vsini row and column are the matrix's where
+    0 < x < max_vsini, else 0, and where x is outside [0, max_vsini] the clamp
+    penalty's second derivative, 2, stands on the diagonal.  log det A and the outside
+    penalty add nothing.  Where chisq_func returns 1e30: (1e30, zeros, zeros)."""
+    mapper = args['paramMapper']
+    pdict = mapper.forward(p)
+    n = len(p)
+    if (pdict['vel'] > args['max_vel'] or pdict['vel'] < args['min_vel']
+            or (~np.isfinite(np.asarray(pdict['params'], dtype=float))).any()):
+        return 1e30, np.zeros(n), np.zeros((n, n))
+    chisq, g0, F0 = spec_fit.get_chisq_fisher(
+        args['specdata'], pdict['vel'], tuple(pdict['params']), pdict['rot_params'],
+        options=args['options'], config=args['config'], outside_penalty=True,
+        resol_params=args.get('resolParams'), vsini_grad=mapper.fitVsini)
+    g0 = np.array(g0, dtype=np.float64)
+    priors = args.get('priors') or {}
+    specParams = list(mapper.specParams)
+    for i, k in enumerate(specParams):
+        if k in priors:
+            mu, sig = priors[k]
+            chisq += ((mu - pdict['params'][i]) / sig)**2
+            g0[1 + i] += 2.0 * (pdict['params'][i] - mu) / sig**2
+    grad = _optimiser_grad(p, mapper, pdict, g0)
+    fitted = mapper.get_fitted_params()
+    tan = [0 if k == 'vel' else (F0.shape[0] - 1 if k == 'vsini'
+                                 else 1 + specParams.index(k)) for k in fitted]
+    H = 2.0 * np.asarray(F0, dtype=np.float64)[np.ix_(tan, tan)]
+    for a, (x, k) in enumerate(zip(p, fitted)):
+        if k == 'vsini':
+            max_vsini = mapper.vsiniMapper.max_vsini
+            if not 0 < x < max_vsini:
+                H[a, :] = 0.0
+                H[:, a] = 0.0
+            if x < 0 or x > max_vsini:
+                H[a, a] += 2.0
+        elif k in priors:
+            H[a, a] += 2.0 / priors[k][1]**2
+    return chisq + pdict['penalty'], grad, H
 
 
 def hess_func(p, pdict, args):
@@ -983,6 +1036,28 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
     # anything is built: nothing falls back to differences
     bfgs_jac = bool(config.get('second_minimizer')
                     and config.get('second_minimizer_jac'))
+    # config['second_minimizer_lm']: Levenberg-Marquardt on the Fisher matrix (rvs_lm_run)
+    # in the place of the BFGS polish; the scope is the gradient's, asked here as well
+    lm_polish = bool(config.get('second_minimizer')
+                     and config.get('second_minimizer_lm'))
+    if lm_polish and config.get('second_minimizer_jac'):
+        raise ValueError("config['second_minimizer_lm'] and "
+                         "config['second_minimizer_jac'] name two polishes: set one")
+    if lm_polish:
+        try:
+            engine.check_grad_scope(batch, spec_inter.get_libs(batch.names, config),
+                                    options.get('npoly') or 5,
+                                    spec_fit._resols(batch, resolParams),
+                                    bool(options.get('fast_interp')),
+                                    vsini_grad=fitVsini,
+                                    nn_gradient=bool(config.get('nn_gradient')))
+        except ValueError as e:
+            raise ValueError("config['second_minimizer_lm']: %s" % e) from None
+        _libs = spec_inter.get_libs(batch.names, config)
+        optimizer.GradChain.choose_cap(
+            S, [_libs[a.name].ntp for a in batch.arms],
+            len(names) + (1 if fitVsini else 0),
+            2 if fitVsini else (1 if 'vsini' in pd0 else 0), fisher=True)
     if bfgs_jac:
         engine.check_grad_scope(batch, spec_inter.get_libs(batch.names, config),
                                 options.get('npoly') or 5,
@@ -1081,7 +1156,34 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
     # vel_fit.py:653-658: optional BFGS polish from the simplex optimum
     second_run = False
     bfgs_info = None
-    if config.get('second_minimizer'):
+    lm_info = None
+    if lm_polish:
+        # Levenberg-Marquardt on (value, gradient, Fisher matrix) rows: the Fisher form
+        # of the gradient chain as the objective, its rounds inside the library
+        # (RVS_BFGS_ON_DEVICE=0: the same machine on the host around the same chain
+        # driven from Python); gtol is the BFGS polish's
+        from . import lm
+        t0 = time.time()
+        jobs_before = pobj.jobs
+        slots_before = pobj.slots
+        chain = optimizer.GradChain(pobj, fisher=True)
+        if BFGS_ON_DEVICE:
+            br = lm.minimize_lockstep_device(pobj, x, chain=chain)
+            x = br['x']
+            br = {k_: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v)
+                  for k_, v in br.items()}
+        else:
+            br = lm.minimize_lockstep_native(chain.rows, x.cpu().numpy())
+            x = torch.as_tensor(br['x']).to(dev)
+        obj.status |= pobj.status
+        obj.nfev += pobj.jobs - jobs_before
+        slots += pobj.slots - slots_before
+        lm_info = dict(nit=br['nit'], nfev=br['nfev'], status=br['status'],
+                       mu=br['mu'], fun=br['fun'], rounds=br['rounds'],
+                       device=BFGS_ON_DEVICE)
+        second_run = True
+        _tick('lm', t0)
+    elif config.get('second_minimizer'):
         from . import bfgs
         t0 = time.time()
         hess_inv0 = get_hess_inv(mapper.get_fitted_params())
@@ -1226,6 +1328,8 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
     ret['second_minimizer_run'] = second_run
     if bfgs_info is not None:
         ret['bfgs'] = bfgs_info
+    if lm_info is not None:
+        ret['lm'] = lm_info
     ret['optimizer_run'] = True
     return ret
 

@@ -116,7 +116,10 @@ extern "C" {
  *      gradient chain; and the Levenberg-Marquardt polish: rvs_proc_finish_fisher,
  *      rvs_fisher_chain_work_size, rvs_lm_begin / _pending / _feed / _result / _end,
  *      rvs_lm_run_bytes and rvs_lm_run with the new structs rvs_fisher_chain and
- *      rvs_lm_state -- rvs_grad_chain and every other struct keep their layout) */
+ *      rvs_lm_state -- rvs_grad_chain and every other struct keep their layout; and
+ *      rvs_chisq_point_grad_resol / rvs_chisq_point_fisher_resol with their work
+ *      sizes, the gradient and the Fisher matrix under resolution matrices:
+ *      rvs_chisq_point_grad and rvs_chisq_point_fisher go on refusing taps) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -626,6 +629,41 @@ int rvs_chisq_point_fisher(const rvs_point_arm *arms, int narm, int npoly, int n
                            const double *basis_const, void *scratch, double *out,
                            double *grad, double *fisher, int32_t *status,
                            void *stream);
+
+/* ------------------------------------------------------------------------
+ * ... both under banded resolution matrices: the arguments, value, gradient, Fisher
+ * matrix, status bits and work sizes of rvs_chisq_point_grad / rvs_chisq_point_fisher,
+ * with arms that may carry taps / taps_stride / nd as in rvs_chisq_point (arms with and
+ * without a matrix may be mixed).  The model row of such an arm is m = R raw,
+ *   m_k = sum_d taps[s][k][d] raw[k - (nd-1)/2 + d]   (d ascending, pixels outside
+ * the arm skipped), and every tangent row is R applied to the raw tangent row -- the
+ * raw velocity tangent of pixel q being S'(x_q) lam_q df/dvel, with lam of q --; the
+ * rest of rvs_chisq_point_grad's mathematics is unchanged.  The block walks the pixels
+ * in tiles of 256, the raw rows of a tile and its halo staged in LDS:
+ *   RVS_GRAD_RESOL_LDS(ntan, nd) = (2 + ntan) * (255 + nd) * 8 bytes, any npix,
+ * for the widest matrix of the call, at most RVS_GRAD_RESOL_LDS_MAX (nd <= 641 at
+ * ntan = 6, nd <= 3329 at ntan = 0).  With nd = 1 and taps of 1 the results are the
+ * bits of the pair above, and so is a call in which no arm has taps (it runs their
+ * kernels).  RVS_E_ARG, before any launch: what the pair above refuses other than
+ * taps (npoly outside 1..16, ntan outside 0..6, G > 1, fast_interp), nd even or < 1,
+ * RVS_GRAD_RESOL_LDS(ntan, nd) > RVS_GRAD_RESOL_LDS_MAX.
+ * ---------------------------------------------------------------------- */
+#define RVS_GRAD_RESOL_LDS_MAX (56 * 1024)
+#define RVS_GRAD_RESOL_LDS(ntan, nd) ((2 + (ntan)) * (255 + (int64_t)(nd)) * 8)
+int64_t rvs_chisq_point_grad_resol_work_size(int J, int narm, int ntan);
+int rvs_chisq_point_grad_resol(const rvs_point_arm *arms, int narm, int npoly,
+                               int ntan, const int32_t *job_spec,
+                               const int32_t *job_templ, int J, const double *vel,
+                               double badchi, const double *basis_const,
+                               void *scratch, double *out, double *grad,
+                               int32_t *status, void *stream);
+int64_t rvs_chisq_point_fisher_resol_work_size(int J, int narm, int ntan);
+int rvs_chisq_point_fisher_resol(const rvs_point_arm *arms, int narm, int npoly,
+                                 int ntan, const int32_t *job_spec,
+                                 const int32_t *job_templ, int J, const double *vel,
+                                 double badchi, const double *basis_const,
+                                 void *scratch, double *out, double *grad,
+                                 double *fisher, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------
  * The same objective as ONE kernel per evaluation for regular-grid libraries:

@@ -65,6 +65,11 @@ SIGNATURES = {
     'rvs_chisq_point_grad': (I, [P, I, I, I, P, P, I, P, D, P, P, P, P, P, P]),
     'rvs_chisq_point_fisher_work_size': (L, [I, I, I]),
     'rvs_chisq_point_fisher': (I, [P, I, I, I, P, P, I, P, D, P, P, P, P, P, P, P]),
+    'rvs_chisq_point_grad_resol_work_size': (L, [I, I, I]),
+    'rvs_chisq_point_grad_resol': (I, [P, I, I, I, P, P, I, P, D, P, P, P, P, P, P]),
+    'rvs_chisq_point_fisher_resol_work_size': (L, [I, I, I]),
+    'rvs_chisq_point_fisher_resol': (I, [P, I, I, I, P, P, I, P, D, P, P, P, P, P, P,
+                                         P]),
     'rvs_nm_begin': (I, [I, I, D, D, I, P, P, P, P, P, P, P, I, P]),
     'rvs_nm_decide': (I, [I, P, P, P, P, P, P, P, P, P, I, P]),
     'rvs_nm_update': (I, [I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P]),

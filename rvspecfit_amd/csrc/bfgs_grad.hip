@@ -343,10 +343,14 @@ int rvs_internal_grad_chain_eval(const rvs_nm_objective *o, const rvs_grad_chain
   }
   if (hipMemsetAsync(o->jstatus, 0, sizeof(int32_t) * J, st) != hipSuccess)
     return RVS_E_LAUNCH;
+  // arms under a resolution matrix: the _resol entry points (R acts after the
+  // resampling, so the template, FIR and spline stages above are as without)
+  bool resol = false;
+  for (int a = 0; a < g->narm; a++) resol = resol || g->point[a].taps;
   if (fc) {   // the Fisher form of the last two calls
-    rc = rvs_chisq_point_fisher(g->point, g->narm, o->npoly, ntan, o->job_spec, nullptr,
-                                J, o->vel, o->badchi, g->basis_const, fc->fisher_work,
-                                g->chi, g->grad, fc->fisher, o->jstatus, st);
+    rc = (resol ? rvs_chisq_point_fisher_resol : rvs_chisq_point_fisher)(
+        g->point, g->narm, o->npoly, ntan, o->job_spec, nullptr, J, o->vel, o->badchi,
+        g->basis_const, fc->fisher_work, g->chi, g->grad, fc->fisher, o->jstatus, st);
     if (rc) return rc;
     return rvs_proc_finish_fisher(J, o->n, ndim, ntan, counts, cidx, g->chi, g->grad,
                                   fc->fisher, X, o->params, o->extra, o->bad,
@@ -354,9 +358,9 @@ int rvs_internal_grad_chain_eval(const rvs_nm_objective *o, const rvs_grad_chain
                                   o->prior_mean, o->prior_isig, o->max_vsini, F,
                                   o->status, st);
   }
-  rc = rvs_chisq_point_grad(g->point, g->narm, o->npoly, ntan, o->job_spec, nullptr, J,
-                            o->vel, o->badchi, g->basis_const, g->point_work, g->chi,
-                            g->grad, o->jstatus, st);
+  rc = (resol ? rvs_chisq_point_grad_resol : rvs_chisq_point_grad)(
+      g->point, g->narm, o->npoly, ntan, o->job_spec, nullptr, J, o->vel, o->badchi,
+      g->basis_const, g->point_work, g->chi, g->grad, o->jstatus, st);
   if (rc) return rc;
   return rvs_proc_finish_grad(J, o->n, ndim, ntan, counts, cidx, g->chi, g->grad, X,
                               o->params, o->extra, o->bad, o->job_spec, o->jstatus,

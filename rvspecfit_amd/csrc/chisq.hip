@@ -2500,6 +2500,402 @@ __global__ void __launch_bounds__(256)
                             armfisher, armst);
 }
 
+// ---------------------------------------------------------------------------
+// point_grad_block under banded resolution matrices (rvs_chisq_point_grad_resol,
+// rvs_chisq_point_fisher_resol): the model row is m = R raw and every tangent row
+// R raw'_i, R acting after the resampling (point_block_kernel's band: m_k = sum_d
+// taps[s][k][d] raw[k - (nd-1)/2 + d], d ascending, pixels outside the arm skipped).
+// The pixels are walked in TILES of 256 outputs: the block stages the raw value row
+// and the raw tangent rows of the pixels [k0 - mres, k0 + 256 + mres) in LDS
+// ((1 + K)(256 + nd - 1) doubles, whatever npix), and after a barrier every thread
+// applies the band of its own pixel to the rows it needs.  All three passes go
+// through the same tiles -- pass 1 stages the value row only, pass 2 the value and
+// the K tangents, the Fisher pass of tangent i the value and the tangents i ... K-1
+// (it needs the products J_ki J_kl of CONVOLVED rows, which no adjoint of the band
+// gives) -- so no convolved row goes to HBM and none is kept for a whole arm.  The
+// tile loops have the same trip count for every thread (a thread past the last pixel
+// stages and waits, and accumulates nothing), so every barrier is reached by all 256.
+// The raw velocity tangent of pixel q is S'(x_q) lam_q df/dvel: lam of the RAW pixel.
+// Sums, the factorisation and the status bits are point_grad_block's, in its order:
+// with nd = 1 and a tap of 1 every fma(1, x, 0) is x and the results are its bits.
+// An arm without taps among arms with them is such an identity band, taps not read.
+// ---------------------------------------------------------------------------
+// rows of L in registers in point_grad_resol_block_kernel<16> and
+// point_fisher_resol_block_kernel<16> (as FISHER_LROWS_P16, from the compiler's
+// resource report with the band's accumulators beside them: the gradient leaves
+// scratch with 4 and 0 rows and none with 8, the Fisher form 20 B with 8, none with 4)
+#define GRAD_RESOL_LROWS_P16 8
+#define FISHER_RESOL_LROWS_P16 4
+// (RVS_GRAD_RESOL_LDS_MAX, the most dynamic LDS of the tiles: with the static sums,
+// 7.3 KB at P = 16, inside the 64 KB every launch is given)
+template <int P, bool FISHER>
+__device__ __forceinline__ void
+    point_grad_resol_block(const PointArms &A, int ntan,
+                           const int32_t *__restrict__ job_spec,
+                           const int32_t *__restrict__ job_templ, int J,
+                           const double *__restrict__ vel,
+                           double *__restrict__ armchi,
+                           double *__restrict__ armgrad,
+                           double *__restrict__ armfisher,
+                           int32_t *__restrict__ armst) {
+  constexpr int NT = P * (P + 1) / 2;
+  constexpr int NV = NT + P;
+  constexpr int KM = 1 + GRAD_MAXTAN;
+  constexpr int NG = FISHER && P + KM > 1 + KM ? P + KM : 1 + KM;
+  constexpr int NR = NV > NG ? NV : NG;
+  __shared__ double red[4][NR + 1];
+  extern __shared__ double rowsh[];   // [1 + K][W]: raw rows of a tile and its halo
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int j = blockIdx.x;
+  const rvs_point_arm &T = A.a[blockIdx.y];
+  const int s = job_spec ? job_spec[j] : j;
+  const int t = job_templ ? job_templ[j] : j;
+  const ArmGrid AG = arm_grid(T, s);
+  const double bb = vel[j] / RVS_C_KMS;
+  const double f = sqrt((1.0 - bb) / (1.0 + bb));
+  const double dfdv = -f / (RVS_C_KMS * (1.0 - bb * bb));
+  const double espec_sys = T.espec_sys;
+  const double sys2 = espec_sys * espec_sys;
+  const int npix = T.npix, K = 1 + ntan;
+  const double *sp = T.spec + (int64_t)s * npix;
+  const double *es = T.espec + (int64_t)s * npix;
+  const double4 *cf = reinterpret_cast<const double4 *>(T.coef) +
+                      (int64_t)t * K * T.ntp;
+  const double x0 = T.knots[0], xlast = T.knots[T.ntp - 1];
+  const double shift = T.log_step ? log(f) / log(T.knots[1] / x0) : 0.0;
+  const double lin_inv_step = T.log_step ? 0.0 : 1.0 / (T.knots[1] - x0);
+  const double *tp = T.taps ? T.taps + (int64_t)s * T.taps_stride : nullptr;
+  const int nd = tp ? T.nd : 1, mres = (nd - 1) / 2;
+  const int W = 256 + nd - 1;
+  // the raw value row and the raw tangent rows lo <= i < hi of the tile at k0
+  auto stage = [&](int k0, int lo, int hi) {
+    for (int u = threadIdx.x; u < W; u += 256) {
+      const int q = k0 - mres + u;
+      if (q < 0 || q >= npix) continue;   // (never read: the band skips them)
+      const double x = AG.lam[q] * f;
+      int pos = T.log_step ? (int)(AG.pix[q] + shift)
+                           : (int)((x - x0) * lin_inv_step);
+      pos = min(max(pos, 0), T.ntp - 2);
+      const double dl = x - T.knots[pos];
+      const double4 c0 = cf[pos];
+      rowsh[u] = fma(fma(fma(c0.w, dl, c0.z), dl, c0.y), dl, c0.x);
+      for (int i = lo; i < hi; i++) {
+        if (i == 0) {
+          const double dtv = fma(dl, fma(3.0 * c0.w, dl, 2.0 * c0.z), c0.y);
+          rowsh[W + u] = dtv * (AG.lam[q] * dfdv);
+        } else {
+          const double4 c = cf[(int64_t)i * T.ntp + pos];
+          rowsh[(1 + i) * W + u] = fma(fma(fma(c.w, dl, c.z), dl, c.y), dl, c.x);
+        }
+      }
+    }
+  };
+  // the band of pixel k (this thread's, in the staged tile) on the value row ...
+  auto band_value = [&](int k) {
+    double v = 0;
+    for (int d = 0; d < nd; d++) {
+      const int q = k - mres + d;
+      if (q >= 0 && q < npix)
+        v = fma(tp ? tp[(int64_t)k * nd + d] : 1.0, rowsh[threadIdx.x + d], v);
+    }
+    return v;
+  };
+  // ... and on the tangent rows lo ... K-1 at once (cv[d]: tangent lo + d)
+  auto band_tangents = [&](int k, int lo, double (&cv)[KM]) {
+#pragma unroll
+    for (int d = 0; d < KM; d++) cv[d] = 0;
+    for (int d = 0; d < nd; d++) {
+      const int q = k - mres + d;
+      if (q < 0 || q >= npix) continue;
+      const double tap = tp ? tp[(int64_t)k * nd + d] : 1.0;
+      const double *rp = rowsh + (1 + lo) * W + threadIdx.x + d;
+#pragma unroll
+      for (int i = 0; i < KM; i++)
+        if (lo + i < K) cv[i] = fma(tap, rp[i * W], cv[i]);
+    }
+  };
+  double acc[NT];
+  double av[P];
+#pragma unroll
+  for (int i = 0; i < NT; i++) acc[i] = 0;
+#pragma unroll
+  for (int i = 0; i < P; i++) av[i] = 0;
+  for (int k0 = 0; k0 < npix; k0 += 256) {
+    stage(k0, 0, 0);
+    __syncthreads();
+    const int k = k0 + threadIdx.x;
+    if (k < npix) {
+      const double tv = band_value(k);
+      double e = es[k];
+      if (espec_sys > 0) e = sqrt(sys2 + e * e);
+      const double ie = 1.0 / e;
+      const double te = tv * ie;
+      const double wt = te * te, u = te * (sp[k] * ie);
+      const double *pr = AG.polysT + (int64_t)k * P;
+      double pv[P], pw[P];
+#pragma unroll
+      for (int i = 0; i < P; i++) {
+        pv[i] = pr[i];
+        pw[i] = pv[i] * wt;
+      }
+#pragma unroll
+      for (int i = 0; i < P; i++) {
+        av[i] = fma(pv[i], u, av[i]);
+#pragma unroll
+        for (int jj = 0; jj <= i; jj++)
+          acc[TRI(i, jj)] = fma(pv[i], pw[jj], acc[TRI(i, jj)]);
+      }
+    }
+    __syncthreads();   // (the next tile is staged over this one)
+  }
+#pragma unroll
+  for (int i = 0; i < NT; i++) {
+    const double v = wave_sum_to63(acc[i]);
+    if (lane == 63) red[w][i] = v;
+  }
+#pragma unroll
+  for (int i = 0; i < P; i++) {
+    const double v = wave_sum_to63(av[i]);
+    if (lane == 63) red[w][NT + i] = v;
+  }
+  __syncthreads();
+  // every lane of every wave factors the same matrix (waves summed in order)
+#pragma unroll
+  for (int i = 0; i < NT; i++)
+    acc[i] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+#pragma unroll
+  for (int i = 0; i < P; i++)
+    av[i] = ((red[0][NT + i] + red[1][NT + i]) + red[2][NT + i]) +
+            red[3][NT + i];
+  bool ok = true;
+  double ldet = 0;
+  double idg[P];  // 1 / L_ii
+#pragma unroll
+  for (int i = 0; i < P; i++) {
+#pragma unroll
+    for (int jj = 0; jj <= i; jj++) {
+      double sum = acc[TRI(i, jj)];
+#pragma unroll
+      for (int q = 0; q < jj; q++) sum -= acc[TRI(i, q)] * acc[TRI(jj, q)];
+      if (jj == i) {
+        if (!(sum > 0)) ok = false;
+        const double d = sqrt(sum);
+        acc[TRI(i, i)] = d;
+        idg[i] = 1.0 / d;
+        ldet += log(d);
+      } else {
+        acc[TRI(i, jj)] = sum / acc[TRI(jj, jj)];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < P; i++) {
+    double sum = av[i];
+#pragma unroll
+    for (int q = 0; q < i; q++) sum -= acc[TRI(i, q)] * av[q];
+    av[i] = sum / acc[TRI(i, i)];
+  }
+#pragma unroll
+  for (int i = P - 1; i >= 0; i--) {
+    double sum = av[i];
+#pragma unroll
+    for (int q = i + 1; q < P; q++) sum -= acc[TRI(q, i)] * av[q];
+    av[i] = sum / acc[TRI(i, i)];
+  }
+  // (the last rows of L in LDS at P = 16, see point_grad_block: here also without the
+  // Fisher pass, the band's accumulators being live beside L in pass 2)
+  constexpr int PL = P > 15 ? (FISHER ? FISHER_RESOL_LROWS_P16 : GRAD_RESOL_LROWS_P16) : P;
+  __shared__ double lsh[PL < P ? NT : 1];
+  if constexpr (PL < P) {
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int q = TRI(PL, 0); q < NT; q++) lsh[q] = acc[q];
+    }
+    __syncthreads();
+  }
+  auto lmat = [&](int p, int qq) {
+    return p < PL ? acc[TRI(p, qq)] : lsh[TRI(p, qq)];
+  };
+  double rr = 0;
+  double gk[KM];
+#pragma unroll
+  for (int i = 0; i < KM; i++) gk[i] = 0;
+  for (int k0 = 0; k0 < npix; k0 += 256) {
+    stage(k0, 0, K);
+    __syncthreads();
+    const int k = k0 + threadIdx.x;
+    if (k < npix) {
+      const double tv = band_value(k);
+      double e = es[k];
+      if (espec_sys > 0) e = sqrt(sys2 + e * e);
+      const double ie = 1.0 / e;
+      const double *pr = AG.polysT + (int64_t)k * P;
+      double y[P];
+      double m = 0, q = 0;
+#pragma unroll
+      for (int i = 0; i < P; i++) {
+        const double ph = pr[i];
+        m = fma(av[i], ph, m);
+        double sum = ph;
+#pragma unroll
+        for (int qq = 0; qq < i; qq++) sum = fma(-lmat(i, qq), y[qq], sum);
+        y[i] = sum * idg[i];
+        q = fma(y[i], y[i], q);
+      }
+      const double r = sp[k] * ie - m * (tv * ie);
+      rr = fma(r, r, rr);
+      const double mbar = 2.0 * ie * ((tv * ie) * q - r * m);
+      double cv[KM];
+      band_tangents(k, 0, cv);
+#pragma unroll
+      for (int i = 0; i < KM; i++)
+        if (i < K) gk[i] = fma(mbar, cv[i], gk[i]);
+    }
+    __syncthreads();
+  }
+  {
+    const double v = wave_sum_to63(rr);
+    if (lane == 63) red[w][0] = v;
+  }
+#pragma unroll
+  for (int i = 0; i < KM; i++) {
+    const double v = wave_sum_to63(gk[i]);
+    if (lane == 63) red[w][1 + i] = v;
+  }
+  __syncthreads();
+  const int64_t o = (int64_t)blockIdx.y * J + j;
+  const double xa = AG.lam[0] * f, xb = AG.lam[npix - 1] * f;
+  const bool range = xa < x0 || xb < x0 || xa >= xlast || xb >= xlast;
+  rr = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+  const double lz = AG.wbase[2ll * T.S * npix + 2 * s];
+  double chi = 2.0 * ldet + 2.0 * lz + rr;
+  int st = 0;
+  if (range) {
+    st |= RVS_ST_SPLINE_RANGE;
+    chi = __builtin_nan("");
+  }
+  if (!ok) st |= RVS_ST_CHOL_FALLBACK;
+  if (!ok || !(fabs(chi) <= 1.79e308)) {
+    st |= RVS_ST_NONFINITE;
+    chi = __builtin_nan("");
+  }
+  if (threadIdx.x == 0) {
+    armchi[o] = chi;
+    armst[o] = st;
+  }
+  if (threadIdx.x < K) {
+    const int i = threadIdx.x;
+    const double g = ((red[0][1 + i] + red[1][1 + i]) + red[2][1 + i]) + red[3][1 + i];
+    armgrad[o * K + i] = (chi == chi) ? g : __builtin_nan("");
+  }
+  if constexpr (FISHER) {
+    __shared__ double bsh[KM][P];
+    __shared__ double gsh[KM][KM];
+    for (int i = 0; i < K; i++) {
+      double bp[P], gl[KM];   // B_.i and G_i,i+d
+#pragma unroll
+      for (int p = 0; p < P; p++) bp[p] = 0;
+#pragma unroll
+      for (int d = 0; d < KM; d++) gl[d] = 0;
+      for (int k0 = 0; k0 < npix; k0 += 256) {
+        stage(k0, i, K);
+        __syncthreads();
+        const int k = k0 + threadIdx.x;
+        if (k < npix) {
+          const double tv = band_value(k);
+          double cv[KM];   // the convolved tangents i, i + 1 ...
+          band_tangents(k, i, cv);
+          double e = es[k];
+          if (espec_sys > 0) e = sqrt(sys2 + e * e);
+          const double ie = 1.0 / e;
+          const double *pr = AG.polysT + (int64_t)k * P;
+          double y[P];
+          double m = 0;
+#pragma unroll
+          for (int p = 0; p < P; p++) {
+            const double ph = pr[p];
+            m = fma(av[p], ph, m);
+            double sum = ph;
+#pragma unroll
+            for (int qq = 0; qq < p; qq++)
+              sum = fma(-lmat(p, qq), y[qq], sum);
+            y[p] = sum * idg[p];
+          }
+          const double se = m * ie;   // J_kl = se * m'_kl
+          const double ji = se * cv[0];
+          const double z = (tv * ie) * ji;
+#pragma unroll
+          for (int p = 0; p < P; p++) bp[p] = fma(y[p], z, bp[p]);
+          gl[0] = fma(ji, ji, gl[0]);
+#pragma unroll
+          for (int d = 1; d < KM; d++)
+            if (i + d < K) gl[d] = fma(ji, se * cv[d], gl[d]);
+        }
+        __syncthreads();   // (also red: the sums of the pass before are read)
+      }
+#pragma unroll
+      for (int p = 0; p < P; p++) {
+        const double v = wave_sum_to63(bp[p]);
+        if (lane == 63) red[w][p] = v;
+      }
+#pragma unroll
+      for (int d = 0; d < KM; d++) {
+        const double v = wave_sum_to63(gl[d]);
+        if (lane == 63) red[w][P + d] = v;
+      }
+      __syncthreads();
+      if (threadIdx.x < P + KM) {
+        const int q = threadIdx.x;
+        const double v = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+        if (q < P)
+          bsh[i][q] = v;
+        else if (i + q - P < K)
+          gsh[i][i + q - P] = v;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < KM * KM) {
+      const int i = threadIdx.x / KM, l = threadIdx.x % KM;
+      if (i <= l && l < K) {
+        double bb2 = 0;
+#pragma unroll
+        for (int p = 0; p < P; p++) bb2 = fma(bsh[i][p], bsh[l][p], bb2);
+        const double v = (chi == chi) ? gsh[i][l] - bb2 : __builtin_nan("");
+        double *fo = armfisher + o * K * K;
+        fo[i * K + l] = v;
+        fo[l * K + i] = v;
+      }
+    }
+  }
+}
+
+template <int P>
+__global__ void __launch_bounds__(256)
+    point_grad_resol_block_kernel(PointArms A, int ntan,
+                                  const int32_t *__restrict__ job_spec,
+                                  const int32_t *__restrict__ job_templ, int J,
+                                  const double *__restrict__ vel,
+                                  double *__restrict__ armchi,
+                                  double *__restrict__ armgrad,
+                                  int32_t *__restrict__ armst) {
+  point_grad_resol_block<P, false>(A, ntan, job_spec, job_templ, J, vel, armchi,
+                                   armgrad, nullptr, armst);
+}
+
+template <int P>
+__global__ void __launch_bounds__(256)
+    point_fisher_resol_block_kernel(PointArms A, int ntan,
+                                    const int32_t *__restrict__ job_spec,
+                                    const int32_t *__restrict__ job_templ, int J,
+                                    const double *__restrict__ vel,
+                                    double *__restrict__ armchi,
+                                    double *__restrict__ armgrad,
+                                    double *__restrict__ armfisher,
+                                    int32_t *__restrict__ armst) {
+  point_grad_resol_block<P, true>(A, ntan, job_spec, job_templ, J, vel, armchi,
+                                  armgrad, armfisher, armst);
+}
+
 // arms summed in order; penalties of A11 (spec_fit.py:888-896) on the value only
 __global__ void point_grad_sum_kernel(PointArms A, int J, int K, double badchi,
                                       double4 bconst,
@@ -2586,7 +2982,8 @@ static int point_grad_launch(const rvs_point_arm *arms, int narm, int npoly,
                              const int32_t *job_templ, int J, const double *vel,
                              double badchi, const double *basis_const,
                              void *scratch, double *out, double *grad,
-                             double *fisher, int32_t *status, void *stream) {
+                             double *fisher, int32_t *status, void *stream,
+                             bool resol = false) {
   if (J < 1 || narm < 1 || narm > RVS_MAX_ARMS || !arms || !scratch ||
       ntan < 0 || ntan > GRAD_MAXTAN)
     return RVS_E_ARG;
@@ -2596,11 +2993,19 @@ static int point_grad_launch(const rvs_point_arm *arms, int narm, int npoly,
   double bc[RVS_MAX_ARMS] = {0, 0, 0, 0};
   for (int i = 0; i < narm; i++) {
     A.a[i] = arms[i];
-    if (arms[i].npix < 1 || arms[i].ntp < 3 || arms[i].G > 1 || arms[i].taps ||
-        arms[i].fast_interp)
+    if (arms[i].npix < 1 || arms[i].ntp < 3 || arms[i].G > 1 ||
+        (arms[i].taps && !resol) || arms[i].fast_interp)
       return RVS_E_ARG;
     if (basis_const) bc[i] = basis_const[i];
   }
+  // the tiles of point_grad_resol_block: (1 + K) rows of 256 + nd - 1 doubles
+  size_t shm = 0;
+  for (int i = 0; i < narm; i++)
+    if (arms[i].taps) {
+      if (arms[i].nd < 1 || (arms[i].nd & 1) == 0) return RVS_E_ARG;
+      shm = max(shm, (size_t)RVS_GRAD_RESOL_LDS(ntan, arms[i].nd));
+    }
+  if (shm > RVS_GRAD_RESOL_LDS_MAX) return RVS_E_ARG;
   for (int i = narm; i < RVS_MAX_ARMS; i++) A.a[i] = arms[0];
   hipStream_t st = rvs_stream(stream);
   const int K = 1 + ntan;
@@ -2612,7 +3017,15 @@ static int point_grad_launch(const rvs_point_arm *arms, int narm, int npoly,
   dim3 grid(J, narm);
 #define RVS_CASE(PP)                                                           \
   case PP:                                                                     \
-    if (fisher)                                                                \
+    if (shm && fisher)                                                         \
+      hipLaunchKernelGGL(point_fisher_resol_block_kernel<PP>, grid, dim3(256), \
+                         shm, st, A, ntan, job_spec, job_templ, J, vel,        \
+                         armchi, armgrad, armfisher, armst);                   \
+    else if (shm)                                                              \
+      hipLaunchKernelGGL(point_grad_resol_block_kernel<PP>, grid, dim3(256),   \
+                         shm, st, A, ntan, job_spec, job_templ, J, vel,        \
+                         armchi, armgrad, armst);                              \
+    else if (fisher)                                                           \
       hipLaunchKernelGGL(point_fisher_block_kernel<PP>, grid, dim3(256), 0,    \
                          st, A, ntan, job_spec, job_templ, J, vel, armchi,     \
                          armgrad, armfisher, armst);                           \
@@ -2664,6 +3077,37 @@ extern "C" int rvs_chisq_point_fisher(const rvs_point_arm *arms, int narm,
   return point_grad_launch(arms, narm, npoly, ntan, job_spec, job_templ, J, vel,
                            badchi, basis_const, scratch, out, grad, fisher, status,
                            stream);
+}
+
+// The same two with arms that carry a resolution matrix (point_grad_resol_block);
+// a call in which no arm has one runs the kernels, and gives the bits, of the pair above
+extern "C" int64_t rvs_chisq_point_grad_resol_work_size(int J, int narm, int ntan) {
+  return point_grad_work(J, narm, ntan, false);
+}
+
+extern "C" int64_t rvs_chisq_point_fisher_resol_work_size(int J, int narm, int ntan) {
+  return point_grad_work(J, narm, ntan, true);
+}
+
+extern "C" int rvs_chisq_point_grad_resol(
+    const rvs_point_arm *arms, int narm, int npoly, int ntan, const int32_t *job_spec,
+    const int32_t *job_templ, int J, const double *vel, double badchi,
+    const double *basis_const, void *scratch, double *out, double *grad,
+    int32_t *status, void *stream) {
+  return point_grad_launch(arms, narm, npoly, ntan, job_spec, job_templ, J, vel,
+                           badchi, basis_const, scratch, out, grad, nullptr,
+                           status, stream, true);
+}
+
+extern "C" int rvs_chisq_point_fisher_resol(
+    const rvs_point_arm *arms, int narm, int npoly, int ntan, const int32_t *job_spec,
+    const int32_t *job_templ, int J, const double *vel, double badchi,
+    const double *basis_const, void *scratch, double *out, double *grad,
+    double *fisher, int32_t *status, void *stream) {
+  if (!fisher) return RVS_E_ARG;
+  return point_grad_launch(arms, narm, npoly, ntan, job_spec, job_templ, J, vel,
+                           badchi, basis_const, scratch, out, grad, fisher, status,
+                           stream, true);
 }
 
 // ---------------------------------------------------------------------------

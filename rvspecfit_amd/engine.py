@@ -886,6 +886,9 @@ def chisq_grid(batch, libs, coefs, outsides, vels, npoly=5, rbf=True,
 POINT_MAXP = 16
 # most tangent rows of rvs_chisq_point_grad (GRAD_MAXTAN of csrc/chisq.hip)
 GRAD_MAXTAN = 6
+# most LDS of the tiles of rvs_chisq_point_grad_resol (RVS_GRAD_RESOL_LDS_MAX of
+# include/rvsgpu.h): (2 + ntan) * (255 + nd) * 8 bytes for a band of nd diagonals
+GRAD_RESOL_LDS_MAX = 56 * 1024
 
 
 def _per_arm(v, n):
@@ -956,11 +959,13 @@ def chisq_point(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
 
 
 def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
-                     vsini_grad=False, nn_gradient=False):
+                     vsini_grad=False, nn_gradient=False, resol_gradient=False):
     """ValueError naming what rvs_chisq_point_grad does not cover.  nn_gradient
     (config['nn_gradient'] of the callers): MLP libraries are admitted -- their
     tangent rows (rvs_template_nn_grad) are float32 arithmetic, which a caller has to
-    ask for; without it they are refused like any other kind without tangents."""
+    ask for; without it they are refused like any other kind without tangents.
+    resol_gradient (config['resol_gradient']): arms under a resolution matrix are
+    admitted (rvs_chisq_point_grad_resol); without it they are refused as before."""
     kinds = ('regulargrid', 'triangulation') + (('nn', ) if nn_gradient else ())
     if npoly > POINT_MAXP:
         raise ValueError('the analytic gradient takes npoly <= %d, not %d'
@@ -969,7 +974,7 @@ def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
         raise ValueError('the analytic gradient does not take fast_interp (the '
                          'nearest-knot template has no velocity derivative)')
     for ia, arm in enumerate(batch.arms):
-        if _arm_resol(arm, ia, resols) is not None:
+        if _arm_resol(arm, ia, resols) is not None and not resol_gradient:
             raise ValueError('the analytic gradient does not take a resolution '
                              'matrix (arm %s)' % arm.name)
         if arm.G > 1:
@@ -988,7 +993,7 @@ def check_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
 def chisq_point_grad(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
                      job_spec=None, job_templ=None, espec_sys=0.0,
                      outside_penalty=True, resols=None, fast_interp=False,
-                     nn_gradient=False):
+                     nn_gradient=False, resol_gradient=False):
     """chisq_point with the gradient (rvs_chisq_point_grad): coefs[ia] are the
     [Tn, 1 + ntan, ntp, 4] records of build_templates(..., tangents=True), ntan =
     ndim, or ndim + 1 with vsini_tangent=True (the vsini row last).
@@ -998,16 +1003,19 @@ def chisq_point_grad(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
     not differentiated.  What the kernel does not cover is refused, never
     finite-differenced: npoly > 16, several wavelength grids per arm, a
     resolution matrix, fast_interp, libraries that are neither regular grids nor
-    Delaunay triangulations (MLP libraries, unless nn_gradient: check_grad_scope)."""
+    Delaunay triangulations (MLP libraries, unless nn_gradient: check_grad_scope).
+    resol_gradient: `resols` / the spectra's own resolution matrices are applied to
+    the model and to every tangent row (rvs_chisq_point_grad_resol); a band whose
+    tiles need more LDS than GRAD_RESOL_LDS_MAX raises ValueError."""
     return _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
                              job_templ, espec_sys, outside_penalty, resols,
-                             fast_interp, False, nn_gradient)
+                             fast_interp, False, nn_gradient, resol_gradient)
 
 
 def chisq_point_fisher(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
                        job_spec=None, job_templ=None, espec_sys=0.0,
                        outside_penalty=True, resols=None, fast_interp=False,
-                       nn_gradient=False):
+                       nn_gradient=False, resol_gradient=False):
     """chisq_point_grad with the Fisher matrix of the fit (rvs_chisq_point_fisher): the
     arguments and the scope of chisq_point_grad.  Returns chisq [J], grad [J, 1 + ntan]
     (the bits of chisq_point_grad), fisher [J, 1 + ntan, 1 + ntan] over (vel,
@@ -1017,17 +1025,34 @@ def chisq_point_fisher(batch, libs, coefs, outsides, vel, npoly=5, rbf=True,
     rounding; the penalties and log det A are not part of it."""
     return _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
                              job_templ, espec_sys, outside_penalty, resols,
-                             fast_interp, True, nn_gradient)
+                             fast_interp, True, nn_gradient, resol_gradient)
+
+
+def check_grad_resol_lds(ntan, nd):
+    """ValueError for a band of nd diagonals whose tiles rvs_chisq_point_grad_resol
+    cannot stage beside ntan tangent rows (it returns RVS_E_ARG for it)"""
+    need = (2 + ntan) * (255 + nd) * 8
+    if need > GRAD_RESOL_LDS_MAX:
+        raise ValueError('the analytic gradient under a resolution matrix of %d '
+                         'diagonals with %d tangents needs %d bytes of LDS, the limit '
+                         'is %d (nd <= %d)'
+                         % (nd, ntan, need, GRAD_RESOL_LDS_MAX,
+                            GRAD_RESOL_LDS_MAX // (8 * (2 + ntan)) - 255))
 
 
 def _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
                       job_templ, espec_sys, outside_penalty, resols, fast_interp,
-                      want_fisher, nn_gradient=False):
+                      want_fisher, nn_gradient=False, resol_gradient=False):
     import ctypes
     ntan = coefs[0].shape[1] - 1
     check_grad_scope(batch, libs, npoly, resols, fast_interp,
                      vsini_grad=ntan > libs[batch.arms[0].name].ndim,
-                     nn_gradient=nn_gradient)
+                     nn_gradient=nn_gradient, resol_gradient=resol_gradient)
+    arm_resols = [_arm_resol(arm, ia, resols) for ia, arm in enumerate(batch.arms)]
+    any_resol = any(r is not None for r in arm_resols)
+    for r in arm_resols:
+        if r is not None:
+            check_grad_resol_lds(ntan, r['nd'])
     narm = len(batch.arms)
     L = _lib.lib()
     dev = batch.device
@@ -1055,7 +1080,8 @@ def _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
         pen = o * batch.badchi_jobs(job_spec) if outside_penalty else torch.where(
             torch.isfinite(o), torch.zeros_like(o), o)
         keep.append(fill_point_arm(arr[ia], arm, libs[arm.name], npoly, rbf,
-                                   esys[ia], None, coefs[ia], pen.contiguous()))
+                                   esys[ia], arm_resols[ia], coefs[ia],
+                                   pen.contiguous()))
         # the orthonormal basis of the same space (ArmData.basis_ortho): the value
         # differs by the constant handed over beside it, the gradient not at all
         qt, const = arm.basis_ortho(npoly, rbf)
@@ -1065,15 +1091,18 @@ def _chisq_point_grad(batch, libs, coefs, outsides, vel, npoly, rbf, job_spec,
     head = (ctypes.addressof(arr), narm, npoly, ntan, _lib.ptr(job_spec),
             _lib.ptr(job_templ), J, _lib.ptr(vel), float(batch.badchi),
             ctypes.addressof(bconst), _lib.ptr(scratch), _lib.ptr(out), _lib.ptr(grad))
+    # (the work sizes of the _resol entry points are those taken above)
     if want_fisher:
+        name = 'rvs_chisq_point_fisher' + ('_resol' if any_resol else '')
         with _ktime('chisq_point_fisher', J):
-            rc = L.rvs_chisq_point_fisher(*head, _lib.ptr(fisher), _lib.ptr(status),
-                                          _lib.stream())
-            _lib.check(rc, 'rvs_chisq_point_fisher')
+            rc = getattr(L, name)(*head, _lib.ptr(fisher), _lib.ptr(status),
+                                  _lib.stream())
+            _lib.check(rc, name)
         return out, grad, fisher, status
+    name = 'rvs_chisq_point_grad' + ('_resol' if any_resol else '')
     with _ktime('chisq_point_grad', J):
-        rc = L.rvs_chisq_point_grad(*head, _lib.ptr(status), _lib.stream())
-        _lib.check(rc, 'rvs_chisq_point_grad')
+        rc = getattr(L, name)(*head, _lib.ptr(status), _lib.stream())
+        _lib.check(rc, name)
     return out, grad, status
 
 

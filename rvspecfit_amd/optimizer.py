@@ -80,6 +80,8 @@ class ProcessObjective:
         self.max_vsini = float(config['max_vsini'])
         # (MLP libraries in the gradient chain are opt-in: engine.check_grad_scope)
         self.nn_gradient = bool(config.get('nn_gradient'))
+        # (and so are resolution matrices)
+        self.resol_gradient = bool(config.get('resol_gradient'))
         cap = S
         self.cap = cap
         self.job_spec = torch.zeros(cap, **i32)
@@ -360,7 +362,8 @@ class GradChain:
         # (refused before anything is built; nothing falls back to differences)
         engine.check_grad_scope(batch, libs, pobj.npoly, pobj.resols, False,
                                 vsini_grad=fit,
-                                nn_gradient=getattr(pobj, 'nn_gradient', False))
+                                nn_gradient=getattr(pobj, 'nn_gradient', False),
+                                resol_gradient=getattr(pobj, 'resol_gradient', False))
         self.pobj = pobj
         self.fisher = bool(fisher)
         dev = pobj.dev
@@ -450,8 +453,12 @@ class GradChain:
                 a.vecs_s = lib.vecs_s.data_ptr()
                 a.lens, a.ptp = lib.lens.ctypes.data, lib.ptp.ctypes.data
             self._keep.append(b)
+            # (the arm's resolution matrix: the chain then ends in the _resol calls)
+            rs = engine._arm_resol(arm, ia, pobj.resols)
+            if rs is not None:
+                engine.check_grad_resol_lds(self.ntan, rs['nd'])
             self._keep.append(engine.fill_point_arm(
-                self.point[ia], arm, lib, pobj.npoly, pobj.rbf, 0.0, None, b['coef'],
+                self.point[ia], arm, lib, pobj.npoly, pobj.rbf, 0.0, rs, b['coef'],
                 b['penalty']))
             # the orthonormal basis of the same space, as engine.chisq_point_grad
             qt, const = arm.basis_ortho(pobj.npoly, pobj.rbf)
@@ -553,7 +560,8 @@ class GradChain:
                 p.batch, p.libs, p.job_spec[:n], p.vel[:n], p.params[:n],
                 None if p.vsini is None else p.vsini[:n], p.npoly, p.rbf, 0.0, True,
                 p.resols, False, p.vsini_col >= 0, self.fisher,
-                nn_gradient=getattr(p, 'nn_gradient', False))
+                nn_gradient=getattr(p, 'nn_gradient', False),
+                resol_gradient=getattr(p, 'resol_gradient', False))
             chi, grad, status = res[0], res[1], res[-1]
             tail = (_p(X_t[a:]), _p(p.params), _p(p.extra), _p(p.bad), _p(p.job_spec),
                     _p(status), p.src, p.vsini_col, _p(p.prior_mean), _p(p.prior_isig),

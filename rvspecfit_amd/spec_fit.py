@@ -504,6 +504,9 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
     device tensors [S] and [S, 1 + ndim] ([.., 2 + ndim] with vsini_grad).
     Regular-grid and Delaunay libraries, npoly <= 16, one wavelength grid per
     setup, no resolution matrix, no fast_interp: anything else raises ValueError.
+    With config['resol_gradient'] true a resolution matrix is taken -- resol_params
+    or the SpecData's own (both together raise, as in get_chisq): the model and every
+    tangent row go through it (rvs_chisq_point_grad_resol).
     An MLP library is among them unless config['nn_gradient'] is true: its tangent
     rows (rvs_template_nn_grad) are float32 arithmetic, exact to float32 rounding only.  On a Delaunay library a point that no simplex
     holds has the value's penalty and a zero gradient."""
@@ -542,7 +545,8 @@ def _get_chisq_grad(specdata, vel, atm_params, rot_params, options, config,
         esys = float(espec_systematic) if espec_systematic is not None else 0.0
     res = _chisq_grad(batch, libs, None, velt[:, 0], params, vsini, npoly, rbf, esys,
                       outside_penalty, resols, fast_interp, vsini_grad, fisher,
-                      nn_gradient=bool((config or {}).get('nn_gradient')))
+                      nn_gradient=bool((config or {}).get('nn_gradient')),
+                      resol_gradient=bool((config or {}).get('resol_gradient')))
     if is_batch:
         return res[:-1]
     _raise_for_status(int(res[-1][0].item()),
@@ -572,10 +576,10 @@ def get_chisq_fisher(specdata, vel, atm_params, rot_params=None, options=None,
 
 def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
                 outside_penalty, resols, fast_interp, vsini_grad=False, fisher=False,
-                nn_gradient=False):
+                nn_gradient=False, resol_gradient=False):
     # (the checks come first: nothing is built for a call that is refused)
     engine.check_grad_scope(batch, libs, npoly, resols, fast_interp, vsini_grad,
-                            nn_gradient=nn_gradient)
+                            nn_gradient=nn_gradient, resol_gradient=resol_gradient)
     coefs, outs = [], []
     for arm in batch.arms:
         c, o = engine.build_templates(libs[arm.name], params, vsini, tangents=True,
@@ -584,8 +588,8 @@ def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
         outs.append(o)
     call = engine.chisq_point_fisher if fisher else engine.chisq_point_grad
     return call(batch, libs, coefs, outs, vel, npoly=npoly, rbf=rbf, job_spec=js,
-                espec_sys=esys, outside_penalty=outside_penalty,
-                nn_gradient=nn_gradient)
+                espec_sys=esys, outside_penalty=outside_penalty, resols=resols,
+                nn_gradient=nn_gradient, resol_gradient=resol_gradient)
 
 
 def chisq_fisher_jobs(batch, idx, vel, params, vsini, options, config,
@@ -627,7 +631,8 @@ def _chisq_grad_jobs(batch, idx, vel, params, vsini, options, config, outside_pe
     js = idx.to(torch.int32).contiguous()
     return _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
                        outside_penalty, resols, False, vsini_grad, fisher,
-                       nn_gradient=bool((config or {}).get('nn_gradient')))
+                       nn_gradient=bool((config or {}).get('nn_gradient')),
+                       resol_gradient=bool((config or {}).get('resol_gradient')))
 
 
 # rows per launch set of the from-template objective (template buffers of

@@ -765,7 +765,8 @@ def _uncertainties_from_fisher(F, names, stellar, prior_isig2=None, fixParam=())
 
 
 def fisher_uncertainties(specdata, vel, atm_params, vsini=None, options=None,
-                         config=None, priors=None, fixParam=None, vsini_grad=False):
+                         config=None, priors=None, fixParam=None, vsini_grad=False,
+                         resolParams=None):
     """Uncertainties from the Fisher matrix of the continuum-marginalised fit
     (spec_fit.get_chisq_fisher) at the given point: one deterministic call instead of the
     33+ objective evaluations of param_uncertainties, and positive semi-definite at any
@@ -781,7 +782,8 @@ def fisher_uncertainties(specdata, vel, atm_params, vsini=None, options=None,
       bad_fisher: an inverse that could not be formed or gave a non-finite error.
     One spectrum (list of SpecData; atm_params a dict or a sequence in the
     interpolator's order): floats and arrays as listed; a SpecBatch: the same with a
-    leading S axis.  The scope is get_chisq_grad's (ValueError otherwise)."""
+    leading S axis.  The scope is get_chisq_grad's (ValueError otherwise): resolution
+    matrices -- resolParams, or the SpecData's own -- with config['resol_gradient']."""
     batch, is_batch = as_batch(specdata)
     dev, S = batch.device, batch.S
     stellar = list(spec_inter.getSpecParams(batch.names[0], config))
@@ -796,7 +798,8 @@ def fisher_uncertainties(specdata, vel, atm_params, vsini=None, options=None,
     if vsini is not None:
         vs = _as_param_tensors(dict(vsini=vsini), S, dev)['vsini']
     _, _, F = spec_fit.get_chisq_fisher(batch, velt, pt, vs, options=options,
-                                        config=config, vsini_grad=vsini_grad)
+                                        config=config, resol_params=resolParams,
+                                        vsini_grad=vsini_grad)
     names = ['vel'] + stellar + (['vsini'] if vsini_grad else [])
     isig2 = {}
     for k, (_, sg) in (priors or {}).items():
@@ -1050,7 +1053,8 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
                                     spec_fit._resols(batch, resolParams),
                                     bool(options.get('fast_interp')),
                                     vsini_grad=fitVsini,
-                                    nn_gradient=bool(config.get('nn_gradient')))
+                                    nn_gradient=bool(config.get('nn_gradient')),
+                                    resol_gradient=bool(config.get('resol_gradient')))
         except ValueError as e:
             raise ValueError("config['second_minimizer_lm']: %s" % e) from None
         _libs = spec_inter.get_libs(batch.names, config)
@@ -1064,7 +1068,8 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
                                 spec_fit._resols(batch, resolParams),
                                 bool(options.get('fast_interp')),
                                 vsini_grad=fitVsini,
-                                nn_gradient=bool(config.get('nn_gradient')))
+                                nn_gradient=bool(config.get('nn_gradient')),
+                                resol_gradient=bool(config.get('resol_gradient')))
         # (and the batch must fit the chain's chunks: known here, not after the
         # simplex stage)
         _libs = spec_inter.get_libs(batch.names, config)
@@ -1084,7 +1089,8 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
                                     spec_fit._resols(batch, resolParams),
                                     bool(options.get('fast_interp')),
                                     vsini_grad=fitVsini,
-                                    nn_gradient=bool(config.get('nn_gradient')))
+                                    nn_gradient=bool(config.get('nn_gradient')),
+                                    resol_gradient=bool(config.get('resol_gradient')))
         except ValueError as e:
             raise ValueError("config['fisher_uncertainties']: %s" % e) from None
 
@@ -1310,7 +1316,8 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
         t0 = time.time()
         fu = fisher_uncertainties(batch if is_batch else specdata, best_vel, bparams,
                                   bvsini, options=options, config=config,
-                                  priors=priors, fixParam=fixParam, vsini_grad=fitVsini)
+                                  priors=priors, fixParam=fixParam, vsini_grad=fitVsini,
+                                  resolParams=resolParams)
         ret['covar_fisher'] = fu['covar']
         ret['names_fisher'] = fu['names']
         ret['vel_err_fisher'] = torch.as_tensor(fu['vel_err']).to(dev) if is_batch \

@@ -4,6 +4,10 @@ spec_fit.chisq_fisher_jobs call against ONE spec_fit.chisq_grad_jobs call on the
 jobs, and against vel_fit.param_uncertainties (the finite-difference Hessian of the
 stellar parameters: 33+ objective evaluations per spectrum) on the same S spectra.
 usage: fisher_ab.py [--jobs J] [--spectra S] [--npoly P] [--rounds R] [--vsini-grad]
+                    [--resolution-matrix]
+--resolution-matrix: every spectrum carries resolution matrices of 11 diagonals
+(tools/perf/_resol.py, as resol_ab.py builds them) and all three run under them, the
+first two with config['resol_gradient'] (rvs_chisq_point_fisher_resol / _grad_resol).
 The workload is bench.py's (its synthetic DESI-shape 3-arm libraries and spectra); the
 jobs are its truth parameters, jittered inside the grid, spread over the S spectra; the
 Hessian is taken at the first S jobs (one per spectrum).  The three run alternately in
@@ -27,6 +31,7 @@ def main():
     ap.add_argument('--npoly', type=int, default=10)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--vsini-grad', action='store_true')
+    ap.add_argument('--resolution-matrix', action='store_true')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
     import numpy as np
@@ -51,6 +56,10 @@ def main():
                               for n, lam, sp, es, bad in
                               bench.make_spectra_device(tp, dev)])
     cfg, opt = dict(bench.CONFIG), dict(bench.OPTIONS, npoly=args.npoly)
+    if args.resolution_matrix:
+        import _resol
+        _resol.attach(batch, S, dev)
+        cfg['resol_gradient'] = True
     libs = spec_inter.get_libs(batch.names, cfg)
     ndim = libs[batch.names[0]].ndim
     g = torch.Generator(device=dev)
@@ -104,6 +113,8 @@ def main():
     med = lambda v: round(float(np.median(v)), 6)   # noqa: E731
     print(json.dumps(dict(
         jobs=J, spectra=S, npoly=args.npoly, ndim=ndim, vsini_grad=vg, rounds=args.rounds,
+        resolution_matrix=args.resolution_matrix,
+        diagonals=11 if args.resolution_matrix else 0,
         fisher_s_median=med(tf), fisher_s_min=round(min(tf), 6),
         grad_s_median=med(tg), grad_s_min=round(min(tg), 6),
         fisher_over_grad_median=round(float(np.median(tf) / np.median(tg)), 3),

@@ -4,11 +4,16 @@ against the (2 + ndim) spec_fit.chisq_jobs calls of a forward difference (the po
 itself, then one call per displaced coordinate: velocity and the ndim parameters --
 what a caller without the gradient has to do, and what BFGS does per gradient).
 usage: grad_ab.py [--jobs J] [--spectra S] [--npoly P] [--rounds R] [--vsini]
-                  [--vsini-grad] [--evaluator polylinear|tri]
+                  [--vsini-grad] [--evaluator polylinear|tri] [--resolution-matrix]
 --evaluator tri: bench.py's Delaunay library (the same grid nodes triangulated, its
 `--evaluator tri`): rvs_template_tri_buckets_grad in front of the same chain.
 --vsini-grad (implies --vsini): the analytic call carries the vsini tangent row
 (vsini_grad=True) and the forward difference displaces vsini too: 3 + ndim calls.
+--resolution-matrix: every spectrum carries resolution matrices of 11 diagonals
+(tools/perf/_resol.py, as resol_ab.py builds them); the analytic call runs with
+config['resol_gradient'] (rvs_chisq_point_grad_resol), the forward difference under the
+same matrices, and a third arm is the same analytic call on the same spectra WITHOUT
+matrices, alternating with the two (no_matrix_s_*, resol_over_no_matrix_median).
 The workload is bench.py's (its synthetic DESI-shape libraries and
 spectra); the jobs are its truth parameters, jittered inside the grid, spread over the
 S spectra.  Both arms run alternately in one process, R rounds after a warm-up; one
@@ -34,6 +39,7 @@ def main():
     ap.add_argument('--vsini', action='store_true')
     ap.add_argument('--vsini-grad', action='store_true')
     ap.add_argument('--evaluator', choices=['polylinear', 'tri'], default='polylinear')
+    ap.add_argument('--resolution-matrix', action='store_true')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
     import numpy as np
@@ -59,6 +65,14 @@ def main():
                               for n, lam, sp, es, bad in
                               bench.make_spectra_device(tp, dev)])
     cfg, opt = dict(bench.CONFIG), dict(bench.OPTIONS, npoly=args.npoly)
+    plain = None
+    if args.resolution_matrix:
+        import _resol
+        plain = engine.SpecBatch([engine.ArmData(n, lam, sp, es, bad, device=dev)
+                                  for n, lam, sp, es, bad in
+                                  bench.make_spectra_device(tp, dev)])
+        _resol.attach(batch, S, dev)
+        cfg['resol_gradient'] = True
     libs = spec_inter.get_libs(batch.names, cfg)
     ndim = libs[batch.names[0]].ndim
     g = torch.Generator(device=dev)
@@ -81,6 +95,10 @@ def main():
         return spec_fit.chisq_grad_jobs(batch, idx, vel, par, vs, opt, cfg,
                                         vsini_grad=vg)
 
+    def no_matrix():
+        return spec_fit.chisq_grad_jobs(plain, idx, vel, par, vs, opt, cfg,
+                                        vsini_grad=vg)
+
     def differenced():
         f0, _ = spec_fit.chisq_jobs(batch, idx, vel, par, vs, opt, cfg)
         cols = []
@@ -101,18 +119,29 @@ def main():
         return time.perf_counter() - t0, out
 
     timed(analytic), timed(differenced)          # warm-up: tables, caches, clocks
-    ta, td = [], []
+    if plain is not None:
+        timed(no_matrix)
+    ta, td, tn = [], [], []
     for _ in range(args.rounds):
         t, (ca, ga, st) = timed(analytic)
         ta.append(t)
         t, (cd, gd) = timed(differenced)
         td.append(t)
+        if plain is not None:
+            tn.append(timed(no_matrix)[0])
+    more = {}
+    if plain is not None:
+        more = dict(no_matrix_s_median=round(float(np.median(tn)), 6),
+                    no_matrix_s_min=round(min(tn), 6),
+                    resol_over_no_matrix_median=round(
+                        float(np.median(ta) / np.median(tn)), 3))
     ok = (st == 0) & torch.isfinite(gd).all(dim=1)
     scale = torch.maximum(ga.abs(), 1e-6 * ga.abs().max(dim=1, keepdim=True).values)
     rel = ((ga - gd).abs() / scale)[ok]
     print(json.dumps(dict(
         jobs=J, spectra=S, npoly=args.npoly, ndim=ndim, evaluator=args.evaluator,
-        vsini=vs is not None,
+        vsini=vs is not None, resolution_matrix=args.resolution_matrix,
+        diagonals=11 if args.resolution_matrix else 0,
         vsini_grad=vg, rounds=args.rounds, chisq_jobs_calls=1 + x.shape[1],
         analytic_s_median=round(float(np.median(ta)), 6),
         analytic_s_min=round(min(ta), 6),
@@ -121,8 +150,8 @@ def main():
         speedup_median=round(float(np.median(td) / np.median(ta)), 2),
         jobs_ok=int(ok.sum()),
         value_max_rel_diff=float(((ca - cd).abs() / cd.abs().clamp(min=1e3))[ok].max()),
-        grad_vs_forward_difference_max_rel=float(rel.max()) if rel.numel() else None)),
-        flush=True)
+        grad_vs_forward_difference_max_rel=float(rel.max()) if rel.numel() else None,
+        **more)), flush=True)
 
 
 if __name__ == '__main__':

@@ -4,7 +4,10 @@
 config['second_minimizer_jac']) and Levenberg-Marquardt on the Fisher matrix (rvs_lm_run,
 config['second_minimizer_lm']), alternating, in one process.
 usage: lm_ab.py [--spectra S] [--npoly P] [--rounds R] [--evaluator polylinear|tri]
-                [--tau T]
+                [--tau T] [--resolution-matrix]
+--resolution-matrix: every spectrum carries resolution matrices of 11 diagonals
+(tools/perf/_resol.py, as resol_ab.py builds them); the differenced polish runs through
+the objective kernel's band, the other two through config['resol_gradient'].
 The workload is bench.py's, built as `bench.py --process` builds it (its synthetic
 DESI-shape libraries and seeded spectra, the start parameters from the CCF stage of
 pipeline.fit_batch).  vel_fit.process runs once without the second minimiser; its
@@ -33,6 +36,7 @@ def main():
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--evaluator', choices=['polylinear', 'tri'], default='polylinear')
     ap.add_argument('--tau', type=float, default=1e-3)
+    ap.add_argument('--resolution-matrix', action='store_true')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
     import numpy as np
@@ -59,6 +63,10 @@ def main():
                               for n, lam, sp, es, bad in
                               bench.make_spectra_device(tp, dev)])
     cfg, opt = dict(bench.CONFIG), dict(bench.OPTIONS, npoly=args.npoly)
+    if args.resolution_matrix:
+        import _resol
+        _resol.attach(batch, S, dev)
+        cfg['resol_gradient'] = True
     # the start of process: the CCF stage's parameters (bench.run_process_addon)
     rec = pipeline.fit_batch(batch, cfg, options=opt)
     F = pipeline.RECORD_FIELDS
@@ -134,6 +142,8 @@ def main():
 
     print(json.dumps(dict(
         spectra=S, npoly=args.npoly, evaluator=args.evaluator, rounds=args.rounds,
+        resolution_matrix=args.resolution_matrix,
+        diagonals=11 if args.resolution_matrix else 0, objective=pobj.form,
         n=len(cols), tau=args.tau, chain_cap=chain.cap, chain_bytes=chain.nbytes,
         fisher_chain_cap=fchain.cap, fisher_chain_bytes=fchain.nbytes,
         fd=mode(t_fd, a), jac=mode(t_jac, b, njev=per(b, 'njev')),

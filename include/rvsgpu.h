@@ -119,7 +119,11 @@ extern "C" {
  *      rvs_lm_state -- rvs_grad_chain and every other struct keep their layout; and
  *      rvs_chisq_point_grad_resol / rvs_chisq_point_fisher_resol with their work
  *      sizes, the gradient and the Fisher matrix under resolution matrices:
- *      rvs_chisq_point_grad and rvs_chisq_point_fisher go on refusing taps) */
+ *      rvs_chisq_point_grad and rvs_chisq_point_fisher go on refusing taps; and the
+ *      joint fit of a star's epochs: rvs_epoch_map, rvs_epoch_finish,
+ *      rvs_alm_row_size, rvs_alm_begin / _pending / _feed / _result / _end,
+ *      rvs_alm_run_bytes and rvs_alm_run with the new structs rvs_epoch_chain and
+ *      rvs_alm_state) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -1428,6 +1432,149 @@ int64_t rvs_lm_run_bytes(void);
 int rvs_lm_run(const rvs_lm_state *b, const rvs_nm_objective *o,
                const rvs_grad_chain *g, const rvs_fisher_chain *fc, int sync_every,
                int64_t *stats, void *stream);
+
+/* ------------------------------------------------------------------------
+ * The joint fit of a star's epochs (vel_fit.process_epochs): one set of stellar
+ * parameters (and one vsini) per star, one velocity per epoch.  Epochs are rows of one
+ * batch sorted by star: star n of a call owns the epochs eoff[n] .. eoff[n + 1] - 1
+ * (eoff device int32 [N + 1], eoff[0] = 0, S = eoff[N] epochs in all).  Its optimiser
+ * vector is z = (theta [m], v [E]): theta in the columns of the fitted parameters
+ * without the velocity -- [vsini,] free stellar parameters -- velocities in km/s.  The two kernels take
+ * m <= 6 (ntan <= 6, the limit of the gradient chain); the host machines m <= 7.
+ *
+ * rvs_epoch_map is the counterpart of rvs_proc_map: theta [N, m] and velin [S] -> per
+ * star star_id[n] = list[n] (the row of fixed / vsini_fixed / safe / prior_mean /
+ * prior_isig [., ndim]), vsini [N] (nullable: no rotation), params [N, ndim], extra [N]
+ * (the priors plus the vsini clamp penalty, counted ONCE per star) and bad [N] (a
+ * non-finite parameter, or ANY epoch's velocity outside [min_vel, max_vel]; the star's
+ * parameters are then `safe` and its velocities 0); per epoch vel [S] and, where
+ * job_templ is not NULL, job_templ[e] = n, the star's row (rvs_chisq_point_fisher's
+ * job_templ).  src [ndim] (HOST): column of THETA feeding library parameter i or -1;
+ * vsini_col: column of theta or -1.  The statements per parameter are rvs_proc_map's.
+ *
+ * rvs_epoch_finish turns the per-epoch rows of rvs_chisq_point_fisher -- chi [S],
+ * grad [S, K], fisher [S, K, K], K = 1 + ntan, computed with job_templ = the star's row
+ * -- into the star's arrow row at F + rowoff[n] (rowoff device int64 [N]):
+ *   f, g_theta [m], Htt packed (lower triangle row-major, m (m + 1) / 2),
+ *   then per epoch (g_e, h_e, c_e [m])
+ * rvs_alm_row_size(m, E) = 1 + m + m (m + 1) / 2 + E (2 + m) doubles (0 for m outside
+ * 1 .. 7 or E < 1).  f = sum_e chi_e + extra; g_theta, Htt from the sums over the star's
+ * epochs of grad and fisher, taken in epoch order as additions only, then mapped entry by
+ * entry as rvs_proc_finish_fisher maps them (factor 2 on the finished sum of the Fisher
+ * matrices, + 2 isig^2 and 2 (p - mean) isig^2 of a prior, the vsini column zeroed
+ * outside (0, max_vsini), the clamp penalty's 2 (x - clamp) and + 2); g_e = d/dv_e,
+ * h_e = 2 fisher_e[0, 0], c_e[i] = 2 fisher_e[row of theta_i, 0].  A bad star's row is
+ * 1e30 followed by zeros.  Status bits of the epochs of the live stars (n <
+ * counts[cidx], or all when counts == NULL) are OR-ed into star_status[star_id[n]].  One
+ * wave per star, no float atomics, no FMA contraction: tests/epochs_truth.py gives the
+ * same bits.  RVS_E_ARG: a NULL array, m > 7, ndim > 6, ntan > 6 (so m <= 6),
+ * ntan != ndim + (vsini_col >= 0), a src entry that is vsini_col or >= m, columns of
+ * theta without exactly one source. */
+int rvs_epoch_map(int N, int S, int m, int ndim, const double *theta,
+                  const double *velin, const int32_t *eoff, const int32_t *list,
+                  const int32_t *src, int vsini_col, const double *fixed,
+                  const double *vsini_fixed, const double *safe,
+                  const double *prior_mean, const double *prior_isig, double min_vel,
+                  double max_vel, double max_vsini, int32_t *star_id,
+                  int32_t *job_templ, double *vel, double *vsini, double *params,
+                  double *extra, int32_t *bad, void *stream);
+int rvs_epoch_finish(int N, int m, int ndim, int ntan, const int32_t *counts, int cidx,
+                     const int32_t *eoff, const int64_t *rowoff, const double *chi,
+                     const double *grad, const double *fisher, const double *theta,
+                     const double *params, const double *extra, const int32_t *bad,
+                     const int32_t *star_id, const int32_t *job_status,
+                     const int32_t *src, int vsini_col, const double *prior_mean,
+                     const double *prior_isig, double max_vsini, double *F,
+                     int32_t *star_status, void *stream);
+int64_t rvs_alm_row_size(int m, int E);
+
+/* Levenberg-Marquardt on the arrow rows, the machines on the host (csrc/alm_machine.h):
+ * the algorithm of rvs_lm_* over z, the dense Cholesky replaced by the elimination of
+ * the velocities (a Cholesky of the m x m Schur complement).  begin -> { pending -> the
+ * caller's objective -> feed } -> result -> end, with ragged buffers: star s (E_s =
+ * eoff[s + 1] - eoff[s] epochs, eoff HOST int32 [N + 1]) has its vector at
+ * s m + eoff[s] (m + E_s entries) and its row at s (1 + m + m (m + 1) / 2) +
+ * eoff[s] (2 + m).
+ *   begin    x0 ragged [N m + S]; gtol, xtol, tau, mu_max, maxiter as rvs_lm_begin
+ *            (maxiter <= 0: 200 (m + E_s)).  NULL for bad arguments, a star without
+ *            epochs among them
+ *   pending  idx [N], X [cap_values] out: the pending stars ascending and their vectors
+ *            one behind the other; returns the stars (0: all runs ended), -1 for a NULL
+ *            argument, -2 where cap_values is too small
+ *   feed     F: the rows of those stars one behind the other; nstars must be what
+ *            pending returned
+ *   result   x, grad ragged as x0; row (nullable) ragged: the row at x; fun, mu, nit,
+ *            nfev, status [N] and rounds as rvs_lm_result */
+void *rvs_alm_begin(int N, int m, const int32_t *eoff, const double *x0, double gtol,
+                    double xtol, double tau, double mu_max, int maxiter);
+int64_t rvs_alm_pending(void *h, int64_t *idx, double *X, int64_t cap_values);
+int rvs_alm_feed(void *h, const double *F, int64_t nstars);
+int rvs_alm_result(void *h, double *x, double *fun, double *grad, double *row,
+                   double *mu, int32_t *nit, int32_t *nfev, int32_t *status,
+                   int64_t *rounds);
+void rvs_alm_end(void *h);
+
+/* The same runs with their rounds inside the library: rvs_alm_run.  A round is
+ *   advance  one thread per star (csrc/alm_machine.h, the source of rvs_alm_begin): the
+ *            reply of the last request -> the run -> the vector it asks for next
+ *   look     nreq [N] is read by the host, which lays the pending stars out in chunks of
+ *            whole stars (at most cap_star stars and cap_epoch epochs each) and uploads a
+ *            chunk's tables (row offsets, local eoff, the star list, job_spec) in one copy
+ *   chunk    emit (the stars' vectors -> theta, velin) -> rvs_epoch_map -> per arm the
+ *            template / broadening / spline stage of rvs_bfgs_run_grad's chain over the
+ *            chunk's STARS -> the epochs' penalties -> rvs_chisq_point_fisher (or
+ *            _resol) with job_templ = the star's row -> rvs_epoch_finish into F
+ * with no interpreter in between.  The rows are those of the same entry points called
+ * from Python (optimizer.EpochChain.rows), so x, fun, nit, nfev and status are the bits
+ * of rvs_alm_begin / _pending / _feed around them.
+ *
+ * rvs_epoch_chain: arms / point / basis_const HOST arrays [narm] as in rvs_grad_chain,
+ * with the arm's templ, templ2, coef, outside, simplex, vs_rows, out_rows for cap_star
+ * rows and its penalty for cap_epoch jobs; fisher_work:
+ * rvs_chisq_point_fisher_work_size(cap_epoch, narm, ntan) bytes; chi [cap_epoch], grad
+ * [cap_epoch, K], fisher [cap_epoch, K, K]; the mapping's tables per star (fixed,
+ * vsini_fixed, safe, prior_mean, prior_isig: rows star 0 .. N - 1) and its buffers theta
+ * [cap_star, m], vsini, extra [cap_star], params [cap_star, ndim], star_id, bad int32
+ * [cap_star], velin, vel [cap_epoch], job_templ, jstatus int32 [cap_epoch]; status int32
+ * [N] (OR-ed into).  The epochs are rows eoff[n] .. eoff[n + 1] - 1 of the arms' spectra.
+ *
+ * rvs_alm_state: runs N * rvs_alm_run_bytes() bytes; state 5 (N m + S) + S + (the rows'
+ * total) doubles; eoff HOST and eoff_dev device int32 [N + 1]; x0, x, grad ragged [N m +
+ * S]; row, F ragged (the rows' total; row nullable); fun, mu [N]; nit, nfev, status, nreq
+ * int32 [N]; tab int32 [6 N + S + 16] (8-byte aligned); chi_x [S] (nullable; with it
+ * chi_trial [S], a work array): out, the chi of every epoch at its star's x (untouched
+ * for a star whose first row is bad).  gtol ... maxiter as
+ * rvs_alm_begin.  stats (nullable) int64[3] = rounds, chunks evaluated, star rows.
+ * RVS_E_ARG: a NULL array, m outside 1 .. 6, a star without epochs or with more than
+ * cap_epoch. */
+typedef struct rvs_epoch_chain {
+  const rvs_grad_arm *arms;
+  const rvs_point_arm *point;
+  const double *basis_const;
+  const double *pen_scale;
+  void *fisher_work;
+  double *chi, *grad, *fisher;
+  const double *fixed, *vsini_fixed, *safe, *prior_mean, *prior_isig;
+  double *theta, *vsini, *params, *extra, *velin, *vel;
+  int32_t *star_id, *bad, *job_templ, *jstatus, *status;
+  double min_vel, max_vel, max_vsini, badchi;
+  int32_t narm, npoly, ntan, vsini_mode, m, ndim, vsini_col, cap_star, cap_epoch,
+      reserved_;
+  int32_t src[8];
+} rvs_epoch_chain;
+typedef struct rvs_alm_state {
+  void *runs;
+  double *state;
+  const int32_t *eoff, *eoff_dev;
+  const double *x0;
+  double *x, *grad, *row, *fun, *mu, *F, *chi_trial, *chi_x;
+  int32_t *nit, *nfev, *status, *nreq, *tab;
+  double gtol, xtol, tau, mu_max;
+  int32_t N, m, maxiter, reserved_;
+} rvs_alm_state;
+int64_t rvs_alm_run_bytes(void);
+int rvs_alm_run(const rvs_alm_state *b, const rvs_epoch_chain *c, int64_t *stats,
+                void *stream);
 
 /* ------------------------------------------------------------------------
  * Template libraries from high-resolution models; replaces rvs_make_interpol's

@@ -104,6 +104,18 @@ SIGNATURES = {
     'rvs_lm_end': (None, [P]),
     'rvs_lm_run_bytes': (L, []),
     'rvs_lm_run': (I, [P, P, P, P, I, P, P]),
+    'rvs_epoch_map': (I, [I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, D, D, D, P, P, P,
+                          P, P, P, P, P]),
+    'rvs_epoch_finish': (I, [I, I, I, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P,
+                             P, D, P, P, P]),
+    'rvs_alm_row_size': (L, [I, I]),
+    'rvs_alm_begin': (P, [I, I, P, P, D, D, D, D, I]),
+    'rvs_alm_pending': (L, [P, P, P, L]),
+    'rvs_alm_feed': (I, [P, P, L]),
+    'rvs_alm_result': (I, [P, P, P, P, P, P, P, P, P, P]),
+    'rvs_alm_end': (None, [P]),
+    'rvs_alm_run_bytes': (L, []),
+    'rvs_alm_run': (I, [P, P, P, P]),
     'rvs_objective_max_ntp': (I, [I]),
     'rvs_objective_resol_ok': (I, [I, I, I, I]),
     'rvs_objective_work_size': (L, [I, I]),
@@ -294,6 +306,31 @@ class LmState(ctypes.Structure):
                     (k, ctypes.c_double) for k in
                     ('gtol', 'xtol', 'tau', 'mu_max')] + [
                     (k, ctypes.c_int32) for k in ('S', 'n', 'maxiter', 'reserved_')]
+
+
+class EpochChain(ctypes.Structure):
+    """rvs_epoch_chain of include/rvsgpu.h"""
+    _fields_ = [(k, ctypes.c_void_p) for k in
+                ('arms', 'point', 'basis_const', 'pen_scale', 'fisher_work', 'chi',
+                 'grad', 'fisher', 'fixed', 'vsini_fixed', 'safe', 'prior_mean',
+                 'prior_isig', 'theta', 'vsini', 'params', 'extra', 'velin', 'vel',
+                 'star_id', 'bad', 'job_templ', 'jstatus', 'status')] + [
+                    (k, ctypes.c_double) for k in
+                    ('min_vel', 'max_vel', 'max_vsini', 'badchi')] + [
+                    (k, ctypes.c_int32) for k in
+                    ('narm', 'npoly', 'ntan', 'vsini_mode', 'm', 'ndim', 'vsini_col',
+                     'cap_star', 'cap_epoch', 'reserved_')] + [
+                    ('src', ctypes.c_int32 * 8)]
+
+
+class AlmState(ctypes.Structure):
+    """rvs_alm_state of include/rvsgpu.h"""
+    _fields_ = [(k, ctypes.c_void_p) for k in
+                ('runs', 'state', 'eoff', 'eoff_dev', 'x0', 'x', 'grad', 'row', 'fun',
+                 'mu', 'F', 'chi_trial', 'chi_x', 'nit', 'nfev', 'status', 'nreq', 'tab')] + [
+                    (k, ctypes.c_double) for k in
+                    ('gtol', 'xtol', 'tau', 'mu_max')] + [
+                    (k, ctypes.c_int32) for k in ('N', 'm', 'maxiter', 'reserved_')]
 
 
 class PointArm(ctypes.Structure):

@@ -18,6 +18,7 @@ synchronisations per round cost more than the GPU work, hence the kernels.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -753,3 +754,347 @@ class TorchObjective:
 
     def eval(self, list_t, X, J, counts, cidx, F):
         F[:J] = self.func(list_t[:J].long(), X[:J])
+
+
+class EpochChain:
+    """The joint objective of vel_fit.process_epochs: one set of stellar parameters (and
+    one vsini) per star, one velocity per epoch.  GradChain(fisher=True) with two
+    capacities -- `cap_star` rows for the template / FIR / spline stage, which runs ONCE
+    per star, and `cap_epoch` jobs for the point stage, which reads a star's records
+    through job_templ:
+
+      rvs_epoch_map            theta [J, m], v -> per star params, vsini, prior / vsini
+                               penalty, bad; per epoch vel and job_templ
+      engine.build_templates   per arm: the star's template, its tangents, the
+                               broadening, the spline records (cap_star rows)
+      rvs_chisq_point_fisher   chi, grad, fisher of every epoch; the penalty of an epoch
+                               is outside[star] x badchi of the epoch's spectrum
+      rvs_epoch_finish         the star's arrow row (alm.row_size)
+
+    `batch` holds the epochs sorted by star: star n owns the rows eoff[n] ..
+    eoff[n + 1] - 1.  pd0 / priors / safe_params are per STAR ([N] / [N, ndim]).  theta's
+    columns are ParamMapper.get_fitted_params() without 'vel': [vsini,] free stellar
+    parameters.  A chunk holds whole stars.  The scope is engine.check_grad_scope's."""
+
+    def __init__(self, batch, libs, names, pd0, fixParam, fitVsini, config, options,
+                 priors, safe_params, eoff, resols=None, cap_star=None, cap_epoch=None):
+        from . import alm
+        self.batch, self.libs = batch, libs
+        dev = batch.device
+        self.dev = dev
+        self.eoff = np.asarray(eoff, dtype=np.int64)
+        self.nE = np.diff(self.eoff)
+        N = len(self.nE)
+        if N < 1 or self.eoff[0] != 0 or self.eoff[-1] != batch.S:
+            raise ValueError('EpochChain: eoff does not cover the %d epochs of the batch'
+                             % batch.S)
+        if (self.nE < 1).any():
+            raise ValueError('EpochChain: star %d has no epochs'
+                             % int(np.nonzero(self.nE < 1)[0][0]))
+        self.N = N
+        self.npoly = options.get('npoly') or 5
+        self.rbf = options.get('rbf_continuum', True)
+        self.resols = resols
+        self.nn_gradient = bool(config.get('nn_gradient'))
+        self.resol_gradient = bool(config.get('resol_gradient'))
+        engine.check_grad_scope(batch, libs, self.npoly, resols,
+                                bool(options.get('fast_interp')), vsini_grad=fitVsini,
+                                nn_gradient=self.nn_gradient,
+                                resol_gradient=self.resol_gradient)
+        self.ndim = len(names)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.has_vsini = 'vsini' in pd0
+        k = 0
+        self.vsini_col = -1
+        if fitVsini:
+            self.vsini_col = k
+            k += 1
+        src = []
+        for x in names:
+            if x in fixParam:
+                src.append(-1)
+            else:
+                src.append(k)
+                k += 1
+        self.m = k
+        if not 1 <= self.m <= alm.MAXM:
+            raise ValueError('the joint fit takes 1 <= m <= %d shared parameters per '
+                             'star, not m = %d' % (alm.MAXM, self.m))
+        self.ntan = self.ndim + (1 if fitVsini else 0)
+        self.src = (ctypes.c_int32 * self.ndim)(*src)
+        self.fixed = torch.stack([pd0[_] for _ in names], dim=1).contiguous()
+        self.vsini_fixed = pd0['vsini'].contiguous() if (
+            self.has_vsini and not fitVsini) else None
+        self.safe = safe_params.contiguous()
+        assert self.fixed.shape == (N, self.ndim) and self.safe.shape == self.fixed.shape
+        self.prior_mean = self.prior_isig = None
+        if priors:
+            pm = torch.zeros((N, self.ndim), **f64)
+            ps = torch.zeros((N, self.ndim), **f64)
+            for i, x in enumerate(names):
+                if x in priors:
+                    mu, sg = priors[x]
+                    pm[:, i] = torch.as_tensor(mu, **f64)
+                    ps[:, i] = 1.0 / torch.as_tensor(sg, **f64)
+            self.prior_mean, self.prior_isig = pm, ps
+        self.min_vel, self.max_vel = float(config['min_vel']), float(config['max_vel'])
+        self.max_vsini = float(config['max_vsini'])
+        # capacities: the template stage's buffers are the chain's big ones
+        ntps = [libs[a.name].ntp for a in batch.arms]
+        if cap_star is None:
+            L = _lib.lib()
+            ntp = (ctypes.c_int32 * len(ntps))(*ntps)
+            one = L.rvs_fisher_chain_work_size(
+                1, len(ntps), self.ntan, ntp,
+                2 if fitVsini else (1 if self.has_vsini else 0))
+            if one <= 0:
+                raise ValueError('EpochChain: %d arms / %d tangents are outside '
+                                 'rvs_fisher_chain_work_size' % (len(ntps), self.ntan))
+            cap_star = max(1, min(N, int(GRAD_CHAIN_BUDGET // one)))
+        self.cap_star = int(cap_star)
+        self.cap_epoch = int(batch.S if cap_epoch is None else cap_epoch)
+        if self.cap_star < 1 or int(self.nE.max()) > self.cap_epoch:
+            raise ValueError('EpochChain: star %d has %d epochs, a chunk holds whole '
+                             'stars and cap_epoch = %d epochs'
+                             % (int(self.nE.argmax()), int(self.nE.max()),
+                                self.cap_epoch))
+        self.status = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.calls = 0          # chunks evaluated
+        self.star_rows = 0      # template-stage rows (stars)
+        self.epoch_jobs = 0     # point-stage jobs (epochs)
+        self.keep_epochs = False
+        self.epochs = None      # the epochs' chi, grad, fisher of the last rows() call
+
+    def _chunk(self, ids, theta, vel):
+        from . import alm
+        L, dev, st = _lib.lib(), self.dev, _lib.stream()
+        n, m, ndim = len(ids), self.m, self.ndim
+        nE = self.nE[ids]
+        leoff = np.concatenate([[0], np.cumsum(nE)])
+        S = int(leoff[-1])
+        ro = alm.offsets(m, leoff)[1]
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        # one upload of the chunk's integer tables (rowoff first: int64 at offset 0) and
+        # one of its vectors, not six small copies per chunk and round
+        ids = np.asarray(ids, dtype=np.int64)
+        spec = np.repeat(self.eoff[ids] - leoff[:-1], nE) + np.arange(S)
+        ints = torch.as_tensor(np.concatenate([
+            ro[:-1].astype(np.int64).view(np.int32), leoff.astype(np.int32),
+            ids.astype(np.int32), spec.astype(np.int32)])).to(dev)
+        ro_t = ints[:2 * n].view(torch.int64)
+        eoff_t = ints[2 * n:3 * n + 1]
+        list_t = ints[3 * n + 1:4 * n + 1]
+        job_spec = ints[4 * n + 1:]
+        vecs = torch.as_tensor(np.concatenate([
+            np.asarray(theta, dtype=np.float64).reshape(-1),
+            np.asarray(vel, dtype=np.float64).reshape(-1)])).to(dev)
+        theta_t, velin = vecs[:n * m].view(n, m), vecs[n * m:]
+        assert theta_t.shape == (n, m) and velin.shape == (S, )
+        star_id, bad = torch.empty(n, **i32), torch.empty(n, **i32)
+        job_templ = torch.empty(S, **i32)
+        velo, params = torch.empty(S, **f64), torch.empty((n, ndim), **f64)
+        vsini = torch.empty(n, **f64) if self.has_vsini else None
+        extra = torch.empty(n, **f64)
+        rc = L.rvs_epoch_map(n, S, m, ndim, _p(theta_t), _p(velin), _p(eoff_t),
+                             _p(list_t), self.src, self.vsini_col, _p(self.fixed),
+                             _p(self.vsini_fixed), _p(self.safe), _p(self.prior_mean),
+                             _p(self.prior_isig), self.min_vel, self.max_vel,
+                             self.max_vsini, _p(star_id), _p(job_templ), _p(velo),
+                             _p(vsini), _p(params), _p(extra), _p(bad), st)
+        _lib.check(rc, 'rvs_epoch_map')
+        coefs, outs = [], []
+        for arm in self.batch.arms:
+            c, o = engine.build_templates(self.libs[arm.name], params, vsini,
+                                          tangents=True,
+                                          vsini_tangent=self.vsini_col >= 0)
+            coefs.append(c)
+            outs.append(o)
+        chi, grad, fisher, status = engine.chisq_point_fisher(
+            self.batch, self.libs, coefs, outs, velo, npoly=self.npoly, rbf=self.rbf,
+            job_spec=job_spec, job_templ=job_templ, resols=self.resols,
+            nn_gradient=self.nn_gradient, resol_gradient=self.resol_gradient)
+        F = torch.empty(int(ro[-1]), **f64)
+        # (named before their pointers are taken: they outlive the launch)
+        grad, fisher = grad.contiguous(), fisher.contiguous()
+        rc = L.rvs_epoch_finish(n, m, ndim, self.ntan, None, 0, _p(eoff_t), _p(ro_t),
+                                _p(chi), _p(grad), _p(fisher),
+                                _p(theta_t), _p(params), _p(extra), _p(bad), _p(star_id),
+                                _p(status), self.src, self.vsini_col,
+                                _p(self.prior_mean), _p(self.prior_isig), self.max_vsini,
+                                _p(F), _p(self.status), st)
+        _lib.check(rc, 'rvs_epoch_finish')
+        self.calls += 1
+        self.star_rows += n
+        self.epoch_jobs += S
+        ep = None
+        if self.keep_epochs == 'values':    # (what process_epochs reports, no more)
+            ep = dict(chi=chi.cpu().numpy(), params=params.cpu().numpy(),
+                      vsini=None if vsini is None else vsini.cpu().numpy())
+        elif self.keep_epochs:
+            ep = dict(chi=chi.cpu().numpy(), grad=grad.cpu().numpy(),
+                      fisher=fisher.cpu().numpy(), status=status.cpu().numpy(),
+                      params=params.cpu().numpy(), extra=extra.cpu().numpy(),
+                      bad=bad.cpu().numpy(), vel=velo.cpu().numpy(),
+                      vsini=None if vsini is None else vsini.cpu().numpy())
+        return F.cpu().numpy(), ep
+
+    def rows(self, star_idx, theta, vel):
+        """the arrow rows of the stars star_idx [J] at theta [J, m] and the velocities
+        `vel` (ragged: the stars' epochs one behind the other), numpy in, the ragged
+        rows as numpy out -- the objective of alm.minimize_lockstep_native."""
+        ids = np.asarray(star_idx, dtype=np.int64).reshape(-1)
+        theta = np.asarray(theta, dtype=np.float64).reshape(len(ids), self.m)
+        vel = np.asarray(vel, dtype=np.float64).reshape(-1)
+        nE = self.nE[ids]
+        if vel.shape[0] != nE.sum():
+            raise ValueError('EpochChain.rows: %d velocities for %d epochs'
+                             % (vel.shape[0], nE.sum()))
+        out, eps = [], []
+        a = va = 0
+        one = len(ids) <= self.cap_star and nE.sum() <= self.cap_epoch
+        while a < len(ids):
+            b, ne = (len(ids), int(nE.sum())) if one else (a, 0)
+            while b < len(ids) and b - a < self.cap_star and \
+                    ne + nE[b] <= self.cap_epoch:
+                ne += int(nE[b])
+                b += 1
+            F, ep = self._chunk(ids[a:b], theta[a:b], vel[va:va + ne])
+            out.append(F)
+            eps.append(ep)
+            a, va = b, va + ne
+        if self.keep_epochs:
+            self.epochs = {k: (None if eps[0][k] is None else
+                               np.concatenate([e[k] for e in eps])) for k in eps[0]}
+        return np.concatenate(out)
+
+    def objective(self, idx, X, xoff):
+        """rows() in the calling convention of alm.minimize_lockstep_native: X holds
+        the vectors (theta [m], v [E]) of the stars idx one behind the other"""
+        m = self.m
+        xoff = np.asarray(xoff, dtype=np.int64)
+        X = np.asarray(X, dtype=np.float64)
+        at = xoff[:-1, None] + np.arange(m)[None, :]
+        isvel = np.ones(int(xoff[-1]), dtype=bool)
+        isvel[at.reshape(-1)] = False
+        return self.rows(idx, X[at], X[:int(xoff[-1])][isvel])
+
+    def native_desc(self):
+        """rvs_epoch_chain: this chain for the rounds inside the library (rvs_alm_run),
+        built once: the arm descriptors of GradChain with the template stage's buffers
+        for cap_star rows and the point stage's for cap_epoch jobs"""
+        if getattr(self, '_native', None) is not None:
+            return self._native
+        L = _lib.lib()
+        batch, libs, dev = self.batch, self.libs, self.dev
+        narm = len(batch.arms)
+        cs, ce = self.cap_star, self.cap_epoch
+        fit = self.vsini_col >= 0
+        mode = 2 if fit else (1 if self.has_vsini else 0)
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        K, R = 1 + self.ntan, 1 + self.ndim
+        arms = (_lib.GradArm * narm)()
+        point = (_lib.PointArm * narm)()
+        bconst = (ctypes.c_double * narm)()
+        keep = []
+        for ia, arm in enumerate(batch.arms):
+            lib = libs[arm.name]
+            b = dict(templ=torch.empty((cs, K, lib.ntp), **f64),
+                     templ2=torch.empty((cs, K, lib.ntp), **f64) if mode else None,
+                     coef=torch.empty((cs, K, lib.ntp, 4), **f64),
+                     outside=torch.empty(cs, **f64), penalty=torch.empty(ce, **f64),
+                     simplex=torch.empty(cs, **i32),
+                     vs_rows=torch.empty(cs * R, **f64) if mode == 1 else None,
+                     out_rows=torch.empty(cs * R, **f64) if mode == 1 else None)
+            a = arms[ia]
+            for k, t in b.items():
+                setattr(a, k, None if t is None else t.data_ptr())
+            a.knots = lib.knots.data_ptr()
+            if lib.kind != 'nn':
+                a.dats = lib.dats.data_ptr()
+            a.factors = None if lib.spline_factors is None else \
+                lib.spline_factors.data_ptr()
+            a.spline_form, a.lnstep = lib.spline_form, lib.lnstep
+            a.ntp, a.log_mask = lib.ntp, lib.log_mask
+            a.exp_flag = getattr(lib, 'exp_flag', 1)
+            if lib.kind == 'nn':
+                lib.check_nn_grad_scope()
+                n = _lib.NmNNArm()
+                nl = len(lib.nn_W)
+                Wp = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in lib.nn_W])
+                bp = (ctypes.c_void_p * nl)(*[x.data_ptr() for x in lib.nn_b])
+                b['a1'] = torch.empty((cs * R, lib.nn_width()), dtype=torch.float32,
+                                      device=dev)
+                b['a0'] = b['a1'][:1]
+                n.M, n.S = lib.nn_M.data_ptr(), lib.nn_S.data_ptr()
+                n.W = ctypes.cast(Wp, ctypes.c_void_p)
+                n.b = ctypes.cast(bp, ctypes.c_void_p)
+                n.dims = lib.nn_dims.ctypes.data
+                n.act0, n.act1 = b['a0'].data_ptr(), b['a1'].data_ptr()
+                n.templ = n.outside = None
+                hull = lib.hull_device()
+                if hull is None:
+                    n.xeqs = n.yeqs = None
+                    n.nfx = n.nfy = 0
+                else:
+                    n.xeqs, n.yeqs = hull[0].data_ptr(), hull[1].data_ptr()
+                    n.nfx, n.nfy = hull[0].shape[0], hull[1].shape[0]
+                n.nlayer, n.log_mask = nl, lib.log_mask
+                a.tri, a.dats = 2, ctypes.addressof(n)
+                keep += [n, Wp, bp, hull]
+            elif lib.kind == 'triangulation':
+                from . import library
+                a.tri, a.nsimplex = 1, lib.tri_nsimplex
+                a.transform = lib.tri_transform.data_ptr()
+                a.extraflags = lib.tri_extraflags.data_ptr()
+                a.simplices = lib.tri_simplices.data_ptr()
+                if lib._tri_bk is not None and library.TRI_BUCKETS:
+                    a.buckets = lib._tri_bk
+            else:
+                a.tri, a.ngrid = 0, lib.ngrid
+                a.idgrid, a.uvecs = lib.idgrid.data_ptr(), lib.uvecs.data_ptr()
+                a.vecs_s = lib.vecs_s.data_ptr()
+                a.lens, a.ptp = lib.lens.ctypes.data, lib.ptp.ctypes.data
+            keep.append(b)
+            rs = engine._arm_resol(arm, ia, self.resols)
+            if rs is not None:
+                engine.check_grad_resol_lds(self.ntan, rs['nd'])
+            keep.append(engine.fill_point_arm(point[ia], arm, lib, self.npoly, self.rbf,
+                                              0.0, rs, b['coef'], b['penalty']))
+            qt, const = arm.basis_ortho(self.npoly, self.rbf)
+            point[ia].polysT = qt.data_ptr()
+            bconst[ia] = const
+            keep.append(qt)
+        nb = L.rvs_chisq_point_fisher_work_size(ce, narm, self.ntan)
+        bufs = dict(fisher_work=torch.empty((nb + 7) // 8, **f64),
+                    chi=torch.empty(ce, **f64), grad=torch.empty((ce, K), **f64),
+                    fisher=torch.empty((ce, K, K), **f64),
+                    theta=torch.empty((cs, self.m), **f64),
+                    vsini=torch.empty(cs, **f64) if self.has_vsini else None,
+                    params=torch.empty((cs, self.ndim), **f64),
+                    extra=torch.empty(cs, **f64), velin=torch.empty(ce, **f64),
+                    vel=torch.empty(ce, **f64), star_id=torch.empty(cs, **i32),
+                    bad=torch.empty(cs, **i32), job_templ=torch.empty(ce, **i32),
+                    jstatus=torch.empty(ce, **i32))
+        c = _lib.EpochChain()
+        c.arms, c.point = ctypes.addressof(arms), ctypes.addressof(point)
+        c.basis_const = ctypes.addressof(bconst)
+        ps = batch.pen_scale
+        c.pen_scale = None if ps is None else ps.data_ptr()
+        for k, t in bufs.items():
+            setattr(c, k, None if t is None else t.data_ptr())
+        for k, t in (('fixed', self.fixed), ('vsini_fixed', self.vsini_fixed),
+                     ('safe', self.safe), ('prior_mean', self.prior_mean),
+                     ('prior_isig', self.prior_isig), ('status', self.status)):
+            setattr(c, k, None if t is None else t.data_ptr())
+        c.min_vel, c.max_vel = self.min_vel, self.max_vel
+        c.max_vsini, c.badchi = self.max_vsini, float(batch.badchi)
+        c.narm, c.npoly, c.ntan, c.vsini_mode = narm, self.npoly, self.ntan, mode
+        c.m, c.ndim, c.vsini_col = self.m, self.ndim, self.vsini_col
+        c.cap_star, c.cap_epoch = cs, ce
+        for i in range(8):
+            c.src[i] = self.src[i] if i < self.ndim else -1
+        self._native_keep = (arms, point, bconst, keep, bufs)
+        self._native = c
+        return c

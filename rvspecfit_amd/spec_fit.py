@@ -603,6 +603,113 @@ def chisq_fisher_jobs(batch, idx, vel, params, vsini, options, config,
                             vsini_grad, True)
 
 
+def epochs_order(star, S, N=None):
+    """star [S] (int, the star 0 .. N - 1 of every epoch, any order) -> (order: the stable
+    sort by star, eoff [N + 1]: star n owns order[eoff[n] : eoff[n + 1]]).  ValueError
+    for labels that are not integers in 0 .. N - 1 or a star without epochs."""
+    star = np.asarray(star)
+    if star.shape != (S, ) or not np.issubdtype(star.dtype, np.integer):
+        raise ValueError('star: one integer per epoch, %d in all, not %s %s'
+                         % (S, star.dtype, star.shape))
+    if S == 0 or star.min() < 0:
+        raise ValueError('star: labels are 0 .. N - 1')
+    N = int(star.max()) + 1 if N is None else int(N)
+    if star.max() >= N:
+        raise ValueError('star: label %d, but there are %d stars' % (star.max(), N))
+    cnt = np.bincount(star, minlength=N)
+    if (cnt == 0).any():
+        raise ValueError('star %d has no epochs' % int(np.nonzero(cnt == 0)[0][0]))
+    return np.argsort(star, kind='stable'), np.concatenate([[0], np.cumsum(cnt)])
+
+
+def chisq_fisher_epochs(batch, star, vel, params, vsini, options, config,
+                        outside_penalty=True, espec_systematic=None, resol_params=None,
+                        vsini_grad=False):
+    """The joint form of chisq_fisher_jobs: the S epochs of `batch` belong to the stars
+    star [S] (int, 0 .. N - 1, any order), every star has ONE row of params [N, ndim]
+    (and vsini [N]) and every epoch its own velocity vel [S].  The template stage runs
+    once per star; rvs_chisq_point_fisher reads a star's records through job_templ and
+    rvs_epoch_finish sums the star's epochs in epoch order.  theta = ([vsini with
+    vsini_grad,] library parameters) -- the columns of process_epochs with nothing fixed
+    -- physical units, 0 < vsini.  Returns a dict of numpy
+    arrays: chisq [N] (the sum over the epochs), grad_theta [N, m], hess_theta [N, m, m],
+    and per epoch, in the order of the input, chisq_epoch, grad_vel, hess_vel [S] and
+    hess_cross [S, m] -- the arrow blocks of the Gauss-Newton Hessian of chisq, twice the
+    Fisher matrix -- and status [S]."""
+    import ctypes
+    from . import alm
+    if vsini_grad and vsini is None:
+        raise ValueError('vsini_grad=True needs vsini: without rotation there is no '
+                         'vsini to differentiate by')
+    options = options or {}
+    npoly = options.get('npoly') or 5
+    rbf = options.get('rbf_continuum', True)
+    dev = batch.device
+    S = batch.S
+    params = torch.as_tensor(params, dtype=torch.float64).to(dev).contiguous()
+    N, ndim = params.shape
+    order, eoff = epochs_order(star, S, N)
+    cnt = np.diff(eoff)
+    libs = spec_inter.get_libs(batch.names, config)
+    esys = float(espec_systematic) if espec_systematic is not None else 0.0
+    resols = _resols(batch, resol_params)
+    nn_g = bool((config or {}).get('nn_gradient'))
+    rs_g = bool((config or {}).get('resol_gradient'))
+    engine.check_grad_scope(batch, libs, npoly, resols, False, vsini_grad,
+                            nn_gradient=nn_g, resol_gradient=rs_g)
+    m = ndim + (1 if vsini_grad else 0)    # (<= 6: check_grad_scope's tangents)
+    if vsini is not None:
+        vsini = torch.as_tensor(vsini, dtype=torch.float64).to(dev).contiguous()
+    vel_s = torch.as_tensor(vel, dtype=torch.float64).to(dev)[
+        torch.as_tensor(order).to(dev)].contiguous()
+    js = torch.as_tensor(order.astype(np.int32)).to(dev)
+    jt = torch.as_tensor(np.repeat(np.arange(N), cnt).astype(np.int32)).to(dev)
+    coefs, outs = [], []
+    for arm in batch.arms:
+        c, o = engine.build_templates(libs[arm.name], params, vsini, tangents=True,
+                                      vsini_tangent=vsini_grad)
+        coefs.append(c)
+        outs.append(o)
+    chi, grad, fisher, status = engine.chisq_point_fisher(
+        batch, libs, coefs, outs, vel_s, npoly=npoly, rbf=rbf, job_spec=js,
+        job_templ=jt, espec_sys=esys, outside_penalty=outside_penalty, resols=resols,
+        nn_gradient=nn_g, resol_gradient=rs_g)
+    theta = params if not vsini_grad else torch.cat([vsini[:, None], params], dim=1)
+    theta = theta.contiguous()
+    ro = alm.offsets(m, eoff)[1]
+    i32 = dict(dtype=torch.int32, device=dev)
+    F = torch.empty(int(ro[-1]), dtype=torch.float64, device=dev)
+    zero = torch.zeros(N, dtype=torch.float64, device=dev)
+    src = (ctypes.c_int32 * ndim)(*range(int(vsini_grad), ndim + int(vsini_grad)))
+    star_status = torch.zeros(N, **i32)
+    L = _lib.lib()
+    # (named, so that every table outlives the launch: a temporary's block goes back to
+    # the allocator at once and the next tensor takes it)
+    eoff_t = torch.as_tensor(eoff.astype(np.int32)).to(dev)
+    ro_t = torch.as_tensor(ro[:-1].copy()).to(dev)
+    bad_t, id_t = torch.zeros(N, **i32), torch.arange(N, **i32)
+    grad, fisher = grad.contiguous(), fisher.contiguous()
+    rc = L.rvs_epoch_finish(
+        N, m, ndim, m, None, 0, _lib.ptr(eoff_t), _lib.ptr(ro_t), _lib.ptr(chi),
+        _lib.ptr(grad), _lib.ptr(fisher), _lib.ptr(theta), _lib.ptr(params),
+        _lib.ptr(zero), _lib.ptr(bad_t), _lib.ptr(id_t), _lib.ptr(status), src,
+        0 if vsini_grad else -1, None, None, 1e300, _lib.ptr(F),
+        _lib.ptr(star_status), _lib.stream())
+    _lib.check(rc, 'rvs_epoch_finish')
+    F = F.cpu().numpy()
+    inv = np.empty(S, dtype=np.int64)
+    inv[order] = np.arange(S)
+    parts = [alm.unpack_row(F[ro[n]:ro[n + 1]], m, cnt[n]) for n in range(N)]
+    return dict(chisq=np.array([q[0] for q in parts]),
+                grad_theta=np.stack([q[1] for q in parts]),
+                hess_theta=np.stack([q[2] for q in parts]),
+                chisq_epoch=chi.cpu().numpy()[inv],
+                grad_vel=np.concatenate([q[3] for q in parts])[inv],
+                hess_vel=np.concatenate([q[4] for q in parts])[inv],
+                hess_cross=np.concatenate([q[5] for q in parts])[inv],
+                status=status.cpu().numpy()[inv], rows=F, eoff=eoff, order=order)
+
+
 def chisq_grad_jobs(batch, idx, vel, params, vsini, options, config,
                     outside_penalty=True, espec_systematic=None, resol_params=None,
                     vsini_grad=False):

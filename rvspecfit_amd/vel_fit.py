@@ -1344,3 +1344,238 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
 def _lib_nonfinite():
     from . import _lib
     return _lib.ST_NONFINITE
+
+
+# --------------------------------------------------------------------------
+# the joint fit of a star's epochs: shared parameters, one velocity each
+# --------------------------------------------------------------------------
+def _epochs_batch(specdata):
+    """SpecBatch of the epochs: a SpecBatch as it is, or a list of epochs, each the list
+    of SpecData of its arms (the same arms in every epoch)"""
+    if isinstance(specdata, SpecBatch):
+        return specdata
+    epochs = [list(e) if isinstance(e, (list, tuple)) else [e] for e in specdata]
+    if not epochs:
+        raise ValueError('process_epochs: no epochs')
+    arms = [sd.name for sd in epochs[0]]
+    for i, e in enumerate(epochs):
+        if [sd.name for sd in e] != arms:
+            raise ValueError('process_epochs: epoch %d has the arms %s, epoch 0 has %s'
+                             % (i, [sd.name for sd in e], arms))
+    return SpecBatch.from_specdata(epochs)
+
+
+def _arrow_uncertainties(rows, m, eoff):
+    """Uncertainties from the arrow rows (alm.row_size) at the optimum, mu = 0, on the
+    host.  The rows hold the Gauss-Newton Hessian of chi^2, twice the Fisher matrix:
+    with S = Htt - sum_e c_e c_e^T / h_e the parameter covariance is 2 S^-1 (through
+    _uncertainties_from_hessians after the symmetric scaling _uncertainties_from_fisher
+    uses) and the variance of a velocity, marginalised over the parameters, is
+    2 (1 / h_e + c_e^T S^-1 c_e / h_e^2).  Returns theta_err [N, m], covar [N, m, m],
+    vel_err [S] (nan where h_e <= 0), bad [N]."""
+    from . import alm
+    eoff = np.asarray(eoff, dtype=np.int64)
+    rows = np.asarray(rows, dtype=np.float64)
+    N = len(eoff) - 1
+    nE = np.diff(eoff)
+    ro = alm.offsets(m, eoff)[1]
+    il = np.tril_indices(m)
+    head = 1 + m + len(il[0])
+    Sm = np.zeros((N, m, m))
+    groups = []
+    # (stars of the same number of epochs together: their rows are one 2-d block)
+    for E in np.unique(nE):
+        sel = np.nonzero(nE == E)[0]
+        R = rows[ro[sel, None] + np.arange(alm.row_size(m, int(E)))[None, :]]
+        H = np.zeros((len(sel), m, m))
+        H[:, il[0], il[1]] = R[:, 1 + m:head]
+        H[:, il[1], il[0]] = R[:, 1 + m:head]
+        rec = R[:, head:].reshape(len(sel), int(E), 2 + m)
+        h, c = rec[:, :, 1], rec[:, :, 2:]
+        with np.errstate(all='ignore'):
+            Sm[sel] = H - np.einsum('kei,kej->kij', c / h[:, :, None], c)
+        groups.append((sel, h, c))
+    M = 0.5 * Sm
+    d = np.diagonal(M, axis1=1, axis2=2)
+    with np.errstate(all='ignore'):
+        sc = np.where(d > 0, 1. / np.sqrt(np.where(d > 0, d, 1.)), 1.)
+    err, inv, bad = _uncertainties_from_hessians(M * sc[:, :, None] * sc[:, None, :])
+    err, covar = err * sc, inv * sc[:, :, None] * sc[:, None, :]
+    vel_err = np.full(int(eoff[-1]), np.nan)
+    for sel, h, c in groups:
+        with np.errstate(all='ignore'):
+            # (covar = 2 S^-1)
+            var = 2.0 / h + np.einsum('kei,kij,kej->ke', c, covar[sel], c) / (h * h)
+            ve = np.sqrt(var)
+        ve[~(h > 0)] = np.nan
+        vel_err[(eoff[sel, None] + np.arange(h.shape[1])[None, :]).reshape(-1)] = \
+            ve.reshape(-1)
+        bad[sel] |= ~np.isfinite(ve).all(axis=1)
+    return err, covar, vel_err, bad
+
+
+def process_epochs(specdata, star, paramDict0, vel0, fixParam=None, options=None,
+                   config=None, resolParams=None, priors=None, gtol=1e-5,
+                   cap_star=None, cap_epoch=None):
+    """The joint fit of the epochs of N stars: ONE set of stellar parameters (and one
+    vsini) per star, one velocity per epoch -- Levenberg-Marquardt (alm.py) on the sum
+    of the epochs' objectives, whose Gauss-Newton matrix is an arrowhead.  The template
+    stage of a row runs once per star, not once per epoch (optimizer.EpochChain).
+
+    specdata     a SpecBatch of the S epochs, or a list of epochs, each the list of
+                 SpecData of its arms
+    star         int [S]: the star (0 .. N - 1) of every epoch, in any order
+    paramDict0   the start, one value per star ([N] or a scalar): the stellar
+                 parameters, and 'vsini' where the templates are broadened (fitted
+                 unless it is in fixParam)
+    vel0         [S] start velocities in km/s (epochs_start: from a per-epoch run)
+    priors       {name: (mean, sigma)} per star, counted once per star
+    Returns numpy arrays: vel, vel_err, chisq [S] in the order of the input; param,
+    param_err {name: [N]}; vsini, vsini_err [N] where fitted; param_covar [N, m, m] over
+    the fitted columns ([vsini,] free parameters); chisq_tot (with the priors), status
+    (alm.py), nit, nfev, bad_fisher [N]; spec_status [N].  The uncertainties are those
+    of the arrow matrix at the returned point (_arrow_uncertainties).  The scope is the
+    analytic gradient's (engine.check_grad_scope); anything else raises ValueError."""
+    from . import alm
+    if config is None:
+        raise RuntimeError('Config must be provided')
+    t_begin = time.time()
+    options = options or {}
+    fixParam = list(fixParam) if fixParam is not None else []
+    batch = _epochs_batch(specdata)
+    S, dev = batch.S, batch.device
+    vel0 = np.asarray(vel0, dtype=np.float64).reshape(-1)
+    if vel0.shape != (S, ):
+        raise ValueError('vel0 has %d entries, there are %d epochs' % (len(vel0), S))
+    lens = {np.size(v) for v in paramDict0.values()} - {1}
+    if len(lens) > 1:
+        raise ValueError('paramDict0: values of %s stars' % sorted(lens))
+    order, eoff = spec_fit.epochs_order(star, S, lens.pop() if lens else None)
+    N = len(eoff) - 1
+    names = spec_inter.getSpecParams(batch.names[0], config)
+    missing = [k for k in names if k not in paramDict0]
+    if missing:
+        raise ValueError('paramDict0 lacks %s' % missing)
+    pd0 = _as_param_tensors(paramDict0, N, dev)
+    fitVsini = 'vsini' in pd0 and 'vsini' not in fixParam
+    if not np.array_equal(order, np.arange(S)):
+        batch = batch.subset(torch.as_tensor(order).to(dev))
+    libs = spec_inter.get_libs(batch.names, config)
+    safe = torch.stack([pd0[_] for _ in names], dim=1)
+    try:
+        chain = optimizer.EpochChain(
+            batch, libs, names, pd0, fixParam, fitVsini, config, options, priors, safe,
+            eoff, resols=spec_fit._resols(batch, resolParams), cap_star=cap_star,
+            cap_epoch=cap_epoch)
+    except ValueError as e:
+        raise ValueError('process_epochs: %s' % e) from None
+    m = chain.m
+    fitted = (['vsini'] if fitVsini else []) + [k for k in names if k not in fixParam]
+    th0 = np.stack([pd0[k].cpu().numpy() for k in fitted], axis=1)
+    xo = alm.offsets(m, eoff)[0]
+    x0 = np.empty(xo[-1])
+    vs = vel0[order]
+    for n in range(N):
+        x0[xo[n]:xo[n] + m] = th0[n]
+        x0[xo[n] + m:xo[n + 1]] = vs[eoff[n]:eoff[n + 1]]
+    t_setup = time.time()
+    # the rounds inside the library (rvs_alm_run); RVS_BFGS_ON_DEVICE=0: the same
+    # machines on the host around the same chain driven from Python
+    if BFGS_ON_DEVICE:
+        res = alm.minimize_lockstep_device(chain, x0, gtol=gtol)
+    else:
+        res = alm.minimize_lockstep_native(chain.objective, m, eoff, x0, gtol=gtol)
+    t_min = time.time()
+    x = res['x']
+    at = xo[:-1, None] + np.arange(m)[None, :]
+    isvel = np.ones(int(xo[-1]), dtype=bool)
+    isvel[at.reshape(-1)] = False
+    theta, vel_s = x[at], x[isvel]
+    if 'chi_x' in res:
+        # the device rounds kept the epochs' chi at x; the mapping of theta is host
+        # arithmetic (a fitted column as it is, vsini clipped; a star whose first row
+        # was bad keeps its start, which is what `safe` holds)
+        rows = res['row']
+        ro_ = alm.offsets(m, eoff)[1]
+        started = ~np.isnan(res['chi_x'][eoff[:-1]])
+        rows = rows.copy()
+        rows[ro_[:-1][~started]] = res['fun'][~started]
+        th0c = th0.copy()
+        use = np.where(started[:, None], theta, th0c)
+        ep = dict(chi=res['chi_x'],
+                  params=np.stack([use[:, fitted.index(k)] if k in fitted
+                                   else pd0[k].cpu().numpy() for k in names], axis=1),
+                  vsini=np.clip(use[:, 0], 0.0, float(config['max_vsini']))
+                  if fitVsini else None)
+    else:
+        # the epochs' own chi^2 at the result (and the row the uncertainties come from)
+        chain.keep_epochs = 'values'
+        rows = chain.rows(np.arange(N), theta, vel_s)
+        chain.keep_epochs = False
+        ep = chain.epochs
+    terr, covar, verr_s, bad = _arrow_uncertainties(rows, m, eoff)
+    inv = np.empty(S, dtype=np.int64)
+    inv[order] = np.arange(S)
+    ret = dict(vel=vel_s[inv], vel_err=verr_s[inv], chisq=ep['chi'][inv])
+    ret['param'] = {k: ep['params'][:, i].copy() for i, k in enumerate(names)}
+    nan = np.full(N, np.nan)
+    ret['param_err'] = {k: (terr[:, fitted.index(k)] if k in fitted else nan.copy())
+                        for k in names}
+    if fitVsini:
+        ret['vsini'] = ep['vsini'].copy()
+        ret['vsini_err'] = terr[:, 0]
+    ret['param_covar'] = covar
+    ret['names_covar'] = fitted
+    ro = alm.offsets(m, eoff)[1]
+    ret['chisq_tot'] = rows[ro[:-1]].copy()
+    ret['status'], ret['nit'], ret['nfev'] = res['status'], res['nit'], res['nfev']
+    ret['bad_fisher'] = bad
+    ret['spec_status'] = chain.status.cpu().numpy()
+    ret['rounds'] = res['rounds']
+    ret['template_rows'], ret['epoch_jobs'] = chain.star_rows, chain.epoch_jobs
+    ret['seconds'] = dict(setup=t_setup - t_begin, minimise=t_min - t_setup,
+                          closing=time.time() - t_min)
+    return ret
+
+
+def epochs_start(results, star):
+    """The start of process_epochs from a per-epoch `process` run: `results` is its
+    batch output (or a list of its single-spectrum dicts), `star` int [S].  Returns
+    (paramDict0, vel0): the velocities as fitted; every parameter the inverse-variance
+    mean over the star's epochs of `param` with `param_err`, and the plain mean where an
+    error is not finite or not positive ('vsini' likewise, with the plain mean: process
+    gives it no error)."""
+    def arr(v):
+        return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+    if isinstance(results, (list, tuple)):
+        keys = list(results[0]['param'])
+        results = dict(
+            vel=np.array([r['vel'] for r in results]),
+            param={k: np.array([r['param'][k] for r in results]) for k in keys},
+            param_err={k: np.array([r['param_err'][k] for r in results]) for k in keys},
+            **({'vsini': np.array([r['vsini'] for r in results])}
+               if 'vsini' in results[0] else {}))
+    vel0 = arr(results['vel']).astype(np.float64)
+    S = len(vel0)
+    order, eoff = spec_fit.epochs_order(star, S)
+    N = len(eoff) - 1
+    star = np.asarray(star)
+    pd = {}
+    for k, v in results['param'].items():
+        v = arr(v).astype(np.float64)
+        e = arr(results['param_err'][k]).astype(np.float64)
+        out = np.empty(N)
+        for n in range(N):
+            sel = star == n
+            en = e[sel]
+            if np.isfinite(en).all() and (en > 0).all():
+                w = 1.0 / (en * en)
+                out[n] = (w * v[sel]).sum() / w.sum()
+            else:
+                out[n] = v[sel].mean()
+        pd[k] = out
+    if 'vsini' in results:
+        v = arr(results['vsini']).astype(np.float64)
+        pd['vsini'] = np.array([v[star == n].mean() for n in range(N)])
+    return pd, vel0

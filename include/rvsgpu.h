@@ -40,7 +40,7 @@ extern "C" {
 #define RVS_ST_CCF_FAILED 0x20    /* non finite CCF minimum (fitter_ccf.py:234-236)                 */
 #define RVS_ST_ALLMASKED 0x40     /* every pixel masked in CCF preprocessing (make_ccf.py:311-315)  */
 #define RVS_ST_QUAD_ASSERT 0x80   /* parabola vertex outside its bracket (spec_fit.py:1014 assert)  */
-#define RVS_ST_ILLCOND 0x100      /* rvs_chisq_grid: normal matrix pivots span > 1e9 (long stretch of weightless pixels); re-evaluate the job with rvs_chisq_point */
+#define RVS_ST_ILLCOND 0x100      /* rvs_chisq_grid, rvs_chisq_grid_resol: normal matrix pivots span > 1e9 (long stretch of weightless pixels); re-evaluate the job with rvs_chisq_point */
 #define RVS_ST_NONPOS_MEDIAN 0x200 /* rvs_ccf_models_build: median of the model row <= 0 (make_ccf.py:133-138) */
 #define RVS_ST_RBF_NOTPD 0x400    /* rvs_rbf_factor: a pivot of the Cholesky factorisation is not positive (duplicate nodes: scipy's "Singular matrix") */
 
@@ -432,7 +432,12 @@ int rvs_chisq_grid_g(const double *lam, const double *polysT, const double *work
  * (spec_fit.py:54-67, 474-492) as used by get_chisq (:920-929).
  * taps [S or 1, npix, nd] row-major: taps[s, k, d] = R_s[k, k - (nd-1)/2 + d]
  * (0 outside the matrix), nd odd <= 33; taps_stride = npix*nd, or 0 when every
- * spectrum shares one matrix (the `resol_params` case). */
+ * spectrum shares one matrix (the `resol_params` case).
+ * status [J] as rvs_chisq_grid: RVS_ST_SPLINE_RANGE (first or last shifted pixel
+ * outside the knots; those entries are NaN, with RVS_ST_NONFINITE),
+ * RVS_ST_CHOL_FALLBACK (a pivot not positive) and RVS_ST_ILLCOND (pivots spanning
+ * > 1e9: a long stretch of weightless pixels -- the band does not change that);
+ * the caller re-evaluates jobs with either of the last two by rvs_chisq_point. */
 int rvs_chisq_grid_resol(const double *lam, const double *polysT,
                          const double *work, int npix, int npoly, int S,
                          const double *knots, const double *coef, int ntp,

@@ -769,6 +769,7 @@ __global__ void __launch_bounds__(256, (P <= 10 ? 2 : 1))
   }
   bool ok = true;
   double ldet = 0;
+  double pmin = 1.79e308, pmax = 0;   // smallest / largest pivot (squared)
 #pragma unroll
   for (int i = 0; i < P; i++) {
 #pragma unroll
@@ -778,6 +779,8 @@ __global__ void __launch_bounds__(256, (P <= 10 ? 2 : 1))
       for (int k = 0; k < jj; k++) sum -= acc[TRI(i, k)] * acc[TRI(jj, k)];
       if (jj == i) {
         if (!(sum > 0)) ok = false;
+        pmin = fmin(pmin, sum);
+        pmax = fmax(pmax, sum);
         const double d = sqrt(sum);
         acc[TRI(i, i)] = d;
         ldet += log(d);
@@ -786,6 +789,9 @@ __global__ void __launch_bounds__(256, (P <= 10 ? 2 : 1))
       }
     }
   }
+  // (the band does nothing for the conditioning a weightless stretch destroys:
+  // flagged and re-evaluated as in chisq_grid_body)
+  if (ok && pmin < 1e-9 * pmax) st |= RVS_ST_ILLCOND;
   double yy = 0;
 #pragma unroll
   for (int i = 0; i < P; i++) {
@@ -1027,6 +1033,7 @@ __global__ void __launch_bounds__(64)
     pixels(std::false_type{});
   bool ok = true;
   double ldet = 0;
+  double pmin = 1.79e308, pmax = 0;   // smallest / largest pivot (squared)
 #pragma unroll
   for (int i = 0; i < P; i++) {
 #pragma unroll
@@ -1036,6 +1043,8 @@ __global__ void __launch_bounds__(64)
       for (int k = 0; k < jj; k++) sum -= acc[TRI(i, k)] * acc[TRI(jj, k)];
       if (jj == i) {
         if (!(sum > 0)) ok = false;
+        pmin = fmin(pmin, sum);
+        pmax = fmax(pmax, sum);
         const double d = sqrt(sum);
         acc[TRI(i, i)] = d;
         ldet += log(d);
@@ -1044,6 +1053,9 @@ __global__ void __launch_bounds__(64)
       }
     }
   }
+  // (the band does nothing for the conditioning a weightless stretch destroys:
+  // flagged and re-evaluated as in chisq_grid_body)
+  if (ok && pmin < 1e-9 * pmax) st |= RVS_ST_ILLCOND;
   double yy = 0;
 #pragma unroll
   for (int i = 0; i < P; i++) {

@@ -123,7 +123,9 @@ extern "C" {
  *      joint fit of a star's epochs: rvs_epoch_map, rvs_epoch_finish,
  *      rvs_alm_row_size, rvs_alm_begin / _pending / _feed / _result / _end,
  *      rvs_alm_run_bytes and rvs_alm_run with the new structs rvs_epoch_chain and
- *      rvs_alm_state) */
+ *      rvs_alm_state; and rvs_chisq_grid_tab / rvs_chisq_grid_tab_work_size, the
+ *      velocity grid on a per-node table of resampled templates, with the option
+ *      "cg_tab") */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -154,6 +156,9 @@ int rvs_abi_version(void);
  *   "nn_pipe"        1  rvs_template_nn(_arms): the wide last layer through the kernel
  *                       whose epilogue runs under the next tile's products (K of 128,
  *                       200 or 256 inputs); 0 = the generic kernel (same bits)
+ *   "cg_tab"         1  rvs_chisq_grid_tab: full waves stream the node templates
+ *                       from the per-velocity table where its gate admits the
+ *                       call; 0 = always rvs_chisq_grid_g's kernels (same bits)
  * Both return 0, or RVS_E_ARG for an unknown name / NULL value pointer.
  * ---------------------------------------------------------------------- */
 int rvs_option_set(const char *name, int value);
@@ -427,7 +432,55 @@ int rvs_chisq_grid_g(const double *lam, const double *polysT, const double *work
                      int pack_min_jobs, const double *pen_scale, double *out,
                      int32_t *status, void *stream);
 
-/* A9  the same with a banded resolution matrix applied to the resampled
+/* rvs_chisq_grid_g with a node table.  When many jobs point at few templates
+ * (one per CCF node) and share one velocity grid and one wavelength grid, the
+ * resampled template of a (node, velocity, pixel) is the same number for every
+ * job of the node: it is evaluated once into `tab` and the full waves (the
+ * Nv / 64 blocks of 64 velocities of each job) stream it instead of evaluating
+ * the spline; the Nv % 64 left-over velocities go through the packed launch.
+ * Every value is the one rvs_chisq_grid_g gives, bit for bit.
+ * order [J]          the call's jobs sorted by job_templ (a stable sort)
+ * node_start [Tn+1]  first place of each template in `order` (prefix counts,
+ *                    node_start[Tn] = J)
+ * call_start [Tn+1], J_call  the same counts over ALL jobs that will read this
+ *                    table (a caller that feeds its jobs in several calls passes
+ *                    the whole list's counts to each; otherwise node_start, J):
+ *                    templates no job uses are not resampled
+ * min_jobs_per_node  the path is taken when J_call >= this * Tn (0 = library
+ *                    default, 1 = whatever J_call is, < 0 = never)
+ * tab, tab_size      rvs_chisq_grid_tab_work_size(npix, Tn, Nv, J_call,
+ *                    min_jobs_per_node, pack_min_jobs) doubles
+ * tab_state          0: the call fills the table first; 1: an earlier call with
+ *                    the same arm, templates, velocities and call_start has
+ *                    filled it
+ * took               HOST int32 (nullable): 1 if the table path ran, else 0
+ * pack_min_jobs      on the table path the Nv % 64 left-over velocities are ALWAYS
+ *                    packed (a positive threshold is not looked at); < 0 (never
+ *                    pack) or more than 50 left-over velocities, which
+ *                    rvs_chisq_grid_g gives a ragged wave, decline the table
+ * The path is taken only with job_templ given, vel_stride == 0, G == 1,
+ * Nv >= 64, left-over velocities that can be packed, a table of at most 1 GiB
+ * that fits tab_size, enough jobs per node and option "cg_tab" on; otherwise the
+ * call IS rvs_chisq_grid_g (tab untouched).
+ * rvs_chisq_grid_tab_work_size returns 0 where the size, the job count or the
+ * option already decide against the table: the caller then needs no buffer. */
+int64_t rvs_chisq_grid_tab_work_size(int npix, int Tn, int Nv, int64_t J_call,
+                                     int min_jobs_per_node, int pack_min_jobs);
+int rvs_chisq_grid_tab(const double *lam, const double *polysT, const double *work,
+                       int npix, int npoly, int S, const int32_t *grid_id, int G,
+                       int64_t polys_stride, const double *knots,
+                       const double *coef, int ntp, int Tn, int log_step,
+                       const int32_t *job_spec, const int32_t *job_templ, int J,
+                       const double *vels, int64_t vel_stride, int Nv,
+                       const double *penalty, double badchi, double beta,
+                       int pack_min_jobs, const double *pen_scale, double *out,
+                       int32_t *status, const int32_t *order,
+                       const int32_t *node_start, const int32_t *call_start,
+                       int64_t J_call, int min_jobs_per_node, double *tab,
+                       int64_t tab_size, int tab_state, int32_t *took,
+                       void *stream);
+
+/* A9 the same with a banded resolution matrix applied to the resampled
  * template before the fit: replaces convolve_resol / ResolMatrix
  * (spec_fit.py:54-67, 474-492) as used by get_chisq (:920-929).
  * taps [S or 1, npix, nd] row-major: taps[s, k, d] = R_s[k, k - (nd-1)/2 + d]

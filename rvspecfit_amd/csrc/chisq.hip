@@ -186,6 +186,10 @@ __device__ cg_v4i cg_sbl128(cg_v4i rsrc, int vindex, int voffset, int soffset,
                             int aux) __asm("llvm.amdgcn.struct.buffer.load.v4i32");
 __device__ cg_v2i cg_sbl64(cg_v4i rsrc, int vindex, int voffset, int soffset,
                            int aux) __asm("llvm.amdgcn.struct.buffer.load.v2i32");
+// (raw form: byte offset per lane + a scalar byte offset, range-checked against
+// the resource's size in bytes -- the node table's streams)
+__device__ cg_v2i cg_rbl64(cg_v4i rsrc, int voffset, int soffset,
+                           int aux) __asm("llvm.amdgcn.raw.buffer.load.v2i32");
 __device__ __forceinline__ cg_v4i cg_rsrc(const void *p, unsigned stride,
                                           unsigned nrec) {
   const unsigned long long a = (unsigned long long)p;
@@ -208,6 +212,95 @@ __device__ __forceinline__ void cg_sload2(double &d, const double *p) { d = *p; 
 __device__ __forceinline__ void cg_sload4(cg_d2 &d, const double2 *p) {
   typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
   d = *reinterpret_cast<const d2u *>(p);
+}
+
+// What a velocity contributes to the resampling: the Doppler factor f and, on
+// logarithmic knots, the shift of the knot coordinate (linear knots: the
+// coordinate scales instead, by lin_inv_step).  One statement for the grid
+// kernels and chisq_resample_kernel: their lanes must hold the same bits.
+__device__ __forceinline__ void cg_velocity(double vel,
+                                            const double *__restrict__ knots,
+                                            int log_step, double &f, double &shift,
+                                            double &lin_inv_step) {
+  const double bb = vel / RVS_C_KMS;
+  f = sqrt((1.0 - bb) / (1.0 + bb));
+  const double x0 = knots[0];
+  if (log_step) {
+    const double inv_step = 1.0 / log(knots[1] / x0);
+    shift = log(f) * inv_step;
+  } else {
+    shift = 0;  // linear knots: coordinate scales instead of shifting
+  }
+  lin_inv_step = log_step ? 0.0 : 1.0 / (knots[1] - x0);
+}
+// knot p / spline record p of a lane.  Full waves (one template per wave):
+// structured buffer loads, the record index is the knot index (no shifts; in
+// round 3's first half, with the loop still waiting for its loads, the same
+// change measured 2 % SLOWER -- issue bound, the two instructions saved per
+// pixel are 1.1 %: cg_bench 30.30 -> 29.96 ms); packed waves (a template per
+// lane): 32-bit byte offsets
+template <bool TAIL>
+__device__ __forceinline__ double cg_knot_at(const cg_v4i rk,
+                                             const double *__restrict__ knots,
+                                             int p) {
+  if (!TAIL) {
+    const cg_v2i v = cg_sbl64(rk, p, 0, 0, 0);
+    return __hiloint2double(v.y, v.x);
+  }
+  return *reinterpret_cast<const double *>(
+      reinterpret_cast<const char *>(knots) + ((uint32_t)p << 3));
+}
+template <bool TAIL>
+__device__ __forceinline__ double4 cg_rec_at(const cg_v4i rc,
+                                             const double4 *__restrict__ cf,
+                                             int p) {
+  if (!TAIL) {
+    const cg_v4i lo = cg_sbl128(rc, p, 0, 0, 0);
+    const cg_v4i hi = cg_sbl128(rc, p, 16, 0, 0);
+    return make_double4(__hiloint2double(lo.y, lo.x),
+                        __hiloint2double(lo.w, lo.z),
+                        __hiloint2double(hi.y, hi.x),
+                        __hiloint2double(hi.w, hi.z));
+  }
+  return *reinterpret_cast<const double4 *>(
+      reinterpret_cast<const char *>(cf) + ((uint32_t)p << 5));
+}
+// The resampled template at one pixel for one lane's velocity: the value every
+// chi^2 grid kernel and the node table hold.  (lamk, pixk) = wavelength / knot
+// coordinate of the pixel; pos = (int)((log x - log x0)/step) evaluated as pixel
+// coordinate + velocity shift, clamped to [0, ntp - 2]; the cubic in powers of
+// x - knot (records built with form 1): 3 fma.  `between` runs after the knot
+// and the record have been requested and before they are used -- the pixel
+// loop puts a whole trip's arithmetic there; PIN: an empty asm "use" of the
+// gathered values behind it, so that the wait for them stays there too.
+template <bool LOG, bool TAIL, bool PIN, class Between>
+__device__ __forceinline__ double
+    cg_resample(double lamk, double pixk, double f, double shift, double x0,
+                double lin_inv_step, int ntp2, const cg_v4i rk,
+                const double *__restrict__ knots, const cg_v4i rc,
+                const double4 *__restrict__ cf, Between &&between) {
+  // rounded product, as numpy's lam * f in the reference: left to itself
+  // the compiler contracts x - knot into fma(lam, f, -knot) in the
+  // LOG instance (x has no other use there) and chi^2 moves by ~1e-10
+  double x;
+  {
+#pragma clang fp contract(off)
+    x = lamk * f;
+  }
+  int pos;
+  if (LOG)
+    pos = (int)(pixk + shift);
+  else
+    pos = (int)((x - x0) * lin_inv_step);
+  int r;
+  asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(pos), "s"(ntp2));
+  double kn = cg_knot_at<TAIL>(rk, knots, r);
+  double4 cn = cg_rec_at<TAIL>(rc, cf, r);
+  between();
+  if (PIN)
+    asm volatile("" : "+v"(kn), "+v"(cn.x), "+v"(cn.y), "+v"(cn.z), "+v"(cn.w));
+  const double dn = x - kn;
+  return fma(fma(fma(cn.w, dn, cn.z), dn, cn.y), dn, cn.x);
 }
 
 // Measured negative (tools/perf/ubench_dpp.hip, round 2): gfx90a+ allows
@@ -256,7 +349,13 @@ __host__ __device__ constexpr int cg_split(int P) {
 // address per job, base in SGPRs + 32-bit lane offset) -- the basis row is
 // still wave-uniform.  A lane's arithmetic is the same sequence of operations
 // in both variants, so where a velocity is computed does not change its value.
-template <int P, bool TAIL>
+//
+// TAB = true (with TAIL = false): the resampled template does not come from the
+// spline but from the node table chisq_resample_kernel has filled: `tstream` is
+// the wave's (node, block of 64 velocities) stream of npix x 64 doubles, pixel
+// major, lane = velocity.  Prologue, sums, Cholesky and tail are the same code.
+#define CG_TAB_AHEAD 4   // pixels whose table values are in flight
+template <int P, bool TAIL, bool TAB = false>
 __device__ __forceinline__ void
     chisq_grid_body(const int bx, const int by, const double *__restrict__ lam,
                       const double *__restrict__ polysT,
@@ -269,7 +368,9 @@ __device__ __forceinline__ void
                       int Nv, int iv0, int lpj,
                       const double *__restrict__ penalty, double badchi,
                       double beta_out, double *__restrict__ out,
-                      int32_t *__restrict__ status, const GridSet GS) {
+                      int32_t *__restrict__ status, const GridSet GS,
+                      const double *__restrict__ tstream = nullptr) {
+  static_assert(!(TAB && TAIL), "the node table serves full waves only");
   // lane -> (job j, velocity index iv)
   int j, iv;
   bool active;
@@ -328,17 +429,9 @@ __device__ __forceinline__ void
   const double4 *cf = coef + (int64_t)t * ntp;
 
   const double vel = vels[(int64_t)j * vel_stride + iv];
-  const double bb = vel / RVS_C_KMS;
-  const double f = sqrt((1.0 - bb) / (1.0 + bb));
   const double x0 = knots[0], xlast = knots[ntp - 1];
-  double shift;  // knot-coordinate shift of this velocity
-  if (log_step) {
-    const double inv_step = 1.0 / log(knots[1] / x0);
-    shift = log(f) * inv_step;
-  } else {
-    shift = 0;  // linear knots: coordinate scales instead of shifting
-  }
-  const double lin_inv_step = log_step ? 0.0 : 1.0 / (knots[1] - x0);
+  double f, shift, lin_inv_step;  // shift: knot-coordinate shift of this velocity
+  cg_velocity(vel, knots, log_step, f, shift, lin_inv_step);
 
   int32_t st = 0;
   {  // evaler's range test on the first and last pixel (spliner.c:78-83)
@@ -406,59 +499,15 @@ __device__ __forceinline__ void
   auto trips = [&](auto log_c, auto i0_c, auto i1_c) {
     constexpr bool LOG = decltype(log_c)::value;
     constexpr int I0 = decltype(i0_c)::value, I1 = decltype(i1_c)::value;
-    // clamped knot index of the pixel with wavelength lamk / coordinate pixk
-    auto pos_of = [&](double lamk, double pixk, double &x) {
-      // rounded product, as numpy's lam * f in the reference: left to itself
-      // the compiler contracts x - knot into fma(lam, f, -knot) in the
-      // LOG instance (x has no other use there) and chi^2 moves by ~1e-10
-      {
-#pragma clang fp contract(off)
-        x = lamk * f;
-      }
-      int pos;
-      if (LOG)
-        pos = (int)(pixk + shift);
-      else
-        pos = (int)((x - x0) * lin_inv_step);
-      int r;
-      asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(pos), "s"(ntp - 2));
-      return r;
-    };
-    // full waves: the knot / record gathers as structured buffer loads (the
-    // record index is the knot index: no shifts; in round 3's first half, with the
-    // loop still waiting for its loads, the same change measured 2 % SLOWER --
-    // issue bound, the two instructions saved per pixel are 1.1 %: cg_bench 30.30
-    // -> 29.96 ms); packed waves (a template per lane): 32-bit byte offsets
+    // the knot / record gathers of cg_resample: cg_knot_at, cg_rec_at
     const cg_v4i rk = cg_rsrc(knots, 8, (unsigned)ntp);
     const cg_v4i rc = cg_rsrc(cf, 32, (unsigned)ntp);
-    auto knot_at = [&](int p) -> double {
-      if (!TAIL) {
-        const cg_v2i v = cg_sbl64(rk, p, 0, 0, 0);
-        return __hiloint2double(v.y, v.x);
-      }
-      return *reinterpret_cast<const double *>(
-          reinterpret_cast<const char *>(knots) + ((uint32_t)p << 3));
-    };
-    auto rec_at = [&](int p) -> double4 {
-      if (!TAIL) {
-        const cg_v4i lo = cg_sbl128(rc, p, 0, 0, 0);
-        const cg_v4i hi = cg_sbl128(rc, p, 16, 0, 0);
-        return make_double4(__hiloint2double(lo.y, lo.x),
-                            __hiloint2double(lo.w, lo.z),
-                            __hiloint2double(hi.y, hi.x),
-                            __hiloint2double(hi.w, hi.z));
-      }
-      return *reinterpret_cast<const double4 *>(
-          reinterpret_cast<const char *>(cf) + ((uint32_t)p << 5));
-    };
     double w, u;   // (t/e)^2 and t s/e^2 of the pixel whose sums are next
     {
-      double x;
-      const int p0 = pos_of(lam[0], pixa[0], x);
-      const double d0 = x - knot_at(p0);
-      const double4 c0 = rec_at(p0);
-      const double2 w0 = weights(0);
-      const double t0 = fma(fma(fma(c0.w, d0, c0.z), d0, c0.y), d0, c0.x);
+      double2 w0;
+      const double t0 = cg_resample<LOG, TAIL, false>(
+          lam[0], pixa[0], f, shift, x0, lin_inv_step, ntp - 2, rk, knots, rc,
+          cf, [&]() { w0 = weights(0); });
       w = t0 * t0 * w0.x;
       u = t0 * w0.y;
     }
@@ -483,29 +532,24 @@ __device__ __forceinline__ void
       if (!TAIL) cg_sload4(wn_s, W + k1);
       cg_sload2(lan, lam + k2);
       cg_sload2(pan, pixa + k2);
-      double xn;
-      const int pn = pos_of(lac, pac, xn);
-      double kn = knot_at(pn);
-      double4 cn = rec_at(pn);
       double2 wn_v;
-      if (TAIL) wn_v = weights(k1);
-      CG_FENCE();
-      // the sums of pixel k
+      // pixel k+1: its gathers have the whole trip
+      const double tn = cg_resample<LOG, TAIL, true>(
+          lac, pac, f, shift, x0, lin_inv_step, ntp - 2, rk, knots, rc, cf, [&]() {
+            if (TAIL) wn_v = weights(k1);
+            CG_FENCE();
+            // the sums of pixel k
 #pragma unroll
-      for (int jj = 0; jj < I1; jj++) {
-        const double pj = Rc.get(jj);
-        const double pwj = pj * w;
-        if (jj >= I0) av[jj] = fma(pj, u, av[jj]);
+            for (int jj = 0; jj < I1; jj++) {
+              const double pj = Rc.get(jj);
+              const double pwj = pj * w;
+              if (jj >= I0) av[jj] = fma(pj, u, av[jj]);
 #pragma unroll
-        for (int i = (jj > I0 ? jj : I0); i < I1; i++)
-          acc[TRI(i, jj)] = fma(Rc.get(i), pwj, acc[TRI(i, jj)]);
-      }
-      CG_FENCE();
-      // pixel k+1: its gathers had the whole trip
-      asm volatile(""
-                   : "+v"(kn), "+v"(cn.x), "+v"(cn.y), "+v"(cn.z), "+v"(cn.w));
-      const double dn = xn - kn;
-      const double tn = fma(fma(fma(cn.w, dn, cn.z), dn, cn.y), dn, cn.x);
+              for (int i = (jj > I0 ? jj : I0); i < I1; i++)
+                acc[TRI(i, jj)] = fma(Rc.get(i), pwj, acc[TRI(i, jj)]);
+            }
+            CG_FENCE();
+          });
       if (TAIL) {
         asm volatile("" : "+s"(lan), "+s"(pan));
         w = tn * tn * wn_v.x;
@@ -525,11 +569,90 @@ __device__ __forceinline__ void
     }
     if (k < npx) trip(k, R0, R1, la0, pa0, la1, pa1);
   };
+  // TAB: the same trips with the template value of a pixel read from the wave's
+  // stream -- one 8-byte buffer load per lane, lane offset 8 * lane, the pixel's
+  // 512 * k as the scalar offset: no vector address arithmetic, no position, no
+  // gathers, no cubic.  The values of the next CG_TAB_AHEAD pixels are in
+  // flight (slot k % CG_TAB_AHEAD holds pixel k; it is refilled with pixel
+  // k + CG_TAB_AHEAD at the top of trip k, one trip after its last use), so the
+  // loop is unrolled CG_TAB_AHEAD times.  No load addresses past its stream: the
+  // pixel index is clamped to klast as everywhere in the loop, and that clamp is
+  // what the bound rests on -- the resource is sized to the stream, but its
+  // range check sees the lane offset only, not the scalar offset of the pixel.
+  auto trips_tab = [&](auto i0_c, auto i1_c) {
+    constexpr int I0 = decltype(i0_c)::value, I1 = decltype(i1_c)::value;
+    constexpr int D = CG_TAB_AHEAD;
+    static_assert(D == 4, "the unrolled trips below are written for 4 slots");
+    const int klast = npx - 1;
+    const cg_v4i rt = cg_rsrc(tstream, 0, (unsigned)npix * 512u);
+    const int lo8 = (int)threadIdx.x * 8;
+    auto t_at = [&](int k) -> double {
+      const cg_v2i v = cg_rbl64(rt, lo8, min(k, klast) * 512, 0);
+      return __hiloint2double(v.y, v.x);
+    };
+    double q[D];
+#pragma unroll
+    for (int d = 0; d < D; d++) q[d] = t_at(d);
+    double w, u;
+    {
+      const double2 w0 = W[0];
+      const double t0 = q[0];
+      w = t0 * t0 * w0.x;
+      u = t0 * w0.y;
+    }
+    CgRow<P> R0, R1;
+    R0.load(polysT);
+    R0.pin();
+    auto trip = [&](int k, auto slot_c, CgRow<P> &Rc, CgRow<P> &Rn) {
+      constexpr int SL = decltype(slot_c)::value;
+      const int k1 = min(k + 1, klast);
+      Rn.load(polysT + (int64_t)k1 * P);
+      cg_d2 wn_s;
+      cg_sload4(wn_s, W + k1);
+      q[SL] = t_at(k + D);
+      CG_FENCE();
+      // the sums of pixel k
+#pragma unroll
+      for (int jj = 0; jj < I1; jj++) {
+        const double pj = Rc.get(jj);
+        const double pwj = pj * w;
+        if (jj >= I0) av[jj] = fma(pj, u, av[jj]);
+#pragma unroll
+        for (int i = (jj > I0 ? jj : I0); i < I1; i++)
+          acc[TRI(i, jj)] = fma(Rc.get(i), pwj, acc[TRI(i, jj)]);
+      }
+      CG_FENCE();
+      double tn = q[(SL + 1) % D];   // pixel k+1
+      asm volatile("" : "+v"(tn));
+      asm volatile("" : "+s"(wn_s));
+      w = tn * tn * wn_s[0];
+      u = tn * wn_s[1];
+      Rn.pin();
+    };
+    using s0_t = std::integral_constant<int, 0>;
+    using s1_t = std::integral_constant<int, 1>;
+    using s2_t = std::integral_constant<int, 2>;
+    using s3_t = std::integral_constant<int, 3>;
+    int k = 0;
+#pragma unroll 1
+    for (; k + 3 < npx; k += 4) {
+      trip(k, s0_t{}, R0, R1);
+      trip(k + 1, s1_t{}, R1, R0);
+      trip(k + 2, s2_t{}, R0, R1);
+      trip(k + 3, s3_t{}, R1, R0);
+    }
+    if (k < npx) trip(k, s0_t{}, R0, R1);
+    if (k + 1 < npx) trip(k + 1, s1_t{}, R1, R0);
+    if (k + 2 < npx) trip(k + 2, s2_t{}, R0, R1);
+  };
   constexpr int PS = cg_split(P);
   using c0_t = std::integral_constant<int, 0>;
   using cs_t = std::integral_constant<int, PS>;
   using cp_t = std::integral_constant<int, P>;
-  if (log_step) {
+  if constexpr (TAB) {
+    trips_tab(c0_t{}, cs_t{});
+    if constexpr (PS < P) trips_tab(cs_t{}, cp_t{});
+  } else if (log_step) {
     trips(std::true_type{}, c0_t{}, cs_t{});
     if constexpr (PS < P) trips(std::true_type{}, cs_t{}, cp_t{});
   } else {
@@ -654,6 +777,103 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(
     cg_clock_dbg[1] = wall_clock64() - r0;
   }
 #endif
+}
+
+// ---------------------------------------------------------------------------
+// The node table.  When the jobs of a call point at a few templates (one per
+// CCF node, pipeline.fit_batch), share one velocity grid and one wavelength
+// grid, the resampled template T_{n,v}(k) is the same number for every job of
+// node n: it is evaluated ONCE into tab[node][vblock][k][64] (float64, vblock =
+// one of the nfull = Nv / 64 blocks of 64 velocities that full waves serve) by
+// the function the grid kernels evaluate it with, and the jobs stream it.
+// One wave per (node, vblock, chunk of CG_TAB_CHUNK pixels), lane = velocity,
+// one coalesced 512-byte store per pixel; nodes no job of the call uses
+// (node_start[n + 1] == node_start[n]) are skipped.
+// ---------------------------------------------------------------------------
+#define CG_TAB_CHUNK 32
+__global__ void __launch_bounds__(64)
+    chisq_resample_kernel(const double *__restrict__ lam,
+                          const double *__restrict__ work, int npix,
+                          const double *__restrict__ knots,
+                          const double4 *__restrict__ coef, int ntp, int log_step,
+                          const double *__restrict__ vels, int nfull,
+                          const int32_t *__restrict__ node_start,
+                          double *__restrict__ tab) {
+  const int n = blockIdx.z, vb = blockIdx.y;
+  if (node_start[n + 1] == node_start[n]) return;
+  const double *pixa = work;   // (one wavelength grid: G = 1)
+  const double4 *cf = coef + (int64_t)n * ntp;
+  const double x0 = knots[0];
+  double f, shift, lin_inv_step;
+  cg_velocity(vels[vb * 64 + (int)threadIdx.x], knots, log_step, f, shift,
+              lin_inv_step);
+  const cg_v4i rk = cg_rsrc(knots, 8, (unsigned)ntp);
+  const cg_v4i rc = cg_rsrc(cf, 32, (unsigned)ntp);
+  double *o = tab + ((int64_t)n * nfull + vb) * npix * 64 + threadIdx.x;
+  const int ka = blockIdx.x * CG_TAB_CHUNK, kb = min(ka + CG_TAB_CHUNK, npix);
+  auto fill = [&](auto log_c) {
+    constexpr bool LOG = decltype(log_c)::value;
+    for (int k = ka; k < kb; k++)
+      o[(int64_t)k * 64] = cg_resample<LOG, false, false>(
+          lam[k], pixa[k], f, shift, x0, lin_inv_step, ntp - 2, rk, knots, rc, cf,
+          []() {});
+  };
+  if (log_step)
+    fill(std::true_type{});
+  else
+    fill(std::false_type{});
+}
+
+// The full waves of a call on the node table.  Work items in the order (node,
+// vblock, job within node), Q = nfull * J of them: `order` lists the jobs by
+// node (a stable sort of job_templ), node_start [Tn + 1] the first place of each
+// node in it.  The list is cut into 8 contiguous ranges of ceil(Q / 8) and block
+// b takes item (b & 7) * ceil(Q / 8) + (b >> 3): with blocks dealt round-robin to
+// the 8 XCDs, the waves resident on an XCD at a time sit on a few consecutive
+// streams, which its L2 then serves, and an XCD's share of the work is Q / 8
+// whatever the node histogram is.  The node of an item: wave-uniform binary
+// search over node_start (scalar loads).
+template <int P>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(
+    CG_WAVES(P))))
+    chisq_grid_tab_kernel(const double *__restrict__ lam,
+                          const double *__restrict__ polysT,
+                          const double *__restrict__ work, int npix, int S,
+                          const double *__restrict__ knots,
+                          const double4 *__restrict__ coef, int ntp, int log_step,
+                          const int32_t *__restrict__ job_spec,
+                          const int32_t *__restrict__ job_templ, int J,
+                          const double *__restrict__ vels, int Nv, int iv0,
+                          int nfull, const double *__restrict__ penalty,
+                          double badchi, double beta_out,
+                          double *__restrict__ out, int32_t *__restrict__ status,
+                          const GridSet GS, const int32_t *__restrict__ order,
+                          const int32_t *__restrict__ node_start, int Tn,
+                          const double *__restrict__ tab) {
+  const int64_t Q = (int64_t)nfull * J, per = (Q + 7) / 8;
+  const int64_t slot = blockIdx.x >> 3;
+  const int64_t item = (int64_t)(blockIdx.x & 7) * per + slot;
+  if (slot >= per || item >= Q) return;
+  int lo = 0, hi = Tn;   // node_start[lo] * nfull <= item < node_start[hi] * nfull
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int64_t)node_start[mid] * nfull <= item)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  const int n = __builtin_amdgcn_readfirstlane(lo);
+  const int s0 = node_start[n], nj = node_start[n + 1] - s0;
+  const int r = (int)(item - (int64_t)s0 * nfull);
+  // (node_start not a prefix count of J jobs: nothing is touched)
+  if (nj < 1 || r < 0 || s0 < 0 || s0 + nj > J) return;
+  const int vb = r / nj;
+  const int j = __builtin_amdgcn_readfirstlane(order[s0 + (r - vb * nj)]);
+  if (vb >= nfull || (unsigned)j >= (unsigned)J) return;
+  chisq_grid_body<P, false, true>(
+      vb, j, lam, polysT, work, npix, S, knots, coef, ntp, log_step, job_spec,
+      job_templ, J, vels, 0, Nv, iv0, 64, penalty, badchi, beta_out, out, status,
+      GS, tab + ((int64_t)n * nfull + vb) * npix * 64);
 }
 
 // ---------------------------------------------------------------------------
@@ -1166,6 +1386,136 @@ static int launch_grid(const double *lam, const double *polysT,
   if (fk && hipStreamWaitEvent(st, fk->join, 0) != hipSuccess)
     return RVS_E_LAUNCH;
   return 0;
+}
+
+// The node table's gate (rvs_chisq_grid_tab).  CG_TAB_MAX_BYTES: the largest
+// table the path builds (a DESI arm at 76 nodes and 400 velocities is 543-673
+// MB).  CG_TAB_MIN_JOBS_PER_NODE: the call must bring at least this many jobs
+// per node template for the resampling (one job's spline work per node, plus
+// the table's trip through memory) to be a small fraction of the work; the
+// sweep that chose it is in DESIGN 4.2.
+#define CG_TAB_MAX_BYTES (1ll << 30)
+#define CG_TAB_MIN_JOBS_PER_NODE 16
+extern "C" int64_t rvs_chisq_grid_tab_work_size(int npix, int Tn, int Nv,
+                                                int64_t J_call,
+                                                int min_jobs_per_node,
+                                                int pack_min_jobs) {
+  if (min_jobs_per_node == 0) min_jobs_per_node = CG_TAB_MIN_JOBS_PER_NODE;
+  // (the call's jobs per template, J_call / Tn, is a lower bound of its jobs per
+  // USED template, which would take a look at the device's job list; 1: a used
+  // template has at least one job whatever J_call is)
+  if (npix < 1 || Tn < 1 || Nv < 64 || J_call < 1 || min_jobs_per_node < 0 ||
+      (min_jobs_per_node > 1 && J_call < (int64_t)min_jobs_per_node * Tn) ||
+      !rvs_opt(RVS_OPT_CG_TAB))
+    return 0;
+  // left-over velocities: the table serves whole blocks of 64 only, so they go
+  // through the packed launch, whatever the job count (table + packed against
+  // launch_grid's ragged wave below 2000 jobs: DESIGN 4.2's sweep); where
+  // launch_grid never packs them -- pack_min_jobs < 0, more than CG_PACK_MAXR
+  // of them (not measured on the table) -- the call is not the table's
+  if (Nv % 64 != 0 && (pack_min_jobs < 0 || Nv % 64 > CG_PACK_MAXR)) return 0;
+  const int64_t n = (int64_t)Tn * (Nv / 64) * npix * 64;   // doubles
+  return n * 8 <= CG_TAB_MAX_BYTES ? n : 0;
+}
+
+// the table path of one call: [resample] + packed left-over velocities + the
+// full waves on the table
+template <int P>
+static int launch_grid_tab(const double *lam, const double *polysT,
+                           const double *work, int npix, int S,
+                           const double *knots, const double *coef, int ntp,
+                           int Tn, int log_step, const int32_t *job_spec,
+                           const int32_t *job_templ, int J, const double *vels,
+                           int Nv, const double *penalty, double badchi,
+                           double beta, double *out, int32_t *status,
+                           const GridSet GS, const int32_t *order,
+                           const int32_t *node_start, const int32_t *call_start,
+                           double *tab, int tab_state, hipStream_t st) {
+  const int r = Nv % 64, nfull = Nv / 64, iv0 = Nv - r;
+  const double4 *cf = reinterpret_cast<const double4 *>(coef);
+  // (the packed waves first and on the side stream, as in launch_grid; they
+  // evaluate the spline themselves and do not read the table)
+  GridFork *fk = r ? grid_fork() : nullptr;
+  if (r) {
+    hipStream_t ts = st;
+    if (fk) {
+      if (hipEventRecord(fk->fork, st) != hipSuccess ||
+          hipStreamWaitEvent(fk->side, fk->fork, 0) != hipSuccess)
+        return RVS_E_LAUNCH;
+      ts = fk->side;
+    }
+    hipLaunchKernelGGL((chisq_grid_kernel<P, true>),
+                       dim3((unsigned)(((int64_t)J * r + 63) / 64)),
+                       dim3(64), 0, ts, lam, polysT, work, npix, S, knots, cf,
+                       ntp, log_step, job_spec, job_templ, J, vels, 0, Nv, iv0, r,
+                       0, penalty, badchi, beta, out, status, GS);
+    RVS_LAUNCH_CHECK();
+    if (fk && hipEventRecord(fk->join, fk->side) != hipSuccess)
+      return RVS_E_LAUNCH;
+  }
+  if (!tab_state) {
+    hipLaunchKernelGGL(chisq_resample_kernel,
+                       dim3((unsigned)((npix + CG_TAB_CHUNK - 1) / CG_TAB_CHUNK),
+                            (unsigned)nfull, (unsigned)Tn),
+                       dim3(64), 0, st, lam, work, npix, knots, cf, ntp, log_step,
+                       vels, nfull, call_start, tab);
+    RVS_LAUNCH_CHECK();
+  }
+  const int64_t nb = (((int64_t)nfull * J + 7) / 8) * 8;
+  hipLaunchKernelGGL((chisq_grid_tab_kernel<P>), dim3((unsigned)nb), dim3(64), 0,
+                     st, lam, polysT, work, npix, S, knots, cf, ntp, log_step,
+                     job_spec, job_templ, J, vels, Nv, iv0, nfull, penalty, badchi,
+                     beta, out, status, GS, order, node_start, Tn, tab);
+  RVS_LAUNCH_CHECK();
+  if (fk && hipStreamWaitEvent(st, fk->join, 0) != hipSuccess)
+    return RVS_E_LAUNCH;
+  return 0;
+}
+
+extern "C" int rvs_chisq_grid_tab(
+    const double *lam, const double *polysT, const double *work, int npix,
+    int npoly, int S, const int32_t *grid_id, int G, int64_t polys_stride,
+    const double *knots, const double *coef, int ntp, int Tn, int log_step,
+    const int32_t *job_spec, const int32_t *job_templ, int J, const double *vels,
+    int64_t vel_stride, int Nv, const double *penalty, double badchi, double beta,
+    int pack_min_jobs, const double *pen_scale, double *out, int32_t *status,
+    const int32_t *order, const int32_t *node_start, const int32_t *call_start,
+    int64_t J_call, int min_jobs_per_node, double *tab, int64_t tab_size,
+    int tab_state, int32_t *took, void *stream) {
+  if (took) *took = 0;
+  // (0: option off, no full wave, too few jobs per node, left-over velocities
+  // that are not packed, or over the byte cap)
+  const int64_t need = rvs_chisq_grid_tab_work_size(
+      npix, Tn, Nv, J_call, min_jobs_per_node, pack_min_jobs);
+  const bool take =
+      job_templ && order && node_start && call_start && tab && vel_stride == 0 &&
+      G == 1 && !grid_id && J >= 1 && ntp >= 3 && npoly >= 1 && npoly <= 16 &&
+      need > 0 && need <= tab_size && J_call >= J &&
+      // (the packed waves address a spectrum's terms with 32-bit offsets)
+      (Nv % 64 == 0 || (int64_t)S * npix * 16 < (1ll << 32)) &&
+      (int64_t)(Nv / 64) * J + 7 <= 0x7fffffffll;
+  if (!take)
+    return rvs_chisq_grid_g(lam, polysT, work, npix, npoly, S, grid_id, G,
+                            polys_stride, knots, coef, ntp, Tn, log_step, job_spec,
+                            job_templ, J, vels, vel_stride, Nv, penalty, badchi,
+                            beta, pack_min_jobs, pen_scale, out, status, stream);
+  if (took) *took = 1;
+  hipStream_t st = rvs_stream(stream);
+  const GridSet GS = {nullptr, polys_stride, 1, pen_scale};
+#define RVS_CASE(PP)                                                           \
+  case PP:                                                                     \
+    return launch_grid_tab<PP>(lam, polysT, work, npix, S, knots, coef, ntp, Tn, \
+                               log_step, job_spec, job_templ, J, vels, Nv,     \
+                               penalty, badchi, beta, out, status, GS, order,  \
+                               node_start, call_start, tab, tab_state, st);
+  switch (npoly) {
+    RVS_CASE(1) RVS_CASE(2) RVS_CASE(3) RVS_CASE(4) RVS_CASE(5) RVS_CASE(6)
+    RVS_CASE(7) RVS_CASE(8) RVS_CASE(9) RVS_CASE(10) RVS_CASE(11) RVS_CASE(12)
+    RVS_CASE(13) RVS_CASE(14) RVS_CASE(15) RVS_CASE(16)
+    default:
+      return RVS_E_ARG;
+  }
+#undef RVS_CASE
 }
 
 extern "C" int rvs_chisq_prepare_g(const double *lam, const double *spec,

@@ -30,6 +30,7 @@ const OptDef kDefs[RVS_OPT_COUNT] = {
     {"nm_split_min", "RVS_NM_SPLIT_MIN", 1024},
     {"nm_spec_max", "RVS_NM_SPEC_MAX", 21},
     {"nm_tail_window", "RVS_NM_TAIL_WINDOW", 16},
+    {"cg_tab", "RVS_CG_TAB", 1},
 };
 std::atomic<int> g_val[RVS_OPT_COUNT];
 std::once_flag g_once;

@@ -12,6 +12,9 @@ HBM layout (per arm of a batch of S spectra, all sharing the wavelength grid):
     templ    float64 [J, ntp]   ->  coef float64 [J, ntp, 4]  spline records
     chisq    float64 [J, Nv]
 """
+import ctypes
+import threading
+
 import numpy as np
 import torch
 
@@ -695,6 +698,24 @@ import os as _os
 # rvs_chisq_grid's pack_min_jobs: 0 = library default (pack the Nv % 64
 # left-over velocities of >= 2000 jobs), 1 = always, -1 = never (tests)
 CG_PACK_MIN_JOBS = 0
+# rvs_chisq_grid_tab's min_jobs_per_node: the full waves stream the node
+# templates from a per-velocity table when the call brings at least this many
+# jobs per template; 0 = library default, 1 = whenever the gate's other
+# conditions hold, -1 = never (tests)
+CG_TAB_MIN_JOBS = 0
+# cg_tab_took(): how many rvs_chisq_grid_tab calls of this host thread's last
+# chisq_grid ran on the table (per thread: the entry points are driven from
+# several)
+_cg_tab_tls = threading.local()
+
+
+def cg_tab_took():
+    return getattr(_cg_tab_tls, 'took', 0)
+
+
+def _cg_tab_work(dev, n):
+    """the node table's buffer: n doubles (rvs_chisq_grid_tab_work_size)"""
+    return torch.empty(n, dtype=torch.float64, device=dev)
 
 
 def _arm_resol(arm, ia, resols):
@@ -720,6 +741,7 @@ def chisq_grid(batch, libs, coefs, outsides, vels, npoly=5, rbf=True,
     Returns chisq [J, Nv], status int32 [J].
     """
     L = _lib.lib()
+    _cg_tab_tls.took = 0
     dev = batch.device
     if job_spec is not None:
         J = job_spec.shape[0]
@@ -802,6 +824,36 @@ def chisq_grid(batch, libs, coefs, outsides, vels, npoly=5, rbf=True,
     status = torch.zeros(J, dtype=torch.int32, device=dev)
     if vel_bounds is None:
         vel_bounds = (float(vels.min().item()), float(vels.max().item()))
+    # The node table (rvs_chisq_grid_tab): jobs that point at shared templates on
+    # one velocity grid.  The jobs are sorted by template once per call -- the
+    # arms share the order -- and the table's buffer is sized for the largest arm
+    # and reused by the arms (they run one after the other on this stream).
+    tab = None
+    took = ctypes.c_int32(0)
+    ntook = 0
+    if job_templ is not None and shared and Nv >= 64 and CG_TAB_MIN_JOBS >= 0 \
+            and all(r is None for r in wide) \
+            and all(a.grid_args()[1] == 1 for a in batch.arms):
+        Tn = coefs[0].shape[0]
+        # (0 where the gate will decline: too few jobs per template, left-over
+        # velocities that are not packed, a table over the byte cap, the option
+        # switched off)
+        ntab = max(L.rvs_chisq_grid_tab_work_size(a.npix, c.shape[0], Nv, J,
+                                                  CG_TAB_MIN_JOBS,
+                                                  CG_PACK_MIN_JOBS)
+                   for a, c in zip(batch.arms, coefs))
+        if all(c.shape[0] == Tn for c in coefs) and ntab > 0:
+            nodes = torch.arange(Tn + 1, dtype=torch.int32, device=dev)
+
+            def by_node(jt):
+                """jobs jt in template order: (order, first place of each)"""
+                srt, order = torch.sort(jt, stable=True)
+                start = torch.searchsorted(srt, nodes, out_int32=True)
+                return order.to(torch.int32).contiguous(), start.contiguous()
+            tab_chunks = [by_node(job_templ[a:b]) for a, b in _chunks(J, 65535)]
+            tab_call = tab_chunks[0][1] if len(tab_chunks) == 1 else \
+                by_node(job_templ)[1]
+            tab = _cg_tab_work(dev, ntab)
     for ia, arm in enumerate(batch.arms):
         lib = libs[arm.name]
         work = arm.work(lib, espec_sys)
@@ -819,7 +871,7 @@ def chisq_grid(batch, libs, coefs, outsides, vels, npoly=5, rbf=True,
         pen = (pen + logdet_off).contiguous()
         coef = coefs[ia]
         rs = _arm_resol(arm, ia, resols)
-        for a, b in _chunks(J, 65535):
+        for ic, (a, b) in enumerate(_chunks(J, 65535)):
           with _ktime('chisq_grid', (b - a) * Nv):   # units: job-velocities
             js = _lib.ptr(job_spec[a:b]) if job_spec is not None else \
                 (_lib.ptr(_arange32(a, b, dev)) if a > 0 else None)
@@ -840,6 +892,25 @@ def chisq_grid(batch, libs, coefs, outsides, vels, npoly=5, rbf=True,
                 _lib.check(rc, 'rvs_chisq_grid_resol')
                 continue
             gid, G = arm.grid_args()
+            if tab is not None:
+                # (the table of an arm is filled by its first chunk)
+                order, start = tab_chunks[ic]
+                rc = L.rvs_chisq_grid_tab(
+                    _lib.ptr(arm.lam), _lib.ptr(polysT), _lib.ptr(work), arm.npix,
+                    npoly, arm.S, gid, G, arm.basis_stride(npoly),
+                    _lib.ptr(lib.knots), _lib.ptr(coef), lib.ntp,
+                    coef.shape[0], int(lib.log_step), js, jt, b - a,
+                    _lib.ptr(vels), vstride, Nv,
+                    _lib.ptr(pen[a:b]), float(batch.badchi),
+                    0.0 if ia == 0 else 1.0, CG_PACK_MIN_JOBS,
+                    _lib.ptr(batch.pen_scale), _lib.ptr(out[a:b]),
+                    _lib.ptr(status[a:b]), _lib.ptr(order), _lib.ptr(start),
+                    _lib.ptr(tab_call), J, CG_TAB_MIN_JOBS, _lib.ptr(tab),
+                    tab.numel(), 1 if ic else 0, ctypes.byref(took),
+                    _lib.stream())
+                _lib.check(rc, 'rvs_chisq_grid_tab')
+                ntook += took.value
+                continue
             rc = L.rvs_chisq_grid_g(
                 _lib.ptr(arm.lam), _lib.ptr(polysT), _lib.ptr(work), arm.npix,
                 npoly, arm.S, gid, G, arm.basis_stride(npoly),
@@ -851,6 +922,7 @@ def chisq_grid(batch, libs, coefs, outsides, vels, npoly=5, rbf=True,
                 _lib.ptr(batch.pen_scale), _lib.ptr(out[a:b]),
                 _lib.ptr(status[a:b]), _lib.stream())
             _lib.check(rc, 'rvs_chisq_grid')
+    _cg_tab_tls.took = ntook
     # Jobs whose normal matrix the velocity-grid kernel could not factor, or
     # found spanning > 1e9 in its pivots (RVS_ST_ILLCOND: a long stretch of
     # weightless pixels), are re-evaluated by the point kernel -- raw basis,

@@ -2,7 +2,12 @@
 // DESI-b-shaped arm (2751 px, 6215 knots).  Includes the kernel source so that
 // variants can be selected with -D flags; prints ms per launch and a checksum
 // of the output (bit-identity between variants).
-//   hipcc -O3 --offload-arch=gfx950 -std=c++17 -I include -o /tmp/cg_bench tools/perf/cg_bench.hip
+//   hipcc -O3 --offload-arch=gfx950 -std=c++17 -I include -o /tmp/cg_bench tools/perf/cg_bench.hip rvspecfit_amd/csrc/options.cpp
+// -DCG_TAB: the node-table form (rvs_chisq_grid_tab, gate forced) with own = 2:
+//   76 node templates on ONE velocity grid; the jobs' nodes are random, or --
+//   argv[7] -- read from a text file with one node id per line (the best_id
+//   column of `bench.py --dump-outputs`, records.npy[:, 0]): a real histogram.
+//   The checksum is that of the same command without -DCG_TAB.
 #include "../../rvspecfit_amd/csrc/chisq.hip"
 #include <cstdio>
 #include <cstdlib>
@@ -53,11 +58,38 @@ int main(int argc, char **argv) {
   hipMemcpy(d_vels, vels.data(), vels.size() * 8, hipMemcpyHostToDevice);
   hipMemset(d_st, 0, S * 4);
   int32_t *d_jt; hipMalloc(&d_jt, S * 4); hipMemset(d_jt, 0, S * 4);  // own = 0: every job uses template 0
+#ifdef CG_TAB
+  int32_t *d_order = nullptr, *d_start = nullptr; double *d_tab = nullptr; int64_t tab_n = 0;
+#endif
   const int NT_NODE = 76;   // own = 2: 76 node templates, jobs pick one at random (the pipeline's case)
   if (own == 2) {
     std::vector<int32_t> jt(S);
     for (int s = 0; s < S; s++) jt[s] = rand() % NT_NODE;
+#ifdef CG_TAB
+    if (argc > 7) {
+      FILE *fh = fopen(argv[7], "r");
+      if (!fh) { printf("cannot read %s\n", argv[7]); return 1; }
+      double v; int s = 0;
+      while (s < S && fscanf(fh, "%lf", &v) == 1) jt[s++] = (int32_t)v % NT_NODE;
+      fclose(fh);
+      for (int q = s; q < S && s > 0; q++) jt[q] = jt[q % s];
+    }
+#endif
     hipMemcpy(d_jt, jt.data(), S * 4, hipMemcpyHostToDevice);
+#ifdef CG_TAB
+    // jobs in node order (stable) + first place of each node
+    std::vector<int32_t> order, start(NT_NODE + 1, 0);
+    for (int t = 0; t < NT_NODE; t++) {
+      start[t] = (int32_t)order.size();
+      for (int s = 0; s < S; s++) if (jt[s] == t) order.push_back(s);
+    }
+    start[NT_NODE] = S;
+    hipMalloc(&d_order, S * 4); hipMalloc(&d_start, (NT_NODE + 1) * 4);
+    hipMemcpy(d_order, order.data(), S * 4, hipMemcpyHostToDevice);
+    hipMemcpy(d_start, start.data(), (NT_NODE + 1) * 4, hipMemcpyHostToDevice);
+    tab_n = rvs_chisq_grid_tab_work_size(npix, NT_NODE, Nv, S, 1, pack);
+    if (tab_n > 0) hipMalloc(&d_tab, tab_n * 8);
+#endif
   }
   int rc = rvs_chisq_prepare(d_lam, d_spec, d_espec, npix, S, knots.data(), 1, 0.0, d_work, nullptr);
   if (rc) { printf("prepare rc %d\n", rc); return 1; }
@@ -65,8 +97,17 @@ int main(int argc, char **argv) {
   float best = 1e30f, sum = 0;
   for (int r = 0; r < reps + 1; r++) {
     hipEventRecord(e0);
+#ifdef CG_TAB
+    int32_t took = 0;
+    if (own != 2) { printf("-DCG_TAB needs own = 2\n"); return 1; }
+    rc = rvs_chisq_grid_tab(d_lam, d_polys, d_work, npix, P, S, nullptr, 1, 0, d_knots, d_coef, ntp, NT_NODE, 1, nullptr, d_jt, S,
+                            d_vels, 0, Nv, nullptr, 1e5, 0.0, pack, nullptr, d_out, d_st, d_order, d_start, d_start, S, 1,
+                            d_tab, tab_n, 0, &took, nullptr);
+    if (!rc && !took) { printf("the table path declined\n"); return 1; }
+#else
     rc = rvs_chisq_grid(d_lam, d_polys, d_work, npix, P, S, d_knots, d_coef, ntp, own == 1 ? S : (own == 2 ? 76 : 1), 1, nullptr, own == 1 ? nullptr : d_jt, S,
                         d_vels, Nv, Nv, nullptr, 1e5, 0.0, pack, d_out, d_st, nullptr);
+#endif
     hipEventRecord(e1); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     if (r) { best = fminf(best, ms); sum += ms; }

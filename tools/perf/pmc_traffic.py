@@ -36,7 +36,10 @@ def main():
     def entry(names, count_name, what):
         f = sum(sum(v) for k, v in fe.items() if any(n in k for n in names))
         w = sum(sum(v) for k, v in wr.items() if any(n in k for n in names))
-        n = sum(len(v) for k, v in fe.items() if all(c in k for c in count_name))
+        # count_name: one tuple of substrings, or a list of them (any may match)
+        alts = count_name if isinstance(count_name, list) else [count_name]
+        n = sum(len(v) for k, v in fe.items()
+                if any(all(c in k for c in alt) for alt in alts))
         return dict(launches=n, fetch_size_raw_kb=f, write_size_raw_kb=w,
                     hbm_bytes_per_launch=(2 * f + w) * 1024 / max(n, 1),
                     fetch_uncorrected_bytes_per_launch=f * 1024 / max(n, 1),
@@ -49,13 +52,17 @@ def main():
         ccf_xcorr=entry(['ccf_xcorr_'], ('ccf_xcorr_', ),
                         'ccf_xcorr_ws_kernel / ccf_xcorr_kernel (one launch = one '
                         'accumulator chunk x T templates x one arm)'),
-        chisq_grid=entry(['chisq_grid_kernel', 'chisq_grid_resol'],
-                         # (one full-wave launch per rvs_chisq_grid call, any npoly)
-                         ('chisq_grid_kernel<', ', false>')
+        chisq_grid=entry(['chisq_grid_kernel', 'chisq_grid_resol',
+                          'chisq_grid_tab_kernel', 'chisq_resample_kernel'],
+                         # (one full-wave launch per rvs_chisq_grid call, any npoly:
+                         # the spline form or, on the node table, chisq_grid_tab_kernel)
+                         [('chisq_grid_kernel<', ', false>'),
+                          ('chisq_grid_tab_kernel<', )]
                          if not any('chisq_grid_resol' in k for k in fe)
                          else ('chisq_grid_resol', ),
                          'every chisq_grid kernel of one rvs_chisq_grid call (full '
-                         'waves + packed left-over velocities); FETCH_SIZE '
+                         'waves, on the node table with its resampling, + packed '
+                         'left-over velocities); FETCH_SIZE '
                          'doubling is calibrated for 16-B streaming reads, this '
                          'kernel gathers 32-B records'))
     json.dump(d, open(out, 'w'), indent=1)

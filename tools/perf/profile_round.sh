@@ -32,14 +32,16 @@ def per_launch(names, count_name):
     gfx950 FETCH_SIZE reports half of wide coalesced reads, WRITE_SIZE exact)"""
     fe = sum(v[1] for k, v in out['FETCH_SIZE'].items() if any(n in k for n in names))
     wr = sum(v[1] for k, v in out['WRITE_SIZE'].items() if any(n in k for n in names))
-    n = sum(v[0] for k, v in out['FETCH_SIZE'].items() if count_name in k)
+    cn = count_name if isinstance(count_name, list) else [count_name]
+    n = sum(v[0] for k, v in out['FETCH_SIZE'].items() if any(c in k for c in cn))
     return dict(launches=n, fetch_size_raw_kb=fe, write_size_raw_kb=wr,
                 hbm_bytes_per_launch=(2 * fe + wr) * 1024 / max(n, 1))
 src = 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate runs of python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline, tag ${tag}'
 t = {'ccf_xcorr': dict(per_launch(['ccf_xcorr_kernel'], 'ccf_xcorr_kernel'), source=src,
                        kernels='ccf_xcorr_kernel (one launch = one accumulator chunk x T templates x one arm)'),
-     'chisq_grid': dict(per_launch(['chisq_grid_kernel'], 'chisq_grid_kernel<10, false>'), source=src,
-                        kernels='chisq_grid_kernel<10,false> + <10,true> (one rvs_chisq_grid call = one arm of the batch)',
+     'chisq_grid': dict(per_launch(['chisq_grid_kernel', 'chisq_grid_tab_kernel', 'chisq_resample_kernel'],
+                                        ['chisq_grid_kernel<10, false>', 'chisq_grid_tab_kernel<10>']), source=src,
+                        kernels='chisq_grid_kernel<10,false> or, on the node table, chisq_grid_tab_kernel<10> + chisq_resample_kernel; + <10,true> (one rvs_chisq_grid call = one arm of the batch)',
                         note='FETCH_SIZE doubling is calibrated for 16-B-per-lane streaming reads; this kernel gathers 32-B records and reads through the scalar cache')}
 json.dump(t, open('gpurun_out/pmc_${tag}_traffic.json', 'w'), indent=1)
 print(json.dumps(t, indent=0)[:1500])

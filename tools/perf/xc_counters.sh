@@ -24,7 +24,7 @@ nl = collections.defaultdict(lambda: collections.defaultdict(int))
 for f in glob.glob('/tmp/xcc_*/**/*counter_collection.csv', recursive=True):
     for r in csv.DictReader(open(f)):
         k = r['Kernel_Name'].split('(')[0]
-        if not any(s in k for s in ('ccf_xcorr', 'chisq_grid_kernel', 'ccf_preprocess', 'ccf_rfft')):
+        if not any(s in k for s in ('ccf_xcorr', 'chisq_grid_kernel', 'chisq_grid_tab_kernel', 'chisq_resample', 'ccf_preprocess', 'ccf_rfft')):
             continue
         acc[k][r['Counter_Name']] += float(r['Counter_Value'])
         nl[k][r['Counter_Name']] += 1

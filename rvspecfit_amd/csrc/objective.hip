@@ -1038,7 +1038,7 @@ __global__ void __launch_bounds__(OBJ_NT)
   OBJ_T(7);
   if constexpr (RESOL) {
     // ---- A9: model[k] = sum_d taps[s, k, d] raw[k - hb + d], d ascending from 0 as
-    // point_block_kernel forms it (chisq.hip), then t/e.  Threads are pixels: a lane's
+    // point_block_kernel forms it (chisq_point.hip), then t/e.  Threads are pixels: a lane's
     // nd taps are one contiguous run on an 8-byte boundary, taken two per request.
     __syncthreads();
     const double *tps = S.taps ? S.taps + (int64_t)s * S.taps_stride : nullptr;

@@ -956,7 +956,7 @@ def chisq_grid(batch, libs, coefs, outsides, vels, npoly=5, rbf=True,
 # widest basis of rvs_chisq_point / rvs_chisq_grid (one lane keeps the packed
 # normal matrix); rvs_chisq_full takes 32
 POINT_MAXP = 16
-# most tangent rows of rvs_chisq_point_grad (GRAD_MAXTAN of csrc/chisq.hip)
+# most tangent rows of rvs_chisq_point_grad (GRAD_MAXTAN of csrc/chisq_point.hip)
 GRAD_MAXTAN = 6
 # most LDS of the tiles of rvs_chisq_point_grad_resol (RVS_GRAD_RESOL_LDS_MAX of
 # include/rvsgpu.h): (2 + ntan) * (255 + nd) * 8 bytes for a band of nd diagonals

@@ -823,6 +823,46 @@ int rvs_objective_from_template_n(const rvs_objective_arm *arms, int narm,
                                   int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------
+ * The objective of rvs_objective_fused WITH its gradient, as one kernel per (job,
+ * arm), by the adjoint method: the template path (gather, rotational FIR, natural
+ * spline, resampling) is linear in the template row, so one adjoint row -- whatever
+ * ntan is -- is carried from the pixels back to the knots in the three LDS buffers the
+ * value uses, and contracted there with the tangents d t / d p_d formed per knot from
+ * the vertex rows (as rvs_template_polylinear_grad forms them) and, with vsini fitted,
+ * with the tap derivatives of rvs_vsini_convolve_grad.  No template row, spline record
+ * or adjoint row goes to HBM; no floating point atomics: repeated calls and permuted
+ * job lists agree to the bit.  Replaces the chain rvs_template_polylinear_grad ->
+ * rvs_vsini_convolve(_grad) -> rvs_spline_construct -> rvs_chisq_point_grad.
+ * Arms as for rvs_objective_fused; pt.polysT may be ANY basis of the continuum space
+ * with basis_const [narm] (host, or NULL) added to the arm's value, as for
+ * rvs_chisq_point_grad.  ntan = ndim, or ndim + 1 with vsini fitted (vsini != NULL).
+ *   out [J]             sum over the arms of chisq + outside*badchi (an arm whose
+ *                       outside flag is not finite: + 1000*badchi and no gradient)
+ *   grad [J, 1 + ntan]  d/d(vel, parameters in library order[, vsini]), the column
+ *                       order of rvs_chisq_point_grad; the penalties are not
+ *                       differentiated.  Nearest-neighbour templates (outside the grid,
+ *                       a missing vertex): parameter columns exactly 0; the copy
+ *                       branches of the FIR (vsini <= 0, NaN, refused width): vsini
+ *                       column exactly 0.  Where the factorisation fails:
+ *                       RVS_ST_CHOL_FALLBACK | RVS_ST_NONFINITE, value and gradient NaN.
+ *   status [J]          OR-ed into, as by rvs_chisq_point_grad
+ *   scratch             rvs_objective_grad_work_size(J, narm, ntan) bytes (0 for
+ *                       arguments out of range)
+ * rvs_objective_grad_ok (host arithmetic only, no device is touched): 1 where the
+ * kernel covers an arm of this geometry -- npoly 1..10, ndim 1..4, 32 <= ntp,
+ * 2*npix <= ntp, 3*ntp doubles + 8 KB <= 160 KB of LDS.  RVS_E_ARG, before any launch:
+ * an arm rvs_objective_grad_ok refuses, a resolution matrix, a grid set, fast_interp,
+ * arms of different ndim, ntan other than ndim or ndim + 1, a NULL array.
+ * ---------------------------------------------------------------------- */
+int rvs_objective_grad_ok(int npoly, int npix, int ntp, int ndim, int vsini_grad);
+int64_t rvs_objective_grad_work_size(int J, int narm, int ntan);
+int rvs_objective_grad(const rvs_objective_arm *arms, int narm, int npoly, int ntan,
+                       const double *params, const double *vsini,
+                       const int32_t *job_spec, int J, const double *vel,
+                       double badchi, const double *basis_const, void *scratch,
+                       double *out, double *grad, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------
  * Host side of the second minimiser of vel_fit.process (vel_fit.py:653-658:
  * scipy.optimize.minimize(method='BFGS', options={'hess_inv0': ...})): S
  * independent BFGS runs (scipy's _minimize_bfgs with its wolfe1 / wolfe2 line
@@ -1399,6 +1439,19 @@ int64_t rvs_grad_chain_work_size(int cap, int narm, int ntan, const int32_t *ntp
 int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective *o,
                       const rvs_grad_chain *g, int sync_every, int64_t *stats,
                       void *stream);
+
+/* rvs_bfgs_run_grad with the rows' (value, gradient) from ONE rvs_objective_grad call
+ * per chunk in place of the per-arm template, broadening and spline stages and the
+ * rvs_chisq_point_grad call; rvs_proc_map and rvs_proc_finish_grad are unchanged.
+ * garms [narm] (HOST): the arms of rvs_objective_grad (pt.polysT the orthonormalised
+ * basis), basis_const [narm] (HOST, or NULL), gwork:
+ * rvs_objective_grad_work_size(g->cap, narm, g->ntan) bytes.  From `g` only chi, grad,
+ * njev, cap, ntan, vsini_mode and narm are read (no row buffer is needed).  RVS_E_ARG
+ * also for what rvs_objective_grad refuses. */
+int rvs_bfgs_run_grad_fused(const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                            const rvs_grad_chain *g, const rvs_objective_arm *garms,
+                            const double *basis_const, void *gwork, int sync_every,
+                            int64_t *stats, void *stream);
 
 /* ------------------------------------------------------------------------
  * The second minimiser as Levenberg-Marquardt on the Fisher matrix

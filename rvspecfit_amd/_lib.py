@@ -128,6 +128,10 @@ SIGNATURES = {
     'rvs_objective_fused_n': (I, [P, I, I, P, P, P, I, P, P, D, I, P, P, P, P]),
     'rvs_objective_from_template_n': (I, [P, I, I, P, P, P, P, I, P, P, D, I, P,
                                           P, P, P]),
+    'rvs_objective_grad_ok': (I, [I, I, I, I, I]),
+    'rvs_objective_grad_work_size': (L, [I, I, I]),
+    'rvs_objective_grad': (I, [P, I, I, I, P, P, P, I, P, D, P, P, P, P, P, P]),
+    'rvs_bfgs_run_grad_fused': (I, [P, P, P, P, P, P, I, P, P]),
     'rvs_grid_moments': (I, [P, P, L, P, I, I, I, I, P, P, P, P]),
     'rvs_basis_build': (I, [P, P, I, I, I, I, P, P, P, P, P]),
     'rvs_ccf_tables_build': (I, [P, P, I, I, P, I, I, P, P, P, I, P, P, P, P, P, P,

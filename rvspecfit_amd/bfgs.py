@@ -111,7 +111,9 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     objective is the gradient chain of an optimizer.GradChain (`chain`, or one
     built here with `cap` rows per chunk -- by default as many as
     optimizer.GRAD_CHAIN_BUDGET holds); the result then carries njev.  Libraries
-    and options the gradient does not cover raise ValueError."""
+    and options the gradient does not cover raise ValueError.  A chain built with
+    fused=True runs rvs_bfgs_run_grad_fused: the rows' value and gradient from one
+    kernel per (row, arm)."""
     import ctypes
     import torch
     from . import _lib
@@ -145,7 +147,15 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     b.S, b.n, b.cap, b.maxiter = S, n, int(pobj.cap), int(maxiter or 0)
     o = pobj.native_desc()
     st3 = (ctypes.c_int64 * 3)()
-    if jac:
+    if jac and getattr(chain, 'fused', False):
+        # optimizer.GradChain(fused=True): one rvs_objective_grad call per chunk
+        g = chain.desc()
+        _lib.check(L.rvs_bfgs_run_grad_fused(
+            ctypes.addressof(b), ctypes.addressof(o), ctypes.addressof(g),
+            ctypes.addressof(chain.garms), ctypes.addressof(chain.bconst),
+            _lib.ptr(chain.gwork), int(sync_every), st3, _lib.stream()),
+            'rvs_bfgs_run_grad_fused')
+    elif jac:
         g = chain.desc()
         _lib.check(L.rvs_bfgs_run_grad(ctypes.addressof(b), ctypes.addressof(o),
                                        ctypes.addressof(g), int(sync_every), st3,

@@ -179,14 +179,22 @@ extern "C" int rvs_bfgs_run(const rvs_bfgs_state *b, const rvs_nm_objective *o,
   return 0;
 }
 
-extern "C" int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective *o,
-                                 const rvs_grad_chain *g, int sync_every,
-                                 int64_t *stats, void *stream) {
-  if (!b || !o || !g || b->S < 1 || b->n < 1 || b->n > 8 || b->n != o->n ||
-      sync_every < 1 || !b->runs || !b->x0 || !b->x || !b->fun || !b->nit ||
-      !b->nfev || !b->status || !b->nreq || !b->off || !b->list || !b->X || !b->F ||
-      !b->counts || !g->njev || !rvs_internal_grad_chain_ok(g, o))
-    return RVS_E_ARG;
+namespace {
+
+// what both forms of the exact-gradient polish ask of b and o beside their own checks
+bool bfgs_jac_args_ok(const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                      const rvs_grad_chain *g, int sync_every) {
+  return b && o && g && b->S >= 1 && b->n >= 1 && b->n <= 8 && b->n == o->n &&
+         sync_every >= 1 && b->runs && b->x0 && b->x && b->fun && b->nit && b->nfev &&
+         b->status && b->nreq && b->off && b->list && b->X && b->F && b->counts &&
+         g->njev;
+}
+
+// the rounds of rvs_bfgs_run_grad over eval(list, X, J, chunk, F, stream): (f, grad f)
+// of a chunk of rows into F [J, 1 + n]
+template <class Eval>
+int bfgs_run_jac(const rvs_bfgs_state *b, const rvs_grad_chain *g, int sync_every,
+                 int64_t *stats, void *stream, Eval eval) {
   const int S = b->S, n = b->n, cap = g->cap;
   const int64_t maxrows = S;   // one row per live run
   if ((maxrows + cap - 1) / cap > BF_NCHUNK) return RVS_E_ARG;
@@ -225,9 +233,7 @@ extern "C" int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective
       if (bound > maxrows) bound = maxrows;
       for (int64_t a = 0, ch = 0; a < bound; a += cap, ch++) {
         const int J = (int)((bound - a < cap) ? bound - a : cap);
-        int rc = rvs_internal_grad_chain_eval(o, g, b->list + a, b->X + a * n, J,
-                                              b->counts, (int)ch,
-                                              b->F + a * (n + 1), st);
+        int rc = eval(b->list + a, b->X + a * n, J, (int)ch, b->F + a * (n + 1), st);
         if (rc) return rc;
         calls++;
         jobs += J;
@@ -249,4 +255,64 @@ extern "C" int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective
     stats[2] = jobs;
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                                 const rvs_grad_chain *g, int sync_every,
+                                 int64_t *stats, void *stream) {
+  if (!bfgs_jac_args_ok(b, o, g, sync_every) || !rvs_internal_grad_chain_ok(g, o))
+    return RVS_E_ARG;
+  return bfgs_run_jac(b, g, sync_every, stats, stream,
+                      [&](const int32_t *list, const double *X, int J, int ch, double *F,
+                          hipStream_t st) {
+                        return rvs_internal_grad_chain_eval(o, g, list, X, J, b->counts,
+                                                            ch, F, st);
+                      });
+}
+
+// ... with the chain's stages between rvs_proc_map and rvs_proc_finish_grad replaced by
+// one rvs_objective_grad call (objective_grad.hip)
+extern "C" int rvs_bfgs_run_grad_fused(const rvs_bfgs_state *b,
+                                       const rvs_nm_objective *o,
+                                       const rvs_grad_chain *g,
+                                       const rvs_objective_arm *garms,
+                                       const double *basis_const, void *gwork,
+                                       int sync_every, int64_t *stats, void *stream) {
+  if (!bfgs_jac_args_ok(b, o, g, sync_every) || !garms || !gwork || !g->chi ||
+      !g->grad || g->cap < 1 || g->narm < 1 || g->narm > RVS_MAX_ARMS ||
+      g->narm != o->narm || g->vsini_mode < 0 || g->vsini_mode > 2 || o->ndim < 1 ||
+      o->ndim > 4 || g->ntan != o->ndim + (g->vsini_mode == 2 ? 1 : 0) ||
+      (g->vsini_mode == 2) != (o->vsini_col >= 0) ||
+      (g->vsini_mode != 0) != (o->vsini != nullptr) || !o->vel || !o->params ||
+      !o->extra || !o->bad || !o->job_spec || !o->jstatus || !o->status || !o->fixed ||
+      !o->safe)
+    return RVS_E_ARG;
+  for (int a = 0; a < g->narm; a++)
+    if (garms[a].ndim != o->ndim || garms[a].pt.taps || garms[a].pt.G > 1 ||
+        garms[a].pt.fast_interp ||
+        !rvs_objective_grad_ok(o->npoly, garms[a].pt.npix, garms[a].ntp, o->ndim,
+                               g->vsini_mode == 2))
+      return RVS_E_ARG;
+  return bfgs_run_jac(
+      b, g, sync_every, stats, stream,
+      [&](const int32_t *list, const double *X, int J, int ch, double *F,
+          hipStream_t st) {
+        int rc = rvs_proc_map(J, o->n, o->ndim, X, list, o->src, o->vsini_col, o->fixed,
+                              o->vsini_fixed, o->safe, o->prior_mean, o->prior_isig,
+                              o->min_vel, o->max_vel, o->max_vsini, o->job_spec, o->vel,
+                              o->vsini, o->params, o->extra, o->bad, st);
+        if (rc) return rc;
+        if (hipMemsetAsync(o->jstatus, 0, sizeof(int32_t) * J, st) != hipSuccess)
+          return RVS_E_LAUNCH;
+        rc = rvs_objective_grad(garms, g->narm, o->npoly, g->ntan, o->params, o->vsini,
+                                o->job_spec, J, o->vel, o->badchi, basis_const, gwork,
+                                g->chi, g->grad, o->jstatus, st);
+        if (rc) return rc;
+        return rvs_proc_finish_grad(J, o->n, o->ndim, g->ntan, b->counts, ch, g->chi,
+                                    g->grad, X, o->params, o->extra, o->bad, o->job_spec,
+                                    o->jstatus, o->src, o->vsini_col, o->prior_mean,
+                                    o->prior_isig, o->max_vsini, F, o->status, st);
+      });
 }

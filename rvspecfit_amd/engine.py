@@ -1382,6 +1382,122 @@ def objective_from_template(batch, libs, templs, outsides, vsini, vel, npoly=5,
                            outsides=outsides)
 
 
+GRAD_FUSED_MAXP = 10     # OG_MAXP of csrc/objective_grad.hip
+GRAD_FUSED_MAXDIM = 4
+
+
+def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
+                           vsini_grad=False, what=None):
+    """ValueError naming the option that config['fused_gradient'] does not go with:
+    what rvs_objective_grad (csrc/objective_grad.hip) does not cover keeps the chain,
+    and the key beside it is an error, never a silent change of path.  `what`: a
+    caller's own option that needs tangent rows (the Fisher matrix, the
+    Levenberg-Marquardt polish, the joint-epoch fit)."""
+    key = "config['fused_gradient']"
+    if what is not None:
+        raise ValueError('%s does not go with %s: it needs the tangent rows of the '
+                         'gradient chain, which the fused kernel never forms'
+                         % (key, what))
+    if fast_interp:
+        raise ValueError('%s does not go with fast_interp (the nearest-knot template '
+                         'has no velocity derivative)' % key)
+    if npoly < 1 or npoly > GRAD_FUSED_MAXP:
+        raise ValueError('%s takes npoly 1..%d, not npoly = %d (beyond, the wave '
+                         'totals of the normal equations live in the template buffer)'
+                         % (key, GRAD_FUSED_MAXP, npoly))
+    ok = _lib.lib().rvs_objective_grad_ok
+    for ia, arm in enumerate(batch.arms):
+        lib = libs[arm.name]
+        if _arm_resol(arm, ia, resols) is not None:
+            raise ValueError('%s does not go with a resolution matrix (resol_params / '
+                             'the spectra\'s own, arm %s)' % (key, arm.name))
+        if arm.G > 1:
+            raise ValueError('%s does not go with a grid set: arm %s has %d wavelength '
+                             'grids' % (key, arm.name, arm.G))
+        if lib.kind != 'regulargrid':
+            raise ValueError('%s needs regular-grid (polylinear) libraries: %s is a %s '
+                             'library (interpolation_type)' % (key, arm.name, lib.kind))
+        if lib.spline_factors is None:
+            raise ValueError('%s needs a (log-)uniform template grid (arm %s)'
+                             % (key, arm.name))
+        if lib.ndim > GRAD_FUSED_MAXDIM:
+            raise ValueError('%s takes libraries of up to %d parameters, %s has ndim = %d'
+                             % (key, GRAD_FUSED_MAXDIM, arm.name, lib.ndim))
+        if not ok(npoly, arm.npix, lib.ntp, lib.ndim, int(bool(vsini_grad))):
+            raise ValueError('%s: arm %s (npix = %d, ntp = %d) is outside the kernel\'s '
+                             'geometry: 32 <= ntp, 2 npix <= ntp, three buffers of ntp '
+                             'doubles in LDS' % (key, arm.name, arm.npix, lib.ntp))
+
+
+def can_fuse_objective_grad(batch, libs, resols=None, fast_interp=False, npoly=10,
+                            vsini_grad=False):
+    """whether rvs_objective_grad covers this batch (check_fused_grad_scope says why
+    not)"""
+    try:
+        check_fused_grad_scope(batch, libs, npoly, resols, fast_interp, vsini_grad)
+    except ValueError:
+        return False
+    return True
+
+
+def fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys=0.0):
+    """fill_objective_arms for rvs_objective_grad: the orthonormal basis of the same
+    continuum space (ArmData.basis_ortho) with its constant, as chisq_point_grad wires
+    the chain's descriptors; returns the tensors to keep alive"""
+    keep = fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys)
+    for ia, arm in enumerate(batch.arms):
+        qt, const = arm.basis_ortho(npoly, rbf)
+        arr[ia].pt.polysT = qt.data_ptr()
+        bconst[ia] = const
+        keep.append(qt)
+    return keep
+
+
+def objective_grad_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
+                         job_spec=None, vsini_grad=False, espec_sys=0.0):
+    """get_chisq and its gradient for J (spectrum, parameters, vsini, velocity) jobs
+    as ONE kernel per (job, arm) (rvs_objective_grad, the adjoint method): no template
+    row, tangent row or spline record in HBM.  Returns chisq [J] (with the outside
+    penalty, which is not differentiated), grad [J, 1 + ndim] = d/d(vel, parameters)
+    -- [J, 2 + ndim] with vsini_grad, d/dvsini last -- and status int32 [J]: the
+    results of build_templates(tangents=True) + chisq_point_grad to rounding.  What
+    the kernel does not cover raises ValueError (check_fused_grad_scope)."""
+    import ctypes
+    if vsini_grad and vsini is None:
+        raise ValueError('vsini_grad=True needs vsini: without rotation there is no '
+                         'vsini to differentiate by')
+    check_fused_grad_scope(batch, libs, npoly, None, False, vsini_grad)
+    L = _lib.lib()
+    dev = batch.device
+    vel = vel.to(device=dev, dtype=torch.float64).contiguous()
+    params = params.to(device=dev, dtype=torch.float64).contiguous()
+    J = vel.shape[0]
+    narm = len(batch.arms)
+    ntan = libs[batch.arms[0].name].ndim + (1 if vsini_grad else 0)
+    arr = (_lib.ObjectiveArm * narm)()
+    bconst = (ctypes.c_double * narm)()
+    keep = fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys)
+    out = torch.empty(J, dtype=torch.float64, device=dev)
+    grad = torch.empty((J, 1 + ntan), dtype=torch.float64, device=dev)
+    status = torch.zeros(J, dtype=torch.int32, device=dev)
+    nb = L.rvs_objective_grad_work_size(J, narm, ntan)
+    scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
+    if vsini is not None:
+        vsini = vsini.to(device=dev, dtype=torch.float64).contiguous()
+    if job_spec is not None:
+        job_spec = job_spec.to(device=dev, dtype=torch.int32).contiguous()
+    with _ktime('objective_grad', J):
+        rc = L.rvs_objective_grad(ctypes.addressof(arr), narm, npoly, ntan,
+                                  _lib.ptr(params), _lib.ptr(vsini), _lib.ptr(job_spec),
+                                  J, _lib.ptr(vel), float(batch.badchi),
+                                  ctypes.addressof(bconst), _lib.ptr(scratch),
+                                  _lib.ptr(out), _lib.ptr(grad), _lib.ptr(status),
+                                  _lib.stream())
+        _lib.check(rc, 'rvs_objective_grad')
+    del keep
+    return out, grad, status
+
+
 _ar_cache = {}
 
 

@@ -354,12 +354,21 @@ class GradChain:
     fisher=True: the Fisher form of the chain (rvs_lm_run: rvs_chisq_point_fisher and
     rvs_proc_finish_fisher as its last two calls) -- `rows` then returns
     [rows, 1 + n + n (n + 1) / 2] = (f, gradient, lower triangle of the Gauss-Newton
-    Hessian), and the Fisher buffers are counted inside the same budget."""
+    Hessian), and the Fisher buffers are counted inside the same budget.
+    fused=True (config['fused_gradient']): the rows' value and gradient come from ONE
+    rvs_objective_grad call per chunk (rvs_bfgs_run_grad_fused; csrc/objective_grad.hip)
+    -- the object then holds no template or record buffers, only the arm descriptors,
+    the kernel's scratch and the chunk's chi / grad; `rows` goes through the same call.
+    What that kernel does not cover, fisher=True included, raises ValueError."""
 
-    def __init__(self, pobj, cap=None, budget=None, fisher=False):
+    def __init__(self, pobj, cap=None, budget=None, fisher=False, fused=False):
         L = _lib.lib()
         batch, libs = pobj.batch, pobj.libs
         fit = pobj.vsini_col >= 0
+        self.fused = bool(fused)
+        if self.fused:
+            self._init_fused(pobj, cap, fisher)
+            return
         # (refused before anything is built; nothing falls back to differences)
         engine.check_grad_scope(batch, libs, pobj.npoly, pobj.resols, False,
                                 vsini_grad=fit,
@@ -476,6 +485,35 @@ class GradChain:
             self.fisher_work = torch.empty((nb + 7) // 8, **f64)
             self.fisher_buf = torch.empty((cap, K, K), **f64)
 
+    def _init_fused(self, pobj, cap, fisher):
+        L = _lib.lib()
+        batch, libs = pobj.batch, pobj.libs
+        fit = pobj.vsini_col >= 0
+        engine.check_fused_grad_scope(
+            batch, libs, pobj.npoly, pobj.resols, False, vsini_grad=fit,
+            what='the Fisher form of the chain (fisher=True)' if fisher else None)
+        self.pobj, self.fisher = pobj, False
+        dev = pobj.dev
+        narm = len(batch.arms)
+        self.ntan = pobj.ndim + (1 if fit else 0)
+        self.vsini_mode = 2 if fit else (1 if pobj.has_vsini else 0)
+        cap = int(min(pobj.S if cap is None else cap, pobj.cap))
+        if cap < 1 or (pobj.S + cap - 1) // cap > GradChain.MAX_CHUNKS:
+            raise ValueError('second_minimizer_jac: a round holds at most %d chunks of '
+                             '%d rows: %d spectra do not fit one call; pass them in '
+                             'smaller batches' % (GradChain.MAX_CHUNKS, cap, pobj.S))
+        self.cap = cap
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.garms = (_lib.ObjectiveArm * narm)()
+        self.bconst = (ctypes.c_double * narm)()
+        self._keep = engine.fill_objective_grad_arms(self.garms, self.bconst, batch, libs,
+                                                     pobj.npoly, pobj.rbf)
+        self.nbytes = int(L.rvs_objective_grad_work_size(cap, narm, self.ntan))
+        self.gwork = torch.empty((self.nbytes + 7) // 8, **f64)
+        self.chi = torch.empty(cap, **f64)
+        self.grad = torch.empty((cap, 1 + self.ntan), **f64)
+        self.njev = torch.zeros(pobj.S, dtype=torch.int32, device=dev)
+
     MAX_CHUNKS = 24     # the chunk counters of the scan kernel (bfgs_dev.hip)
 
     @staticmethod
@@ -513,14 +551,15 @@ class GradChain:
 
     def desc(self):
         g = _lib.GradChain()
-        g.arms, g.point = ctypes.addressof(self.arms), ctypes.addressof(self.point)
         g.basis_const = ctypes.addressof(self.bconst)
         ps = self.pobj.batch.pen_scale
         g.pen_scale = None if ps is None else ps.data_ptr()
-        g.point_work = self.point_work.data_ptr()
+        if not self.fused:   # (rvs_bfgs_run_grad_fused reads none of the three)
+            g.arms, g.point = ctypes.addressof(self.arms), ctypes.addressof(self.point)
+            g.point_work = self.point_work.data_ptr()
         g.chi, g.grad = self.chi.data_ptr(), self.grad.data_ptr()
         g.njev = self.njev.data_ptr()
-        g.narm, g.ntan = len(self.arms), self.ntan
+        g.narm, g.ntan = len(self.pobj.batch.arms), self.ntan
         g.cap, g.vsini_mode = self.cap, self.vsini_mode
         return g
 
@@ -562,7 +601,7 @@ class GradChain:
                 None if p.vsini is None else p.vsini[:n], p.npoly, p.rbf, 0.0, True,
                 p.resols, False, p.vsini_col >= 0, self.fisher,
                 nn_gradient=getattr(p, 'nn_gradient', False),
-                resol_gradient=getattr(p, 'resol_gradient', False))
+                resol_gradient=getattr(p, 'resol_gradient', False), fused=self.fused)
             chi, grad, status = res[0], res[1], res[-1]
             tail = (_p(X_t[a:]), _p(p.params), _p(p.extra), _p(p.bad), _p(p.job_spec),
                     _p(status), p.src, p.vsini_col, _p(p.prior_mean), _p(p.prior_isig),

@@ -507,6 +507,10 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
     With config['resol_gradient'] true a resolution matrix is taken -- resol_params
     or the SpecData's own (both together raise, as in get_chisq): the model and every
     tangent row go through it (rvs_chisq_point_grad_resol).
+    With config['fused_gradient'] true value and gradient come from one kernel per
+    (spectrum, setup) (rvs_objective_grad, the adjoint method: no template or tangent
+    row in HBM) -- regular-grid libraries of up to 4 parameters, npoly <= 10; anything
+    else beside that key raises ValueError naming the option and the key.
     An MLP library is among them unless config['nn_gradient'] is true: its tangent
     rows (rvs_template_nn_grad) are float32 arithmetic, exact to float32 rounding only.  On a Delaunay library a point that no simplex
     holds has the value's penalty and a zero gradient."""
@@ -546,7 +550,8 @@ def _get_chisq_grad(specdata, vel, atm_params, rot_params, options, config,
     res = _chisq_grad(batch, libs, None, velt[:, 0], params, vsini, npoly, rbf, esys,
                       outside_penalty, resols, fast_interp, vsini_grad, fisher,
                       nn_gradient=bool((config or {}).get('nn_gradient')),
-                      resol_gradient=bool((config or {}).get('resol_gradient')))
+                      resol_gradient=bool((config or {}).get('resol_gradient')),
+                      fused=bool((config or {}).get('fused_gradient')))
     if is_batch:
         return res[:-1]
     _raise_for_status(int(res[-1][0].item()),
@@ -576,8 +581,19 @@ def get_chisq_fisher(specdata, vel, atm_params, rot_params=None, options=None,
 
 def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
                 outside_penalty, resols, fast_interp, vsini_grad=False, fisher=False,
-                nn_gradient=False, resol_gradient=False):
+                nn_gradient=False, resol_gradient=False, fused=False):
     # (the checks come first: nothing is built for a call that is refused)
+    if fused:
+        # config['fused_gradient']: value and gradient in one kernel per (job, arm)
+        # (rvs_objective_grad); what it does not cover is an error, not the chain
+        engine.check_fused_grad_scope(batch, libs, npoly, resols, fast_interp,
+                                      vsini_grad,
+                                      what='the Fisher matrix' if fisher else None)
+        if not outside_penalty:
+            raise ValueError("config['fused_gradient'] does not go with "
+                             'outside_penalty=False: the kernel adds the penalty')
+        return engine.objective_grad_fused(batch, libs, params, vsini, vel, npoly, rbf,
+                                           js, vsini_grad, esys)
     engine.check_grad_scope(batch, libs, npoly, resols, fast_interp, vsini_grad,
                             nn_gradient=nn_gradient, resol_gradient=resol_gradient)
     coefs, outs = [], []
@@ -739,7 +755,8 @@ def _chisq_grad_jobs(batch, idx, vel, params, vsini, options, config, outside_pe
     return _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
                        outside_penalty, resols, False, vsini_grad, fisher,
                        nn_gradient=bool((config or {}).get('nn_gradient')),
-                       resol_gradient=bool((config or {}).get('resol_gradient')))
+                       resol_gradient=bool((config or {}).get('resol_gradient')),
+                       fused=bool((config or {}).get('fused_gradient')))
 
 
 # rows per launch set of the from-template objective (template buffers of

@@ -1046,6 +1046,19 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
     if lm_polish and config.get('second_minimizer_jac'):
         raise ValueError("config['second_minimizer_lm'] and "
                          "config['second_minimizer_jac'] name two polishes: set one")
+    # config['fused_gradient']: the polish's rows from rvs_objective_grad, one kernel
+    # per (row, arm) (rvs_bfgs_run_grad_fused).  What needs the chain's tangent rows
+    # beside the key is an error that says so; nothing changes path silently
+    fused_grad = bool(config.get('fused_gradient'))
+    if fused_grad:
+        engine.check_fused_grad_scope(
+            batch, spec_inter.get_libs(batch.names, config), options.get('npoly') or 5,
+            spec_fit._resols(batch, resolParams), bool(options.get('fast_interp')),
+            vsini_grad=fitVsini,
+            what="config['second_minimizer_lm'] (the Levenberg-Marquardt polish on the "
+                 "Fisher matrix)" if lm_polish else
+                 ("config['fisher_uncertainties'] (the Fisher matrix)"
+                  if config.get('fisher_uncertainties') else None))
     if lm_polish:
         try:
             engine.check_grad_scope(batch, spec_inter.get_libs(batch.names, config),
@@ -1073,10 +1086,11 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
         # (and the batch must fit the chain's chunks: known here, not after the
         # simplex stage)
         _libs = spec_inter.get_libs(batch.names, config)
-        optimizer.GradChain.choose_cap(
-            S, [_libs[a.name].ntp for a in batch.arms],
-            len(names) + (1 if fitVsini else 0),
-            2 if fitVsini else (1 if 'vsini' in pd0 else 0))
+        if not fused_grad:   # (the fused form holds no row buffers to budget)
+            optimizer.GradChain.choose_cap(
+                S, [_libs[a.name].ntp for a in batch.arms],
+                len(names) + (1 if fitVsini else 0),
+                2 if fitVsini else (1 if 'vsini' in pd0 else 0))
 
     # config['fisher_uncertainties']: the joint covariance of (vel, parameters[, vsini])
     # from the Fisher matrix at the returned optimum, beside the Hessian's products.
@@ -1199,7 +1213,7 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
             # same machine on the host around the same chain driven from Python)
             jobs_before = pobj.jobs
             slots_before = pobj.slots
-            chain = optimizer.GradChain(pobj)
+            chain = optimizer.GradChain(pobj, fused=fused_grad)
             if BFGS_ON_DEVICE:
                 br = bfgs.minimize_lockstep_device(pobj, x, hess_inv0=hess_inv0,
                                                    jac=True, chain=chain)
@@ -1215,7 +1229,7 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
             slots += pobj.slots - slots_before
             bfgs_info = dict(nit=br['nit'], nfev=br['nfev'], njev=br['njev'],
                              status=br['status'], rounds=br['rounds'],
-                             device=BFGS_ON_DEVICE, jac=True)
+                             device=BFGS_ON_DEVICE, jac=True, fused=fused_grad)
         elif BFGS_ON_DEVICE and optimizer.NATIVE_ROUNDS and pobj.native:
             # the rounds inside the library (rvs_bfgs_run), on the objective the
             # simplex stage ran on
@@ -1461,6 +1475,10 @@ def process_epochs(specdata, star, paramDict0, vel0, fixParam=None, options=None
     if not np.array_equal(order, np.arange(S)):
         batch = batch.subset(torch.as_tensor(order).to(dev))
     libs = spec_inter.get_libs(batch.names, config)
+    if config.get('fused_gradient'):
+        engine.check_fused_grad_scope(batch, libs, options.get('npoly') or 5,
+                                      what='the joint fit of a star\'s epochs '
+                                           '(process_epochs: its rows are Fisher rows)')
     safe = torch.stack([pd0[_] for _ in names], dim=1)
     try:
         chain = optimizer.EpochChain(

@@ -3,6 +3,9 @@
 (rvs_bfgs_run) against the polish on the analytic gradient (rvs_bfgs_run_grad,
 config['second_minimizer_jac']), alternating, in one process.
 usage: bfgs_jac_ab.py [--spectra S] [--npoly P] [--rounds R] [--evaluator polylinear|tri]
+                      [--fused]
+--fused: a third polish, the analytic gradient from rvs_objective_grad
+(rvs_bfgs_run_grad_fused, config['fused_gradient']), alternating with the two.
 The workload is bench.py's, built as `bench.py --process` builds it (its synthetic
 DESI-shape libraries and seeded spectra, the start parameters from the CCF stage of
 pipeline.fit_batch).  vel_fit.process runs once without the second minimiser; its
@@ -27,6 +30,7 @@ def main():
     ap.add_argument('--npoly', type=int, default=10)
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--evaluator', choices=['polylinear', 'tri'], default='polylinear')
+    ap.add_argument('--fused', action='store_true')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
     import numpy as np
@@ -81,6 +85,12 @@ def main():
         return bfgs.minimize_lockstep_device(pobj, x0, hess_inv0=hess_inv0, jac=True,
                                              chain=chain)
 
+    fchain = optimizer.GradChain(pobj, fused=True) if args.fused else None
+
+    def fused():
+        return bfgs.minimize_lockstep_device(pobj, x0, hess_inv0=hess_inv0, jac=True,
+                                             chain=fchain)
+
     def timed(fn):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -89,12 +99,17 @@ def main():
         return time.perf_counter() - t0, out
 
     timed(fd), timed(jac)          # warm-up
-    t_fd, t_jac = [], []
+    if args.fused:
+        timed(fused)
+    t_fd, t_jac, t_fu = [], [], []
     for _ in range(args.rounds):
         t, a = timed(fd)
         t_fd.append(t)
         t, b = timed(jac)
         t_jac.append(t)
+        if args.fused:
+            t, c = timed(fused)
+            t_fu.append(t)
 
     def per(res, k):
         x = res[k].double()
@@ -106,6 +121,24 @@ def main():
 
     d = (b['fun'] - a['fun']).cpu().numpy()
     q = [0, 1, 5, 25, 50, 75, 95, 99, 100]
+    more = {}
+    if args.fused:
+        df = (c['fun'] - a['fun']).cpu().numpy()
+        dj = (c['fun'] - b['fun']).cpu().numpy()
+        more = dict(
+            fused=dict(stage_s_median=round(float(np.median(t_fu)), 4),
+                       stage_s_min=round(min(t_fu), 4), lockstep_rounds=c['rounds'],
+                       rows_launched=c['rows_launched'], nit=per(c, 'nit'),
+                       nfev=per(c, 'nfev'), njev=per(c, 'njev'), status_counts=hist(c),
+                       work_bytes=fchain.nbytes),
+            fused_over_fd_time=round(float(np.median(t_fu) / np.median(t_fd)), 3),
+            fused_over_jac_time=round(float(np.median(t_fu) / np.median(t_jac)), 3),
+            f_fused_minus_f_fd=dict(
+                percentiles={str(p): float(np.percentile(df, p)) for p in q},
+                fused_lower=int((df < 0).sum()), equal=int((df == 0).sum()),
+                fused_higher=int((df > 0).sum()), mean=float(df.mean())),
+            f_fused_minus_f_jac_abs_max=float(np.abs(dj).max()),
+            f_fused_equals_f_jac=int((dj == 0).sum()))
     print(json.dumps(dict(
         spectra=S, npoly=args.npoly, evaluator=args.evaluator, rounds=args.rounds,
         n=len(cols), chain_cap=chain.cap, chain_bytes=chain.nbytes,
@@ -121,7 +154,7 @@ def main():
         f_jac_minus_f_fd=dict(
             percentiles={str(p): float(np.percentile(d, p)) for p in q},
             jac_lower=int((d < 0).sum()), equal=int((d == 0).sum()),
-            jac_higher=int((d > 0).sum()), mean=float(d.mean())))), flush=True)
+            jac_higher=int((d > 0).sum()), mean=float(d.mean())), **more)), flush=True)
 
 
 if __name__ == '__main__':

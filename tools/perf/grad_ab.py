@@ -5,6 +5,11 @@ itself, then one call per displaced coordinate: velocity and the ndim parameters
 what a caller without the gradient has to do, and what BFGS does per gradient).
 usage: grad_ab.py [--jobs J] [--spectra S] [--npoly P] [--rounds R] [--vsini]
                   [--vsini-grad] [--evaluator polylinear|tri] [--resolution-matrix]
+                  [--fused]
+--fused: a third leg, the same chisq_grad_jobs call with config['fused_gradient']
+(rvs_objective_grad: value and gradient in one kernel per (job, arm)), alternating
+with the two (fused_s_*, chain_over_fused_median, differenced_over_fused_median, and
+the largest difference of the fused gradient from the chain's).
 --evaluator tri: bench.py's Delaunay library (the same grid nodes triangulated, its
 `--evaluator tri`): rvs_template_tri_buckets_grad in front of the same chain.
 --vsini-grad (implies --vsini): the analytic call carries the vsini tangent row
@@ -40,6 +45,7 @@ def main():
     ap.add_argument('--vsini-grad', action='store_true')
     ap.add_argument('--evaluator', choices=['polylinear', 'tri'], default='polylinear')
     ap.add_argument('--resolution-matrix', action='store_true')
+    ap.add_argument('--fused', action='store_true')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
     import numpy as np
@@ -99,6 +105,12 @@ def main():
         return spec_fit.chisq_grad_jobs(plain, idx, vel, par, vs, opt, cfg,
                                         vsini_grad=vg)
 
+    fcfg = dict(cfg, fused_gradient=True)
+
+    def fused():
+        return spec_fit.chisq_grad_jobs(batch, idx, vel, par, vs, opt, fcfg,
+                                        vsini_grad=vg)
+
     def differenced():
         f0, _ = spec_fit.chisq_jobs(batch, idx, vel, par, vs, opt, cfg)
         cols = []
@@ -121,7 +133,9 @@ def main():
     timed(analytic), timed(differenced)          # warm-up: tables, caches, clocks
     if plain is not None:
         timed(no_matrix)
-    ta, td, tn = [], [], []
+    if args.fused:
+        timed(fused)
+    ta, td, tn, tf = [], [], [], []
     for _ in range(args.rounds):
         t, (ca, ga, st) = timed(analytic)
         ta.append(t)
@@ -129,9 +143,27 @@ def main():
         td.append(t)
         if plain is not None:
             tn.append(timed(no_matrix)[0])
+        if args.fused:
+            t, (cf, gf, sf) = timed(fused)
+            tf.append(t)
     more = {}
+    if args.fused:
+        okf = (st == 0) & (sf == 0)
+        sc = torch.maximum(ga.abs(), 1e-6 * ga.abs().max(dim=1, keepdim=True).values)
+        more.update(
+            fused_s_median=round(float(np.median(tf)), 6), fused_s_min=round(min(tf), 6),
+            chain_over_fused_median=round(float(np.median(ta) / np.median(tf)), 3),
+            differenced_over_fused_median=round(float(np.median(td) / np.median(tf)), 3),
+            fused_status_equal=bool(torch.equal(st, sf)),
+            fused_vs_chain_grad_max_rel=float(((gf - ga).abs() / sc)[okf].max()),
+            # (... and relative to |g|_inf of the job: components at the 1e-6 floor of
+            # the figure above carry the rounding of the whole sum)
+            fused_vs_chain_grad_max_rel_to_norm=float(
+                ((gf - ga).abs() / ga.abs().max(dim=1, keepdim=True).values)[okf].max()),
+            fused_vs_chain_value_max_rel=float(
+                ((cf - ca).abs() / ca.abs().clamp(min=1e3))[okf].max()))
     if plain is not None:
-        more = dict(no_matrix_s_median=round(float(np.median(tn)), 6),
+        more.update(no_matrix_s_median=round(float(np.median(tn)), 6),
                     no_matrix_s_min=round(min(tn), 6),
                     resol_over_no_matrix_median=round(
                         float(np.median(ta) / np.median(tn)), 3))

@@ -1031,7 +1031,9 @@ int rvs_ccf_preprocess_g(const double *lam, const double *spec, const double *es
  *         prune[p>>6] has bit ((p>>3)&7) set (the outputs of the second-last
  *         pass that feed a needed 8-group).  Values are bit-identical to the
  *         unpruned transform.
- * work  complex128 [B, 2, nfft/2+1] scratch for conj rfft of spec*ivar, ivar
+ * work  complex128 [B, 2, nfft/2+1] scratch for conj rfft of spec*ivar, ivar (not
+ *         touched by the persistent kernel of nfft 8192, whose block transforms its
+ *         own spectrum in LDS; every other kernel reads it back)
  * Kernels behind the call (same interface, results equal to a few ulp): at nfft
  * 8192 (with `prune`) and 4096, nlag and nvel <= 512, T >= 2, one persistent
  * wave-specialised block per spectrum walks the T templates (ccf_xcorr_ws_kernel /
@@ -1040,6 +1042,11 @@ int rvs_ccf_preprocess_g(const double *lam, const double *spec, const double *es
  * rvs_option_set("xc_ws", 0) forces the latter.
  * ---------------------------------------------------------------------- */
 int rvs_ccf_fft_pos(int nfft, int f);  /* host helper, see lag_pos */
+/* doubles of `work` that rvs_ccf_xcorr with these shapes reads or writes (host; added
+ * under ABI 18): 0 where the persistent kernel of nfft 8192 runs (work may be NULL
+ * then), else B * 2 * (nfft/2 + 1) * 2.  has_prune: `prune` will not be NULL. */
+int64_t rvs_ccf_xcorr_work_size(int nfft, int B, int T, int nlag, int nvel,
+                                int has_prune);
 int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar, int nfft,
                   int B, const double *tfft, const double *tfft2, int T,
                   const double *twid, int continuum, const int32_t *lag_pos,
@@ -1101,6 +1108,24 @@ int rvs_ccf_models_build(const double *rows, const uint8_t *f32row,
 int rvs_ccf_select(const double *chisq, const double *sse, int narm_sse, int B,
                    int T, const double *vgrid, int nvel, double *res,
                    double *best_ccf, int32_t *status, void *stream);
+
+/* rvs_ccf_xcorr of the LAST arm of a chunk and rvs_ccf_select in one call (added under
+ * ABI 18): the persistent block of a spectrum keeps the minimum of what it stores to
+ * chisq (+ the sum of sse [narm, B] over the arms) and, behind its walk, does the
+ * selection for its spectrum -- res, best_ccf and status with the bits rvs_ccf_select
+ * gives on the chisq the call leaves behind (which is still written in full).
+ * Arguments as the two calls'.  RVS_E_ARG, before any launch, where rvs_ccf_xcorr
+ * would not take the persistent kernel of nfft 8192 (another nfft, no `prune`, nlag or
+ * nvel > 512, T < 2, option "xc_ws" 0) and for sse, res or best_ccf NULL: the caller
+ * then makes the two calls. */
+int rvs_ccf_xcorr_select(const double *proc_spec, const double *proc_ivar, int nfft,
+                         int B, const double *tfft, const double *tfft2, int T,
+                         const double *twid, int continuum, const int32_t *lag_pos,
+                         const double *lag_vel, int nlag, const int32_t *ilo,
+                         const double *vgrid, int nvel, double beta,
+                         const uint8_t *prune, double *chisq, double *work,
+                         const double *sse, int narm, double *res, double *best_ccf,
+                         int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------
  * A4  NN template evaluator; replaces NNInterpolator.forward

@@ -144,6 +144,9 @@ SIGNATURES = {
     'rvs_ccf_xcorr': (I, [P, P, I, I, P, P, I, P, I, P, P, I, P, P, I, D, P, P,
                           P, P]),
     'rvs_ccf_select': (I, [P, P, I, I, I, P, I, P, P, P, P]),
+    'rvs_ccf_xcorr_work_size': (L, [I, I, I, I, I, I]),
+    'rvs_ccf_xcorr_select': (I, [P, P, I, I, P, P, I, P, I, P, P, I, P, P, I, D, P, P,
+                                 P, P, I, P, P, P, P]),
     'rvs_ccf_model_rows': (I, [P, L, P, I, I, I, P, P]),
     'rvs_ccf_models_build': (I, [P, P, P, I, I, I, P, P, P, P, I, P, P, P, P, I, P,
                                  P, P, P, P, P, P, P]),

@@ -1223,15 +1223,7 @@ extern "C" int rvs_ccf_models_build(const double *rows, const uint8_t *f32row,
 // ---------------------------------------------------------------------------
 // argmin over (template, velocity), parabola refinement (fitter_ccf.py:218-236)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ bool nan_less(double a, long long ka, double b,
-                                         long long kb) {
-  // "a before b" for numpy argmin: NaN is the minimum, first occurrence wins
-  const bool an = !(a == a), bn = !(b == b);
-  if (an != bn) return an;
-  if (an) return ka < kb;
-  return (a < b) || (a == b && ka < kb);
-}
-
+// (nan_less, numpy argmin's order with NaN first: common.h)
 __global__ void __launch_bounds__(256)
     ccf_select_kernel(const double *__restrict__ chisq,
                       const double *__restrict__ sse, int narm, int T,

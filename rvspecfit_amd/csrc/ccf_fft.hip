@@ -42,28 +42,30 @@ struct XcLds {
   int t1c;       // ws: T1c [XW_NT1C] double2, the twiddles of pass 1 and of the fold
   int ca;        // ws, RATIO: cA [nlag] doubles
   int lt;        // ws: the lag table [XW_NLT] int32 (ccf_xcorr_ws_kernel)
+  int dc;        // ws: S*[0], S*[n2], V*[0], V*[n2] of the block's spectrum [XW_NDC] double2
   size_t bytes;  // of the launch
 };
 #define XW_NT1C 73   // 64 + 8 twiddles and one spare entry
 #define XW_NLT 256   // 64-block x end (position 0 / 63) x part (re / im) -> lag or -1
+#define XW_NDC 4     // the DC / Nyquist bins of the spectrum's two transforms
 #define XC_LDS_MAX (159 * 1024)   // dynamic LDS a block may ask for
 // ccf_xcorr_kernel; nlag = 0: ccf_rfft_kernel (the image and T1)
 __host__ __device__ constexpr XcLds xc_lds_pair(int n2, int nlag) {
   const int t1 = n2, c0 = t1 + XC_NTW(n2);
-  return {t1, c0, 0, 0, 0,
+  return {t1, c0, 0, 0, 0, 0,
           sizeof(double2) * (size_t)c0 + sizeof(double) * 2 * (size_t)nlag};
 }
 // ccf_xcorr_ws_kernel: two images; c0 and cA are rounded up to whole double2
 __host__ __device__ constexpr XcLds xc_lds_ws(int n2, int nlag, bool ratio) {
   const int t1 = 2 * n2, c0 = t1 + XC_NTW(n2), t1c = c0 + ((nlag + 1) >> 1),
-            ca = t1c + XW_NT1C, lt = ca + (ratio ? (nlag + 1) >> 1 : 0);
-  return {t1, c0, t1c, ca, lt,
-          sizeof(double2) * (size_t)lt + sizeof(int32_t) * (size_t)XW_NLT};
+            ca = t1c + XW_NT1C, lt = ca + (ratio ? (nlag + 1) >> 1 : 0),
+            dc = lt + (int)(sizeof(int32_t) * XW_NLT / sizeof(double2));
+  return {t1, c0, t1c, ca, lt, dc, sizeof(double2) * (size_t)(dc + XW_NDC)};
 }
 // ccf_xcorr_ws2_kernel: four images
 __host__ __device__ constexpr XcLds xc_lds_ws2(int n2, int nlag) {
   const int t1 = 4 * n2, c0 = t1 + XC_NTW(n2);
-  return {t1, c0, 0, 0, 0,
+  return {t1, c0, 0, 0, 0, 0,
           sizeof(double2) * (size_t)c0 + sizeof(double) * 2 * (size_t)nlag};
 }
 // every array of a layout lies behind the one before it and inside `bytes`
@@ -83,6 +85,8 @@ __host__ __device__ constexpr bool xc_lds_fits(const XcLds &L, int n2, int nimg,
     end = D2 * L.ca + (ratio ? D * (size_t)nlag : 0);
     if (D2 * L.lt < end) return false;
     end = D2 * L.lt + sizeof(int32_t) * (size_t)XW_NLT;
+    if (D2 * L.dc < end) return false;
+    end = D2 * (L.dc + XW_NDC);
   }
   return end <= L.bytes && L.bytes <= XC_LDS_MAX;
 }
@@ -847,9 +851,38 @@ __device__ __forceinline__ void xw_pass(double2 *a, const double2 *T1, int p, in
 // that reads it: the lag table or pre_pos gives a lag to the same lane in every
 // iteration) and only then the interpolation runs.  2 T iterations, the same passes,
 // barriers and formulas per bin as ccf_xcorr_kernel's two passes.
-template <int LOG2N, bool RATIO>
+//
+// LOG2N = 12: the block makes S*, V* itself (no ccf_rfft_kernel in front, `work` is not
+// touched).  Prologue, all 1024 threads and before the roles part: the rows proc_spec *
+// proc_ivar and proc_ivar are packed into the two images (even / odd samples as re / im),
+// waves 0-7 run the four forward radix-8 passes on image 0 while waves 8-15 run them on
+// image 1 (a block barrier behind each pass), then every producer lane unfolds its four
+// bin pairs of both transforms from LDS into the registers that hold them for the walk
+// (ccf_rfft_kernel's formulas and twiddle table) and one lane parks the DC / Nyquist
+// bins S*[0], S*[n2], V*[0], V*[n2] in LDS (dc[]: form() reads them per template from
+// there -- held in vector registers they spill, section 4.1).  One more barrier, which
+// both roles execute, and the first form() may overwrite image 0.
+//
+// SELECT (LOG2N = 12, rvs_ccf_xcorr_select: the last arm of a chunk): the block also does
+// what ccf_select_kernel does for its spectrum.  Consumer lane pt < nvel keeps the nan_less
+// minimum of out[pt] + tot, key t nvel + pt, over the templates it stores; behind the walk
+// the eight consumer waves reduce it (wave shuffles, then eight pairs through LDS -- the
+// images are free by then), the lanes read back row best_id of `out`, which this block
+// wrote (block-scope fence + barrier), write best_ccf, reduce the row's first minimum
+// the same way and one lane forms the parabola and the status bit with ccf_select_kernel's
+// expressions.  Two barriers, which the producers execute as well before they end.
+struct XwSelect {
+  const double *sse;   // [narm, B]
+  int narm;
+  double *res;         // [B, 4]
+  double *best_ccf;    // [B, nvel]
+  int32_t *status;     // [B], OR-ed into (nullable)
+};
+template <int LOG2N, bool RATIO, bool SELECT = false>
 __global__ void __launch_bounds__(XW_NT)
     ccf_xcorr_ws_kernel(const double2 *__restrict__ work,
+                        const double *__restrict__ proc_spec,
+                        const double *__restrict__ proc_ivar,
                         const double2 *__restrict__ tfft,
                         const double2 *__restrict__ tfft2, int T,
                         const double2 *__restrict__ tw,
@@ -858,12 +891,14 @@ __global__ void __launch_bounds__(XW_NT)
                         const int32_t *__restrict__ ilo,
                         const double *__restrict__ vgrid, int nvel, double beta,
                         const uint8_t *__restrict__ prune,
-                        double *__restrict__ chisq) {
+                        double *__restrict__ chisq, const XwSelect sel) {
   extern __shared__ double2 fa[];
   constexpr int log2n = LOG2N, n2 = 1 << LOG2N, nfft = 2 * n2, npair = n2 / 2;
   constexpr int NPP = npair / XW_HALF;   // bin pairs of a producer lane: 4 or 2
   constexpr bool P12 = (LOG2N == 12);
+  constexpr int NBAR_SEL = 2;   // barriers of the SELECT epilogue, both roles
   static_assert(LOG2N == 12 || LOG2N == 11, "plans 8,8,8,8 and 8,8,8,4 only");
+  static_assert(!SELECT || P12, "the select epilogue belongs to the nfft 8192 form");
   auto img = [&](int i) -> double2 * { return fa + (i & 1) * n2; };
   const XcLds lds = xc_lds_ws(n2, nlag, RATIO);
   const double2 *T1 = fa + lds.t1;                         // [n2 / 8]
@@ -872,6 +907,7 @@ __global__ void __launch_bounds__(XW_NT)
   double2 *T1c = fa + lds.t1c;                             // [64 + 8]
   double *cA = reinterpret_cast<double *>(fa + lds.ca);    // RATIO: c0 at the lags [nlag]
   int32_t *lt = reinterpret_cast<int32_t *>(fa + lds.lt);  // the lag table [XW_NLT]
+  double2 *dcs = fa + lds.dc;   // LOG2N = 12: S*[0], S*[n2], V*[0], V*[n2]
   const int TI = RATIO ? 2 * T : T;   // image iterations
   const int b = blockIdx.x, tid = threadIdx.x;
   const bool producer = tid >= XW_HALF;
@@ -880,6 +916,21 @@ __global__ void __launch_bounds__(XW_NT)
   if (P12 && tid < 72)   // (straight from the table: the LDS copy of T1 is in flight)
     T1c[tid] = tid < 64 ? tw[2 * (tid << 3)] : tw[2 * ((tid - 64) << (log2n - 6))];
   xc_fill_twiddles<XW_NT>(fa + n2, n2, tw);   // -> fa[2 n2 + i]
+  if constexpr (P12) {
+    // the two real rows, packed as in ccf_rfft_kernel.  These loads are requested behind
+    // the LDS-DMA of T1 and a wave's loads complete in order: a wave that has stored its
+    // share of the images has its share of T1 in LDS, in front of the barriers below
+    const double *ps = proc_spec + (int64_t)b * nfft;
+    const double *pi = proc_ivar + (int64_t)b * nfft;
+#pragma unroll
+    for (int j = 0; j < n2 / XW_NT; j++) {
+      const int n = tid + j * XW_NT;
+      const double s0 = ps[2 * n], s1 = ps[2 * n + 1];
+      const double i0 = pi[2 * n], i1 = pi[2 * n + 1];
+      fa[n] = make_double2(s0 * i0, s1 * i1);
+      fa[n2 + n] = make_double2(i0, i1);
+    }
+  }
   // output masks of the last two passes (consumers), and the block-wide vote on the
   // folded form of those passes (see fft_lds)
   XcMasks pmask = {0u, 0u, 0u};
@@ -902,8 +953,24 @@ __global__ void __launch_bounds__(XW_NT)
     }
     __syncthreads();
   }
-  const double2 *Sc = work + ((int64_t)b * 2) * (n2 + 1);
-  const double2 *Vc = Sc + (n2 + 1);
+  if constexpr (P12) {
+    // forward transform of the packed rows: one butterfly per lane and pass, image 0 on
+    // waves 0-7, image 1 on waves 8-15, four barriers for every wave of the block
+    double2 *ap = fa + (producer ? n2 : 0);
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+      xw_pass<-1, LOG2N>(ap, T1, p, pt);
+      __syncthreads();
+    }
+  }
+  // LOG2N = 11: conj(rfft) of the two rows from ccf_rfft_kernel
+  const double2 *Sc = P12 ? nullptr : work + ((int64_t)b * 2) * (n2 + 1);
+  const double2 *Vc = P12 ? nullptr : Sc + (n2 + 1);
+  // S*[0], S*[n2], V*[0], V*[n2] (i = 0 ... 3), wave-uniform
+  auto spec_dc = [&](int i) -> double2 {
+    if constexpr (P12) return dcs[i];
+    return ((i & 2) ? Vc : Sc)[(i & 1) ? n2 : 0];
+  };
   typedef int v4i_t __attribute__((ext_vector_type(4)));
   auto ld = [](const __amdgpu_buffer_rsrc_t &r, int off) {
     const v4i_t v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
@@ -913,10 +980,37 @@ __global__ void __launch_bounds__(XW_NT)
   if (producer) {
     // ---- producers -------------------------------------------------------
     double2 Sk[NPP], Vk[NPP], Sm[NPP], Vm[NPP];
+    if constexpr (P12) {
+      // conj(X[k]) of the real row whose packed transform is Z (digit-reversed in LDS):
+      // zk = Z[k], zm = Z[n2 - k], w = exp(-2 pi i k / nfft) (ccf_rfft_kernel)
+      auto unfold = [](double2 zk, double2 zm, double2 w) {
+        const double2 e = make_double2(zk.x + zm.x, zk.y - zm.y);   // zk + conj(zm)
+        const double2 d = make_double2(zk.x - zm.x, zk.y + zm.y);   // zk - conj(zm)
+        const double2 q = cmul(w, d);
+        return make_double2(0.5 * (e.x + q.y), -(0.5 * (e.y - q.x)));
+      };
+      const double2 *Z0 = fa, *Z1 = fa + n2;
 #pragma unroll
-    for (int u = 0; u < NPP; u++) {
-      const int k = 1 + pt + u * XW_HALF, m = n2 - k;
-      Sk[u] = Sc[k], Vk[u] = Vc[k], Sm[u] = Sc[m], Vm[u] = Vc[m];
+      for (int u = 0; u < NPP; u++) {
+        const int k = 1 + pt + u * XW_HALF, m = n2 - k;
+        const int pk = fft_pos(k, log2n), pm = fft_pos(m, log2n);
+        const double2 wk = twid<-1>(tw, k, nfft), wm = twid<-1>(tw, m, nfft);
+        const double2 s_k = Z0[pk], s_m = Z0[pm], v_k = Z1[pk], v_m = Z1[pm];
+        Sk[u] = unfold(s_k, s_m, wk), Sm[u] = unfold(s_m, s_k, wm);
+        Vk[u] = unfold(v_k, v_m, wk), Vm[u] = unfold(v_m, v_k, wm);
+      }
+      if (pt == 0) {
+        const double2 s = Z0[0], v = Z1[0];
+        dcs[0] = make_double2(s.x + s.y, -0.0), dcs[1] = make_double2(s.x - s.y, -0.0);
+        dcs[2] = make_double2(v.x + v.y, -0.0), dcs[3] = make_double2(v.x - v.y, -0.0);
+      }
+      __syncthreads();   // (the consumers' twin: in front of their walk)
+    } else {
+#pragma unroll
+      for (int u = 0; u < NPP; u++) {
+        const int k = 1 + pt + u * XW_HALF, m = n2 - k;
+        Sk[u] = Sc[k], Vk[u] = Vc[k], Sm[u] = Sc[m], Vm[u] = Vc[m];
+      }
     }
     const __amdgpu_buffer_rsrc_t rT = __builtin_amdgcn_make_buffer_rsrc(
         (void *)tw, 0, (npair + 1) * 16, 0x00020000);
@@ -965,16 +1059,17 @@ __global__ void __launch_bounds__(XW_NT)
       dst[k] = make_double2(e.x - q.y, e.y + q.x);
       if (m != k) dst[m] = make_double2(e.x + q.y, -e.y + q.x);
       if (u == NPP - 1 && ptv == 0) {
-        // the DC / Nyquist pair: wave-uniform addresses (scalar loads, requested in the
-        // template's first interval), formed with its last batch by one lane
+        // the DC / Nyquist pair: wave-uniform addresses (the template's by scalar loads,
+        // requested in its first interval; the spectrum's from dc[] in LDS or, LOG2N =
+        // 11, from `work`), formed with the template's last batch by one lane
         double xk, xm;
         if (RATIO) {
           const bool second = (tcur & 1) != 0;
-          xk = cmul(second ? dc[1] : dc[0], second ? Vc[0] : Sc[0]).x;
-          xm = cmul(second ? dc[3] : dc[2], second ? Vc[n2] : Sc[n2]).x;
+          xk = cmul(second ? dc[1] : dc[0], spec_dc(second ? 2 : 0)).x;
+          xm = cmul(second ? dc[3] : dc[2], spec_dc(second ? 3 : 1)).x;
         } else {
-          const double2 a1 = cmul(dc[0], Sc[0]), a2 = cmul(dc[1], Vc[0]);
-          const double2 b1 = cmul(dc[2], Sc[n2]), b2 = cmul(dc[3], Vc[n2]);
+          const double2 a1 = cmul(dc[0], spec_dc(0)), a2 = cmul(dc[1], spec_dc(2));
+          const double2 b1 = cmul(dc[2], spec_dc(1)), b2 = cmul(dc[3], spec_dc(3));
           xk = a2.x - 2 * a1.x, xm = b2.x - 2 * b1.x;
         }
         // numpy irfft ignores the imaginary parts of the DC and Nyquist bins
@@ -1024,6 +1119,8 @@ __global__ void __launch_bounds__(XW_NT)
         for (int q = 0; q < nbar; q++) __syncthreads();
       }
     }
+    if constexpr (SELECT)
+      for (int q = 0; q < NBAR_SEL; q++) __syncthreads();
     return;
   }
   // ---- consumers ---------------------------------------------------------
@@ -1036,6 +1133,14 @@ __global__ void __launch_bounds__(XW_NT)
   typedef int v4i32_t __attribute__((ext_vector_type(4)));
   v4i32_t lag = {-1, -1, -1, -1};
   if (P12) lag = reinterpret_cast<const v4i32_t *>(lt)[pt >> 3];
+  // SELECT: total_sse (ccf_select_kernel's order of the arms) and the lane's running
+  // minimum over the templates
+  double tot = 0, bv = __builtin_inf();
+  long long bk = (1ll << 62);
+  if constexpr (SELECT)
+    for (int a = 0; a < sel.narm; a++) tot += sel.sse[(int64_t)a * gridDim.x + b];
+  // (the producers unfold S*, V* from the two images: their barrier behind it)
+  if constexpr (P12) __syncthreads();
   for (int it = -1; it < TI; it++) {
     if (it < 0) {
       const int nbar = (P12 && fold) ? 2 : 5;
@@ -1165,7 +1270,60 @@ __global__ void __launch_bounds__(XW_NT)
     if ((!RATIO || (it & 1)) && pt < nvel) {
       const double sl = (c0[pre_lo + 1] - c0[pre_lo]) / (pre_x1 - pre_x0);
       const double val = sl * (pre_xg - pre_x0) + c0[pre_lo];
-      out[pt] = (beta != 0.0) ? beta * pre_old + val : val;
+      const double o = (beta != 0.0) ? beta * pre_old + val : val;
+      out[pt] = o;
+      if constexpr (SELECT) {
+        const double x = o + tot;
+        const long long key = (long long)(RATIO ? (it >> 1) : it) * nvel + pt;
+        if (nan_less(x, key, bv, bk)) bv = x, bk = key;
+      }
+    }
+  }
+  if constexpr (SELECT) {
+    // behind the last barrier of the walk nobody reads or writes the images: fa[0 .. 15]
+    // take the waves' minima (value, key), the doubles behind them the winning row
+    auto block_min = [&](double2 *part, double &v, long long &k) {
+      wave_nan_min(v, k);
+      if ((pt & 63) == 0) part[pt >> 6] = make_double2(v, __longlong_as_double(k));
+      __threadfence_block();   // (first use: the block's stores to `out` as well)
+      __syncthreads();
+      v = part[0].x, k = __double_as_longlong(part[0].y);
+      for (int w = 1; w < XW_HALF / 64; w++) {
+        const double ov = part[w].x;
+        const long long ok = __double_as_longlong(part[w].y);
+        if (nan_less(ov, ok, v, k)) v = ov, k = ok;
+      }
+    };
+    block_min(fa, bv, bk);
+    const int best_id = (int)(bk / nvel);
+    const double *row = chisq + ((int64_t)b * T + best_id) * nvel;
+    double *xs = reinterpret_cast<double *>(fa + 16);   // [nvel] best_ccf of the spectrum
+    double mv = __builtin_inf();
+    long long bp = (1ll << 62);
+    if (pt < nvel) {
+      mv = row[pt] + tot, bp = pt;
+      sel.best_ccf[(int64_t)b * nvel + pt] = mv;
+      xs[pt] = mv;
+    }
+    // first minimum inside the winning row (np.argmin(best_ccf))
+    block_min(fa + 8, mv, bp);
+    if (pt == 0) {
+      double vel = vgrid[bp];
+      if (bp != 0 && bp != nvel - 1) {
+        const double xa = vgrid[bp - 1], xb = vgrid[bp], xc = vgrid[bp + 1];
+        const double ya = xs[bp - 1], yb = xs[bp], yc = xs[bp + 1];
+        const double d1 = (yb - ya) / (xb - xa), d2 = (yc - yb) / (xc - xb);
+        const double a2 = (d2 - d1) / (xc - xa);
+        if (a2 > 0) vel = xb - (d1 + a2 * (xb - xa)) / (2 * a2);
+      }
+      int st = 0;
+      if (!(fabs(mv) <= 1.79e308)) st |= RVS_ST_CCF_FAILED;
+      double *r = sel.res + (int64_t)b * 4;
+      r[0] = best_id;
+      r[1] = vel;
+      r[2] = bp;
+      r[3] = mv;
+      if (st && sel.status) atomicOr(&sel.status[b], st);
     }
   }
 }
@@ -1331,14 +1489,28 @@ __global__ void __launch_bounds__(XW_NT)
   }
 }
 
-extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
-                             int nfft, int B, const double *tfft,
-                             const double *tfft2, int T, const double *twid_,
-                             int continuum, const int32_t *lag_pos,
-                             const double *lag_vel, int nlag, const int32_t *ilo,
-                             const double *vgrid, int nvel, double beta,
-                             const uint8_t *prune, double *chisq, double *work,
-                             void *stream) {
+// does a call take the persistent kernel of nfft 8192 (no ccf_rfft_kernel, no `work`)?
+static bool xc_takes_ws12(int nfft, int T, int nlag, int nvel, bool has_prune) {
+  return rvs_opt(RVS_OPT_XC_WS) != 0 && nfft == 8192 && has_prune && nlag <= XW_HALF &&
+         nvel <= XW_HALF && T >= 2;
+}
+extern "C" int64_t rvs_ccf_xcorr_work_size(int nfft, int B, int T, int nlag, int nvel,
+                                           int has_prune) {
+  if (nfft < 64 || B < 1) return RVS_E_ARG;
+  return xc_takes_ws12(nfft, T, nlag, nvel, has_prune != 0)
+             ? 0
+             : (int64_t)B * 2 * ((nfft >> 1) + 1) * 2;
+}
+
+// rvs_ccf_xcorr (psel == nullptr) and rvs_ccf_xcorr_select (the descriptor of the select
+// epilogue: RVS_E_ARG, before any launch, unless the call takes the persistent kernel of
+// nfft 8192)
+static int xc_launch(const double *proc_spec, const double *proc_ivar, int nfft, int B,
+                     const double *tfft, const double *tfft2, int T, const double *twid_,
+                     int continuum, const int32_t *lag_pos, const double *lag_vel,
+                     int nlag, const int32_t *ilo, const double *vgrid, int nvel,
+                     double beta, const uint8_t *prune, double *chisq, double *work,
+                     void *stream, const XwSelect *psel) {
   int log2n = 0;
   while ((2 << log2n) < nfft) log2n++;
   if ((2 << log2n) != nfft || nfft < 64 || nfft > 16384) return RVS_E_ARG;
@@ -1360,22 +1532,35 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
     (void)hipGetLastError();
     attr_set = true;
   }
-  hipLaunchKernelGGL(ccf_rfft_kernel<false>, dim3(B, 2), dim3(XC_NT), shm1, st,
-                     proc_spec, proc_ivar, nfft, log2n, tw,
-                     reinterpret_cast<double2 *>(work), (double2 *)nullptr);
-  RVS_LAUNCH_CHECK();
+  // the wave-specialised persistent form (one block per spectrum), where it applies
+  const bool ws_on = rvs_opt(RVS_OPT_XC_WS) != 0;   // xc_ws = 0: the per-pair kernel
+  const bool p12 = (nfft == 8192 && prune), p11 = (nfft == 4096);
+  const bool ws = ws_on && (p12 || p11) && nlag <= XW_HALF && nvel <= XW_HALF && T >= 2;
+  if (psel && !xc_takes_ws12(nfft, T, nlag, nvel, prune != nullptr)) return RVS_E_ARG;
+  const XwSelect sel = psel ? *psel : XwSelect{nullptr, 0, nullptr, nullptr, nullptr};
+  // conj(rfft) of the two rows of every spectrum into `work`, for every kernel but the
+  // wave-specialised one of nfft 8192, whose block transforms its own spectrum
+  if (!(ws && p12)) {
+    hipLaunchKernelGGL(ccf_rfft_kernel<false>, dim3(B, 2), dim3(XC_NT), shm1, st,
+                       proc_spec, proc_ivar, nfft, log2n, tw,
+                       reinterpret_cast<double2 *>(work), (double2 *)nullptr);
+    RVS_LAUNCH_CHECK();
+  }
   const int G = xc_group(T, nfft);
   {
-    // the wave-specialised persistent form (one block per spectrum), where it applies
-    const bool ws_on = rvs_opt(RVS_OPT_XC_WS) != 0;   // xc_ws = 0: the per-pair kernel
-    const bool p12 = (nfft == 8192 && prune), p11 = (nfft == 4096);
-    if (ws_on && (p12 || p11) && nlag <= XW_HALF && nvel <= XW_HALF && T >= 2) {
+    if (ws) {
       static bool ws_attr = false;
       if (!ws_attr) {
         (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<12, false>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
                                   XC_LDS_MAX);
         (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<12, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  XC_LDS_MAX);
+        (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<12, false, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  XC_LDS_MAX);
+        (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<12, true, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
                                   XC_LDS_MAX);
         (void)hipFuncSetAttribute((const void *)ccf_xcorr_ws_kernel<11, true>,
@@ -1389,9 +1574,19 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
       }
       const size_t shmw = xc_lds_ws(n2, nlag, !continuum).bytes;
 #define RVS_XW_ARGS                                                                 \
-  reinterpret_cast<const double2 *>(work), reinterpret_cast<const double2 *>(tfft),  \
-      reinterpret_cast<const double2 *>(tfft2), T, tw, lag_pos, lag_vel, nlag, ilo,  \
-      vgrid, nvel, beta, prune, chisq
+  reinterpret_cast<const double2 *>(work), proc_spec, proc_ivar,                     \
+      reinterpret_cast<const double2 *>(tfft), reinterpret_cast<const double2 *>(tfft2), \
+      T, tw, lag_pos, lag_vel, nlag, ilo, vgrid, nvel, beta, prune, chisq, sel
+      if (psel) {   // (p12) the walk and the selection of the spectrum's best template
+        if (!continuum)
+          hipLaunchKernelGGL((ccf_xcorr_ws_kernel<12, true, true>), dim3(B), dim3(XW_NT),
+                             shmw, st, RVS_XW_ARGS);
+        else
+          hipLaunchKernelGGL((ccf_xcorr_ws_kernel<12, false, true>), dim3(B), dim3(XW_NT),
+                             shmw, st, RVS_XW_ARGS);
+        RVS_LAUNCH_CHECK();
+        return 0;
+      }
       if (!continuum) {
         // -c0^2 / c1: one correlation per iteration (the two-templates-per-iteration
         // form of nfft 4096 pairs TEMPLATES, so 4096 takes the one-image form here)
@@ -1406,10 +1601,7 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
       }
       if (p12)
         hipLaunchKernelGGL((ccf_xcorr_ws_kernel<12, false>), dim3(B), dim3(XW_NT), shmw, st,
-                           reinterpret_cast<const double2 *>(work),
-                           reinterpret_cast<const double2 *>(tfft),
-                           reinterpret_cast<const double2 *>(tfft2), T, tw, lag_pos,
-                           lag_vel, nlag, ilo, vgrid, nvel, beta, prune, chisq);
+                           RVS_XW_ARGS);
       else
         hipLaunchKernelGGL(ccf_xcorr_ws2_kernel, dim3(B), dim3(XW_NT),
                            xc_lds_ws2(n2, nlag).bytes, st,
@@ -1435,4 +1627,33 @@ extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
     RVS_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int rvs_ccf_xcorr(const double *proc_spec, const double *proc_ivar,
+                             int nfft, int B, const double *tfft,
+                             const double *tfft2, int T, const double *twid_,
+                             int continuum, const int32_t *lag_pos,
+                             const double *lag_vel, int nlag, const int32_t *ilo,
+                             const double *vgrid, int nvel, double beta,
+                             const uint8_t *prune, double *chisq, double *work,
+                             void *stream) {
+  return xc_launch(proc_spec, proc_ivar, nfft, B, tfft, tfft2, T, twid_, continuum,
+                   lag_pos, lag_vel, nlag, ilo, vgrid, nvel, beta, prune, chisq, work,
+                   stream, nullptr);
+}
+
+extern "C" int rvs_ccf_xcorr_select(const double *proc_spec, const double *proc_ivar,
+                                    int nfft, int B, const double *tfft,
+                                    const double *tfft2, int T, const double *twid_,
+                                    int continuum, const int32_t *lag_pos,
+                                    const double *lag_vel, int nlag, const int32_t *ilo,
+                                    const double *vgrid, int nvel, double beta,
+                                    const uint8_t *prune, double *chisq, double *work,
+                                    const double *sse, int narm, double *res,
+                                    double *best_ccf, int32_t *status, void *stream) {
+  if (!sse || narm < 0 || !res || !best_ccf) return RVS_E_ARG;
+  const XwSelect sel = {sse, narm, res, best_ccf, status};
+  return xc_launch(proc_spec, proc_ivar, nfft, B, tfft, tfft2, T, twid_, continuum,
+                   lag_pos, lag_vel, nlag, ilo, vgrid, nvel, beta, prune, chisq, work,
+                   stream, &sel);
 }

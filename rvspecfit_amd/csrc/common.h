@@ -46,6 +46,29 @@ __device__ __forceinline__ double wave_sum_to63(double v) {
   return t;                                    // lane 63: total of the wave
 }
 
+// "a before b" for numpy argmin over keyed values: NaN is the minimum, first occurrence
+// (smaller key) wins.  A total order on (value, key) pairs with distinct keys, so the
+// minimum does not depend on the order in which the pairs are compared.
+__device__ __forceinline__ bool nan_less(double a, long long ka, double b,
+                                         long long kb) {
+  const bool an = !(a == a), bn = !(b == b);
+  if (an != bn) return an;
+  if (an) return ka < kb;
+  return (a < b) || (a == b && ka < kb);
+}
+// the nan_less minimum of the wave's 64 pairs, in every lane
+__device__ __forceinline__ void wave_nan_min(double &v, long long &k) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(v, o, 64);
+    const long long ok = __shfl_xor(k, o, 64);
+    if (nan_less(ov, ok, v, k)) {
+      v = ov;
+      k = ok;
+    }
+  }
+}
+
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -1692,29 +1692,43 @@ def ccf_fit(batch, libs, config, keep_all=False, max_chunk=None):
     for a, b in _chunks(S, max_chunk):
         n = b - a
         acc = torch.empty((n, Tn, nvel), dtype=torch.float64, device=dev)
+        sse_c = sse[:, a:b].contiguous()
+        selected = False
         for ia, arm in enumerate(batch.arms):
             cc = libs[arm.name].ccf_set(config)
             T = tabs[ia]
             nfft = cc['npoints']
-            work = torch.empty((n, 2, nfft // 2 + 1, 2), dtype=torch.float64,
-                               device=dev)
+            # (nothing where the persistent block transforms its own spectrum)
+            nwork = L.rvs_ccf_xcorr_work_size(nfft, n, Tn, T['nlag'], nvel,
+                                              int(T['prune'] is not None))
+            work = (torch.empty(nwork, dtype=torch.float64, device=dev)
+                    if nwork > 0 else None)
+            args = (_lib.ptr(pre[ia]['proc_spec'][a:b]),
+                    _lib.ptr(pre[ia]['proc_ivar'][a:b]), nfft, n,
+                    _lib.ptr(cc['fft']), _lib.ptr(cc['fft2']), Tn,
+                    _lib.ptr(T['twid']), int(cc['continuum']),
+                    _lib.ptr(T['lag_pos']), _lib.ptr(T['lag_vel']), T['nlag'],
+                    _lib.ptr(T['ilo']), _lib.ptr(T['vgrid']), nvel,
+                    0.0 if ia == 0 else 1.0, _lib.ptr(T['prune']), _lib.ptr(acc),
+                    _lib.ptr(work))
             with _ktime('ccf_xcorr', n):
-              rc = L.rvs_ccf_xcorr(
-                _lib.ptr(pre[ia]['proc_spec'][a:b]),
-                _lib.ptr(pre[ia]['proc_ivar'][a:b]), nfft, n,
-                _lib.ptr(cc['fft']), _lib.ptr(cc['fft2']), Tn,
-                _lib.ptr(T['twid']), int(cc['continuum']),
-                _lib.ptr(T['lag_pos']), _lib.ptr(T['lag_vel']), T['nlag'],
-                _lib.ptr(T['ilo']), _lib.ptr(T['vgrid']), nvel,
-                0.0 if ia == 0 else 1.0, _lib.ptr(T['prune']), _lib.ptr(acc),
-                _lib.ptr(work), _lib.stream())
+              rc = -1
+              if ia == len(batch.arms) - 1:
+                  # the last arm's persistent block also selects (RVS_E_ARG, before any
+                  # launch, where that kernel does not apply: the two calls then)
+                  rc = L.rvs_ccf_xcorr_select(
+                      *args, _lib.ptr(sse_c), len(batch.arms), _lib.ptr(res[a:b]),
+                      _lib.ptr(best_ccf[a:b]), _lib.ptr(status[a:b]), _lib.stream())
+                  selected = rc == 0
+              if rc != 0:
+                  rc = L.rvs_ccf_xcorr(*args, _lib.stream())
             _lib.check(rc, 'rvs_ccf_xcorr')
-        sse_c = sse[:, a:b].contiguous()
-        rc = L.rvs_ccf_select(_lib.ptr(acc), _lib.ptr(sse_c), len(batch.arms),
-                              n, Tn, _lib.ptr(tabs[0]['vgrid']), nvel,
-                              _lib.ptr(res[a:b]), _lib.ptr(best_ccf[a:b]),
-                              _lib.ptr(status[a:b]), _lib.stream())
-        _lib.check(rc, 'rvs_ccf_select')
+        if not selected:
+            rc = L.rvs_ccf_select(_lib.ptr(acc), _lib.ptr(sse_c), len(batch.arms),
+                                  n, Tn, _lib.ptr(tabs[0]['vgrid']), nvel,
+                                  _lib.ptr(res[a:b]), _lib.ptr(best_ccf[a:b]),
+                                  _lib.ptr(status[a:b]), _lib.stream())
+            _lib.check(rc, 'rvs_ccf_select')
         if keep_all:
             allchi = acc + sse_c.sum(dim=0)[:, None, None]
     out = dict(best_id=res[:, 0].long(), best_vel=res[:, 1].contiguous(),

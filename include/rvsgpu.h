@@ -390,6 +390,16 @@ int rvs_spline_eval(const double *knots, const double *coef, int ntp,
  *          device), forked from and joined to `stream` inside the call: to the
  *          caller the call is ordered on `stream` like any other.
  * out     [J, Nv];   status int32 [J] OR-ed (caller zeroes it)
+ * Device memory of the library's own: where rvs_chisq_grid_pair_cols(npoly) > 0,
+ * on one wavelength grid
+ * (this call, rvs_chisq_grid_g with G = 1, rvs_chisq_grid_tab) the kernels read
+ * 128-byte rows {basis values, pair products of the last columns} that a small
+ * kernel at the head of the call builds from polysT into a buffer kept per
+ * (device, stream): npix rounded up to 1024, times 128 bytes; allocated on a
+ * stream's first call and when an arm is longer than any before it on that
+ * stream; the buffers of the 64 streams used last are kept (RVS_E_LAUNCH when
+ * an allocation fails).  A call queues its row kernel and its grid kernels under
+ * a lock of the library's, so host threads may share a stream as before.
  * ---------------------------------------------------------------------- */
 int64_t rvs_chisq_work_size(int npix, int S);
 int rvs_chisq_prepare(const double *lam, const double *spec,
@@ -466,6 +476,10 @@ int rvs_chisq_grid_g(const double *lam, const double *polysT, const double *work
  * option already decide against the table: the caller then needs no buffer. */
 int64_t rvs_chisq_grid_tab_work_size(int npix, int Tn, int Nv, int64_t J_call,
                                      int min_jobs_per_node, int pack_min_jobs);
+/* How many of the last columns of the packed normal matrix the velocity-grid
+ * kernels of `npoly` functions accumulate from pair products P_i P_j of the row
+ * (one wavelength grid; 0 = none: the arithmetic of a grid set; tests). */
+int rvs_chisq_grid_pair_cols(int npoly);
 int rvs_chisq_grid_tab(const double *lam, const double *polysT, const double *work,
                        int npix, int npoly, int S, const int32_t *grid_id, int G,
                        int64_t polys_stride, const double *knots,

@@ -45,6 +45,7 @@ SIGNATURES = {
     'rvs_chisq_grid_g': (I, [P, P, P, I, I, I, P, I, L, P, P, I, I, I, P, P, I, P, L,
                              I, P, D, D, I, P, P, P, P]),
     'rvs_chisq_grid_tab_work_size': (L, [I, I, I, L, I, I]),
+    'rvs_chisq_grid_pair_cols': (I, [I]),
     'rvs_chisq_grid_tab': (I, [P, P, P, I, I, I, P, I, L, P, P, I, I, I, P, P, I, P, L,
                                I, P, D, D, I, P, P, P, P, P, P, L, I, P, L, I, P, P]),
     'rvs_chisq_prepare': (I, [P, P, P, I, I, P, I, D, P, P]),

@@ -20,7 +20,9 @@
 // v_i = sum_k (P_i t/e)(s/e); -2logL = logdet + 2 sum log e + (D.D - y.y),
 // y = L^-1 v, which equals |D - a^T ST|^2 of spec_fit.py:249/298.
 #include "common.h"
+#include <mutex>
 #include <type_traits>
+#include <vector>
 
 // ---------------------------------------------------------------------------
 // work buffer layout (doubles): [0, G*npix) pixel knot coordinate
@@ -125,8 +127,10 @@ struct GridSet {
 // right behind such a load -- copied the not-yet-loaded register and reused it
 // as an address, which the load then overwrote: a fault.  Nothing here depends
 // on instructions the compiler does not know about.
-// A basis row of P doubles is held in SGPR tuples that cover it exactly
-// (16/8/4/2-dword loads: nothing is read past a row).
+// A row of N doubles -- the P basis values, or with pair columns (cg_pair_cols)
+// the P + K (K + 1) / 2 doubles that are read of a 16-double row -- is held in
+// SGPR tuples that cover it exactly (16/8/4/2-dword loads: nothing is read past
+// what the loop uses).
 // ---------------------------------------------------------------------------
 typedef double cg_d8 __attribute__((ext_vector_type(8)));
 typedef double cg_d4 __attribute__((ext_vector_type(4)));
@@ -139,7 +143,8 @@ struct CgRow {
   cg_d2 c;
   double d;
   static constexpr int N8 = P / 8, R = P % 8;
-  // request the row at p (rows are 8-byte aligned only)
+  // request the row at p (plain rows of P doubles are 8-byte aligned only;
+  // pair-column rows are 128-byte aligned, which these loads do not rely on)
   __device__ __forceinline__ void load(const double *p) {
     typedef double d8u __attribute__((ext_vector_type(8), aligned(8)));
     typedef double d4u __attribute__((ext_vector_type(4), aligned(8)));
@@ -335,6 +340,98 @@ __host__ __device__ constexpr int cg_split(int P) {
   return pa;
 }
 
+// ---------------------------------------------------------------------------
+// Pair columns.  A term of the normal matrix has three factors, P_i P_j w, and
+// an FMA takes two: each column j of the packed triangle pays one multiplication
+// pwj = P_j w per pixel.  Column j loses it when the P - j products P_i P_j
+// (i >= j) arrive as wave-uniform operands beside the row: acc_ij += (P_i P_j) w.
+// The LAST columns are the cheap ones -- column P-1 needs one product, P-2 two --
+// and a row of P <= 13 doubles leaves room for K of them in one 128-byte line:
+// cg_pair_cols(P) = the largest K with P + K (K + 1) / 2 <= 16 (P = 10: K = 3,
+// 10 + 6 = 16 doubles; a column count, so min(K, P) of them exist).  The row of
+// pixel k is then 16 doubles, 128-byte aligned:
+//   [0, P)                    P_0 .. P_{P-1}
+//   [P, P + KE (KE + 1) / 2)  round(P_i P_j), P - KE <= j <= i < P, at
+//                             P + TRI(i - (P - KE), j - (P - KE))
+//   zeros behind.
+// chisq_pair_rows_kernel builds the rows from the caller's polysT at the head of
+// a grid call, into a buffer the library owns (pair_rows_buffer).  One-pass
+// kernels on one wavelength grid only: a two-pass kernel (P >= 14) would fetch
+// the products twice, and a 128-byte row per pixel of every grid of a grid set
+// (10 000 SDSS plates) is gigabytes -- both keep today's rows of P doubles.
+// A term changes from fma(P_i, round(P_j w), acc) to fma(round(P_i P_j), w, acc):
+// one rounding in front of the FMA either way.  All three placements of a
+// velocity (full wave, packed wave, node table) take their sums from cg_sums, so
+// where a velocity is computed still does not change its bits.
+// ---------------------------------------------------------------------------
+#define CG_PAIR_STRIDE 16
+__host__ __device__ constexpr int cg_pair_cols(int P) {
+  if (P < 1 || cg_split(P) != P) return 0;
+  int K = 0;
+  while (P + (K + 1) * (K + 2) / 2 <= CG_PAIR_STRIDE) K++;
+  return K;
+}
+// Where the rule is in effect.  The wider row pays where the pixel loop is bound
+// by its vector instructions and costs where the loop is short: on the node
+// table (13 to 36 vector instructions per pixel at npoly 1 to 6) the contract
+// step's chi^2 stage went from 21.1 to 23.5 ms at npoly 1, 25.9 to 35.1 at 4, 32.1
+// to 37.9 at 5, 38.4 to 42.7 at 6 with rows of up to 16 doubles instead of npoly
+// (the scalar cache's bytes per vector instruction triple); at 7 it is even, from
+// 8 to 13 it gains 0.7 to 2.1 ms with the table and 1.5 to 2.0 without (DESIGN
+// 4.2, profiles/pair_columns_npoly.json).  One bit per npoly:
+#define CG_PAIR_ON 0x3f00u   // npoly 8 .. 13
+// the columns that take their products from the row: min(K, P), or none
+__host__ __device__ constexpr int cg_pair_eff(int P) {
+  if (P < 1 || P > 31 || !((CG_PAIR_ON >> P) & 1u)) return 0;
+  return cg_pair_cols(P) < P ? cg_pair_cols(P) : P;
+}
+extern "C" int rvs_chisq_grid_pair_cols(int npoly) {
+  return npoly >= 1 && npoly <= 16 ? cg_pair_eff(npoly) : 0;
+}
+// doubles of a row that the loop reads: P, and the products of KE columns
+__host__ __device__ constexpr int cg_row_len(int P, int KE) {
+  return P + KE * (KE + 1) / 2;
+}
+__global__ void __launch_bounds__(64)
+    chisq_pair_rows_kernel(const double *__restrict__ polysT, int npix, int P,
+                           int KE, double *__restrict__ rows) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= npix) return;
+  const double *p = polysT + (int64_t)k * P;
+  double *o = rows + (int64_t)k * CG_PAIR_STRIDE;
+  int n = 0;
+  for (; n < P; n++) o[n] = p[n];
+  for (int i = P - KE; i < P; i++)
+    for (int j = P - KE; j <= i; j++) o[n++] = p[i] * p[j];
+  for (; n < CG_PAIR_STRIDE; n++) o[n] = 0.0;
+}
+// The sums of one pixel: R = its row (CgRow of cg_row_len(P, KE) doubles, the
+// products behind the P basis values: the whole row is requested one pixel ahead,
+// as two 16-dword tuples at P = 10), w = (t/e)^2, u = t s/e^2.  Columns
+// I0 <= .. < I1 of a pass (KE > 0: the one pass, 0 .. P).
+template <int P, int KE, int I0, int I1, class Row>
+__device__ __forceinline__ void cg_sums(const Row &R, const double w,
+                                        const double u, double *acc, double *av) {
+  static_assert(KE == 0 || (I0 == 0 && I1 == P), "pair columns: one pass");
+  constexpr int C0 = P - KE;   // first column with products in the row
+#pragma unroll
+  for (int jj = 0; jj < I1; jj++) {
+    const double pj = R.get(jj);
+    if (jj >= I0) av[jj] = fma(pj, u, av[jj]);
+    if (jj < C0) {
+      const double pwj = pj * w;
+#pragma unroll
+      for (int i = (jj > I0 ? jj : I0); i < I1; i++)
+        acc[TRI(i, jj)] = fma(R.get(i), pwj, acc[TRI(i, jj)]);
+    } else {
+#pragma unroll
+      for (int i = jj; i < I1; i++)
+        acc[TRI(i, jj)] =
+            fma(R.get(P + TRI(i - C0, jj - C0)), w, acc[TRI(i, jj)]);
+    }
+  }
+}
+
 // One WAVE per block.  With four waves per block the second block of a
 // 400-velocity job (64 + 64 + 16 lanes) held its CU slot as long as a full one:
 // 384, 400, 448 and 512 velocities all took the time of 512 (tools/perf/cg_bench).
@@ -355,7 +452,8 @@ __host__ __device__ constexpr int cg_split(int P) {
 // the wave's (node, block of 64 velocities) stream of npix x 64 doubles, pixel
 // major, lane = velocity.  Prologue, sums, Cholesky and tail are the same code.
 #define CG_TAB_AHEAD 4   // pixels whose table values are in flight
-template <int P, bool TAIL, bool TAB = false>
+// KE > 0: polysT is the call's pair-column rows (cg_pair_eff(P) columns).
+template <int P, bool TAIL, bool TAB = false, int KE = 0>
 __device__ __forceinline__ void
     chisq_grid_body(const int bx, const int by, const double *__restrict__ lam,
                       const double *__restrict__ polysT,
@@ -371,6 +469,9 @@ __device__ __forceinline__ void
                       int32_t *__restrict__ status, const GridSet GS,
                       const double *__restrict__ tstream = nullptr) {
   static_assert(!(TAB && TAIL), "the node table serves full waves only");
+  static_assert(KE == 0 || KE == cg_pair_eff(P), "pair columns: all or none");
+  using Row = CgRow<cg_row_len(P, KE)>;
+  constexpr int RS = KE ? CG_PAIR_STRIDE : P;   // doubles from row to row
   // lane -> (job j, velocity index iv)
   int j, iv;
   bool active;
@@ -512,7 +613,7 @@ __device__ __forceinline__ void
       u = t0 * w0.y;
     }
     const int klast = npx - 1;
-    CgRow<P> R0, R1;
+    Row R0, R1;
     double la0, pa0, la1, pa1;   // wavelength / knot coordinate of the NEXT pixel
     R0.load(polysT);
     cg_sload2(la0, lam + min(1, klast));
@@ -524,10 +625,10 @@ __device__ __forceinline__ void
     // (the row / coordinate addresses are recomputed from k with scalar
     // instructions; running pointers with an unclamped main loop were measured:
     // no difference, the scalar unit is idle)
-    auto trip = [&](int k, CgRow<P> &Rc, CgRow<P> &Rn, double lac, double pac,
+    auto trip = [&](int k, Row &Rc, Row &Rn, double lac, double pac,
                     double &lan, double &pan) {
       const int k1 = min(k + 1, klast), k2 = min(k + 2, klast);
-      Rn.load(polysT + (int64_t)k1 * P);
+      Rn.load(polysT + (int64_t)k1 * RS);
       cg_d2 wn_s;
       if (!TAIL) cg_sload4(wn_s, W + k1);
       cg_sload2(lan, lam + k2);
@@ -539,15 +640,7 @@ __device__ __forceinline__ void
             if (TAIL) wn_v = weights(k1);
             CG_FENCE();
             // the sums of pixel k
-#pragma unroll
-            for (int jj = 0; jj < I1; jj++) {
-              const double pj = Rc.get(jj);
-              const double pwj = pj * w;
-              if (jj >= I0) av[jj] = fma(pj, u, av[jj]);
-#pragma unroll
-              for (int i = (jj > I0 ? jj : I0); i < I1; i++)
-                acc[TRI(i, jj)] = fma(Rc.get(i), pwj, acc[TRI(i, jj)]);
-            }
+            cg_sums<P, KE, I0, I1>(Rc, w, u, acc, av);
             CG_FENCE();
           });
       if (TAIL) {
@@ -600,27 +693,19 @@ __device__ __forceinline__ void
       w = t0 * t0 * w0.x;
       u = t0 * w0.y;
     }
-    CgRow<P> R0, R1;
+    Row R0, R1;
     R0.load(polysT);
     R0.pin();
-    auto trip = [&](int k, auto slot_c, CgRow<P> &Rc, CgRow<P> &Rn) {
+    auto trip = [&](int k, auto slot_c, Row &Rc, Row &Rn) {
       constexpr int SL = decltype(slot_c)::value;
       const int k1 = min(k + 1, klast);
-      Rn.load(polysT + (int64_t)k1 * P);
+      Rn.load(polysT + (int64_t)k1 * RS);
       cg_d2 wn_s;
       cg_sload4(wn_s, W + k1);
       q[SL] = t_at(k + D);
       CG_FENCE();
       // the sums of pixel k
-#pragma unroll
-      for (int jj = 0; jj < I1; jj++) {
-        const double pj = Rc.get(jj);
-        const double pwj = pj * w;
-        if (jj >= I0) av[jj] = fma(pj, u, av[jj]);
-#pragma unroll
-        for (int i = (jj > I0 ? jj : I0); i < I1; i++)
-          acc[TRI(i, jj)] = fma(Rc.get(i), pwj, acc[TRI(i, jj)]);
-      }
+      cg_sums<P, KE, I0, I1>(Rc, w, u, acc, av);
       CG_FENCE();
       double tn = q[(SL + 1) % D];   // pixel k+1
       asm volatile("" : "+v"(tn));
@@ -727,7 +812,9 @@ __device__ unsigned long long cg_clock_dbg[2];
 // with a block-uniform branch between the two bodies was measured: the full-wave
 // path lost 4 % to the shared register allocation, 32.5 against 31.6 ms per
 // 10 000 spectra.)
-template <int P, bool TAIL>
+// KE: pair columns of the rows behind polysT (cg_pair_eff(P) on one wavelength
+// grid, 0 on a grid set; the packed waves never serve a grid set)
+template <int P, bool TAIL, int KE>
 // (three waves per SIMD are demanded for P <= 10 in both variants: with the
 // hand-pipelined loop the compiler has nothing left to reorder, the 168-VGPR
 // budget only moves post-loop values to scratch outside the loop.  The packed
@@ -767,10 +854,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(
     bx = r >> 3;
     if (by >= J) return;
   }
-  chisq_grid_body<P, TAIL>(bx, by, lam, polysT, work, npix, S,
-                           knots, coef, ntp, log_step, job_spec, job_templ, J,
-                           vels, vel_stride, Nv, iv0, lpj, penalty, badchi,
-                           beta_out, out, status, GS);
+  chisq_grid_body<P, TAIL, false, KE>(
+      bx, by, lam, polysT, work, npix, S, knots, coef, ntp, log_step, job_spec,
+      job_templ, J, vels, vel_stride, Nv, iv0, lpj, penalty, badchi, beta_out,
+      out, status, GS);
 #ifdef CG_CLOCK
   if (blockIdx.x == 4096 && threadIdx.x == 0) {
     cg_clock_dbg[0] = __builtin_readcyclecounter() - c0;
@@ -870,7 +957,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(
   const int vb = r / nj;
   const int j = __builtin_amdgcn_readfirstlane(order[s0 + (r - vb * nj)]);
   if (vb >= nfull || (unsigned)j >= (unsigned)J) return;
-  chisq_grid_body<P, false, true>(
+  chisq_grid_body<P, false, true, cg_pair_eff(P)>(
       vb, j, lam, polysT, work, npix, S, knots, coef, ntp, log_step, job_spec,
       job_templ, J, vels, 0, Nv, iv0, 64, penalty, badchi, beta_out, out, status,
       GS, tab + ((int64_t)n * nfull + vb) * npix * 64);
@@ -1322,6 +1409,86 @@ static GridFork *grid_fork() {
   return &f;
 }
 
+// The pair-column rows of a call (chisq_pair_rows_kernel) live in device memory
+// the library owns: one buffer per (device, stream), grown to the largest arm
+// seen on it and kept.  Two things order the buffer's uses.  The stream: the
+// build kernel of a call runs behind the grid kernels of the call before it on
+// that stream (the packed waves' side stream is joined into it at the end of
+// every call) -- no event, no host synchronisation.  And g_pair_mu, which a call
+// holds from its look at the table until its last launch is queued (PairLock in
+// launch_grid / launch_grid_tab; the launches are asynchronous, so it is held
+// for microseconds): host threads that share a stream (desi_fit.proc_many's fit
+// threads on the default stream) queue build and grid kernels of one call as a
+// unit, never build A, build B, grid A.  An allocation happens on the first call
+// of a stream and when an arm is longer than any before it on that stream
+// (hipFree of the old buffer waits for the device: the kernels that read it have
+// finished).  The table holds CG_PAIR_MAX_STREAMS entries; a stream beyond that
+// takes the place of the one whose last call is longest ago (a destroyed stream's
+// entry goes this way; its buffer is freed under the lock, which no call that
+// uses it can hold, and hipFree waits for what is queued).
+#define CG_PAIR_MAX_STREAMS 64
+namespace {
+struct PairRows {
+  int dev;
+  hipStream_t st;
+  double *rows;
+  int64_t cap;    // rows of CG_PAIR_STRIDE doubles
+  uint64_t used;  // g_pair_clock of the entry's last call
+};
+std::mutex g_pair_mu;
+std::vector<PairRows> g_pair;
+uint64_t g_pair_clock = 0;
+typedef std::unique_lock<std::mutex> PairLock;
+}  // namespace
+// (g_pair_mu held)
+static double *pair_rows_buffer(hipStream_t st, int npix) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  PairRows *e = nullptr;
+  for (PairRows &q : g_pair)
+    if (q.dev == dev && q.st == st) e = &q;
+  if (!e && g_pair.size() >= CG_PAIR_MAX_STREAMS) {
+    e = &g_pair[0];
+    for (PairRows &q : g_pair)
+      if (q.used < e->used) e = &q;
+    // (freed from its own device, so that the wait is for that device's work)
+    if (e->dev != dev) (void)hipSetDevice(e->dev);
+    (void)hipFree(e->rows);
+    if (e->dev != dev) (void)hipSetDevice(dev);
+    *e = {dev, st, nullptr, 0, 0};
+  }
+  if (!e) {
+    g_pair.push_back({dev, st, nullptr, 0, 0});
+    e = &g_pair.back();
+  }
+  e->used = ++g_pair_clock;
+  if (e->cap >= npix) return e->rows;
+  // (growth in steps of 1024 rows: arms of a survey differ by a few pixels)
+  const int64_t cap = ((int64_t)npix + 1023) / 1024 * 1024;
+  double *rows = nullptr;
+  if (hipMalloc((void **)&rows, (size_t)cap * CG_PAIR_STRIDE * sizeof(double)) !=
+      hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;   // (the entry keeps its smaller buffer)
+  }
+  if (e->rows) (void)hipFree(e->rows);
+  e->rows = rows;
+  e->cap = cap;
+  return rows;
+}
+// rows of the call behind polysT [npix][P], built on st; takes g_pair_mu into
+// `lk`, which the caller keeps until its last launch; nullptr: no buffer / launch
+static const double *pair_rows(const double *polysT, int npix, int P, int KE,
+                               hipStream_t st, PairLock &lk) {
+  lk = PairLock(g_pair_mu);
+  double *rows = pair_rows_buffer(st, npix);
+  if (!rows) return nullptr;
+  hipLaunchKernelGGL(chisq_pair_rows_kernel, dim3((unsigned)((npix + 63) / 64)),
+                     dim3(64), 0, st, polysT, npix, P, KE, rows);
+  if (hipGetLastError() != hipSuccess) return nullptr;
+  return rows;
+}
+
 template <int P>
 static int launch_grid(const double *lam, const double *polysT,
                        const double *work, int npix, int S, const double *knots,
@@ -1350,6 +1517,13 @@ static int launch_grid(const double *lam, const double *polysT,
   const int nfull = r ? Nv / 64 : (Nv + 63) / 64;   // waves per job, TAIL=false
   const int iv0 = r ? Nv - r : Nv;
   const double4 *cf = reinterpret_cast<const double4 *>(coef);
+  // one wavelength grid: the kernels read the call's pair-column rows (built
+  // here, ahead of the fork: the packed waves read them too)
+  constexpr int KE = cg_pair_eff(P);
+  const bool pair = KE > 0 && GS.G == 1 && !GS.gid;
+  PairLock rows_lock;   // (held to the end of the call: pair_rows_buffer)
+  if (pair && !(polysT = pair_rows(polysT, npix, P, KE, st, rows_lock)))
+    return RVS_E_LAUNCH;
   // The packed waves go first and on a side stream: alone they are latency bound
   // (2500 waves for 10 000 jobs = 2.4 per SIMD, one dependent scalar-load ->
   // gather round trip per pixel: 4.4 ms per DESI arm for 4 % of the velocities);
@@ -1364,7 +1538,8 @@ static int launch_grid(const double *lam, const double *polysT,
         return RVS_E_LAUNCH;
       ts = fk->side;
     }
-    hipLaunchKernelGGL((chisq_grid_kernel<P, true>),
+    // (r > 0: no grid set, so the rows are the pair-column rows)
+    hipLaunchKernelGGL((chisq_grid_kernel<P, true, KE>),
                        dim3((unsigned)(((int64_t)J * r + 63) / 64)),
                        dim3(64), 0, ts, lam, polysT, work, npix, S, knots, cf,
                        ntp, log_step, job_spec, job_templ, J, vels, vel_stride,
@@ -1376,11 +1551,18 @@ static int launch_grid(const double *lam, const double *polysT,
   if (nfull > 0) {
     const int64_t nb = (int64_t)((J + 7) / 8) * 8 * nfull;
     if (nb > 0x7fffffffll) return RVS_E_ARG;
-    hipLaunchKernelGGL((chisq_grid_kernel<P, false>), dim3((unsigned)nb),
-                       dim3(64), 0, st, lam, polysT, work, npix, S, knots, cf,
-                       ntp, log_step, job_spec, job_templ, J, vels, vel_stride,
-                       Nv, iv0, 64, nfull, penalty, badchi, beta, out, status,
-                       GS);
+    if (pair)
+      hipLaunchKernelGGL((chisq_grid_kernel<P, false, KE>), dim3((unsigned)nb),
+                         dim3(64), 0, st, lam, polysT, work, npix, S, knots, cf,
+                         ntp, log_step, job_spec, job_templ, J, vels, vel_stride,
+                         Nv, iv0, 64, nfull, penalty, badchi, beta, out, status,
+                         GS);
+    else
+      hipLaunchKernelGGL((chisq_grid_kernel<P, false, 0>), dim3((unsigned)nb),
+                         dim3(64), 0, st, lam, polysT, work, npix, S, knots, cf,
+                         ntp, log_step, job_spec, job_templ, J, vels, vel_stride,
+                         Nv, iv0, 64, nfull, penalty, badchi, beta, out, status,
+                         GS);
     RVS_LAUNCH_CHECK();
   }
   if (fk && hipStreamWaitEvent(st, fk->join, 0) != hipSuccess)
@@ -1433,6 +1615,11 @@ static int launch_grid_tab(const double *lam, const double *polysT,
                            double *tab, int tab_state, hipStream_t st) {
   const int r = Nv % 64, nfull = Nv / 64, iv0 = Nv - r;
   const double4 *cf = reinterpret_cast<const double4 *>(coef);
+  // (the table's gate admits one wavelength grid only: pair-column rows)
+  constexpr int KE = cg_pair_eff(P);
+  PairLock rows_lock;   // (held to the end of the call: pair_rows_buffer)
+  if (KE > 0 && !(polysT = pair_rows(polysT, npix, P, KE, st, rows_lock)))
+    return RVS_E_LAUNCH;
   // (the packed waves first and on the side stream, as in launch_grid; they
   // evaluate the spline themselves and do not read the table)
   GridFork *fk = r ? grid_fork() : nullptr;
@@ -1444,7 +1631,7 @@ static int launch_grid_tab(const double *lam, const double *polysT,
         return RVS_E_LAUNCH;
       ts = fk->side;
     }
-    hipLaunchKernelGGL((chisq_grid_kernel<P, true>),
+    hipLaunchKernelGGL((chisq_grid_kernel<P, true, KE>),
                        dim3((unsigned)(((int64_t)J * r + 63) / 64)),
                        dim3(64), 0, ts, lam, polysT, work, npix, S, knots, cf,
                        ntp, log_step, job_spec, job_templ, J, vels, 0, Nv, iv0, r,

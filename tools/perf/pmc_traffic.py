@@ -56,7 +56,7 @@ def main():
                           'chisq_grid_tab_kernel', 'chisq_resample_kernel'],
                          # (one full-wave launch per rvs_chisq_grid call, any npoly:
                          # the spline form or, on the node table, chisq_grid_tab_kernel)
-                         [('chisq_grid_kernel<', ', false>'),
+                         [('chisq_grid_kernel<', ', false'),
                           ('chisq_grid_tab_kernel<', )]
                          if not any('chisq_grid_resol' in k for k in fe)
                          else ('chisq_grid_resol', ),

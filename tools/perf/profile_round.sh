@@ -40,7 +40,7 @@ src = 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate runs of python3 b
 t = {'ccf_xcorr': dict(per_launch(['ccf_xcorr_kernel'], 'ccf_xcorr_kernel'), source=src,
                        kernels='ccf_xcorr_kernel (one launch = one accumulator chunk x T templates x one arm)'),
      'chisq_grid': dict(per_launch(['chisq_grid_kernel', 'chisq_grid_tab_kernel', 'chisq_resample_kernel'],
-                                        ['chisq_grid_kernel<10, false>', 'chisq_grid_tab_kernel<10>']), source=src,
+                                        ['chisq_grid_kernel<10, false', 'chisq_grid_tab_kernel<10>']), source=src,
                         kernels='chisq_grid_kernel<10,false> or, on the node table, chisq_grid_tab_kernel<10> + chisq_resample_kernel; + <10,true> (one rvs_chisq_grid call = one arm of the batch)',
                         note='FETCH_SIZE doubling is calibrated for 16-B-per-lane streaming reads; this kernel gathers 32-B records and reads through the scalar cache')}
 json.dump(t, open('gpurun_out/pmc_${tag}_traffic.json', 'w'), indent=1)

@@ -41,6 +41,54 @@ def _spline_matrix_inverse(lam):
     return _spline_inv[key]
 
 
+# knot sets longer than this take the banded solve below; None: always the dense
+# inverse (what every caller gets that does not ask: see banded_spline)
+BANDED_ABOVE = None
+
+
+class banded_spline:
+    """with banded_spline(n): spline_eval solves knot sets of more than n knots by
+    scipy.linalg.solveh_banded instead of the dense inverse (2-7 s and 340 MB per set of
+    ~6000 knots).  The same symmetric system, the same second derivatives to rounding
+    (tests/test_objective_grad_shapes_cpu.py pins one to the other at 977 knots)."""
+
+    def __init__(self, above=2000):
+        self.above = above
+
+    def __enter__(self):
+        global BANDED_ABOVE
+        self.keep, BANDED_ABOVE = BANDED_ABOVE, self.above
+
+    def __exit__(self, *exc):
+        global BANDED_ABOVE
+        BANDED_ABOVE = self.keep
+
+
+class _BandedSolve(torch.autograd.Function):
+    """x = M^-1 rhs, M the symmetric positive definite tridiagonal matrix of
+    _spline_matrix_inverse in upper banded storage `ab` [2, n] (a constant); M is
+    symmetric, so the backward pass is the same solve"""
+
+    @staticmethod
+    def forward(ctx, ab, rhs):
+        from scipy.linalg import solveh_banded
+        ctx.ab = ab
+        return torch.as_tensor(solveh_banded(ab, rhs.detach().numpy()))
+
+    @staticmethod
+    def backward(ctx, g):
+        from scipy.linalg import solveh_banded
+        return None, torch.as_tensor(solveh_banded(ctx.ab, g.detach().numpy()))
+
+
+def _spline_banded(lam):
+    h = np.diff(lam)
+    ab = np.zeros((2, len(lam) - 2))
+    ab[1] = 2 * (h[:-1] + h[1:])
+    ab[0, 1:] = h[1:-1]
+    return ab
+
+
 def template(lib, p, vsini=None):
     """(template [ntp] as a torch function of the float64 tensor p [ndim], outside)"""
     pn = p.detach().numpy()
@@ -80,7 +128,11 @@ def spline_eval(lam, t, x):
     lam_t = torch.as_tensor(lam)
     h = lam_t[1:] - lam_t[:-1]
     sl = (t[1:] - t[:-1]) / h
-    zi = _spline_matrix_inverse(lam) @ (6.0 * (sl[1:] - sl[:-1]))
+    rhs = 6.0 * (sl[1:] - sl[:-1])
+    if BANDED_ABOVE is not None and len(lam) > BANDED_ABOVE:
+        zi = _BandedSolve.apply(_spline_banded(np.asarray(lam, dtype=np.float64)), rhs)
+    else:
+        zi = _spline_matrix_inverse(lam) @ rhs
     z = torch.cat([torch.zeros(1, dtype=torch.float64), zi,
                    torch.zeros(1, dtype=torch.float64)])
     pos = np.clip(np.searchsorted(lam, x.detach().numpy(), 'right') - 1, 0,

@@ -79,11 +79,12 @@ __global__ void __launch_bounds__(OG_NT)
   const int N = T.ntp, m = N - 2;
   const int nd = T.ndim, nv = 1 << nd;
   const int K = 1 + nd + (vsini_grad ? 1 : 0);
-  const int64_t o = (int64_t)blockIdx.y * J + j;
+  const int64_t o = obj_out_index(J, j);
   double *B0 = lds, *B1 = lds + N, *B2 = lds + 2 * (int64_t)N;
   PolyLoc &PL = sh.PL;
 
-  // ---- cell search, dw/dp, the job's Doppler scalars ----------------------------
+  // ---- the grid cell: cell search, dw/dp, the job's Doppler scalars -------------------------
+  // hands over: PL, mode, sh.dw, sh.jobsc
   const GridDesc G = obj_grid_desc(T);
   const double *prow = params + (int64_t)j * nd;
   poly_locate<OG_NT>(PL, G, prow, T.idgrid, T.uvecs, T.vecs_s, T.ngrid);
@@ -106,7 +107,8 @@ __global__ void __launch_bounds__(OG_NT)
   if (tid == 64) obj_job_scalars(T.pt, vel[j], sh.jobsc);
   __syncthreads();
 
-  // ---- A3/A5: the template into B0 ------------------------------------------------
+  // ---- gather (A3/A5): the template into B0 -------------------------------------------------
+  // hands over: B0; for the template guard every thread's {mx, anynan} of a nearest row
   const float *nrow = T.dats + (int64_t)(mode == 0 ? 0 : PL.nearest) * N;
   double outside = 0.0;
   if (mode == 0) {
@@ -122,87 +124,27 @@ __global__ void __launch_bounds__(OG_NT)
     for (int k = tid; k < N; k += OG_NT) {
       const double val = T.exp_flag ? (double)np_expf(nrow[k]) : (double)nrow[k];
       B0[k] = val;
-      if (!(val == val)) anynan = true;
-      mx = fmax(mx, fabs(val));
+      obj_guard_scan(val, mx, anynan);
     }
-    // MAX_VAL guard of getCurTempl (spec_fit.py:392-397)
-    mx = wave_max(mx);
-    const double nanf = wave_sum(anynan ? 1.0 : 0.0);
-    if (lane == 0) {
-      sh.red8[w] = mx;
-      sh.red8[OG_NW + w] = nanf;
-    }
-    __syncthreads();
-    double mm = 0, nn = 0;
-    for (int i = 0; i < OG_NW; i++) {
-      mm = fmax(mm, sh.red8[i]);
-      nn += sh.red8[OG_NW + i];
-    }
-    outside = PL.dist;
-    if (outside > 0 && (mm > 1e100 || nn > 0 || isinf(mm))) outside = __builtin_nan("");
+    // ---- template guard ---------------------------------------------------------------------
+    // hands over: `outside`, the arm's penalty term
+    outside = obj_template_guard<OG_NW>(mx, anynan, &PL.dist, sh.red8);
   }
   __syncthreads();
-  if (!(fabs(outside) <= 1.79e308)) {   // unusable template: the arm is skipped
-    if (tid == 0) {
-      armout[o] = __builtin_nan("");
-      armchi[o] = 0.0;
-      armst[o] = 0;
-    }
+  if (obj_template_unusable(outside)) {
+    obj_store_skipped(o, armchi, armst, armout);
     if (tid < K) armgrad[o * K + tid] = 0.0;
     return;
   }
 
-  // ---- the rotational kernel ------------------------------------------------------
+  // ---- rotational kernel ----------------------------------------------------------------------
+  // hands over: kmax (0: `copy`, no FIR), R, st_extra; the taps are built where they are used
   bool refused = false;
   int kmax = 0;
-  if (vsini) {
-    double R_;
-    kmax = obj_rot_kmax(T, vsini[j], R_, refused);
-  }
+  double R = 0;
+  if (vsini) kmax = obj_rot_kmax(T, vsini[j], R, refused);
   const bool copy = kmax == 0;
   const int st_extra = refused ? RVS_ST_NONFINITE : 0;
-  // normalised taps 0 .. kmax into wt and, with dwt, their derivatives by vsini
-  // (vsini_kernel<true>: W' over the clipped legs of the value, dw = (W' - w S') / S /
-  // (c lnstep)); `stage` holds the primitives at x_j = clip(j / R), j = -1 .. kmax + 1,
-  // as two runs of kmax + 3 doubles.  Called by the whole block.
-  auto build_taps = [&](double *stage, double *wt, double *dwt) {
-    const double R = (vsini[j] / RVS_C_KMS) / T.lnstep;   // (obj_rot_kmax's)
-    double *pk0 = stage, *pk1 = stage + (kmax + 3);
-    for (int jj = tid; jj <= kmax + 2; jj += OG_NT) {
-      const double x = fmin(fmax((jj - 1) / R, -1.0), 1.0);
-      double k0, k1;
-      rot_prim(x, eps_ld, k0, k1);
-      pk0[jj] = k0;
-      pk1[jj] = k1;
-    }
-    __syncthreads();
-    double psum = 0, dsum = 0;
-    for (int k = tid; k <= kmax; k += OG_NT) {
-      const double ww = obj_rot_tap_raw(k, R, pk0, pk1);
-      wt[k] = ww;
-      psum += (k == 0) ? ww : 2 * ww;
-      if (dwt) {
-        double d = 0;
-        double lo = fmin(fmax(k / R, -1.0), 1.0), hi = fmin(fmax((k + 1) / R, -1.0), 1.0);
-        if (hi > lo) d += -1.0 * (pk1[k + 2] - pk1[k + 1]);   // rot_segment(lo, hi, -1, 0)
-        lo = fmin(fmax((k - 1) / R, -1.0), 1.0);
-        hi = fmin(fmax(k / R, -1.0), 1.0);
-        if (hi > lo) d += 1.0 * (pk1[k + 1] - pk1[k]);        // rot_segment(lo, hi, 1, 0)
-        dwt[k] = d;
-        dsum += (k == 0) ? d : 2 * d;
-      }
-    }
-    psum = block_sum<OG_NW>(psum, sh.red8);
-    if (dwt) dsum = block_sum<OG_NW>(dsum, sh.red8);
-    const double inv = 1.0 / psum;
-    const double dscale = inv / (RVS_C_KMS * T.lnstep);
-    for (int k = tid; k <= kmax; k += OG_NT) {
-      const double ww = wt[k];
-      if (dwt) dwt[k] = (dwt[k] - ww * inv * dsum) * dscale;
-      wt[k] = ww * inv;
-    }
-    __syncthreads();
-  };
   // 'same' convolution with zero padding and the symmetric taps tp[|m|], ascending
   // input index (vsini_fir)
   auto fir_at = [&](const double *in, const double *tp, int i) {
@@ -215,56 +157,27 @@ __global__ void __launch_bounds__(OG_NT)
     return acc;
   };
 
-  // ---- A6: y = w (*) t ------------------------------------------------------------
+  // ---- FIR (A6): y = w (*) t ----------------------------------------------------------------
   // Y, Z: the buffers of y and z; F: the third one (taps, then the pixel pair)
   double *Y = B0, *Z = B1, *F = B2;
   if (!copy) {
-    build_taps(B1, B2, nullptr);
+    obj_build_taps<OG_NT, false>(kmax, R, eps_ld, T.lnstep, B1, B2, nullptr, sh.red8);
     for (int i = tid; i < N; i += OG_NT) B1[i] = fir_at(B0, B2, i);
     Y = B1;
     Z = B0;
     __syncthreads();
   }
 
-  // ---- A7 construct: the natural spline's tridiagonal solve ------------------------
-  // Thread t owns the rows [a0, a1) (CH of them) of the m unknowns; both sweeps are
-  // linear in the value that enters the chunk, d_i = d0_i + P_i d_in, so one pass over
-  // the chunk yields (alpha, beta) at its last row and
-  //   d_in(t) = alpha(t-1) + beta(t-1) (alpha(t-2) + beta(t-2) alpha(t-3))
-  // to |beta|^3 <= (0.268^12)^3 (objective.hip).  The factors are the chunk-ordered
+  // ---- spline construct (A7): the natural spline's tridiagonal solve ------------------------
+  // hands over: Z (second derivatives of Y)
+  // Thread t owns the rows [a0, a1) (CH of them) of the m unknowns; the chunks are joined
+  // by obj_chain3 (barriers between the two solves).  The factors are the chunk-ordered
   // copy of rvs_spline_factors: record {1/h_u, 1/h_{u+1}, g_u, e_u} of row t CH + q at
   // [q][t], then the backward multipliers in pairs.
   const int CH = rvs_obj_chunk_len(m);
   const int a0 = min(m, tid * CH), a1 = min(m, a0 + CH);
   const double *FT = T.factors + 5 * (int64_t)N;
   const double *FC = FT + 4 * (int64_t)OG_NT * OG_CHMAX;
-  auto chain3 = [&](double al, double be, int dir) -> double {
-    double (*eds)[6] = sh.edge[dir < 0 ? 0 : 1];
-    double av3[3], bv3[3];
-#pragma unroll
-    for (int k = 1; k <= 3; k++) {
-      av3[k - 1] = (dir < 0) ? __shfl_up(al, k, 64) : __shfl_down(al, k, 64);
-      bv3[k - 1] = (dir < 0) ? __shfl_up(be, k, 64) : __shfl_down(be, k, 64);
-    }
-    const int edge = (dir < 0) ? (63 - lane) : lane;   // 0..2: published lanes
-    if (edge < 3) {   // (one array per direction; barriers between the two solves)
-      eds[w][2 * edge] = al;
-      eds[w][2 * edge + 1] = be;
-    }
-    __syncthreads();
-    const int mine = (dir < 0) ? lane : (63 - lane);   // distance to the boundary
-#pragma unroll
-    for (int k = 1; k <= 3; k++) {
-      if (mine < k) {   // neighbour k lives in the adjacent wave
-        const int ww = w + dir;
-        const int sl = k - 1 - mine;   // its distance from that wave's boundary
-        const bool have = (ww >= 0 && ww < OG_NW);
-        av3[k - 1] = have ? eds[ww][2 * sl] : 0.0;
-        bv3[k - 1] = have ? eds[ww][2 * sl + 1] : 0.0;
-      }
-    }
-    return av3[0] + bv3[0] * (av3[1] + bv3[1] * av3[2]);
-  };
   // M x = rhs: rhs(u, 1/h_u, 1/h_{u+1}) is read by the row's owner ahead of every
   // barrier and x written behind them, so `out` may be the buffer rhs reads
   auto tri_solve = [&](auto rhs, double *out) {
@@ -280,7 +193,7 @@ __global__ void __launch_bounds__(OG_NT)
         loc[q] = d;
         pr[q] = pb;
       }
-    const double d_in = chain3(d, pb, -1);
+    const double d_in = obj_chain3<OG_NW>(sh.edge, d, pb, -1);
     double z = 0;
     pb = 1;
 #pragma unroll
@@ -292,7 +205,7 @@ __global__ void __launch_bounds__(OG_NT)
         loc[q] = z;
         pr[q] = pb;
       }
-    const double z_in = chain3(z, pb, +1);
+    const double z_in = obj_chain3<OG_NW>(sh.edge, z, pb, +1);
 #pragma unroll
     for (int q = 0; q < OG_CHMAX; q++)
       if (q < CH && a0 + q < a1) out[a0 + q] = loc[q] + pr[q] * z_in;
@@ -305,47 +218,49 @@ __global__ void __launch_bounds__(OG_NT)
   }, Z);
   __syncthreads();
 
-  // ---- the pixels -----------------------------------------------------------------
+  // ---- model pass (A7 eval): the pixels' spline values -------------------------------------
+  // hands over: F ([npix] m/e, [npix] D/e)
   const rvs_point_arm &S = T.pt;
   const int npix = S.npix;
   const int s = job_spec ? job_spec[j] : j;
   const ObjArmGrid AG = obj_arm_grid(S, s);
-  // {1/e, D/e} of the spectrum's pixels (rvs_chisq_prepare)
-  const double2 *sig = reinterpret_cast<const double2 *>(
-                           AG.wbase + 2ll * S.S * npix + 2ll * S.S) + (int64_t)s * npix;
-  const double x0 = S.knots[0], xlast = S.knots[N - 1];
+  const double2 *sig = AG.sig;   // {1/e, D/e} of the spectrum's pixels
+  const double xlast = S.knots[N - 1];
   const double *hh = T.factors + 3 * (int64_t)N, *ih = T.factors + 4 * (int64_t)N;
-  const double f = sh.jobsc[0], shift = sh.jobsc[1], lin_inv_step = sh.jobsc[2];
-  auto pix_pos = [&](int k) {   // the knot interval of pixel k (point_knot)
+  const ObjKnotMap KM = {S.log_step, N, sh.jobsc[0], sh.jobsc[1], sh.jobsc[2], S.knots[0]};
+  const double f = KM.f;
+  // The knot interval and the spline piece in this kernel's own spelling: through
+  // obj_knot_interval / obj_piece the same arithmetic measured 0.6 % slower per call
+  // (DESIGN 4.22); the value and the derivative of the piece are the shared ones.
+  const double shift = KM.shift, lin_inv_step = KM.lin_inv_step, x0 = KM.x0;
+  auto pix_pos = [&](int k) {   // (obj_knot_interval)
     int pos = S.log_step ? (int)(AG.pix[k] + shift)
                          : (int)((AG.lam[k] * f - x0) * lin_inv_step);
     return min(max(pos, 0), N - 2);
   };
-  // spline piece of the interval in powers of dl, as rvs_spline_construct(form 1)
-  auto piece = [&](int pos, double &yi, double &cb, double &c2, double &c3) {
+  auto piece = [&](int pos) {   // (obj_piece)
+    ObjPiece p;
     const double h = hh[pos], hinv = ih[pos];
     const double zi = (pos == 0) ? 0.0 : Z[pos - 1];
     const double zi1 = (pos + 1 == N - 1) ? 0.0 : Z[pos];
     const double yi1 = Y[pos + 1];
-    yi = Y[pos];
+    p.yi = Y[pos];
     const double t1 = hinv * (1.0 / 6), t2 = h * (1.0 / 6);
-    cb = (yi1 - yi) * hinv - t2 * (2 * zi + zi1);
-    c2 = 0.5 * zi;
-    c3 = (zi1 - zi) * t1;
+    p.cb = (yi1 - p.yi) * hinv - t2 * (2 * zi + zi1);
+    p.c2 = 0.5 * zi;
+    p.c3 = (zi1 - zi) * t1;
+    return p;
   };
-  // pass 1: model and data in units of sigma into F ([npix] m/e, [npix] D/e), the
-  // normal equations per lane
   // (a loop of its own, which holds no accumulators, as in objective_kernel)
   for (int k = tid; k < npix; k += OG_NT) {
     const int pos = pix_pos(k);
     const double dl = AG.lam[k] * f - S.knots[pos];
-    double yi, cb, c2, c3;
-    piece(pos, yi, cb, c2, c3);
-    const double tv = fma(fma(fma(c3, dl, c2), dl, cb), dl, yi);
+    const double tv = obj_piece_value(piece(pos), dl);
     const double2 sg = sig[k];
     F[k] = tv * sg.x;
     F[npix + k] = sg.y;
   }
+  // ---- normal equations (A10): the sums per lane, waves' totals into sh.red ---------------
   {
     double vals[NV];   // [NTR] packed lower triangle, then [P] right-hand sides
 #pragma unroll
@@ -381,6 +296,9 @@ __global__ void __launch_bounds__(OG_NT)
     sh.red[0][tid] = v;
   }
   __syncthreads();
+  // ---- solve (A10): Cholesky factor, coefficients, log det ---------------------------------
+  // hands over: acc[] (L with 1 / L_ii on the diagonal) and av[] (the coefficients) in
+  // every lane's registers; sh.fact
   // every lane factors the same matrix: A = L L^T in place with 1 / L_ii on the diagonal
   // (the only form the substitutions need), c = A^-1 v by the two substitutions
   // (point_grad_block)
@@ -429,6 +347,8 @@ __global__ void __launch_bounds__(OG_NT)
     sh.fact[0] = ldet;
     sh.fact[1] = okl ? 1.0 : 0.0;
   }
+  // ---- residual (A11) and the pixel adjoint ---------------------------------------------------
+  // hands over: rr, gvel (this thread's shares); mbar in F[0, npix)
   // pass 2: residual, the pixel adjoint into F[0, npix), the velocity component
   //   d chi^2 / d vel = sum_k mbar_k S'(x_k) lam_k df/dvel
   const double bb = vel[j] / RVS_C_KMS;
@@ -455,9 +375,7 @@ __global__ void __launch_bounds__(OG_NT)
     const int pos = pix_pos(k);
     const double lamk = AG.lam[k];
     const double dl = lamk * f - S.knots[pos];
-    double yi, cb, c2, c3;
-    piece(pos, yi, cb, c2, c3);
-    const double dtv = fma(dl, fma(3.0 * c3, dl, 2.0 * c2), cb);
+    const double dtv = obj_piece_deriv(piece(pos), dl);
     gvel = fma(mbar, dtv * (lamk * dfdv), gvel);
     F[k] = mbar;
   }
@@ -527,7 +445,8 @@ __global__ void __launch_bounds__(OG_NT)
   double *tbar = Yb;
   const double *dwt = nullptr;
   if (!copy) {
-    build_taps(Zb, F, vs_grad ? F + kmax + 1 : nullptr);
+    obj_build_taps<OG_NT, false>(kmax, R, eps_ld, T.lnstep, Zb, F, vs_grad ? F + kmax + 1 : nullptr,
+                          sh.red8);
     for (int i = tid; i < N; i += OG_NT) Zb[i] = fir_at(Yb, F, i);
     tbar = Zb;
     dwt = F + kmax + 1;
@@ -562,7 +481,7 @@ __global__ void __launch_bounds__(OG_NT)
     if (vs_grad) gvs = fma(fir_at(Yb, dwt, n), tn, gvs);
   }
 
-  // ---- the block's sums: lanes by butterfly, waves in order ---------------------------
+  // ---- tail: the block's sums (lanes by butterfly, waves in order), value and status --------
   {
     double fin[OG_MAXK + 1];
     fin[0] = rr;
@@ -584,21 +503,10 @@ __global__ void __launch_bounds__(OG_NT)
     sh.red[0][tid] = v;
   }
   __syncthreads();
-  // value and status as rvs_chisq_point forms them
-  const double lz = AG.wbase[2ll * S.S * npix + 2 * s];
-  const bool ok = sh.fact[1] != 0.0;
-  double chi = 2.0 * sh.fact[0] + 2.0 * lz + sh.red[0][0];
-  int st = st_extra;
-  const double xa = AG.lam[0] * f, xb = AG.lam[npix - 1] * f;
-  if (xa < x0 || xb < x0 || xa >= xlast || xb >= xlast) {
-    st |= RVS_ST_SPLINE_RANGE;
-    chi = __builtin_nan("");
-  }
-  if (!ok) st |= RVS_ST_CHOL_FALLBACK;
-  if (!ok || !(fabs(chi) <= 1.79e308)) {
-    st |= RVS_ST_NONFINITE;
-    chi = __builtin_nan("");
-  }
+  double chi;
+  int st;
+  obj_value_status(S, AG, s, KM, xlast, sh.fact[0], sh.fact[1] != 0.0, sh.red[0][0], st_extra,
+                   chi, st);
   if (tid == 0) {
     armchi[o] = chi;
     armst[o] = st;

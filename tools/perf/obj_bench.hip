@@ -21,10 +21,6 @@
 #define objective_sum_kernel bench_objective_sum_kernel
 #define obj_dbg bench_obj_dbg
 #include "../../rvspecfit_amd/csrc/objective.hip"
-#ifdef OBJ_PIPE_EXPERIMENT
-#define objective_pipe_kernel bench_objective_pipe_kernel
-#include "experiments/objective_pipe.hip"
-#endif
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -197,8 +193,7 @@ int main(int argc, char **argv) {
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
-  // the one-block-per-item kernel first (RVS_OBJ_PIPE=0): the values the
-  // persistent kernel is compared with
+  // the caller's job order first: the values the run in cell order is compared with
   std::vector<double> out0(J);
   float best0 = 1e30f;
   const bool skip_ref = getenv("OBJ_BENCH_SKIP_REF") != nullptr;   // (counter runs)
@@ -207,7 +202,6 @@ int main(int argc, char **argv) {
   if (skip_ref) {
     rvs_option_set("obj_sort", want_sort);
   } else {
-    setenv("RVS_OBJ_PIPE", "0", 1);
     rvs_option_set("obj_sort", 0);      // first run: the caller's job order
     for (int r = 0; r < reps + 1; r++) {
       hipEventRecord(e0);
@@ -219,12 +213,11 @@ int main(int argc, char **argv) {
       float ms;
       hipEventElapsedTime(&ms, e0, e1);
       if (r) best0 = fminf(best0, ms);
-      if (rc0) return printf("objective (per-block) rc %d\n", rc0), 1;
+      if (rc0) return printf("objective (unsorted) rc %d\n", rc0), 1;
     }
     CK(hipDeviceSynchronize());
     hipMemcpy(out0.data(), d_out, J * 8, hipMemcpyDeviceToHost);
     hipMemset(d_out, 0, J * 8);
-    setenv("RVS_OBJ_PIPE", getenv("OBJ_BENCH_PIPE") ? getenv("OBJ_BENCH_PIPE") : "1", 1);
     rvs_option_set("obj_sort", want_sort);
   }
   float best = 1e30f, sum = 0;
@@ -270,7 +263,7 @@ int main(int argc, char **argv) {
     else if ((out[j] == out[j]) != (out0[j] == out0[j]))
       nnan++;
   }
-  printf("unsorted, per-block kernel: best %.3f ms (%.2f us per block-CU); max rel diff %.3g, NaN mismatches %d\n",
+  printf("unsorted: best %.3f ms (%.2f us per block-CU); max rel diff %.3g, NaN mismatches %d\n",
          best0, 1e3 * best0 * 256 / ((double)J * NARM), maxrel, nnan);
   const double nblk = (double)J * NARM;
   printf("J %d grid %d,%d,%d,%d sorted %d sort %d vsini<=%g: best %.3f ms mean %.3f ms  "

@@ -125,7 +125,10 @@ extern "C" {
  *      rvs_alm_run_bytes and rvs_alm_run with the new structs rvs_epoch_chain and
  *      rvs_alm_state; and rvs_chisq_grid_tab / rvs_chisq_grid_tab_work_size, the
  *      velocity grid on a per-node table of resampled templates, with the option
- *      "cg_tab") */
+ *      "cg_tab"; and rvs_objective_fisher_ok / rvs_objective_fisher_work_size /
+ *      rvs_objective_fisher, value, gradient and Fisher matrix in one forward-mode
+ *      kernel per (job, arm), with rvs_lm_run_fused, the Levenberg-Marquardt rounds on
+ *      it) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -877,6 +880,48 @@ int rvs_objective_grad(const rvs_objective_arm *arms, int narm, int npoly, int n
                        double *out, double *grad, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------
+ * The objective of rvs_objective_grad WITH the Fisher matrix of the marginalised fit
+ * (rvs_chisq_point_fisher's F = J^T (1 - U U^T) J), as one kernel per (job, arm), in
+ * FORWARD mode: behind the value phases of rvs_objective_grad (the same value and
+ * status) each of the K = 1 + ntan tangent rows -- the velocity's from the spline's
+ * derivative, a parameter's gathered at the knots as rvs_template_polylinear_grad forms
+ * it, vsini's from the tap derivatives of rvs_vsini_convolve_grad -- goes through the
+ * value's own FIR, spline solve and resampling, one at a time, in the LDS buffers the
+ * value has left.  The pixel-side state (the pixel adjoint, m/e and the K columns J_ki)
+ * lives in a work row of (K + 2) npix doubles per (job, arm), written and read back by
+ * the thread that owns the pixel.  No template row, tangent row or spline record goes to
+ * HBM; no floating point atomics: repeated calls, permuted job lists and another work
+ * size agree to the bit.  Replaces the chain rvs_template_polylinear_grad ->
+ * rvs_vsini_convolve(_grad) -> rvs_spline_construct -> rvs_chisq_point_fisher (the
+ * Jacobian of spec_fit.py:888-896's chi^2 that the reference takes by differences).
+ * Arguments as for rvs_objective_grad, and
+ *   fisher [J, K, K]    ordered (vel, parameters in library order[, vsini]), exactly
+ *                       symmetric, as rvs_chisq_point_fisher delivers it
+ *                       (rvs_proc_finish_fisher consumes it unchanged); rows and columns
+ *                       exactly 0 where the gradient's column is; NaN where the value is;
+ *                       an arm whose outside flag is not finite adds nothing
+ *   work, work_bytes    rvs_objective_fisher_work_size(J, narm, ntan, npix_max) bytes
+ *                       (npix_max: the largest pt.npix of the arms; 0 for arguments out
+ *                       of range) hold all J jobs in one launch.  A smaller buffer is
+ *                       taken too, down to the size of ONE job,
+ *                       rvs_objective_fisher_work_size(1, narm, ntan, npix_max): the jobs
+ *                       then go in launches of as many as fit, with the same results to
+ *                       the bit.
+ * rvs_objective_fisher_ok (host arithmetic only): rvs_objective_grad_ok's rule -- npoly
+ * 1..10, ndim 1..4, 32 <= ntp, 2*npix <= ntp, 3*ntp doubles + 8 KB <= 160 KB of LDS.
+ * RVS_E_ARG, before any launch: everything rvs_objective_grad refuses, and a work buffer
+ * below the one-job size.
+ * ---------------------------------------------------------------------- */
+int rvs_objective_fisher_ok(int npoly, int npix, int ntp, int ndim, int vsini_grad);
+int64_t rvs_objective_fisher_work_size(int J, int narm, int ntan, int npix_max);
+int rvs_objective_fisher(const rvs_objective_arm *arms, int narm, int npoly, int ntan,
+                         const double *params, const double *vsini,
+                         const int32_t *job_spec, int J, const double *vel,
+                         double badchi, const double *basis_const, void *work,
+                         int64_t work_bytes, double *out, double *grad, double *fisher,
+                         int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------
  * Host side of the second minimiser of vel_fit.process (vel_fit.py:653-658:
  * scipy.optimize.minimize(method='BFGS', options={'hess_inv0': ...})): S
  * independent BFGS runs (scipy's _minimize_bfgs with its wolfe1 / wolfe2 line
@@ -1582,6 +1627,21 @@ int64_t rvs_lm_run_bytes(void);
 int rvs_lm_run(const rvs_lm_state *b, const rvs_nm_objective *o,
                const rvs_grad_chain *g, const rvs_fisher_chain *fc, int sync_every,
                int64_t *stats, void *stream);
+/* rvs_lm_run with the rows' (value, gradient, Fisher matrix) from ONE rvs_objective_fisher
+ * call per chunk of g->cap rows, between rvs_proc_map and rvs_proc_finish_fisher, in the
+ * place of rvs_lm_run's chain (rvs_template_polylinear_grad -> rvs_vsini_convolve(_grad)
+ * -> rvs_spline_construct -> rvs_chisq_point_fisher): the polish of vel_fit.py:653-658
+ * as rvs_bfgs_run_grad_fused runs it, on Levenberg-Marquardt steps.  The same machine
+ * (lm_machine.h), rounds, counts and results as rvs_lm_run.  Of g only cap, narm, ntan,
+ * vsini_mode, chi [cap] and grad [cap, 1 + ntan] are read; garms / basis_const as for
+ * rvs_objective_fisher.  fwork: g->cap * (1 + ntan)^2 doubles (the chunk's matrices)
+ * followed by rvs_objective_fisher's work buffer -- fwork_bytes at least those matrices
+ * plus rvs_objective_fisher_work_size(1, narm, ntan, npix_max); more than the size for
+ * cap jobs is of no use.  RVS_E_ARG: what rvs_lm_run or rvs_objective_fisher refuse. */
+int rvs_lm_run_fused(const rvs_lm_state *b, const rvs_nm_objective *o,
+                     const rvs_grad_chain *g, const rvs_objective_arm *garms,
+                     const double *basis_const, void *fwork, int64_t fwork_bytes,
+                     int sync_every, int64_t *stats, void *stream);
 
 /* ------------------------------------------------------------------------
  * The joint fit of a star's epochs (vel_fit.process_epochs): one set of stellar

@@ -108,6 +108,7 @@ SIGNATURES = {
     'rvs_lm_end': (None, [P]),
     'rvs_lm_run_bytes': (L, []),
     'rvs_lm_run': (I, [P, P, P, P, I, P, P]),
+    'rvs_lm_run_fused': (I, [P, P, P, P, P, P, L, I, P, P]),
     'rvs_epoch_map': (I, [I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, D, D, D, P, P, P,
                           P, P, P, P, P]),
     'rvs_epoch_finish': (I, [I, I, I, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P,
@@ -132,6 +133,9 @@ SIGNATURES = {
     'rvs_objective_grad_ok': (I, [I, I, I, I, I]),
     'rvs_objective_grad_work_size': (L, [I, I, I]),
     'rvs_objective_grad': (I, [P, I, I, I, P, P, P, I, P, D, P, P, P, P, P, P]),
+    'rvs_objective_fisher_ok': (I, [I, I, I, I, I]),
+    'rvs_objective_fisher_work_size': (L, [I, I, I, I]),
+    'rvs_objective_fisher': (I, [P, I, I, I, P, P, P, I, P, D, P, P, L, P, P, P, P, P]),
     'rvs_bfgs_run_grad_fused': (I, [P, P, P, P, P, P, I, P, P]),
     'rvs_grid_moments': (I, [P, P, L, P, I, I, I, I, P, P, P, P]),
     'rvs_basis_build': (I, [P, P, I, I, I, I, P, P, P, P, P]),

@@ -10,7 +10,9 @@
 //   rounds_emit_kernel   / row, the rows of each chunk, the live runs; the rows' list
 //   <objective>          per chunk of g->cap rows the Fisher form of the gradient chain
 //                        (bfgs_grad.hip: ... rvs_chisq_point_fisher ->
-//                        rvs_proc_finish_fisher)
+//                        rvs_proc_finish_fisher), or -- rvs_lm_run_fused -- one
+//                        rvs_objective_fisher call (objective_fisher.hip) between
+//                        rvs_proc_map and rvs_proc_finish_fisher
 // with the counts on the device and the host looking at them under rvs_bfgs_run's policy.
 #include "common.h"
 #include "lm_machine.h"
@@ -83,19 +85,26 @@ __global__ void __launch_bounds__(LM_NT)
 
 extern "C" int64_t rvs_lm_run_bytes(void) { return (int64_t)sizeof(Run); }
 
-extern "C" int rvs_lm_run(const rvs_lm_state *b, const rvs_nm_objective *o,
-                          const rvs_grad_chain *g, const rvs_fisher_chain *fc,
-                          int sync_every, int64_t *stats, void *stream) {
-  if (!b || !o || !g || !fc || b->S < 1 || b->n < 1 || b->n > rvs_lm::MAXN ||
-      b->n != o->n || sync_every < 1 || !b->runs || !b->x0 || !b->x || !b->fun ||
-      !b->grad || !b->mu || !b->nit || !b->nfev || !b->status || !b->nreq || !b->off ||
-      !b->list || !b->X || !b->F || !b->counts || !fc->fisher_work || !fc->fisher ||
-      !rvs_internal_grad_chain_ok(g, o))
-    return RVS_E_ARG;
-  const int S = b->S, n = b->n, cap = g->cap;
+namespace {
+
+// what both forms of the polish ask of b and o beside their own checks
+bool lm_args_ok(const rvs_lm_state *b, const rvs_nm_objective *o, const rvs_grad_chain *g,
+                int sync_every) {
+  return b && o && g && b->S >= 1 && b->n >= 1 && b->n <= rvs_lm::MAXN && b->n == o->n &&
+         sync_every >= 1 && b->runs && b->x0 && b->x && b->fun && b->grad && b->mu &&
+         b->nit && b->nfev && b->status && b->nreq && b->off && b->list && b->X && b->F &&
+         b->counts;
+}
+
+// the rounds of rvs_lm_run over eval(list, X, J, chunk, F, stream): (f, grad f, H packed)
+// of a chunk of rows into F [J, npack(n)]
+template <class Eval>
+int lm_run_rows(const rvs_lm_state *b, int cap, int sync_every, int64_t *stats,
+                void *stream, Eval eval) {
+  const int S = b->S, n = b->n;
   const int m = rvs_lm::npack(n);
   const int64_t maxrows = S;   // one row per live run
-  if ((maxrows + cap - 1) / cap > BF_NCHUNK) return RVS_E_ARG;
+  if (cap < 1 || (maxrows + cap - 1) / cap > BF_NCHUNK) return RVS_E_ARG;
   hipStream_t st = rvs_stream(stream);
   LmDev D;
   D.runs = static_cast<Run *>(b->runs);
@@ -131,8 +140,7 @@ extern "C" int rvs_lm_run(const rvs_lm_state *b, const rvs_nm_objective *o,
       if (bound > maxrows) bound = maxrows;
       for (int64_t a = 0, ch = 0; a < bound; a += cap, ch++) {
         const int J = (int)((bound - a < cap) ? bound - a : cap);
-        int rc = rvs_internal_grad_chain_eval(o, g, b->list + a, b->X + a * n, J,
-                                              b->counts, (int)ch, b->F + a * m, st, fc);
+        int rc = eval(b->list + a, b->X + a * n, J, (int)ch, b->F + a * m, st);
         if (rc) return rc;
         calls++;
         jobs += J;
@@ -152,4 +160,77 @@ extern "C" int rvs_lm_run(const rvs_lm_state *b, const rvs_nm_objective *o,
     stats[2] = jobs;
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int rvs_lm_run(const rvs_lm_state *b, const rvs_nm_objective *o,
+                          const rvs_grad_chain *g, const rvs_fisher_chain *fc,
+                          int sync_every, int64_t *stats, void *stream) {
+  if (!lm_args_ok(b, o, g, sync_every) || !fc || !fc->fisher_work || !fc->fisher ||
+      !rvs_internal_grad_chain_ok(g, o))
+    return RVS_E_ARG;
+  return lm_run_rows(b, g->cap, sync_every, stats, stream,
+                     [&](const int32_t *list, const double *X, int J, int ch, double *F,
+                         hipStream_t st) {
+                       return rvs_internal_grad_chain_eval(o, g, list, X, J, b->counts, ch,
+                                                           F, st, fc);
+                     });
+}
+
+// ... with the chain's stages between rvs_proc_map and rvs_proc_finish_fisher replaced by
+// one rvs_objective_fisher call (objective_fisher.hip).  fwork: the chunk's matrices
+// [cap, K, K] first, the kernel's work buffer behind them
+extern "C" int rvs_lm_run_fused(const rvs_lm_state *b, const rvs_nm_objective *o,
+                                const rvs_grad_chain *g, const rvs_objective_arm *garms,
+                                const double *basis_const, void *fwork,
+                                int64_t fwork_bytes, int sync_every, int64_t *stats,
+                                void *stream) {
+  if (!lm_args_ok(b, o, g, sync_every) || !garms || !fwork || !g->chi || !g->grad ||
+      g->cap < 1 || g->narm < 1 || g->narm > RVS_MAX_ARMS || g->narm != o->narm ||
+      g->vsini_mode < 0 || g->vsini_mode > 2 || o->ndim < 1 || o->ndim > 4 ||
+      g->ntan != o->ndim + (g->vsini_mode == 2 ? 1 : 0) ||
+      (g->vsini_mode == 2) != (o->vsini_col >= 0) ||
+      (g->vsini_mode != 0) != (o->vsini != nullptr) || !o->vel || !o->params ||
+      !o->extra || !o->bad || !o->job_spec || !o->jstatus || !o->status || !o->fixed ||
+      !o->safe)
+    return RVS_E_ARG;
+  int npix_max = 0;
+  for (int a = 0; a < g->narm; a++) {
+    if (garms[a].ndim != o->ndim || garms[a].pt.taps || garms[a].pt.G > 1 ||
+        garms[a].pt.fast_interp ||
+        !rvs_objective_fisher_ok(o->npoly, garms[a].pt.npix, garms[a].ntp, o->ndim,
+                                 g->vsini_mode == 2))
+      return RVS_E_ARG;
+    npix_max = garms[a].pt.npix > npix_max ? garms[a].pt.npix : npix_max;
+  }
+  const int64_t K = 1 + g->ntan;
+  const int64_t fisher_bytes = (int64_t)g->cap * K * K * (int64_t)sizeof(double);
+  if (fwork_bytes < fisher_bytes +
+                        rvs_objective_fisher_work_size(1, g->narm, g->ntan, npix_max))
+    return RVS_E_ARG;
+  double *fisher = static_cast<double *>(fwork);
+  void *kwork = fisher + (int64_t)g->cap * K * K;
+  const int64_t kwork_bytes = fwork_bytes - fisher_bytes;
+  return lm_run_rows(
+      b, g->cap, sync_every, stats, stream,
+      [&](const int32_t *list, const double *X, int J, int ch, double *F,
+          hipStream_t st) {
+        int rc = rvs_proc_map(J, o->n, o->ndim, X, list, o->src, o->vsini_col, o->fixed,
+                              o->vsini_fixed, o->safe, o->prior_mean, o->prior_isig,
+                              o->min_vel, o->max_vel, o->max_vsini, o->job_spec, o->vel,
+                              o->vsini, o->params, o->extra, o->bad, st);
+        if (rc) return rc;
+        if (hipMemsetAsync(o->jstatus, 0, sizeof(int32_t) * J, st) != hipSuccess)
+          return RVS_E_LAUNCH;
+        rc = rvs_objective_fisher(garms, g->narm, o->npoly, g->ntan, o->params, o->vsini,
+                                  o->job_spec, J, o->vel, o->badchi, basis_const, kwork,
+                                  kwork_bytes, g->chi, g->grad, fisher, o->jstatus, st);
+        if (rc) return rc;
+        return rvs_proc_finish_fisher(J, o->n, o->ndim, g->ntan, b->counts, ch, g->chi,
+                                      g->grad, fisher, X, o->params, o->extra, o->bad,
+                                      o->job_spec, o->jstatus, o->src, o->vsini_col,
+                                      o->prior_mean, o->prior_isig, o->max_vsini, F,
+                                      o->status, st);
+      });
 }

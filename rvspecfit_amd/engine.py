@@ -1398,6 +1398,13 @@ def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
         raise ValueError('%s does not go with %s: it needs the tangent rows of the '
                          'gradient chain, which the fused kernel never forms'
                          % (key, what))
+    _check_fused_scope(key, _lib.lib().rvs_objective_grad_ok, batch, libs, npoly, resols,
+                       fast_interp, vsini_grad)
+
+
+def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_grad):
+    # what rvs_objective_grad and rvs_objective_fisher both leave to the chain; ok: the
+    # kernel's own rvs_objective_*_ok
     if fast_interp:
         raise ValueError('%s does not go with fast_interp (the nearest-knot template '
                          'has no velocity derivative)' % key)
@@ -1405,7 +1412,6 @@ def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
         raise ValueError('%s takes npoly 1..%d, not npoly = %d (beyond, the wave '
                          'totals of the normal equations live in the template buffer)'
                          % (key, GRAD_FUSED_MAXP, npoly))
-    ok = _lib.lib().rvs_objective_grad_ok
     for ia, arm in enumerate(batch.arms):
         lib = libs[arm.name]
         if _arm_resol(arm, ia, resols) is not None:
@@ -1496,6 +1502,93 @@ def objective_grad_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
         _lib.check(rc, 'rvs_objective_grad')
     del keep
     return out, grad, status
+
+
+# bytes the work rows of one objective_fisher_fused call may take by default ((3 + ntan)
+# npix doubles per job and arm: 0.55 MB per job on the three DESI arms, 4.5 GB at 8192)
+FISHER_FUSED_WORK_BUDGET = 8 << 30
+
+
+def check_fused_fisher_scope(batch, libs, npoly, resols=None, fast_interp=False,
+                             vsini_grad=False, what=None):
+    """ValueError naming the option that config['fused_fisher'] does not go with: what
+    rvs_objective_fisher (csrc/objective_fisher.hip) does not cover keeps the chain, and
+    the key beside it is an error, never a silent change of path.  `what`: a caller's
+    own option the kernel has no form for (the joint-epoch fit)."""
+    key = "config['fused_fisher']"
+    if what is not None:
+        raise ValueError('%s does not go with %s: the forward-mode kernel has no form '
+                         'for it' % (key, what))
+    _check_fused_scope(key, _lib.lib().rvs_objective_fisher_ok, batch, libs, npoly,
+                       resols, fast_interp, vsini_grad)
+
+
+def can_fuse_objective_fisher(batch, libs, resols=None, fast_interp=False, npoly=10,
+                              vsini_grad=False):
+    """whether rvs_objective_fisher covers this batch (check_fused_fisher_scope says why
+    not)"""
+    try:
+        check_fused_fisher_scope(batch, libs, npoly, resols, fast_interp, vsini_grad)
+    except ValueError:
+        return False
+    return True
+
+
+def objective_fisher_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
+                           job_spec=None, vsini_grad=False, espec_sys=0.0,
+                           work_bytes=None):
+    """get_chisq, its gradient and the Fisher matrix of the marginalised fit for J
+    (spectrum, parameters, vsini, velocity) jobs as ONE kernel per (job, arm)
+    (rvs_objective_fisher, forward mode): no template row, tangent row or spline record
+    in HBM.  Returns chisq [J], grad [J, K], fisher [J, K, K] with K = 1 + ndim -- 2 +
+    ndim with vsini_grad, vsini last -- and status int32 [J]: the results of
+    build_templates(tangents=True) + chisq_point_fisher to rounding.  work_bytes: the
+    size of the work buffer (default: all jobs in one launch, up to
+    FISHER_FUSED_WORK_BUDGET bytes; smaller, down to one job's, the jobs go in several
+    launches with the same bits).  What the kernel does not cover
+    raises ValueError (check_fused_fisher_scope)."""
+    import ctypes
+    if vsini_grad and vsini is None:
+        raise ValueError('vsini_grad=True needs vsini: without rotation there is no '
+                         'vsini to differentiate by')
+    check_fused_fisher_scope(batch, libs, npoly, None, False, vsini_grad)
+    L = _lib.lib()
+    dev = batch.device
+    vel = vel.to(device=dev, dtype=torch.float64).contiguous()
+    params = params.to(device=dev, dtype=torch.float64).contiguous()
+    J = vel.shape[0]
+    narm = len(batch.arms)
+    ntan = libs[batch.arms[0].name].ndim + (1 if vsini_grad else 0)
+    K = 1 + ntan
+    arr = (_lib.ObjectiveArm * narm)()
+    bconst = (ctypes.c_double * narm)()
+    keep = fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys)
+    out = torch.empty(J, dtype=torch.float64, device=dev)
+    grad = torch.empty((J, K), dtype=torch.float64, device=dev)
+    fisher = torch.empty((J, K, K), dtype=torch.float64, device=dev)
+    status = torch.zeros(J, dtype=torch.int32, device=dev)
+    npix_max = max(arm.npix for arm in batch.arms)
+    nb = L.rvs_objective_fisher_work_size(J, narm, ntan, npix_max)
+    if work_bytes is not None:
+        nb = int(work_bytes)
+    elif nb > FISHER_FUSED_WORK_BUDGET:   # whole jobs, at least one
+        one = L.rvs_objective_fisher_work_size(1, narm, ntan, npix_max)
+        nb = max(1, FISHER_FUSED_WORK_BUDGET // one) * one
+    work = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
+    if vsini is not None:
+        vsini = vsini.to(device=dev, dtype=torch.float64).contiguous()
+    if job_spec is not None:
+        job_spec = job_spec.to(device=dev, dtype=torch.int32).contiguous()
+    with _ktime('objective_fisher', J):
+        rc = L.rvs_objective_fisher(ctypes.addressof(arr), narm, npoly, ntan,
+                                    _lib.ptr(params), _lib.ptr(vsini),
+                                    _lib.ptr(job_spec), J, _lib.ptr(vel),
+                                    float(batch.badchi), ctypes.addressof(bconst),
+                                    _lib.ptr(work), nb, _lib.ptr(out), _lib.ptr(grad),
+                                    _lib.ptr(fisher), _lib.ptr(status), _lib.stream())
+        _lib.check(rc, 'rvs_objective_fisher')
+    del keep
+    return out, grad, fisher, status
 
 
 _ar_cache = {}

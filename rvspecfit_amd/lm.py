@@ -7,7 +7,7 @@ machine, as bfgs.py has:
   minimize_lockstep_device  the rounds on the GPU (rvs_lm_run: one thread per run, the
                             Fisher form of optimizer.GradChain's chain as the objective)
   minimize_lockstep_native  the machines on the host (rvs_lm_begin / _pending / _feed)
-                            around any Python objective
+                            around any Python objective (GradChain.rows of either form)
 The Python statement of the algorithm lives with the tests
 (tests/refmachines/lm_restated.py); tests/test_lm_cpu.py holds the C++ machine against it.
 
@@ -100,7 +100,9 @@ def minimize_lockstep_device(pobj, x0, gtol=1e-5, xtol=XTOL, tau=TAU, mu_max=MU_
                              maxiter=None, sync_every=4, chain=None, cap=None):
     """The runs on the device (csrc/lm_dev.hip, rvs_lm_run) around an
     optimizer.ProcessObjective: x0 [S, n] device tensor; `chain` an
-    optimizer.GradChain(pobj, fisher=True), or one built here with `cap` rows per chunk.
+    optimizer.GradChain(pobj, fisher=True), or one built here with `cap` rows per chunk;
+    a GradChain(pobj, fused_fisher=True) takes rvs_lm_run_fused (one rvs_objective_fisher
+    call per chunk in the place of the chain's stages).
     Returns device tensors x, grad [S, n], fun, mu [S], hess [S, n, n], nit, nfev,
     status [S] and the statistics of the run (rounds, objective calls, rows launched).
     Libraries and options the gradient does not cover raise ValueError."""
@@ -138,11 +140,20 @@ def minimize_lockstep_device(pobj, x0, gtol=1e-5, xtol=XTOL, tau=TAU, mu_max=MU_
     b.S, b.n, b.maxiter = S, n, int(maxiter or 0)
     o = pobj.native_desc()
     g = chain.desc()
-    fc = chain.fisher_desc()
     st3 = (ctypes.c_int64 * 3)()
-    _lib.check(L.rvs_lm_run(ctypes.addressof(b), ctypes.addressof(o),
-                            ctypes.addressof(g), ctypes.addressof(fc), int(sync_every),
-                            st3, _lib.stream()), 'rvs_lm_run')
+    if getattr(chain, 'fused_fisher', False):
+        # optimizer.GradChain(fused_fisher=True): one rvs_objective_fisher call per chunk
+        _lib.check(L.rvs_lm_run_fused(ctypes.addressof(b), ctypes.addressof(o),
+                                      ctypes.addressof(g), ctypes.addressof(chain.garms),
+                                      ctypes.addressof(chain.bconst),
+                                      chain.fwork.data_ptr(), int(chain.nbytes),
+                                      int(sync_every), st3, _lib.stream()),
+                   'rvs_lm_run_fused')
+    else:
+        fc = chain.fisher_desc()
+        _lib.check(L.rvs_lm_run(ctypes.addressof(b), ctypes.addressof(o),
+                                ctypes.addressof(g), ctypes.addressof(fc),
+                                int(sync_every), st3, _lib.stream()), 'rvs_lm_run')
     pobj.calls += int(st3[1])
     pobj.slots += int(st3[2])
     pobj.jobs += int(st3[2])

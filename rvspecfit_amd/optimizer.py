@@ -345,6 +345,10 @@ class ProcessObjective:
 # spline records of `cap` rows per arm: 48 (1 + ntan) ntp bytes per row and arm, 2.7 MB
 # at ntan = 6 and 8000 template pixels); a round with more rows runs in chunks
 GRAD_CHAIN_BUDGET = 4 << 30
+# bytes the work rows of GradChain(fused_fisher=True) may take ((3 + ntan) npix doubles
+# per row and arm: 0.55 MB per row on the three DESI arms); a chunk with more rows goes
+# through rvs_objective_fisher in several launches, with the same bits
+FISHER_FUSED_WORK_BUDGET = 512 << 20
 
 
 class GradChain:
@@ -359,15 +363,26 @@ class GradChain:
     rvs_objective_grad call per chunk (rvs_bfgs_run_grad_fused; csrc/objective_grad.hip)
     -- the object then holds no template or record buffers, only the arm descriptors,
     the kernel's scratch and the chunk's chi / grad; `rows` goes through the same call.
-    What that kernel does not cover, fisher=True included, raises ValueError."""
+    What that kernel does not cover, fisher=True included, raises ValueError.
+    fused_fisher=True (config['fused_fisher']): the Fisher form with the rows' value,
+    gradient and matrix from ONE rvs_objective_fisher call per chunk (rvs_lm_run_fused;
+    csrc/objective_fisher.hip) -- no row buffers either: the arm descriptors, the chunk's
+    chi / grad and one buffer for the chunk's matrices and the kernel's work rows, at
+    most FISHER_FUSED_WORK_BUDGET bytes of the latter (the call goes through a chunk's
+    jobs in as many launches as that takes)."""
 
-    def __init__(self, pobj, cap=None, budget=None, fisher=False, fused=False):
+    def __init__(self, pobj, cap=None, budget=None, fisher=False, fused=False,
+                 fused_fisher=False):
         L = _lib.lib()
         batch, libs = pobj.batch, pobj.libs
         fit = pobj.vsini_col >= 0
         self.fused = bool(fused)
+        self.fused_fisher = bool(fused_fisher) and not self.fused
         if self.fused:
             self._init_fused(pobj, cap, fisher)
+            return
+        if self.fused_fisher:
+            self._init_fused_fisher(pobj, cap)
             return
         # (refused before anything is built; nothing falls back to differences)
         engine.check_grad_scope(batch, libs, pobj.npoly, pobj.resols, False,
@@ -514,6 +529,38 @@ class GradChain:
         self.grad = torch.empty((cap, 1 + self.ntan), **f64)
         self.njev = torch.zeros(pobj.S, dtype=torch.int32, device=dev)
 
+    def _init_fused_fisher(self, pobj, cap):
+        L = _lib.lib()
+        batch, libs = pobj.batch, pobj.libs
+        fit = pobj.vsini_col >= 0
+        engine.check_fused_fisher_scope(batch, libs, pobj.npoly, pobj.resols, False,
+                                        vsini_grad=fit)
+        self.pobj, self.fisher = pobj, True
+        dev = pobj.dev
+        narm = len(batch.arms)
+        self.ntan = pobj.ndim + (1 if fit else 0)
+        self.vsini_mode = 2 if fit else (1 if pobj.has_vsini else 0)
+        cap = int(min(pobj.S if cap is None else cap, pobj.cap))
+        if cap < 1 or (pobj.S + cap - 1) // cap > GradChain.MAX_CHUNKS:
+            raise ValueError('second_minimizer_lm: a round holds at most %d chunks of '
+                             '%d rows: %d spectra do not fit one call; pass them in '
+                             'smaller batches' % (GradChain.MAX_CHUNKS, cap, pobj.S))
+        self.cap = cap
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.garms = (_lib.ObjectiveArm * narm)()
+        self.bconst = (ctypes.c_double * narm)()
+        self._keep = engine.fill_objective_grad_arms(self.garms, self.bconst, batch, libs,
+                                                     pobj.npoly, pobj.rbf)
+        K = 1 + self.ntan
+        npix_max = max(a.npix for a in batch.arms)
+        one = int(L.rvs_objective_fisher_work_size(1, narm, self.ntan, npix_max))
+        rows = max(1, min(cap, FISHER_FUSED_WORK_BUDGET // one))
+        self.nbytes = cap * K * K * 8 + rows * one
+        self.fwork = torch.empty(self.nbytes // 8, **f64)
+        self.chi = torch.empty(cap, **f64)
+        self.grad = torch.empty((cap, K), **f64)
+        self.njev = torch.zeros(pobj.S, dtype=torch.int32, device=dev)
+
     MAX_CHUNKS = 24     # the chunk counters of the scan kernel (bfgs_dev.hip)
 
     @staticmethod
@@ -554,7 +601,7 @@ class GradChain:
         g.basis_const = ctypes.addressof(self.bconst)
         ps = self.pobj.batch.pen_scale
         g.pen_scale = None if ps is None else ps.data_ptr()
-        if not self.fused:   # (rvs_bfgs_run_grad_fused reads none of the three)
+        if not (self.fused or self.fused_fisher):   # (the fused runs read none of the three)
             g.arms, g.point = ctypes.addressof(self.arms), ctypes.addressof(self.point)
             g.point_work = self.point_work.data_ptr()
         g.chi, g.grad = self.chi.data_ptr(), self.grad.data_ptr()
@@ -577,7 +624,8 @@ class GradChain:
         bfgs.minimize_lockstep_native(jac=True), and what rvs_bfgs_run_grad's rounds
         are held against.  With fisher=True: [J, 1 + n + n (n + 1) / 2] through
         rvs_chisq_point_fisher and rvs_proc_finish_fisher, the objective of
-        lm.minimize_lockstep_native and what rvs_lm_run's rounds are held against."""
+        lm.minimize_lockstep_native and what rvs_lm_run's rounds are held against (with
+        fused_fisher=True: through rvs_objective_fisher, against rvs_lm_run_fused's)."""
         from . import spec_fit
         p, L = self.pobj, _lib.lib()
         dev = p.dev
@@ -601,7 +649,8 @@ class GradChain:
                 None if p.vsini is None else p.vsini[:n], p.npoly, p.rbf, 0.0, True,
                 p.resols, False, p.vsini_col >= 0, self.fisher,
                 nn_gradient=getattr(p, 'nn_gradient', False),
-                resol_gradient=getattr(p, 'resol_gradient', False), fused=self.fused)
+                resol_gradient=getattr(p, 'resol_gradient', False), fused=self.fused,
+                fused_fisher=self.fused_fisher)
             chi, grad, status = res[0], res[1], res[-1]
             tail = (_p(X_t[a:]), _p(p.params), _p(p.extra), _p(p.bad), _p(p.job_spec),
                     _p(status), p.src, p.vsini_col, _p(p.prior_mean), _p(p.prior_isig),

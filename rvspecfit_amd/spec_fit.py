@@ -551,7 +551,8 @@ def _get_chisq_grad(specdata, vel, atm_params, rot_params, options, config,
                       outside_penalty, resols, fast_interp, vsini_grad, fisher,
                       nn_gradient=bool((config or {}).get('nn_gradient')),
                       resol_gradient=bool((config or {}).get('resol_gradient')),
-                      fused=bool((config or {}).get('fused_gradient')))
+                      fused=bool((config or {}).get('fused_gradient')),
+                      fused_fisher=bool((config or {}).get('fused_fisher')))
     if is_batch:
         return res[:-1]
     _raise_for_status(int(res[-1][0].item()),
@@ -573,7 +574,12 @@ def get_chisq_fisher(specdata, vel, atm_params, rot_params=None, options=None,
     One spectrum: returns (float, ndarray [K], ndarray [K, K]), K = 1 + ndim (2 + ndim
     with vsini_grad).  SpecBatch: device tensors [S], [S, K], [S, K, K].  Value and
     gradient are the bits of get_chisq_grad; arguments and scope are its own (anything
-    else raises ValueError)."""
+    else raises ValueError).
+    With config['fused_fisher'] true value, gradient and matrix come from one kernel per
+    (spectrum, setup) (rvs_objective_fisher, forward mode: no template row, tangent row
+    or spline record in HBM) -- regular-grid libraries of up to 4 parameters, npoly <=
+    10, no resolution matrix, no fast_interp, one wavelength grid per setup; anything
+    else beside that key raises ValueError naming the option and the key."""
     return _get_chisq_grad(specdata, vel, atm_params, rot_params, options, config,
                            outside_penalty, espec_systematic, resol_params, fast_interp,
                            vsini_grad, True)
@@ -581,7 +587,8 @@ def get_chisq_fisher(specdata, vel, atm_params, rot_params=None, options=None,
 
 def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
                 outside_penalty, resols, fast_interp, vsini_grad=False, fisher=False,
-                nn_gradient=False, resol_gradient=False, fused=False):
+                nn_gradient=False, resol_gradient=False, fused=False,
+                fused_fisher=False):
     # (the checks come first: nothing is built for a call that is refused)
     if fused:
         # config['fused_gradient']: value and gradient in one kernel per (job, arm)
@@ -594,6 +601,17 @@ def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
                              'outside_penalty=False: the kernel adds the penalty')
         return engine.objective_grad_fused(batch, libs, params, vsini, vel, npoly, rbf,
                                            js, vsini_grad, esys)
+    if fused_fisher and fisher:
+        # config['fused_fisher']: value, gradient and Fisher matrix in one forward-mode
+        # kernel per (job, arm) (rvs_objective_fisher); what it does not cover is an
+        # error, not the chain
+        engine.check_fused_fisher_scope(batch, libs, npoly, resols, fast_interp,
+                                        vsini_grad)
+        if not outside_penalty:
+            raise ValueError("config['fused_fisher'] does not go with "
+                             'outside_penalty=False: the kernel adds the penalty')
+        return engine.objective_fisher_fused(batch, libs, params, vsini, vel, npoly, rbf,
+                                             js, vsini_grad, esys)
     engine.check_grad_scope(batch, libs, npoly, resols, fast_interp, vsini_grad,
                             nn_gradient=nn_gradient, resol_gradient=resol_gradient)
     coefs, outs = [], []
@@ -756,7 +774,8 @@ def _chisq_grad_jobs(batch, idx, vel, params, vsini, options, config, outside_pe
                        outside_penalty, resols, False, vsini_grad, fisher,
                        nn_gradient=bool((config or {}).get('nn_gradient')),
                        resol_gradient=bool((config or {}).get('resol_gradient')),
-                       fused=bool((config or {}).get('fused_gradient')))
+                       fused=bool((config or {}).get('fused_gradient')),
+                       fused_fisher=bool((config or {}).get('fused_fisher')))
 
 
 # rows per launch set of the from-template objective (template buffers of

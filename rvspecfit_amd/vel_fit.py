@@ -1059,7 +1059,17 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
                  "Fisher matrix)" if lm_polish else
                  ("config['fisher_uncertainties'] (the Fisher matrix)"
                   if config.get('fisher_uncertainties') else None))
-    if lm_polish:
+    # config['fused_fisher']: the Fisher matrix -- the rows of the Levenberg-Marquardt
+    # polish (rvs_lm_run_fused) and config['fisher_uncertainties'] -- from
+    # rvs_objective_fisher, one forward-mode kernel per (row, arm).  What the kernel does
+    # not cover beside the key is an error that says so
+    fused_fisher = bool(config.get('fused_fisher'))
+    if fused_fisher and (lm_polish or config.get('fisher_uncertainties')):
+        engine.check_fused_fisher_scope(
+            batch, spec_inter.get_libs(batch.names, config), options.get('npoly') or 5,
+            spec_fit._resols(batch, resolParams), bool(options.get('fast_interp')),
+            vsini_grad=fitVsini)
+    if lm_polish and not fused_fisher:   # (the fused form holds no row buffers to budget)
         try:
             engine.check_grad_scope(batch, spec_inter.get_libs(batch.names, config),
                                     options.get('npoly') or 5,
@@ -1096,7 +1106,7 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
     # from the Fisher matrix at the returned optimum, beside the Hessian's products.
     # The scope is the gradient's and is checked here, before anything is built
     fisher_unc = bool(config.get('fisher_uncertainties'))
-    if fisher_unc:
+    if fisher_unc and not fused_fisher:   # (fused: checked with the key above)
         try:
             engine.check_grad_scope(batch, spec_inter.get_libs(batch.names, config),
                                     options.get('npoly') or 5,
@@ -1186,7 +1196,7 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
         t0 = time.time()
         jobs_before = pobj.jobs
         slots_before = pobj.slots
-        chain = optimizer.GradChain(pobj, fisher=True)
+        chain = optimizer.GradChain(pobj, fisher=True, fused_fisher=fused_fisher)
         if BFGS_ON_DEVICE:
             br = lm.minimize_lockstep_device(pobj, x, chain=chain)
             x = br['x']
@@ -1201,6 +1211,8 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
         lm_info = dict(nit=br['nit'], nfev=br['nfev'], status=br['status'],
                        mu=br['mu'], fun=br['fun'], rounds=br['rounds'],
                        device=BFGS_ON_DEVICE)
+        if fused_fisher:   # (the rows came from rvs_objective_fisher)
+            lm_info['fused'] = True
         second_run = True
         _tick('lm', t0)
     elif config.get('second_minimizer'):
@@ -1479,6 +1491,10 @@ def process_epochs(specdata, star, paramDict0, vel0, fixParam=None, options=None
         engine.check_fused_grad_scope(batch, libs, options.get('npoly') or 5,
                                       what='the joint fit of a star\'s epochs '
                                            '(process_epochs: its rows are Fisher rows)')
+    if config.get('fused_fisher'):
+        engine.check_fused_fisher_scope(batch, libs, options.get('npoly') or 5,
+                                        what='the joint fit of a star\'s epochs '
+                                             '(process_epochs)')
     safe = torch.stack([pd0[_] for _ in names], dim=1)
     try:
         chain = optimizer.EpochChain(

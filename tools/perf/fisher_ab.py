@@ -4,7 +4,12 @@ spec_fit.chisq_fisher_jobs call against ONE spec_fit.chisq_grad_jobs call on the
 jobs, and against vel_fit.param_uncertainties (the finite-difference Hessian of the
 stellar parameters: 33+ objective evaluations per spectrum) on the same S spectra.
 usage: fisher_ab.py [--jobs J] [--spectra S] [--npoly P] [--rounds R] [--vsini-grad]
-                    [--resolution-matrix]
+                    [--resolution-matrix] [--fused]
+--fused: a fourth leg, the same chisq_fisher_jobs call under config['fused_fisher']
+(rvs_objective_fisher: one forward-mode kernel per (job, arm)), alternating with the
+others; the line then carries its seconds, its ratio to the chain's Fisher call of the
+same round set and its largest differences from the chain's results.  (Profile kept:
+profiles/fisher_fused_ab_8192.json.)
 --resolution-matrix: every spectrum carries resolution matrices of 11 diagonals
 (tools/perf/_resol.py, as resol_ab.py builds them) and all three run under them, the
 first two with config['resol_gradient'] (rvs_chisq_point_fisher_resol / _grad_resol).
@@ -32,6 +37,7 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--vsini-grad', action='store_true')
     ap.add_argument('--resolution-matrix', action='store_true')
+    ap.add_argument('--fused', action='store_true')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
     import numpy as np
@@ -79,6 +85,10 @@ def main():
         return spec_fit.chisq_fisher_jobs(batch, idx, vel, par, vs, opt, cfg,
                                           vsini_grad=vg)
 
+    def fused():
+        return spec_fit.chisq_fisher_jobs(batch, idx, vel, par, vs, opt,
+                                          dict(cfg, fused_fisher=True), vsini_grad=vg)
+
     def gradient():
         return spec_fit.chisq_grad_jobs(batch, idx, vel, par, vs, opt, cfg,
                                         vsini_grad=vg)
@@ -96,10 +106,15 @@ def main():
         return time.perf_counter() - t0, out
 
     timed(fisher), timed(gradient), timed(hessian)   # warm-up: tables, caches, clocks
-    tf, tg, th = [], [], []
+    if args.fused:
+        timed(fused)
+    tf, tg, th, tu = [], [], [], []
     for _ in range(args.rounds):
         t, (cf, gf, F, stf) = timed(fisher)
         tf.append(t)
+        if args.fused:
+            t, (cu, gu, Fu, stu) = timed(fused)
+            tu.append(t)
         t, (cg, gg, stg) = timed(gradient)
         tg.append(t)
         t, hs = timed(hessian)
@@ -111,6 +126,24 @@ def main():
     d = np.sqrt(np.clip(np.diagonal(Fn, axis1=1, axis2=2), 1e-300, None))
     ev = np.linalg.eigvalsh(Fn / (d[:, :, None] * d[:, None, :]))
     med = lambda v: round(float(np.median(v)), 6)   # noqa: E731
+    more = {}
+    if args.fused:
+        Fun = Fu.cpu().numpy()
+        relF = np.abs(Fun - Fn) / (d[:, :, None] * d[:, None, :])
+        gn, gun = gf.cpu().numpy(), gu.cpu().numpy()
+        relg = np.abs(gun - gn) / np.maximum(np.abs(gn), 1e-6 * np.abs(gn).max(
+            axis=1, keepdims=True))
+        more = dict(
+            fused_s_median=med(tu), fused_s_min=round(min(tu), 6),
+            fused_s_all=[round(x, 6) for x in tu], fisher_s_all=[round(x, 6) for x in tf],
+            fused_over_fisher_median=round(float(np.median(tu) / np.median(tf)), 3),
+            fused_over_grad_median=round(float(np.median(tu) / np.median(tg)), 3),
+            fused_status_equal=bool(torch.equal(stu, stf)),
+            fused_value_bits_equal=bool(torch.equal(cu, cf)),
+            fused_value_max_rel=float(((cu - cf).abs() / cf.abs().clamp(min=1e3)).max()),
+            fused_fisher_max_err_of_sqrt_FiiFll=float(np.nanmax(relF)),
+            fused_grad_max_rel=float(np.nanmax(relg)),
+            fused_asymmetry_max=float(np.abs(Fun - Fun.transpose(0, 2, 1)).max()))
     print(json.dumps(dict(
         jobs=J, spectra=S, npoly=args.npoly, ndim=ndim, vsini_grad=vg, rounds=args.rounds,
         resolution_matrix=args.resolution_matrix,
@@ -123,7 +156,7 @@ def main():
         bad_fisher_share=float(np.mean(fu['bad_fisher'])),
         bad_hessian_share=float(np.mean(hs['bad_hessian'])),
         fisher_asymmetry_max=float(np.abs(Fn - Fn.transpose(0, 2, 1)).max()),
-        fisher_scaled_min_eigenvalue=float(ev.min()))), flush=True)
+        fisher_scaled_min_eigenvalue=float(ev.min()), **more)), flush=True)
 
 
 if __name__ == '__main__':

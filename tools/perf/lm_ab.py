@@ -4,7 +4,12 @@
 config['second_minimizer_jac']) and Levenberg-Marquardt on the Fisher matrix (rvs_lm_run,
 config['second_minimizer_lm']), alternating, in one process.
 usage: lm_ab.py [--spectra S] [--npoly P] [--rounds R] [--evaluator polylinear|tri]
-                [--tau T] [--resolution-matrix]
+                [--tau T] [--resolution-matrix] [--fused]
+--fused: two more legs in every round -- Levenberg-Marquardt on the rows of
+rvs_objective_fisher (rvs_lm_run_fused, config['fused_fisher']) and BFGS on the rows of
+rvs_objective_grad (rvs_bfgs_run_grad_fused, config['fused_gradient']); the line then
+carries both and their ratios to the legs of the same rounds.  (Profile kept:
+profiles/lm_fused_ab_2000.json.)
 --resolution-matrix: every spectrum carries resolution matrices of 11 diagonals
 (tools/perf/_resol.py, as resol_ab.py builds them); the differenced polish runs through
 the objective kernel's band, the other two through config['resol_gradient'].
@@ -37,6 +42,7 @@ def main():
     ap.add_argument('--evaluator', choices=['polylinear', 'tri'], default='polylinear')
     ap.add_argument('--tau', type=float, default=1e-3)
     ap.add_argument('--resolution-matrix', action='store_true')
+    ap.add_argument('--fused', action='store_true')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
     import numpy as np
@@ -99,6 +105,17 @@ def main():
     def lmq():
         return lm.minimize_lockstep_device(pobj, x0, tau=args.tau, chain=fchain)
 
+    if args.fused:
+        gchain = optimizer.GradChain(pobj, fused=True)
+        uchain = optimizer.GradChain(pobj, fused_fisher=True)
+
+    def jac_fused():
+        return bfgs.minimize_lockstep_device(pobj, x0, hess_inv0=hess_inv0, jac=True,
+                                             chain=gchain)
+
+    def lm_fused():
+        return lm.minimize_lockstep_device(pobj, x0, tau=args.tau, chain=uchain)
+
     def timed(fn):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -107,8 +124,15 @@ def main():
         return time.perf_counter() - t0, out
 
     timed(fd), timed(jac), timed(lmq)          # warm-up
-    t_fd, t_jac, t_lm = [], [], []
+    if args.fused:
+        timed(jac_fused), timed(lm_fused)
+    t_fd, t_jac, t_lm, t_jf, t_lf = [], [], [], [], []
     for _ in range(args.rounds):
+        if args.fused:
+            t, e = timed(lm_fused)
+            t_lf.append(t)
+            t, g = timed(jac_fused)
+            t_jf.append(t)
         t, a = timed(fd)
         t_fd.append(t)
         t, b = timed(jac)
@@ -140,6 +164,20 @@ def main():
                     lm_lower=int((d < 0).sum()), equal=int((d == 0).sum()),
                     lm_higher=int((d > 0).sum()), mean=float(d.mean()))
 
+    more = {}
+    if args.fused:
+        more = dict(
+            lm_fused=mode(t_lf, e, mu_median=float(e['mu'].median()),
+                          stage_s_all=[round(x, 4) for x in t_lf],
+                          work_bytes=uchain.nbytes),
+            jac_fused=mode(t_jf, g, njev=per(g, 'njev'),
+                           stage_s_all=[round(x, 4) for x in t_jf]),
+            lm_stage_s_all=[round(x, 4) for x in t_lm],
+            lm_fused_over_lm_time=round(float(np.median(t_lf) / np.median(t_lm)), 3),
+            lm_fused_over_jac_fused_time=round(float(np.median(t_lf) / np.median(t_jf)), 3),
+            lm_fused_over_fd_time=round(float(np.median(t_lf) / np.median(t_fd)), 3),
+            jac_fused_over_fd_time=round(float(np.median(t_jf) / np.median(t_fd)), 3),
+            f_lmfused_minus_f_lm=dist(e, c), f_lmfused_minus_f_jacfused=dist(e, g))
     print(json.dumps(dict(
         spectra=S, npoly=args.npoly, evaluator=args.evaluator, rounds=args.rounds,
         resolution_matrix=args.resolution_matrix,
@@ -150,7 +188,7 @@ def main():
         lm=mode(t_lm, c, mu_median=float(c['mu'].median())),
         jac_over_fd_time=round(float(np.median(t_jac) / np.median(t_fd)), 3),
         lm_over_fd_time=round(float(np.median(t_lm) / np.median(t_fd)), 3),
-        f_lm_minus_f_fd=dist(c, a), f_lm_minus_f_jac=dist(c, b))), flush=True)
+        f_lm_minus_f_fd=dist(c, a), f_lm_minus_f_jac=dist(c, b), **more)), flush=True)
 
 
 if __name__ == '__main__':

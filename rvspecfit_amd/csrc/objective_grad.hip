@@ -32,192 +32,65 @@
 // No template row, spline record or adjoint row goes to HBM.  There is no floating
 // point atomic: every sum has a fixed order (lanes by butterfly, waves in order), so
 // repeated runs and permuted job lists agree to the bit.  The value phases repeat the
-// arithmetic of the stand-alone kernels they replace.
-#include "objective_dev.h"
-
-#define OG_NT RVS_OBJ_NT
-#define OG_NW (OG_NT / 64)
-#define OG_CHMAX RVS_OBJ_CHMAX
-#define OG_MAXP 10     // beyond: the value kernel's wave totals live in the template buffer
-#define OG_MAXDIM 4    // the bound of the cell record (OBJ_LOC_NV vertices)
-#define OG_MAXK (2 + OG_MAXDIM)   // vel, parameters, vsini
-// upper bound of the kernel's static LDS (OgShared): what rvs_objective_grad_ok, host
-// arithmetic only, counts beside the three template buffers
-#define OG_STATIC_MAX 8192
-#define OG_LDS_MAX (160 * 1024)
+// arithmetic of the stand-alone kernels they replace.  Cell, gather and guard, rotational
+// kernel, FIR and spline construct are objective_point_dev.h's, shared with
+// objective_fisher.hip, as are the host side and the sum over the arms; the passes over
+// the pixels are this kernel's own text.
+#include "objective_point_dev.h"
 
 namespace {
 
 template <int P>
-struct OgShared {
-  static constexpr int NV = P * (P + 1) / 2 + P;
-  PolyLoc PL;
-  double dw[OG_MAXDIM << OG_MAXDIM];   // dw_v/dp_d [d][v] (polylinear_kernel<true>)
-  double red[OG_NW][(NV > OG_MAXK + 1 ? NV : OG_MAXK + 1) + 1];
-  double edge[2][OG_NW][6];   // chunk coefficients across wave boundaries
-  double red8[2 * OG_NW];
-  double fact[2];             // log det L, 1: every pivot positive
-  double jobsc[3];            // obj_job_scalars
-};
+using OgShared = OpShared<P, (op_nv(P) > OP_MAXK + 1 ? op_nv(P) : OP_MAXK + 1)>;
 
 template <int P>
-__global__ void __launch_bounds__(OG_NT)
+__global__ void __launch_bounds__(OP_NT)
     objective_grad_kernel(ObjArms A, const double *__restrict__ params,
                           const double *__restrict__ vsini, int vsini_grad,
                           const int32_t *__restrict__ job_spec, int J,
                           const double *__restrict__ vel, double eps_ld,
                           double *__restrict__ armchi, double *__restrict__ armgrad,
                           int32_t *__restrict__ armst, double *__restrict__ armout) {
-  constexpr int NTR = P * (P + 1) / 2;
-  constexpr int NV = NTR + P;
-  static_assert(sizeof(OgShared<P>) <= OG_STATIC_MAX, "rvs_objective_grad_ok's bound");
+  static_assert(sizeof(OgShared<P>) <= OP_STATIC_MAX, "op_point_ok's bound");
   extern __shared__ double lds[];
   __shared__ OgShared<P> sh;
-  const rvs_objective_arm &T = A.a[blockIdx.y];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int j = blockIdx.x;
-  const int N = T.ntp, m = N - 2;
-  const int nd = T.ndim, nv = 1 << nd;
-  const int K = 1 + nd + (vsini_grad ? 1 : 0);
   const int64_t o = obj_out_index(J, j);
-  double *B0 = lds, *B1 = lds + N, *B2 = lds + 2 * (int64_t)N;
-  PolyLoc &PL = sh.PL;
+  ObjPoint<P, OgShared<P>::REDW> pt(sh, A.a[blockIdx.y], lds, j, eps_ld);
+  const rvs_objective_arm &T = pt.T;
+  const PolyLoc &PL = pt.PL;
+  const int tid = pt.tid, lane = pt.lane, w = pt.w;
+  const int N = pt.N, m = pt.m, nd = pt.nd, nv = pt.nv;
+  const int K = 1 + nd + (vsini_grad ? 1 : 0);
+  constexpr int NTR = P * (P + 1) / 2;
+  constexpr int NV = NTR + P;
 
-  // ---- the grid cell: cell search, dw/dp, the job's Doppler scalars -------------------------
-  // hands over: PL, mode, sh.dw, sh.jobsc
-  const GridDesc G = obj_grid_desc(T);
-  const double *prow = params + (int64_t)j * nd;
-  poly_locate<OG_NT>(PL, G, prow, T.idgrid, T.uvecs, T.vecs_s, T.ngrid);
-  const int mode = PL.mode;
-  if (mode == 0) {
-    // the weight's factor of dimension d replaced by -+1 / (cell width), per PHYSICAL
-    // unit of p_d (the chain through log10 of a log_mask parameter included)
-    for (int i = tid; i < nd * nv; i += OG_NT) {
-      const int d = i >> nd, v = i & (nv - 1);
-      const double *u = T.uvecs + sel_dim(G.uoff, d);
-      const int p = PL.pos[d];
-      double wd = 1.0 / (u[p + 1] - u[p]);
-      if (G.log_mask & (1u << d)) wd /= prow[d] * 2.302585092994046;
-      if (!((v >> (nd - 1 - d)) & 1)) wd = -wd;
-      for (int e = 0; e < nd; e++)
-        if (e != d) wd *= ((v >> (nd - 1 - e)) & 1) ? PL.x[e] : (1 - PL.x[e]);
-      sh.dw[d * nv + v] = wd;
-    }
-  }
-  if (tid == 64) obj_job_scalars(T.pt, vel[j], sh.jobsc);
-  __syncthreads();
-
-  // ---- gather (A3/A5): the template into B0 -------------------------------------------------
-  // hands over: B0; for the template guard every thread's {mx, anynan} of a nearest row
-  const float *nrow = T.dats + (int64_t)(mode == 0 ? 0 : PL.nearest) * N;
-  double outside = 0.0;
-  if (mode == 0) {
-    for (int k = tid; k < N; k += OG_NT) {
-      double acc = 0;
-      for (int v = 0; v < nv; v++)
-        acc = fma(PL.w[v], (double)T.dats[PL.id[v] * N + k], acc);
-      B0[k] = T.exp_flag ? exp(acc) : acc;
-    }
-  } else {
-    double mx = 0;
-    bool anynan = false;
-    for (int k = tid; k < N; k += OG_NT) {
-      const double val = T.exp_flag ? (double)np_expf(nrow[k]) : (double)nrow[k];
-      B0[k] = val;
-      obj_guard_scan(val, mx, anynan);
-    }
-    // ---- template guard ---------------------------------------------------------------------
-    // hands over: `outside`, the arm's penalty term
-    outside = obj_template_guard<OG_NW>(mx, anynan, &PL.dist, sh.red8);
-  }
-  __syncthreads();
-  if (obj_template_unusable(outside)) {
+  // ---- cell, gather and guard, rotational kernel, FIR, spline construct ---------------------
+  // (objective_point_dev.h, shared with objective_fisher_kernel) hands over: PL, sh.dw,
+  // sh.jobsc, mode, nrow, outside; kmax, R, copy, st_extra; Y, Z, F; the chunk tables
+  pt.cell(params, vel);
+  pt.gather_and_guard();
+  if (obj_template_unusable(pt.outside)) {
     obj_store_skipped(o, armchi, armst, armout);
     if (tid < K) armgrad[o * K + tid] = 0.0;
     return;
   }
-
-  // ---- rotational kernel ----------------------------------------------------------------------
-  // hands over: kmax (0: `copy`, no FIR), R, st_extra; the taps are built where they are used
-  bool refused = false;
-  int kmax = 0;
-  double R = 0;
-  if (vsini) kmax = obj_rot_kmax(T, vsini[j], R, refused);
-  const bool copy = kmax == 0;
-  const int st_extra = refused ? RVS_ST_NONFINITE : 0;
-  // 'same' convolution with zero padding and the symmetric taps tp[|m|], ascending
-  // input index (vsini_fir)
-  auto fir_at = [&](const double *in, const double *tp, int i) {
-    double acc = 0;
-    const int q0 = max(i - kmax, 0), q1 = min(i + kmax, N - 1);
-    for (int q = q0; q <= q1; q++) {
-      const int mm = q - i;
-      acc = fma(in[q], tp[mm < 0 ? -mm : mm], acc);
-    }
-    return acc;
-  };
-
-  // ---- FIR (A6): y = w (*) t ----------------------------------------------------------------
-  // Y, Z: the buffers of y and z; F: the third one (taps, then the pixel pair)
-  double *Y = B0, *Z = B1, *F = B2;
-  if (!copy) {
-    obj_build_taps<OG_NT, false>(kmax, R, eps_ld, T.lnstep, B1, B2, nullptr, sh.red8);
-    for (int i = tid; i < N; i += OG_NT) B1[i] = fir_at(B0, B2, i);
-    Y = B1;
-    Z = B0;
-    __syncthreads();
-  }
-
-  // ---- spline construct (A7): the natural spline's tridiagonal solve ------------------------
-  // hands over: Z (second derivatives of Y)
-  // Thread t owns the rows [a0, a1) (CH of them) of the m unknowns; the chunks are joined
-  // by obj_chain3 (barriers between the two solves).  The factors are the chunk-ordered
-  // copy of rvs_spline_factors: record {1/h_u, 1/h_{u+1}, g_u, e_u} of row t CH + q at
-  // [q][t], then the backward multipliers in pairs.
-  const int CH = rvs_obj_chunk_len(m);
-  const int a0 = min(m, tid * CH), a1 = min(m, a0 + CH);
-  const double *FT = T.factors + 5 * (int64_t)N;
-  const double *FC = FT + 4 * (int64_t)OG_NT * OG_CHMAX;
-  // M x = rhs: rhs(u, 1/h_u, 1/h_{u+1}) is read by the row's owner ahead of every
-  // barrier and x written behind them, so `out` may be the buffer rhs reads
-  auto tri_solve = [&](auto rhs, double *out) {
-    double loc[OG_CHMAX], pr[OG_CHMAX];
-    double d = 0, pb = 1;
-#pragma unroll
-    for (int q = 0; q < OG_CHMAX; q++)
-      if (q < CH && a0 + q < a1) {
-        const double *rec = FT + ((int64_t)q * OG_NT + tid) * 4;
-        const double ei = rec[3];
-        d = rhs(a0 + q, rec[0], rec[1]) * rec[2] - ei * d;
-        pb = -ei * pb;
-        loc[q] = d;
-        pr[q] = pb;
-      }
-    const double d_in = obj_chain3<OG_NW>(sh.edge, d, pb, -1);
-    double z = 0;
-    pb = 1;
-#pragma unroll
-    for (int q = OG_CHMAX - 1; q >= 0; q--)
-      if (q < CH && a0 + q < a1) {
-        const double ci = FC[((int64_t)(q >> 1) * OG_NT + tid) * 2 + (q & 1)];
-        z = (loc[q] + pr[q] * d_in) - ci * z;   // d of the forward sweep, then z
-        pb = -ci * pb;
-        loc[q] = z;
-        pr[q] = pb;
-      }
-    const double z_in = obj_chain3<OG_NW>(sh.edge, z, pb, +1);
-#pragma unroll
-    for (int q = 0; q < OG_CHMAX; q++)
-      if (q < CH && a0 + q < a1) out[a0 + q] = loc[q] + pr[q] * z_in;
-  };
-  // right-hand sides 6 ((y_{u+2} - y_{u+1}) / h_{u+1} - (y_{u+1} - y_u) / h_u); Z[u] =
-  // z at knot u + 1
-  tri_solve([&](int u, double ih0, double ih1) {
-    const double s0 = (Y[u + 1] - Y[u]) * ih0, s1 = (Y[u + 2] - Y[u + 1]) * ih1;
-    return 6 * (s1 - s0);
-  }, Z);
+  pt.rotational_kernel(vsini);
+  pt.fir();
+  const int mode = pt.mode, kmax = pt.kmax, st_extra = pt.st_extra;
+  const float *nrow = pt.nrow;
+  const double outside = pt.outside, R = pt.R;
+  const bool copy = pt.copy;
+  double *Y = pt.Y, *Z = pt.Z, *F = pt.F;
+  pt.spline_chunks();
+  pt.spline_construct();
   __syncthreads();
 
+  // From here to the end of pass 2 this kernel keeps its own text: through ObjPoint's
+  // model_pass, normal_equations, solve and pixel_adjoint -- the statements
+  // objective_fisher_kernel runs, and faster there -- grad_ab.py --fused --vsini-grad
+  // measured 17.80 ms against 17.48 (spread 0.05); with these passes its own 17.50
+  // (DESIGN 4.24).  A change to one of them is a change to the other.
   // ---- model pass (A7 eval): the pixels' spline values -------------------------------------
   // hands over: F ([npix] m/e, [npix] D/e)
   const rvs_point_arm &S = T.pt;
@@ -252,7 +125,7 @@ __global__ void __launch_bounds__(OG_NT)
     return p;
   };
   // (a loop of its own, which holds no accumulators, as in objective_kernel)
-  for (int k = tid; k < npix; k += OG_NT) {
+  for (int k = tid; k < npix; k += OP_NT) {
     const int pos = pix_pos(k);
     const double dl = AG.lam[k] * f - S.knots[pos];
     const double tv = obj_piece_value(piece(pos), dl);
@@ -265,7 +138,7 @@ __global__ void __launch_bounds__(OG_NT)
     double vals[NV];   // [NTR] packed lower triangle, then [P] right-hand sides
 #pragma unroll
     for (int i = 0; i < NV; i++) vals[i] = 0;
-    for (int k = tid; k < npix; k += OG_NT) {
+    for (int k = tid; k < npix; k += OP_NT) {
       const double te = F[k], dk = F[npix + k];   // (written by this same thread)
       // (the rows ST = phi m/e themselves: one register row where the value kernel
       // keeps phi and phi (m/e)^2 -- this kernel has the adjoint's state beside it)
@@ -292,7 +165,7 @@ __global__ void __launch_bounds__(OG_NT)
   if (tid < NV) {   // the waves' totals in wave order, one sum per thread
     double v = sh.red[0][tid];
 #pragma unroll
-    for (int q = 1; q < OG_NW; q++) v += sh.red[q][tid];
+    for (int q = 1; q < OP_NW; q++) v += sh.red[q][tid];
     sh.red[0][tid] = v;
   }
   __syncthreads();
@@ -354,7 +227,7 @@ __global__ void __launch_bounds__(OG_NT)
   const double bb = vel[j] / RVS_C_KMS;
   const double dfdv = -f / (RVS_C_KMS * (1.0 - bb * bb));
   double rr = 0, gvel = 0;
-  for (int k = tid; k < npix; k += OG_NT) {
+  for (int k = tid; k < npix; k += OP_NT) {
     const double te = F[k], dk = F[npix + k];
     const double ie = sig[k].x;
     const double *pr = AG.polysT + (int64_t)k * P;
@@ -386,7 +259,7 @@ __global__ void __launch_bounds__(OG_NT)
   // so the pixels of interval n are [first[n], first[n + 1])); every entry is written
   // once, by the first pixel at or behind it
   int32_t *first = reinterpret_cast<int32_t *>(F + npix);
-  for (int k = tid; k <= npix; k += OG_NT) {
+  for (int k = tid; k <= npix; k += OP_NT) {
     const int lo = (k == 0) ? 0 : pix_pos(k - 1) + 1;
     const int hi = (k == npix) ? N - 1 : pix_pos(k);
     for (int n = lo; n <= hi; n++) first[n] = k;
@@ -397,7 +270,7 @@ __global__ void __launch_bounds__(OG_NT)
   // (clamped: were the pixels not ascending, entries of the table would be unwritten)
   auto first_at = [&](int n) { return min(max(first[n], 0), npix); };
   double *Yb = Y, *Zb = Z;
-  for (int n = tid; n < N; n += OG_NT) {
+  for (int n = tid; n < N; n += OP_NT) {
     double yb = 0, zb = 0;
     if (n >= 1) {
       const double kn = S.knots[n - 1], h = hh[n - 1], hinv = ih[n - 1];
@@ -425,13 +298,13 @@ __global__ void __launch_bounds__(OG_NT)
   __syncthreads();
 
   // ---- spline, transposed: M u = zbar (M is symmetric: the sweeps of the value) ----
-  tri_solve([&](int u, double, double) { return Zb[u]; }, Zb);
+  pt.tri_solve([&](int u, double, double) { return Zb[u]; }, Zb);
   __syncthreads();
   // sl_j = 6 (u_{j-1} - u_j), u_j at knot j + 1, 0 beyond both ends;
   // ybar_{j+1} += sl_j / h_j, ybar_j -= sl_j / h_j
   {
     auto U = [&](int i) { return (i >= 0 && i < m) ? Zb[i] : 0.0; };
-    for (int n = tid; n < N; n += OG_NT) {
+    for (int n = tid; n < N; n += OP_NT) {
       double add = 0;
       if (n >= 1) add = 6 * (U(n - 2) - U(n - 1)) * ih[n - 1];
       if (n <= N - 2) add -= 6 * (U(n - 1) - U(n)) * ih[n];
@@ -445,61 +318,61 @@ __global__ void __launch_bounds__(OG_NT)
   double *tbar = Yb;
   const double *dwt = nullptr;
   if (!copy) {
-    obj_build_taps<OG_NT, false>(kmax, R, eps_ld, T.lnstep, Zb, F, vs_grad ? F + kmax + 1 : nullptr,
+    obj_build_taps<OP_NT, false>(kmax, R, eps_ld, T.lnstep, Zb, F, vs_grad ? F + kmax + 1 : nullptr,
                           sh.red8);
-    for (int i = tid; i < N; i += OG_NT) Zb[i] = fir_at(Yb, F, i);
+    for (int i = tid; i < N; i += OP_NT) Zb[i] = pt.fir_at(Yb, F, i);
     tbar = Zb;
     dwt = F + kmax + 1;
     __syncthreads();
   }
 
   // ---- contraction at the knots -----------------------------------------------------
-  double gp[OG_MAXDIM], gvs = 0;
+  double gp[OP_MAXDIM], gvs = 0;
 #pragma unroll
-  for (int d = 0; d < OG_MAXDIM; d++) gp[d] = 0;
-  for (int n = tid; n < N; n += OG_NT) {
+  for (int d = 0; d < OP_MAXDIM; d++) gp[d] = 0;
+  for (int n = tid; n < N; n += OP_NT) {
     double tn;
     if (mode == 0) {
-      double a = 0, g[OG_MAXDIM];
+      double a = 0, g[OP_MAXDIM];
 #pragma unroll
-      for (int d = 0; d < OG_MAXDIM; d++) g[d] = 0;
+      for (int d = 0; d < OP_MAXDIM; d++) g[d] = 0;
       for (int v = 0; v < nv; v++) {
         const double Lv = (double)T.dats[PL.id[v] * N + n];
         a = fma(PL.w[v], Lv, a);
 #pragma unroll
-        for (int d = 0; d < OG_MAXDIM; d++)
+        for (int d = 0; d < OP_MAXDIM; d++)
           if (d < nd) g[d] = fma(sh.dw[d * nv + v], Lv, g[d]);
       }
       tn = T.exp_flag ? exp(a) : a;
       const double tb = tbar[n];
 #pragma unroll
-      for (int d = 0; d < OG_MAXDIM; d++)
+      for (int d = 0; d < OP_MAXDIM; d++)
         if (d < nd) gp[d] = fma(tb, T.exp_flag ? tn * g[d] : g[d], gp[d]);
     } else {
       tn = T.exp_flag ? (double)np_expf(nrow[n]) : (double)nrow[n];
     }
-    if (vs_grad) gvs = fma(fir_at(Yb, dwt, n), tn, gvs);
+    if (vs_grad) gvs = fma(pt.fir_at(Yb, dwt, n), tn, gvs);
   }
 
   // ---- tail: the block's sums (lanes by butterfly, waves in order), value and status --------
   {
-    double fin[OG_MAXK + 1];
+    double fin[OP_MAXK + 1];
     fin[0] = rr;
     fin[1] = gvel;
 #pragma unroll
-    for (int d = 0; d < OG_MAXDIM; d++) fin[2 + d] = gp[d];
-    fin[2 + OG_MAXDIM] = gvs;
+    for (int d = 0; d < OP_MAXDIM; d++) fin[2 + d] = gp[d];
+    fin[2 + OP_MAXDIM] = gvs;
 #pragma unroll
-    for (int i = 0; i <= OG_MAXK; i++) {
+    for (int i = 0; i <= OP_MAXK; i++) {
       const double v = wave_sum(fin[i]);
       if (lane == 0) sh.red[w][i] = v;
     }
   }
   __syncthreads();
-  if (tid <= OG_MAXK) {
+  if (tid <= OP_MAXK) {
     double v = sh.red[0][tid];
 #pragma unroll
-    for (int q = 1; q < OG_NW; q++) v += sh.red[q][tid];
+    for (int q = 1; q < OP_NW; q++) v += sh.red[q][tid];
     sh.red[0][tid] = v;
   }
   __syncthreads();
@@ -515,75 +388,22 @@ __global__ void __launch_bounds__(OG_NT)
   if (tid < K) {
     // columns: vel, the parameters in library order (exactly 0 in the nearest-neighbour
     // modes), vsini (exactly 0 in the FIR's copy branches)
-    const int src = (tid == 0) ? 1 : (tid <= nd ? 1 + tid : 2 + OG_MAXDIM);
+    const int src = (tid == 0) ? 1 : (tid <= nd ? 1 + tid : 2 + OP_MAXDIM);
     armgrad[o * K + tid] = (chi == chi) ? sh.red[0][src] : __builtin_nan("");
   }
 }
 
-// arms summed in order; the penalties of A11 (spec_fit.py:888-896) on the value only
-__global__ void objective_grad_sum_kernel(int narm, int J, int K, double badchi,
-                                          double4 bconst,
-                                          const double *__restrict__ pen_scale,
-                                          const int32_t *__restrict__ job_spec,
-                                          const double *__restrict__ armchi,
-                                          const double *__restrict__ armgrad,
-                                          const int32_t *__restrict__ armst,
-                                          const double *__restrict__ armout,
-                                          double *__restrict__ out,
-                                          double *__restrict__ grad,
-                                          int32_t *__restrict__ status) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= J) return;
-  if (pen_scale) badchi *= pen_scale[job_spec ? job_spec[j] : j];
-  const double bc[RVS_MAX_ARMS] = {bconst.x, bconst.y, bconst.z, bconst.w};
-  double tot = 0;
-  double g[OG_MAXK];
-#pragma unroll
-  for (int i = 0; i < OG_MAXK; i++) g[i] = 0;
-  int st = 0;
-#pragma unroll
-  for (int ia = 0; ia < RVS_MAX_ARMS; ia++) {
-    if (ia >= narm) break;
-    const int64_t o = (int64_t)ia * J + j;
-    const double ov = armout[o];
-    if (!(fabs(ov) <= 1.79e308)) {
-      tot += 1000.0 * badchi;
-      continue;
-    }
-    tot += armchi[o] + bc[ia] + ov * badchi;
-    st |= armst[o];
-#pragma unroll
-    for (int i = 0; i < OG_MAXK; i++)
-      if (i < K) g[i] += armgrad[o * K + i];
-  }
-  out[j] = tot;
-#pragma unroll
-  for (int i = 0; i < OG_MAXK; i++)
-    if (i < K) grad[(int64_t)j * K + i] = g[i];
-  if (st) atomicOr(&status[j], st);
-}
-
 }  // namespace
 
-// What the kernel covers, in host arithmetic only: npoly 1..10 (beyond, the value
-// kernel's wave totals live in the template buffer), grids of up to 4 dimensions, a
-// template grid whose three buffers fit LDS beside the kernel's static part, and the
-// pixels twice in one buffer (the sigma-scaled pair; then the pixel adjoint with the
-// first-pixel table of ntp int32 behind it: npix + ntp / 2 <= ntp).
+// (what the kernel covers: op_point_ok)
 extern "C" int rvs_objective_grad_ok(int npoly, int npix, int ntp, int ndim,
                                      int vsini_grad) {
-  if (npoly < 1 || npoly > OG_MAXP || npix < 1 || ntp < 32 ||
-      ntp > RVS_OBJ_FT_MAX_NTP)
-    return 0;
-  if (ndim < 1 || ndim > OG_MAXDIM || vsini_grad < 0 || vsini_grad > 1) return 0;
-  if (2 * (int64_t)npix > ntp) return 0;
-  if (3 * (int64_t)ntp * (int64_t)sizeof(double) + OG_STATIC_MAX > OG_LDS_MAX) return 0;
-  return 1;
+  return op_point_ok(npoly, npix, ntp, ndim, vsini_grad);
 }
 
 // per (arm, job): chi^2, outside, 1 + ntan gradient entries, status (padded to 8 bytes)
 extern "C" int64_t rvs_objective_grad_work_size(int J, int narm, int ntan) {
-  if (J < 1 || narm < 1 || narm > RVS_MAX_ARMS || ntan < 1 || ntan > OG_MAXDIM + 1)
+  if (J < 1 || narm < 1 || narm > RVS_MAX_ARMS || ntan < 1 || ntan > OP_MAXDIM + 1)
     return 0;
   return (int64_t)narm * J * (int64_t)((4 + ntan) * sizeof(double));
 }
@@ -594,62 +414,25 @@ extern "C" int rvs_objective_grad(const rvs_objective_arm *arms, int narm, int n
                                   double badchi, const double *basis_const,
                                   void *scratch, double *out, double *grad,
                                   int32_t *status, void *stream) {
-  if (J < 1 || narm < 1 || narm > RVS_MAX_ARMS || !arms || !params || !vel ||
-      !scratch || !out || !grad || !status || npoly < 1 || npoly > OG_MAXP ||
-      ntan < 1 || ntan > OG_MAXDIM + 1)
+  OpCall c;
+  if (J < 1 || !params || !vel || !scratch || !out || !grad || !status ||
+      !op_check_arms(arms, narm, npoly, ntan, vsini, basis_const, c))
     return RVS_E_ARG;
-  static_assert(RVS_MAX_ARMS == 4, "basis constants travel as a double4");
-  const int ndim = arms[0].ndim;
-  // ntan = ndim: vel and the parameters; ndim + 1: vsini fitted, its column last
-  const int vsini_grad = (ntan == ndim + 1) ? 1 : 0;
-  if (ntan != ndim + vsini_grad || (vsini_grad && !vsini)) return RVS_E_ARG;
-  ObjArms A;
-  A.n = narm;
-  double bc[RVS_MAX_ARMS] = {0, 0, 0, 0};
-  size_t shm = 0;
-  for (int i = 0; i < narm; i++) {
-    const rvs_objective_arm &a = arms[i];
-    if (a.ndim != ndim || a.pt.fast_interp || a.pt.taps || a.pt.G > 1 || !a.factors ||
-        !a.dats || !a.idgrid || !a.uvecs || !a.vecs_s || a.pt.ntp != a.ntp ||
-        !rvs_objective_grad_ok(npoly, a.pt.npix, a.ntp, ndim, vsini_grad))
-      return RVS_E_ARG;
-    A.a[i] = a;
-    if (basis_const) bc[i] = basis_const[i];
-    shm = max(shm, (size_t)3 * a.ntp * sizeof(double));
-  }
-  for (int i = narm; i < RVS_MAX_ARMS; i++) A.a[i] = arms[0];
   hipStream_t st = rvs_stream(stream);
   const int K = 1 + ntan;
   double *armchi = (double *)scratch;
   double *armout = armchi + (int64_t)narm * J;
   double *armgrad = armout + (int64_t)narm * J;
   int32_t *armst = (int32_t *)(armgrad + (int64_t)narm * J * K);
-  dim3 grid(J, narm);
-#define RVS_CASE(PP)                                                              \
-  case PP: {                                                                      \
-    static bool attr_set = false;                                                 \
-    if (!attr_set) {                                                              \
-      (void)hipFuncSetAttribute((const void *)objective_grad_kernel<PP>,          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                OG_LDS_MAX - (int)sizeof(OgShared<PP>));          \
-      (void)hipGetLastError();                                                    \
-      attr_set = true;                                                            \
-    }                                                                             \
-    hipLaunchKernelGGL(objective_grad_kernel<PP>, grid, dim3(OG_NT), shm, st, A,  \
-                       params, vsini, vsini_grad, job_spec, J, vel, 0.6, armchi,  \
-                       armgrad, armst, armout);                                   \
-  } break;
-  switch (npoly) {
-    RVS_CASE(1) RVS_CASE(2) RVS_CASE(3) RVS_CASE(4) RVS_CASE(5)
-    RVS_CASE(6) RVS_CASE(7) RVS_CASE(8) RVS_CASE(9) RVS_CASE(10)
-    default:
-      return RVS_E_ARG;
-  }
-#undef RVS_CASE
-  hipLaunchKernelGGL(objective_grad_sum_kernel, dim3((J + 255) / 256), dim3(256), 0, st,
-                     narm, J, K, badchi, make_double4(bc[0], bc[1], bc[2], bc[3]),
-                     arms[0].pt.pen_scale, job_spec, armchi, armgrad, armst, armout, out,
-                     grad, status);
+  op_for_npoly(npoly, [&](auto p) {
+    constexpr int PP = decltype(p)::value;
+    op_launch<objective_grad_kernel<PP>, (int)sizeof(OgShared<PP>)>(
+        dim3(J, narm), c.shm, st, c.A, params, vsini, c.vsini_grad, job_spec, J, vel, 0.6,
+        armchi, armgrad, armst, armout);
+  });
+  hipLaunchKernelGGL(objective_point_sum_kernel, dim3((J + 255) / 256), dim3(256), 0, st,
+                     narm, J, 0, K, badchi, c.bc, arms[0].pt.pen_scale, job_spec, armchi,
+                     armgrad, nullptr, armst, armout, out, grad, nullptr, status);
   RVS_LAUNCH_CHECK();
   return 0;
 }

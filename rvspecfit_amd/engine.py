@@ -1382,7 +1382,7 @@ def objective_from_template(batch, libs, templs, outsides, vsini, vel, npoly=5,
                            outsides=outsides)
 
 
-GRAD_FUSED_MAXP = 10     # OG_MAXP of csrc/objective_grad.hip
+GRAD_FUSED_MAXP = 10     # OP_MAXP of csrc/objective_point_dev.h
 GRAD_FUSED_MAXDIM = 4
 
 

@@ -27,7 +27,11 @@ Largest error per group seen on an MI355X on the first run (the whole module: 68
     dimensions      1.9e-15 / 1.3e-13       there; the other eleven cases <= 3.6e-12)
     linear knots    1.2e-15 / 1.3e-13     mixed arms      2.7e-15 / 1.2e-12
 Against the chain: Fisher 8.7e-16, gradient 2.2e-13; against rvs_objective_grad: gradient
-4.1e-12, the value's bits equal on the golden jobs.  None of these set a bound."""
+4.1e-12.  None of these set a bound.  The value is held to the BITS of
+rvs_objective_grad: the two kernels share the value phases up to the spline construct and
+state the passes over the pixels each in the same words; this is the test
+that a change to one of the two statements meets.  (The build before that section already
+gave equal bits on every case here.)"""
 import ctypes
 
 import numpy as np
@@ -179,12 +183,9 @@ def test_agreement_with_the_chain_and_the_gradient_kernel(setup, olibs, npoly, v
     gchi, ggrad, gst = _grad(su, npoly, vsini_grad, vs)
     assert torch.equal(st, gst), (st, gst)
     assert torch.equal(st, cst), (st, cst)
-    same_bits = torch.equal(chi, gchi)
-    print('npoly %d vsini %d value bits equal to rvs_objective_grad: %s'
-          % (npoly, vsini_grad, same_bits))
-    for j in range(J):
-        a, b = chi[j].item(), gchi[j].item()
-        assert abs(a - b) <= 1e-11 * max(abs(b), 1e3), (j, a, b)
+    # the same value phases in both kernels: the bits
+    assert torch.equal(torch.isnan(chi), torch.isnan(gchi))
+    assert torch.equal(torch.nan_to_num(chi), torch.nan_to_num(gchi)), (chi, gchi)
     grad, F, cgrad, cF = (x.cpu().numpy() for x in (grad, F, cgrad, cF))
     ggrad = ggrad.cpu().numpy()
     wf = wg = wgg = 0.0
@@ -343,7 +344,8 @@ def _device(c):
 
 def _check_shape(name):
     """an in-cell case of tests/objective_grad_shapes.py: status 0, the value within 1e-7
-    |truth|, g and F within the bound; status and value those of rvs_objective_grad"""
+    |truth|, g and F within the bound; status and value (bit for bit) those of
+    rvs_objective_grad"""
     from rvspecfit_amd import engine
     c = shapes.case(name)
     d = _device(c)
@@ -354,6 +356,9 @@ def _check_shape(name):
     K = 1 + c.ndim + (1 if c.vsini_grad else 0)
     assert grad.shape == (len(c.jobs), K) and F.shape == (len(c.jobs), K, K)
     assert torch.equal(st, gst) and not st.any()
+    # the same value phases in both kernels: the bits
+    assert torch.equal(torch.isnan(chi), torch.isnan(gchi))
+    assert torch.equal(torch.nan_to_num(chi), torch.nan_to_num(gchi)), (name, chi, gchi)
     assert torch.equal(F, F.transpose(-1, -2))
     grad, F = grad.cpu().numpy(), F.cpu().numpy()
     wf = wg = 0.0
@@ -365,8 +370,6 @@ def _check_shape(name):
                                                    npoly=c.npoly, rbf=c.rbf,
                                                    vsini_grad=c.vsini_grad)
         assert abs(chi[j].item() - val) <= 1e-7 * abs(val), (name, j)
-        a, b = chi[j].item(), gchi[j].item()
-        assert abs(a - b) <= 1e-11 * max(abs(b), 1e3), (name, j, a, b)
         wf = max(wf, float(fwd.rel_fisher(F[j], Ft, G).max()))
         wg = max(wg, float(shapes.rel_err(grad[j], g).max()))
     w = _note(c.group, wf, wg)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Outputs of the objective kernels' five entry points on seeded cases, for a bit
-comparison of two builds (DESIGN 4.22):
+"""Outputs of the objective kernels' six entry points on seeded cases, for a bit
+comparison of two builds (DESIGN 4.22, 4.24):
 
     python tools/perf/objective_bits.py path/to/librvsgpu.so out.npz     (once per build,
                                                                   a process of its own)
@@ -8,9 +8,14 @@ comparison of two builds:
 
 rvs_objective_fused, _fused_n, _from_template, _from_template_n: value and status per job
 and the per-arm value / outside / status rows of the work buffer; rvs_objective_grad:
-value, gradient, status.  The cases come from the builders of the tests
-(tests/objective_grad_shapes.py, the goldens of tests/conftest.py) at the smallest shapes
-that reach each branch of csrc/objective.hip and csrc/objective_grad.hip."""
+value, gradient, status (`grad%d`, by vsini_grad); rvs_objective_fisher wherever
+engine.can_fuse_objective_fisher holds: value, gradient, Fisher matrix, status, once with
+the default work buffer (`fisher%d`) and once with the one-job buffer, one launch per job
+(`fisher%d/onejob`; `fisher%d/forms_agree`: the two gave the same bits).  The cases come
+from the builders of the tests (tests/objective_grad_shapes.py, the jobs of
+tests/chisq_grad_truth.py, the goldens of tests/conftest.py) at the smallest shapes that
+reach each branch of csrc/objective.hip, csrc/objective_grad.hip and
+csrc/objective_fisher.hip."""
 import ctypes
 import json
 import os
@@ -94,9 +99,30 @@ def value_forms(key, batch, libs, npoly, vel, par, vs, idx, rbf=True):
     OUT[key + '/forms_agree'] = np.array(same)
 
 
+def point_kernels(key, batch, libs, npoly, rbf, par, vs, vel, idx, vg):
+    """rvs_objective_grad and, with both work buffers, rvs_objective_fisher, where each
+    admits the case"""
+    from rvspecfit_amd import _lib, engine
+    args = (batch, libs, par, vs, vel, npoly, rbf, idx, vg)
+    if engine.can_fuse_objective_grad(batch, libs, npoly=npoly, vsini_grad=vg):
+        put('%s/grad%d' % (key, vg), *engine.objective_grad_fused(*args))
+    if engine.can_fuse_objective_fisher(batch, libs, npoly=npoly, vsini_grad=vg):
+        ntan = libs[batch.arms[0].name].ndim + int(vg)
+        one = _lib.lib().rvs_objective_fisher_work_size(
+            1, len(batch.arms), ntan, max(a.npix for a in batch.arms))
+        full = engine.objective_fisher_fused(*args)
+        single = engine.objective_fisher_fused(*args, work_bytes=one)
+        put('%s/fisher%d' % (key, vg), *full)
+        put('%s/fisher%d/onejob' % (key, vg), *single)
+        OUT['%s/fisher%d/forms_agree' % (key, vg)] = np.array(all(
+            np.array_equal(a.cpu().numpy(), b.cpu().numpy(), equal_nan=True)
+            for a, b in zip(full, single)))
+
+
 def shapes_cases():
-    """every case of tests/objective_grad_shapes.py through rvs_objective_grad and, in
-    all launch forms, rvs_objective_fused; more value-kernel shapes on its libraries"""
+    """every case of tests/objective_grad_shapes.py through rvs_objective_grad,
+    rvs_objective_fisher and, in all launch forms, rvs_objective_fused; more value-kernel
+    shapes on its libraries"""
     import torch
     import objective_grad_shapes as shapes
     from rvspecfit_amd import engine, spec_fit, spec_inter
@@ -142,11 +168,8 @@ def shapes_cases():
             d['vs'] = torch.tensor([j[3] or 0.0 for j in c.jobs], **f64)
         key = 'shapes/' + c.name
         for vg in ((False, True) if d['vs'] is not None else (False, )):
-            if engine.can_fuse_objective_grad(d['batch'], d['libs'], npoly=c.npoly,
-                                              vsini_grad=vg):
-                put('%s/grad%d' % (key, vg), *engine.objective_grad_fused(
-                    d['batch'], d['libs'], d['par'], d['vs'], d['vel'], c.npoly, c.rbf,
-                    d['idx'], vg))
+            point_kernels(key, d['batch'], d['libs'], c.npoly, c.rbf, d['par'], d['vs'],
+                          d['vel'], d['idx'], vg)
         if engine.can_fuse_objective(d['batch'], d['libs'], None, npoly=c.npoly):
             value_forms(key, d['batch'], d['libs'], c.npoly, d['vel'], d['par'], d['vs'],
                         d['idx'], c.rbf)
@@ -165,6 +188,38 @@ def _jobs(J, seed, S=1, rot=True):
     vs = torch.as_tensor(rng.uniform(0, 200, J)).to('cuda') if rot else None
     return (torch.as_tensor(rng.randint(0, S, J), dtype=torch.int32).to('cuda'),
             torch.as_tensor(vel).to('cuda'), torch.as_tensor(par).to('cuda'), vs)
+
+
+def golden_point_jobs():
+    """the jobs of tests/chisq_grad_truth.py on the golden arms (in the cell, outside the
+    grid, a non-finite parameter), one and two arms, without rotation, at the jobs' own
+    vsini and at rotational kernels of half width 2 .. 11 with the vsini column"""
+    import torch
+    import chisq_grad_truth as truth
+    from conftest import GOLD, GOLD_CONFIG, gold_lib_dict
+    from rvspecfit_amd import spec_fit, spec_inter
+    from rvspecfit_amd.engine import SpecBatch
+    from rvspecfit_amd.library import TemplateLibrary
+    for n in ('gold_b', 'gold_r'):
+        spec_inter.register_library(TemplateLibrary(n, gold_lib_dict(n)), 'golden://')
+    cases = dict(np.load(os.path.join(GOLD, 'cases.npz')))
+    for narm in (1, 2):
+        batch = SpecBatch.from_specdata(
+            [sd[:narm] for sd in truth.spectra(cases, spec_fit.SpecData)])
+        libs = spec_inter.get_libs(batch.names, dict(GOLD_CONFIG, template_lib='golden://'))
+        f64 = dict(dtype=torch.float64, device=batch.device)
+        idx = torch.tensor([j[0] for j in truth.JOBS], dtype=torch.int32,
+                           device=batch.device)
+        vel = torch.tensor([j[1] for j in truth.JOBS], **f64)
+        par = torch.tensor([j[2] for j in truth.JOBS], **f64)
+        own = torch.tensor([j[3] or 0.0 for j in truth.JOBS], **f64)
+        wide = torch.tensor([r * truth.C_KMS * libs['gold_b'].lnstep for r in
+                             (0.4, 1.6, 3 + 5e-4, 9.3, 0.0, 0.7, 2 - 4e-4)], **f64)
+        for npoly in (1, 5, 10):
+            for tag, vs, vg in (('plain', None, False), ('own', own, False),
+                                ('own', own, True), ('wide', wide, True)):
+                point_kernels('point/arms%d/p%d/%s' % (narm, npoly, tag), batch, libs,
+                              npoly, True, par, vs, vel, idx, vg)
 
 
 def golden_cases():
@@ -313,7 +368,7 @@ def main():
     _lib.LIB_PATH = os.path.abspath(sys.argv[1])
     _lib.require_gpu()
     rc = 0
-    for part in (shapes_cases, golden_cases, five_dimensions):
+    for part in (shapes_cases, golden_point_jobs, golden_cases, five_dimensions):
         try:
             with np.errstate(all='ignore'):
                 part()

@@ -128,7 +128,10 @@ extern "C" {
  *      "cg_tab"; and rvs_objective_fisher_ok / rvs_objective_fisher_work_size /
  *      rvs_objective_fisher, value, gradient and Fisher matrix in one forward-mode
  *      kernel per (job, arm), with rvs_lm_run_fused, the Levenberg-Marquardt rounds on
- *      it) */
+ *      it; and rvs_objective_grad_from_template with its _ok and _work_size,
+ *      rvs_objective_grad_join, rvs_template_nn_vjp and rvs_template_nn_vjp_work_size:
+ *      value and gradient on MLP libraries by one adjoint row back through the net,
+ *      with rvs_bfgs_run_grad_fused_nn, the BFGS rounds on it) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -879,6 +882,42 @@ int rvs_objective_grad(const rvs_objective_arm *arms, int narm, int npoly, int n
                        double badchi, const double *basis_const, void *scratch,
                        double *out, double *grad, int32_t *status, void *stream);
 
+/* The from-template form of rvs_objective_grad, for an evaluator that is no grid gather
+ * (the MLP of rvs_template_nn): the unbroadened template of (job, arm) is row j of
+ * templ[a] [J, ntp] float64 with its outside flag outside[a][j], taken -- MAX_VAL guard
+ * included -- as rvs_objective_from_template takes them.  Behind the row everything is the
+ * kernel of rvs_objective_grad; in place of its contraction at the knots the adjoint row
+ *   tbar[a][j, n] = d chi^2_a / d templ[a][j, n]                   [J, ntp] float64
+ * is written out (zeros for an arm that is skipped: a non-finite outside flag), the row
+ * the evaluator's own reverse pass (rvs_template_nn_vjp) contracts with its Jacobian.
+ * templ, outside and tbar are HOST arrays of narm device pointers.
+ *   grad [J, 1 + vsini_grad]  d/d(vel[, vsini]); value, status and the rules for skipped
+ *                             arms, copy branches and a failed factorisation as for
+ *                             rvs_objective_grad
+ *   scratch   rvs_objective_grad_from_template_work_size(J, narm, vsini_grad) bytes
+ * rvs_objective_grad_from_template_ok (host arithmetic only): rvs_objective_grad_ok's rule
+ * without the ndim bound of the cell record, which this form does not read.  RVS_E_ARG,
+ * before any launch: what rvs_objective_grad refuses of an arm's geometry and options,
+ * vsini_grad without vsini, a NULL array or row pointer.
+ * rvs_objective_grad_join assembles grad [J, 1 + ndim + vsini_grad] = (vel, parameters,
+ * vsini) from grad_vv, the [J, 1 + vsini_grad] gradient of that call, and gparams [narm]
+ * (host array of device pointers to [J, ndim], the arms' rvs_template_nn_vjp results),
+ * summed in arm order: exactly nothing from an arm whose outside flag -- read from that
+ * call's scratch -- is not finite, NaN where out[j] is; the penalties are on the value
+ * only. */
+int rvs_objective_grad_from_template_ok(int npoly, int npix, int ntp, int vsini_grad);
+int64_t rvs_objective_grad_from_template_work_size(int J, int narm, int vsini_grad);
+int rvs_objective_grad_from_template(const rvs_objective_arm *arms, int narm, int npoly,
+                                     int vsini_grad, const double *const *templ,
+                                     const double *const *outside, const double *vsini,
+                                     const int32_t *job_spec, int J, const double *vel,
+                                     double badchi, const double *basis_const,
+                                     void *scratch, double *const *tbar, double *out,
+                                     double *grad, int32_t *status, void *stream);
+int rvs_objective_grad_join(int narm, int J, int ndim, int vsini_grad, const void *scratch,
+                            const double *const *gparams, const double *out,
+                            const double *grad_vv, double *grad, void *stream);
+
 /* ------------------------------------------------------------------------
  * The objective of rvs_objective_grad WITH the Fisher matrix of the marginalised fit
  * (rvs_chisq_point_fisher's F = J^T (1 - U U^T) J), as one kernel per (job, arm), in
@@ -1237,6 +1276,36 @@ int rvs_template_nn_grad(const double *params, int B, int ndim, uint32_t log_mas
                          const int32_t *dims, float *act0, float *act1,
                          double *templ /* [B, 1 + ndim, ntp] */, void *stream);
 
+/* The reverse pass of the same network: ONE adjoint row per job back through the net,
+ * whatever ndim is (rvs_template_nn_grad sends ndim rows forward),
+ *   gparams[j, k] = sum_n tbar[j, n] d templ[j, n] / d p_k        [B, ndim] float64
+ * for templ [B, ntp], the value rows rvs_template_nn / rvs_template_nn_arms wrote for
+ * `params`, and tbar [B, ntp], the adjoint rows d chi^2 / d templ that
+ * rvs_objective_grad_from_template writes.  Network arguments as rvs_template_nn.
+ *   Last.    ybar_n = tbar_n templ_n in float64, exactly 0 where templ_n is one of the
+ *            clip's own two values exp(+-300) (the clip is flat there).  Each row is
+ *            divided by the power of two 2^e, e = the exponent of max_n |ybar_n|, before
+ *            the float32 cast, and 2^e is multiplied back in float64: exact both ways, so
+ *            the result scales exactly with tbar.  abar = ybar W_L on the float32-input
+ *            MFMA, ntp cut into runs of 256 pixels, one partial sum per run in `work`,
+ *            added in run order: no float atomics, and the partition does not depend on B.
+ *   Hidden.  The forward pass of the job's row is computed again, every layer's z kept in
+ *            LDS; delta_l = abar_l sigma (1 + z (1 - sigma)), abar_{l-1} = delta_l W_l.
+ *   Input.   gparams_k = xbar_k s_k / S_k in float64, s_k as for rvs_template_nn_grad; NaN
+ *            in all components of a job whose mapped parameters are not all finite.
+ * Float32 arithmetic: exact to float32 rounding of the sum over the pixels.  Two calls
+ * give the same bits; a job has the same bits alone and inside any batch.
+ *   work     rvs_template_nn_vjp_work_size(B, nlayer, dims) bytes (0 out of scope)
+ * Scope (RVS_E_ARG beyond, before any launch): that of rvs_template_nn_grad -- 3 <=
+ * nlayer <= 7, hidden widths <= 256 and multiples of 32 from the second layer's input on
+ * (the last layer's input excepted), ndim <= 6. */
+int64_t rvs_template_nn_vjp_work_size(int B, int nlayer, const int32_t *dims);
+int rvs_template_nn_vjp(const double *params, int B, int ndim, uint32_t log_mask,
+                        const double *M, const double *S, int nlayer,
+                        const float *const *W, const float *const *b,
+                        const int32_t *dims, const double *templ, const double *tbar,
+                        void *work, double *gparams, void *stream);
+
 /* Outside flag of an NN library; replaces OutsideInterpolator.__call__
  * (nn/RVSInterpolator.py:63-71) as SpecInterpolator.outsideFlag calls it on the
  * Mapper-transformed point (spec_inter.py:257-272, nn/NNInterpolator.py:159-171):
@@ -1536,6 +1605,23 @@ int rvs_bfgs_run_grad_fused(const rvs_bfgs_state *b, const rvs_nm_objective *o,
                             const rvs_grad_chain *g, const rvs_objective_arm *garms,
                             const double *basis_const, void *gwork, int sync_every,
                             int64_t *stats, void *stream);
+
+/* rvs_bfgs_run_grad_fused on MLP libraries: per chunk rvs_proc_map, the rows' templates
+ * and outside flags from the networks of o->nn (rvs_template_nn_arms_n),
+ * rvs_objective_grad_from_template, rvs_template_nn_vjp per arm, rvs_objective_grad_join,
+ * rvs_proc_finish_grad.  garms [narm] (HOST) as for rvs_objective_grad_from_template,
+ * gwork: rvs_objective_grad_from_template_work_size(g->cap, narm, vsini fitted) bytes.
+ * The adjoint rows and the reverse pass's work are the caller's, HOST arrays of narm
+ * device pointers: tbar [cap, ntp], vjp_work (rvs_template_nn_vjp_work_size(g->cap, ...)
+ * bytes), gparams [cap, ndim]; grad_vv [cap, 1 + (vsini fitted)].  From `g` what
+ * rvs_bfgs_run_grad_fused reads; no struct changed.  ndim <= 6.  RVS_E_ARG also for what
+ * rvs_objective_grad_from_template and rvs_template_nn_vjp refuse. */
+int rvs_bfgs_run_grad_fused_nn(const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                               const rvs_grad_chain *g, const rvs_objective_arm *garms,
+                               const double *basis_const, void *gwork,
+                               double *const *tbar, void *const *vjp_work,
+                               double *const *gparams, double *grad_vv, int sync_every,
+                               int64_t *stats, void *stream);
 
 /* ------------------------------------------------------------------------
  * The second minimiser as Levenberg-Marquardt on the Fisher matrix

@@ -113,7 +113,8 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     optimizer.GRAD_CHAIN_BUDGET holds); the result then carries njev.  Libraries
     and options the gradient does not cover raise ValueError.  A chain built with
     fused=True runs rvs_bfgs_run_grad_fused: the rows' value and gradient from one
-    kernel per (row, arm)."""
+    kernel per (row, arm) -- on MLP libraries rvs_bfgs_run_grad_fused_nn, with the
+    networks' reverse pass behind it."""
     import ctypes
     import torch
     from . import _lib
@@ -147,7 +148,17 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     b.S, b.n, b.cap, b.maxiter = S, n, int(pobj.cap), int(maxiter or 0)
     o = pobj.native_desc()
     st3 = (ctypes.c_int64 * 3)()
-    if jac and getattr(chain, 'fused', False):
+    if jac and getattr(chain, 'fused', False) and getattr(chain, 'fused_nn', False):
+        # ... on MLP libraries: the adjoint rows back through the networks
+        g = chain.desc()
+        _lib.check(L.rvs_bfgs_run_grad_fused_nn(
+            ctypes.addressof(b), ctypes.addressof(o), ctypes.addressof(g),
+            ctypes.addressof(chain.garms), ctypes.addressof(chain.bconst),
+            _lib.ptr(chain.gwork), ctypes.cast(chain.tbar_p, ctypes.c_void_p),
+            ctypes.cast(chain.vjp_work_p, ctypes.c_void_p),
+            ctypes.cast(chain.gparams_p, ctypes.c_void_p), _lib.ptr(chain.grad_vv),
+            int(sync_every), st3, _lib.stream()), 'rvs_bfgs_run_grad_fused_nn')
+    elif jac and getattr(chain, 'fused', False):
         # optimizer.GradChain(fused=True): one rvs_objective_grad call per chunk
         g = chain.desc()
         _lib.check(L.rvs_bfgs_run_grad_fused(

@@ -316,3 +316,74 @@ extern "C" int rvs_bfgs_run_grad_fused(const rvs_bfgs_state *b,
                                     o->prior_isig, o->max_vsini, F, o->status, st);
       });
 }
+
+// ... on MLP libraries: the rows' template rows from the networks of o->nn,
+// value, velocity and vsini components and the adjoint rows from one
+// rvs_objective_grad_from_template call per chunk, the parameter components from the
+// networks' reverse pass (rvs_template_nn_vjp per arm), the arms summed by
+// rvs_objective_grad_join.  The adjoint rows and the reverse pass's work belong to the
+// caller: tbar, vjp_work, gparams are HOST arrays of narm device pointers ([cap, ntp],
+// rvs_template_nn_vjp_work_size(cap, ...) bytes, [cap, ndim]), grad_vv [cap, 1 + (vsini
+// fitted)].
+extern "C" int rvs_bfgs_run_grad_fused_nn(
+    const rvs_bfgs_state *b, const rvs_nm_objective *o, const rvs_grad_chain *g,
+    const rvs_objective_arm *garms, const double *basis_const, void *gwork,
+    double *const *tbar, void *const *vjp_work, double *const *gparams, double *grad_vv,
+    int sync_every, int64_t *stats, void *stream) {
+  if (!bfgs_jac_args_ok(b, o, g, sync_every) || !garms || !gwork || !tbar || !vjp_work ||
+      !gparams || !grad_vv || !g->chi || !g->grad || g->cap < 1 || g->narm < 1 ||
+      g->narm > RVS_MAX_ARMS || g->narm != o->narm || g->vsini_mode < 0 ||
+      g->vsini_mode > 2 || o->ndim < 1 || o->ndim > 6 || !o->nn ||
+      g->ntan != o->ndim + (g->vsini_mode == 2 ? 1 : 0) ||
+      (g->vsini_mode == 2) != (o->vsini_col >= 0) ||
+      (g->vsini_mode != 0) != (o->vsini != nullptr) || !o->vel || !o->params ||
+      !o->extra || !o->bad || !o->job_spec || !o->jstatus || !o->status || !o->fixed ||
+      !o->safe)
+    return RVS_E_ARG;
+  const int vg = g->vsini_mode == 2 ? 1 : 0;
+  const double *tp[RVS_MAX_ARMS], *op[RVS_MAX_ARMS];
+  for (int a = 0; a < g->narm; a++) {
+    const rvs_nm_nn_arm &N = o->nn[a];
+    if (!tbar[a] || !vjp_work[a] || !gparams[a] || !N.templ || !N.outside || !N.dims ||
+        N.dims[0] != o->ndim || N.nlayer < 1 || N.dims[N.nlayer] != garms[a].ntp ||
+        garms[a].pt.taps || garms[a].pt.G > 1 || garms[a].pt.fast_interp ||
+        !rvs_objective_grad_from_template_ok(o->npoly, garms[a].pt.npix, garms[a].ntp, vg) ||
+        rvs_template_nn_vjp_work_size(g->cap, N.nlayer, N.dims) <= 0)
+      return RVS_E_ARG;
+    tp[a] = N.templ;
+    op[a] = N.outside;
+  }
+  return bfgs_run_jac(
+      b, g, sync_every, stats, stream,
+      [&](const int32_t *list, const double *X, int J, int ch, double *F,
+          hipStream_t st) {
+        int rc = rvs_proc_map(J, o->n, o->ndim, X, list, o->src, o->vsini_col, o->fixed,
+                              o->vsini_fixed, o->safe, o->prior_mean, o->prior_isig,
+                              o->min_vel, o->max_vel, o->max_vsini, o->job_spec, o->vel,
+                              o->vsini, o->params, o->extra, o->bad, st);
+        if (rc) return rc;
+        if (hipMemsetAsync(o->jstatus, 0, sizeof(int32_t) * J, st) != hipSuccess)
+          return RVS_E_LAUNCH;
+        rc = rvs_template_nn_arms_n(o->params, J, nullptr, o->ndim, o->narm, o->nn, st);
+        if (rc) return rc;
+        rc = rvs_objective_grad_from_template(garms, g->narm, o->npoly, vg, tp, op,
+                                              o->vsini, o->job_spec, J, o->vel, o->badchi,
+                                              basis_const, gwork, tbar, g->chi, grad_vv,
+                                              o->jstatus, st);
+        if (rc) return rc;
+        for (int a = 0; a < g->narm; a++) {
+          const rvs_nm_nn_arm &N = o->nn[a];
+          rc = rvs_template_nn_vjp(o->params, J, o->ndim, N.log_mask, N.M, N.S, N.nlayer,
+                                   N.W, N.b, N.dims, N.templ, tbar[a], vjp_work[a],
+                                   gparams[a], st);
+          if (rc) return rc;
+        }
+        rc = rvs_objective_grad_join(g->narm, J, o->ndim, vg, gwork, gparams, g->chi,
+                                     grad_vv, g->grad, st);
+        if (rc) return rc;
+        return rvs_proc_finish_grad(J, o->n, o->ndim, g->ntan, b->counts, ch, g->chi,
+                                    g->grad, X, o->params, o->extra, o->bad, o->job_spec,
+                                    o->jstatus, o->src, o->vsini_col, o->prior_mean,
+                                    o->prior_isig, o->max_vsini, F, o->status, st);
+      });
+}

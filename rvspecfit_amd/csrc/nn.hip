@@ -1084,6 +1084,17 @@ extern "C" int rvs_template_nn(const double *params, int B, int ndim,
   return 0;
 }
 
+// The networks rvs_template_nn_grad and rvs_template_nn_vjp take: those of the fused
+// hidden stack, ndim <= 6 (host arithmetic; dims HOST [nlayer + 1])
+static bool nn_grad_scope(int B, int ndim, int nlayer, const int32_t *dims) {
+  if (B < 1 || ndim < 1 || ndim > 6 || nlayer < 3 || nlayer - 1 > NH_MAXL || !dims ||
+      dims[0] != ndim || dims[nlayer] < 1)
+    return false;
+  for (int l = 0; l < nlayer - 1; l++)
+    if (dims[l + 1] < 1 || dims[l + 1] > 256 || (l > 0 && (dims[l] & 31))) return false;
+  return true;
+}
+
 // rvs_template_nn with its tangent rows: include/rvsgpu.h.  Two launches: the
 // hidden stack in forward mode (nn_hidden_grad_kernel), then the last layer with
 // the float64 epilogue of all 1 + ndim rows of a job (nn_linear_grad_kernel) --
@@ -1094,13 +1105,9 @@ extern "C" int rvs_template_nn_grad(const double *params, int B, int ndim,
                                     const float *const *W, const float *const *b,
                                     const int32_t *dims, float *act0, float *act1,
                                     double *templ, void *stream) {
-  if (B < 1 || ndim < 1 || ndim > 6 || nlayer < 3 || nlayer - 1 > NH_MAXL ||
-      !params || !M || !S || !W || !b || !dims || !act0 || !act1 || !templ ||
-      dims[0] != ndim || dims[nlayer] < 1)
+  if (!params || !M || !S || !W || !b || !act0 || !act1 || !templ ||
+      !nn_grad_scope(B, ndim, nlayer, dims))
     return RVS_E_ARG;
-  for (int l = 0; l < nlayer - 1; l++)
-    if (dims[l + 1] < 1 || dims[l + 1] > 256 || (l > 0 && (dims[l] & 31)))
-      return RVS_E_ARG;
   for (int l = 0; l < nlayer; l++)
     if (!W[l] || !b[l]) return RVS_E_ARG;
   const int R = 1 + ndim;
@@ -1293,3 +1300,339 @@ extern "C" int rvs_template_nn_arms_n(const double *params, int B,
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// rvs_template_nn_vjp: the network's reverse pass.  One adjoint row
+// tbar = d chi^2 / d t per job goes back through the net, whatever ndim is:
+//   gparams_k = sum_n tbar_n d t_n / d p_k.
+// Three launches, no floating point atomic, every sum in a fixed order that does not
+// depend on B: a job has the same bits alone and inside any batch.
+//   scale    per job: the exponent e of max_n |ybar_n|, ybar_n = tbar_n t_n in float64
+//            (exactly 0 where t_n is one of the clip's two values: the clip is flat)
+//   last     abar = ybar W_L, [B, ntp] x [ntp, K_L]: ybar 2^-e is cast to float32 as a
+//            tile is staged; ntp is cut into runs of NV_SPLIT pixels, one block per (run,
+//            32 jobs), one partial sum per run in HBM
+//   hidden   16 jobs per block: the partial sums added in run order; the forward pass of
+//            the jobs' rows again, every layer's z kept in LDS; delta_l = abar_l sigma (1
+//            + z (1 - sigma)), abar_{l-1} = delta_l W_l; at the input x_k s_k / S_k 2^e in
+//            float64
+// A product takes the MFMA of the value path (v_mfma_f32_32x32x2_f32: exact float32
+// products, one fma chain per output), its B operand straight from the weights in
+// global memory as nn_hidden_body takes it -- here along a COLUMN of the Linear's
+// weight, 32 consecutive outputs per wave instruction.
+// ---------------------------------------------------------------------------
+#define NV_SPLIT 256   // pixels of one partial sum of the last layer
+#define NV_ROWS 16     // jobs of a block of the hidden stack's reverse pass
+
+// ybar_n; thi, tlo: exp_clip300(+-300), the values the clip leaves
+__device__ __forceinline__ double nn_vjp_ybar(double t, double tb, double thi, double tlo) {
+  return (t >= thi || t <= tlo) ? 0.0 : tb * t;
+}
+
+__global__ void __launch_bounds__(256)
+    nn_vjp_scale_kernel(const double *__restrict__ templ, const double *__restrict__ tbar,
+                        int ntp, int32_t *__restrict__ ex) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * ntp;
+  const double thi = exp_clip300(300.0), tlo = exp_clip300(-300.0);
+  double mx = 0;
+  for (int n = tid; n < ntp; n += 256)
+    mx = fmax(mx, fabs(nn_vjp_ybar(templ[r0 + n], tbar[r0 + n], thi, tlo)));
+  mx = wave_max(mx);
+  if ((tid & 63) == 0) red[tid >> 6] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    const double mm = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    // mm = f 2^e with f in [0.5, 1): the row divided by 2^e has its largest entry there
+    int e = 0;
+    if (mm > 0 && mm <= 1.79e308) (void)frexp(mm, &e);
+    ex[blockIdx.x] = e;
+  }
+}
+
+// part [B][nsplit][KL]: the sum over the pixels of run s = blockIdx.x, 32 jobs per block,
+// wave w the outputs 32 w ... 32 w + 31 (KL <= 256)
+__global__ void __launch_bounds__(512)
+    nn_vjp_last_kernel(const double *__restrict__ templ, const double *__restrict__ tbar,
+                       const int32_t *__restrict__ ex, int B, int ntp,
+                       const float *__restrict__ W, int KL, float *__restrict__ part) {
+  __shared__ __attribute__((aligned(16))) float ys[32 * NH_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s = blockIdx.x, nsplit = gridDim.x;
+  const int row0 = blockIdx.y * 32, n0 = s * NV_SPLIT;
+  const double thi = exp_clip300(300.0), tlo = exp_clip300(-300.0);
+  {
+    // the tile of ybar 2^-e as float32: thread = pixel of the run, every second row
+    const int c = tid & (NV_SPLIT - 1), n = n0 + c;
+#pragma unroll 4
+    for (int i = 0; i < 16; i++) {
+      const int r = (tid >> 8) + 2 * i;
+      const int b = min(row0 + r, B - 1);   // (rows behind B: stored nowhere)
+      float v = 0.f;
+      if (n < ntp) {
+        const int64_t q = (int64_t)b * ntp + n;
+        v = (float)ldexp(nn_vjp_ybar(templ[q], tbar[q], thi, tlo), -ex[b]);
+      }
+      ys[r * NH_LD + c] = v;
+    }
+  }
+  __syncthreads();
+  const int col0 = wave * 32;
+  if (col0 >= KL) return;   // (wave-uniform, behind the kernel's only barrier)
+  const int fm = lane & 31, fh = (lane >> 5) * 16;
+  const int col = min(col0 + fm, KL - 1);
+  f32x16 acc;
+#pragma unroll
+  for (int q = 0; q < 16; q++) acc[q] = 0.f;
+  // B fragment: W[n][col] for 16 consecutive pixels n per lane and 32-pixel chunk (lower
+  // half-wave n = G .. G + 15, upper G + 16 .. G + 31; pixels behind ntp: clamped, their
+  // ybar is zero)
+  const int nlen = min(NV_SPLIT, ntp - n0);
+  auto wload = [&](int G, float (&bw)[16]) {
+#pragma unroll
+    for (int q = 0; q < 16; q++)
+      bw[q] = W[(int64_t)min(n0 + G + fh + q, ntp - 1) * KL + col];
+  };
+  float nb[16];
+  wload(0, nb);
+  for (int G = 0; G < nlen; G += 32) {
+    float cb[16];
+    f32x4 a[4];
+#pragma unroll
+    for (int q = 0; q < 16; q++) cb[q] = nb[q];
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+      a[q] = *reinterpret_cast<const f32x4 *>(ys + fm * NH_LD + G + fh + 4 * q);
+    if (G + 32 < nlen) wload(G + 32, nb);
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+      for (int e = 0; e < 4; e++)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q][e], cb[4 * q + e], acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 16; r++) {
+    const int b = row0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    if (b < B && col0 + fm < KL) part[((int64_t)b * nsplit + s) * KL + col0 + fm] = acc[r];
+  }
+}
+
+// img: [nl + 1][NV_ROWS][NH_LD] floats of dynamic LDS -- z of the nl hidden layers (then
+// delta in its place), and one image that holds the activations on the way forward and
+// abar on the way back; zeros behind every width up to 256.  The MFMA's rows 16 .. 31
+// repeat rows 0 .. 15 and are stored nowhere.
+__global__ void __launch_bounds__(512)
+    nn_vjp_hidden_kernel(const double *__restrict__ params, int B, int ndim,
+                         uint32_t log_mask, const double *__restrict__ M,
+                         const double *__restrict__ S, NNHidden H,
+                         const float *__restrict__ part, int nsplit,
+                         const int32_t *__restrict__ ex, double *__restrict__ gparams) {
+  extern __shared__ __attribute__((aligned(16))) float img[];
+  __shared__ float xin[NV_ROWS * 8];
+  constexpr int IMG = NV_ROWS * NH_LD;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nl = H.nl, row0 = blockIdx.x * NV_ROWS;
+  float *work = img + nl * IMG;
+  auto dsilu = [](float z) {
+    const float sg = 1.0f / (1.0f + expf(-z));
+    return sg * (1.0f + z * (1.0f - sg));
+  };
+  // Mapper.forward of the block's rows (nn_hidden_body)
+  if (tid < NV_ROWS * 8) {
+    const int r = tid >> 3, d = tid & 7;
+    float v = 0.f;
+    if (d < ndim) {
+      const int gr = min(row0 + r, B - 1);
+      float y = (float)params[(int64_t)gr * ndim + d];
+      if (log_mask & (1u << d)) y = (float)log10((double)y);
+      v = (float)(((double)y - M[d]) / S[d]);
+    }
+    xin[tid] = v;
+  }
+  __syncthreads();
+  // ---- forward: first layer on the VALU (thread = column and half of the rows) -------------
+  {
+    const int N = H.dims[1], c = tid & 255, rh = (tid >> 8) * (NV_ROWS / 2);
+    float w[8], bv = 0.f;
+#pragma unroll
+    for (int d = 0; d < 8; d++) w[d] = (c < N && d < ndim) ? H.W[0][c * ndim + d] : 0.f;
+    if (c < N) bv = H.b[0][c];
+    for (int r = rh; r < rh + NV_ROWS / 2; r++) {
+      float y = bv;
+#pragma unroll
+      for (int d = 0; d < 8; d++) y = fmaf(w[d], xin[r * 8 + d], y);
+      img[r * NH_LD + c] = c < N ? y : 0.f;
+      work[r * NH_LD + c] = c < N ? y / (1.0f + expf(-y)) : 0.f;
+    }
+  }
+  __syncthreads();
+  const int fm = lane & 31, fr = fm & (NV_ROWS - 1), fh = (lane >> 5) * 16;
+  const int col0 = wave * 32, col = col0 + fm;
+  // ---- forward: the MFMA layers, z_l kept ------------------------------------------------------
+  for (int l = 1; l < nl; l++) {
+    const int K = H.dims[l], N = H.dims[l + 1];   // K % 32 == 0
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; q++) acc[q] = 0.f;
+    const bool cok = col < N;
+    if (col0 < N) {
+      const f32x4 *w0 =
+          reinterpret_cast<const f32x4 *>(H.W[l] + (int64_t)min(col, N - 1) * K + fh);
+      const float z0 = cok ? 1.f : 0.f;
+      for (int G = 0; G < K; G += 32) {
+        f32x4 cb[4], a[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          cb[q] = w0[G / 4 + q] * z0;
+          a[q] = *reinterpret_cast<const f32x4 *>(work + fr * NH_LD + G + fh + 4 * q);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+          for (int e = 0; e < 4; e++)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q][e], cb[q][e], acc, 0, 0, 0);
+      }
+    }
+    const float bv = H.b[l][cok ? col : 0];
+    float *zl = img + l * IMG;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {   // rows 0 .. 15 of the tile
+      const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      zl[row * NH_LD + col] = cok ? acc[r] + bv : 0.f;
+    }
+    __syncthreads();   // every wave has read the activations
+    if (l + 1 < nl) {
+#pragma unroll
+      for (int r = 0; r < 8; r++) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const float y = acc[r] + bv;
+        work[row * NH_LD + col] = cok ? y / (1.0f + expf(-y)) : 0.f;
+      }
+      __syncthreads();
+    }
+  }
+  // ---- back: abar of the last hidden layer, the runs' partial sums in run order -----------------
+  {
+    const int KL = H.dims[nl];
+    for (int i = tid; i < NV_ROWS * 256; i += 512) {
+      const int r = i >> 8, c = i & 255, b = row0 + r;
+      float v = 0.f;
+      if (b < B && c < KL) {
+        const float *p = part + (int64_t)b * nsplit * KL + c;
+        for (int s = 0; s < nsplit; s++) v += p[(int64_t)s * KL];
+      }
+      work[r * NH_LD + c] = v;
+    }
+  }
+  __syncthreads();
+  for (int l = nl - 1; l >= 0; l--) {
+    float *zl = img + l * IMG;
+    // delta_l = abar_l sigma (1 + z (1 - sigma)) where z_l was (0 behind the width: abar is)
+    for (int i = tid; i < NV_ROWS * 256; i += 512) {
+      const int o = (i >> 8) * NH_LD + (i & 255);
+      zl[o] = work[o] * dsilu(zl[o]);
+    }
+    __syncthreads();
+    if (l == 0) break;
+    // abar_{l-1} = delta_l W_l: the sum over the N outputs of layer l (delta is zero up to
+    // the next multiple of 32), wave w the inputs 32 w ... 32 w + 31 of its K
+    const int K = H.dims[l], N = H.dims[l + 1];
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; q++) acc[q] = 0.f;
+    if (col0 < K) {
+      const float *wc = H.W[l] + min(col, K - 1);
+      for (int G = 0; G < N; G += 32) {
+        float cb[16];
+        f32x4 a[4];
+#pragma unroll
+        for (int q = 0; q < 16; q++) cb[q] = wc[(int64_t)min(G + fh + q, N - 1) * K];
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+          a[q] = *reinterpret_cast<const f32x4 *>(zl + fr * NH_LD + G + fh + 4 * q);
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+          for (int e = 0; e < 4; e++)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q][e], cb[4 * q + e], acc, 0, 0, 0);
+      }
+    }
+    // (abar_l was last read ahead of the barrier above)
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      work[row * NH_LD + col] = col < K ? acc[r] : 0.f;
+    }
+    __syncthreads();
+  }
+  // ---- the input: xbar_k = sum_n delta_0n W_0[n][k] in column order; s_k / S_k and the
+  // row's power of two in float64 (rvs_template_nn_grad's s_k); NaN for a job whose mapped
+  // parameters are not all finite
+  if (tid < NV_ROWS * 8) {
+    const int r = tid >> 3, k = tid & 7, b = row0 + r;
+    if (k < ndim && b < B) {
+      const int N = H.dims[1];
+      float v = 0.f;
+      for (int n = 0; n < N; n++) v = fmaf(img[r * NH_LD + n], H.W[0][n * ndim + k], v);
+      bool bad = false;
+      for (int d = 0; d < ndim; d++) bad = bad || !(fabsf(xin[r * 8 + d]) <= 3.402823466e38f);
+      double sk = 1.0;
+      if (log_mask & (1u << k))
+        sk = 1.0 / (params[(int64_t)b * ndim + k] * 2.302585092994045684);
+      sk = sk / S[k];
+      gparams[(int64_t)b * ndim + k] =
+          bad ? __builtin_nan("") : ldexp((double)v, ex[b]) * sk;
+    }
+  }
+}
+
+// the jobs' exponents (int32, padded to 8 bytes), then the partial sums [B][runs][K_L]
+extern "C" int64_t rvs_template_nn_vjp_work_size(int B, int nlayer, const int32_t *dims) {
+  if (!dims || nlayer < 1 || !nn_grad_scope(B, dims[0], nlayer, dims)) return 0;
+  const int64_t nsplit = (dims[nlayer] + NV_SPLIT - 1) / NV_SPLIT;
+  return 8 * (((int64_t)B + 1) / 2) + (int64_t)B * nsplit * dims[nlayer - 1] * 4;
+}
+
+extern "C" int rvs_template_nn_vjp(const double *params, int B, int ndim,
+                                   uint32_t log_mask, const double *M, const double *S,
+                                   int nlayer, const float *const *W,
+                                   const float *const *b, const int32_t *dims,
+                                   const double *templ, const double *tbar, void *work,
+                                   double *gparams, void *stream) {
+  if (!params || !M || !S || !W || !b || !templ || !tbar || !work || !gparams ||
+      !nn_grad_scope(B, ndim, nlayer, dims))
+    return RVS_E_ARG;
+  for (int l = 0; l < nlayer; l++)
+    if (!W[l] || !b[l]) return RVS_E_ARG;
+  hipStream_t st = rvs_stream(stream);
+  const int ntp = dims[nlayer], KL = dims[nlayer - 1];
+  const int nsplit = (ntp + NV_SPLIT - 1) / NV_SPLIT;
+  if (nsplit > 65535 || (B + 31) / 32 > 65535) return RVS_E_ARG;
+  int32_t *ex = (int32_t *)work;
+  float *part = (float *)((char *)work + 8 * (((int64_t)B + 1) / 2));
+  NNHidden H;
+  H.nl = nlayer - 1;
+  for (int l = 0; l < H.nl; l++) {
+    H.W[l] = W[l];
+    H.b[l] = b[l];
+  }
+  for (int l = 0; l <= H.nl; l++) H.dims[l] = dims[l];
+  const size_t shm = (size_t)(H.nl + 1) * NV_ROWS * NH_LD * sizeof(float);
+  // (per call: the attribute belongs to the current device's copy of the kernel)
+  if (hipFuncSetAttribute((const void *)nn_vjp_hidden_kernel,
+                          hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (NH_MAXL + 1) * NV_ROWS * NH_LD * (int)sizeof(float)) !=
+      hipSuccess) {
+    (void)hipGetLastError();
+    return RVS_E_LAUNCH;
+  }
+  hipLaunchKernelGGL(nn_vjp_scale_kernel, dim3(B), dim3(256), 0, st, templ, tbar, ntp, ex);
+  RVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(nn_vjp_last_kernel, dim3(nsplit, (B + 31) / 32), dim3(512), 0, st,
+                     templ, tbar, ex, B, ntp, W[nlayer - 1], KL, part);
+  RVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(nn_vjp_hidden_kernel, dim3((B + NV_ROWS - 1) / NV_ROWS), dim3(512),
+                     shm, st, params, B, ndim, log_mask, M, S, H, part, nsplit, ex, gparams);
+  RVS_LAUNCH_CHECK();
+  return 0;
+}

@@ -43,14 +43,29 @@ namespace {
 template <int P>
 using OgShared = OpShared<P, (op_nv(P) > OP_MAXK + 1 ? op_nv(P) : OP_MAXK + 1)>;
 
-template <int P>
+// FROMT (rvs_objective_grad_from_template): the unbroadened template of a
+// (job, arm) is a row an evaluator that is no grid gather left in HBM (the MLP of
+// rvs_template_nn), with its outside flag, as objective_kernel<P, true> takes it.  There is
+// no cell and no contraction at the knots: the adjoint row tbar = d chi^2 / d t goes to HBM
+// as it stands in LDS behind the transposed FIR -- the row the evaluator's own reverse
+// pass contracts with its Jacobian -- and the gradient has the velocity and, with vsini
+// fitted, the vsini column.  Everything between is the text below, unchanged.
+struct OgNoTempl {};
+struct OgTempl {
+  const double *templ[RVS_MAX_ARMS];    // [J, ntp] per arm
+  const double *outside[RVS_MAX_ARMS];  // [J] per arm
+  double *tbar[RVS_MAX_ARMS];           // [J, ntp] per arm
+};
+
+template <int P, bool FROMT = false>
 __global__ void __launch_bounds__(OP_NT)
     objective_grad_kernel(ObjArms A, const double *__restrict__ params,
                           const double *__restrict__ vsini, int vsini_grad,
                           const int32_t *__restrict__ job_spec, int J,
                           const double *__restrict__ vel, double eps_ld,
                           double *__restrict__ armchi, double *__restrict__ armgrad,
-                          int32_t *__restrict__ armst, double *__restrict__ armout) {
+                          int32_t *__restrict__ armst, double *__restrict__ armout,
+                          std::conditional_t<FROMT, OgTempl, OgNoTempl> TT) {
   static_assert(sizeof(OgShared<P>) <= OP_STATIC_MAX, "op_point_ok's bound");
   extern __shared__ double lds[];
   __shared__ OgShared<P> sh;
@@ -60,19 +75,30 @@ __global__ void __launch_bounds__(OP_NT)
   const rvs_objective_arm &T = pt.T;
   const PolyLoc &PL = pt.PL;
   const int tid = pt.tid, lane = pt.lane, w = pt.w;
-  const int N = pt.N, m = pt.m, nd = pt.nd, nv = pt.nv;
+  const int N = pt.N, m = pt.m, nd = FROMT ? 0 : pt.nd, nv = pt.nv;
   const int K = 1 + nd + (vsini_grad ? 1 : 0);
   constexpr int NTR = P * (P + 1) / 2;
   constexpr int NV = NTR + P;
+  // FROMT: this (job, arm)'s template row and the row its adjoint goes to
+  const double *trow = nullptr;
+  double *tbrow = nullptr;
 
   // ---- cell, gather and guard, rotational kernel, FIR, spline construct ---------------------
   // (objective_point_dev.h, shared with objective_fisher_kernel) hands over: PL, sh.dw,
   // sh.jobsc, mode, nrow, outside; kmax, R, copy, st_extra; Y, Z, F; the chunk tables
-  pt.cell(params, vel);
-  pt.gather_and_guard();
+  if constexpr (FROMT) {
+    trow = TT.templ[blockIdx.y] + (int64_t)j * N;
+    tbrow = TT.tbar[blockIdx.y] + (int64_t)j * N;
+    pt.template_row(trow, TT.outside[blockIdx.y][j], vel);
+  } else {
+    pt.cell(params, vel);
+    pt.gather_and_guard();
+  }
   if (obj_template_unusable(pt.outside)) {
     obj_store_skipped(o, armchi, armst, armout);
     if (tid < K) armgrad[o * K + tid] = 0.0;
+    if constexpr (FROMT)   // (a skipped arm adds nothing to the parameters' gradient)
+      for (int n = tid; n < N; n += OP_NT) tbrow[n] = 0.0;
     return;
   }
   pt.rotational_kernel(vsini);
@@ -330,7 +356,15 @@ __global__ void __launch_bounds__(OP_NT)
   double gp[OP_MAXDIM], gvs = 0;
 #pragma unroll
   for (int d = 0; d < OP_MAXDIM; d++) gp[d] = 0;
-  for (int n = tid; n < N; n += OP_NT) {
+  if constexpr (FROMT) {
+    // tbar to HBM, coalesced (every thread the knots it wrote); with vsini fitted
+    // vbar_n t_n with t_n read again from the template row: t is dead in LDS
+    for (int n = tid; n < N; n += OP_NT) {
+      tbrow[n] = tbar[n];
+      if (vs_grad) gvs = fma(pt.fir_at(Yb, dwt, n), trow[n], gvs);
+    }
+  }
+  for (int n = tid; !FROMT && n < N; n += OP_NT) {
     double tn;
     if (mode == 0) {
       double a = 0, g[OP_MAXDIM];
@@ -428,11 +462,120 @@ extern "C" int rvs_objective_grad(const rvs_objective_arm *arms, int narm, int n
     constexpr int PP = decltype(p)::value;
     op_launch<objective_grad_kernel<PP>, (int)sizeof(OgShared<PP>)>(
         dim3(J, narm), c.shm, st, c.A, params, vsini, c.vsini_grad, job_spec, J, vel, 0.6,
-        armchi, armgrad, armst, armout);
+        armchi, armgrad, armst, armout, OgNoTempl());
   });
   hipLaunchKernelGGL(objective_point_sum_kernel, dim3((J + 255) / 256), dim3(256), 0, st,
                      narm, J, 0, K, badchi, c.bc, arms[0].pt.pen_scale, job_spec, armchi,
                      armgrad, nullptr, armst, armout, out, grad, nullptr, status);
+  RVS_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- the from-template form ---------------------------------------------------
+// (op_point_ok without the ndim bound of the cell record: the kernel reads no cell)
+extern "C" int rvs_objective_grad_from_template_ok(int npoly, int npix, int ntp,
+                                                   int vsini_grad) {
+  return op_geometry_ok(npoly, npix, ntp, vsini_grad);
+}
+
+// per (arm, job): chi^2, outside, 1 + vsini_grad gradient entries, status (padded to 8
+// bytes)
+extern "C" int64_t rvs_objective_grad_from_template_work_size(int J, int narm,
+                                                              int vsini_grad) {
+  if (J < 1 || narm < 1 || narm > RVS_MAX_ARMS || vsini_grad < 0 || vsini_grad > 1)
+    return 0;
+  return (int64_t)narm * J * (int64_t)((4 + vsini_grad) * sizeof(double));
+}
+
+extern "C" int rvs_objective_grad_from_template(
+    const rvs_objective_arm *arms, int narm, int npoly, int vsini_grad,
+    const double *const *templ, const double *const *outside, const double *vsini,
+    const int32_t *job_spec, int J, const double *vel, double badchi,
+    const double *basis_const, void *scratch, double *const *tbar, double *out,
+    double *grad, int32_t *status, void *stream) {
+  OpCall c;
+  if (J < 1 || !templ || !outside || !tbar || !vel || !scratch || !out || !grad ||
+      !status || !op_check_arms_templ(arms, narm, npoly, vsini_grad, vsini, basis_const, c))
+    return RVS_E_ARG;
+  OgTempl tt = {};
+  for (int i = 0; i < RVS_MAX_ARMS; i++) {
+    const int a = i < narm ? i : 0;
+    if (!templ[a] || !outside[a] || !tbar[a]) return RVS_E_ARG;
+    tt.templ[i] = templ[a];
+    tt.outside[i] = outside[a];
+    tt.tbar[i] = tbar[a];
+  }
+  hipStream_t st = rvs_stream(stream);
+  const int K = 1 + vsini_grad;
+  double *armchi = (double *)scratch;
+  double *armout = armchi + (int64_t)narm * J;
+  double *armgrad = armout + (int64_t)narm * J;
+  int32_t *armst = (int32_t *)(armgrad + (int64_t)narm * J * K);
+  op_for_npoly(npoly, [&](auto p) {
+    constexpr int PP = decltype(p)::value;
+    op_launch<objective_grad_kernel<PP, true>, (int)sizeof(OgShared<PP>)>(
+        dim3(J, narm), c.shm, st, c.A, (const double *)nullptr, vsini, c.vsini_grad,
+        job_spec, J, vel, 0.6, armchi, armgrad, armst, armout, tt);
+  });
+  hipLaunchKernelGGL(objective_point_sum_kernel, dim3((J + 255) / 256), dim3(256), 0, st,
+                     narm, J, 0, K, badchi, c.bc, arms[0].pt.pen_scale, job_spec, armchi,
+                     armgrad, nullptr, armst, armout, out, grad, nullptr, status);
+  RVS_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- the sum over the arms of the evaluator's reverse pass --------------------------------
+// grad [J, 1 + ndim + vsini_grad] = (vel, parameters, vsini) from the from-template call's
+// own gradient [J, 1 + vsini_grad] and the arms' gparams [J, ndim] (rvs_template_nn_vjp of
+// the arm's tbar rows), arms in order.  An arm whose outside flag -- read from the
+// from-template call's scratch -- is not finite adds exactly nothing; where the value is
+// NaN so are the parameters' components; the penalties are on the value only.
+namespace {
+struct OgJoin {
+  const double *gparams[RVS_MAX_ARMS];
+};
+__global__ void objective_grad_join_kernel(int narm, int J, int ndim, int vg,
+                                           const double *__restrict__ armout, OgJoin G,
+                                           const double *__restrict__ out,
+                                           const double *__restrict__ gvv,
+                                           double *__restrict__ grad) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= J) return;
+  const int K2 = 1 + vg, K = 1 + ndim + vg;
+  const double chi = out[j];
+  bool counts[RVS_MAX_ARMS];
+#pragma unroll
+  for (int ia = 0; ia < RVS_MAX_ARMS; ia++)
+    counts[ia] = ia < narm && fabs(armout[(int64_t)min(ia, narm - 1) * J + j]) <= 1.79e308;
+  grad[(int64_t)j * K] = gvv[(int64_t)j * K2];
+  for (int d = 0; d < ndim; d++) {
+    double v = 0;
+#pragma unroll
+    for (int ia = 0; ia < RVS_MAX_ARMS; ia++)
+      if (counts[ia]) v += G.gparams[ia][(int64_t)j * ndim + d];
+    grad[(int64_t)j * K + 1 + d] = (chi == chi) ? v : __builtin_nan("");
+  }
+  if (vg) grad[(int64_t)j * K + 1 + ndim] = gvv[(int64_t)j * K2 + 1];
+}
+}  // namespace
+
+extern "C" int rvs_objective_grad_join(int narm, int J, int ndim, int vsini_grad,
+                                       const void *scratch, const double *const *gparams,
+                                       const double *out, const double *grad_vv,
+                                       double *grad, void *stream) {
+  if (narm < 1 || narm > RVS_MAX_ARMS || J < 1 || ndim < 1 || ndim > 8 || vsini_grad < 0 ||
+      vsini_grad > 1 || !scratch || !gparams || !out || !grad_vv || !grad)
+    return RVS_E_ARG;
+  OgJoin G = {};
+  for (int i = 0; i < RVS_MAX_ARMS; i++) {
+    G.gparams[i] = gparams[i < narm ? i : 0];
+    if (!G.gparams[i]) return RVS_E_ARG;
+  }
+  // (the layout of rvs_objective_grad_from_template's scratch: [narm, J] values, then flags)
+  const double *armout = (const double *)scratch + (int64_t)narm * J;
+  hipLaunchKernelGGL(objective_grad_join_kernel, dim3((J + 255) / 256), dim3(256), 0,
+                     rvs_stream(stream), narm, J, ndim, vsini_grad, armout, G, out, grad_vv,
+                     grad);
   RVS_LAUNCH_CHECK();
   return 0;
 }

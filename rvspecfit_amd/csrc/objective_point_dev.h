@@ -147,6 +147,29 @@ struct ObjPoint {
     __syncthreads();
   }
 
+  // ---- template row: an evaluator's row from HBM into B0; the template guard ----------------
+  // (in place of cell and gather_and_guard where the template is no grid gather: the MLP of
+  // rvs_template_nn, as objective_kernel<P, true> takes it)
+  // hands over: B0, mode (0: inside the evaluator's domain), sh.jobsc; `outside`, the arm's
+  // penalty term (outside_in, or NaN where the MAX_VAL guard refuses the row)
+  __device__ __forceinline__ void template_row(const double *__restrict__ row,
+                                               double outside_in,
+                                               const double *__restrict__ vel) {
+    mode = (outside_in == 0.0) ? 0 : 1;
+    nrow = nullptr;
+    outside = 0.0;
+    if (tid == 64) obj_job_scalars(T.pt, vel[j], sh.jobsc);
+    double mx = 0;
+    bool anynan = false;
+    for (int k = tid; k < N; k += OP_NT) {
+      const double val = row[k];
+      B0[k] = val;
+      if (mode != 0) obj_guard_scan(val, mx, anynan);
+    }
+    if (mode != 0) outside = obj_template_guard<OP_NW>(mx, anynan, &outside_in, sh.red8);
+    __syncthreads();
+  }
+
   // ---- rotational kernel ----------------------------------------------------------------------
   // hands over: kmax (0: `copy`, no FIR), R, st_extra; the taps are built where they are used
   __device__ __forceinline__ void rotational_kernel(const double *__restrict__ vsini) {
@@ -519,13 +542,19 @@ __global__ void objective_point_sum_kernel(int narm, int Jl, int j0, int K, doub
 // npix + ntp / 2 <= ntp).  The Fisher kernel's tangent passes add no condition: the taps
 // and their derivatives (2 kmax + 2 doubles) and the primitives' stage (2 (kmax + 3)) fit
 // a buffer of ntp doubles wherever obj_rot_kmax admits kmax.
-inline int op_point_ok(int npoly, int npix, int ntp, int ndim, int vsini_grad) {
+// (the geometry alone: what the from-template form of the gradient kernel, which reads no
+// cell record, asks of an arm)
+inline int op_geometry_ok(int npoly, int npix, int ntp, int vsini_grad) {
   if (npoly < 1 || npoly > OP_MAXP || npix < 1 || ntp < 32 || ntp > RVS_OBJ_FT_MAX_NTP)
     return 0;
-  if (ndim < 1 || ndim > OP_MAXDIM || vsini_grad < 0 || vsini_grad > 1) return 0;
+  if (vsini_grad < 0 || vsini_grad > 1) return 0;
   if (2 * (int64_t)npix > ntp) return 0;
   if (3 * (int64_t)ntp * (int64_t)sizeof(double) + OP_STATIC_MAX > OP_LDS_MAX) return 0;
   return 1;
+}
+inline int op_point_ok(int npoly, int npix, int ntp, int ndim, int vsini_grad) {
+  if (ndim < 1 || ndim > OP_MAXDIM) return 0;
+  return op_geometry_ok(npoly, npix, ntp, vsini_grad);
 }
 
 // the arms of a call, checked and copied for the launch
@@ -562,6 +591,35 @@ inline bool op_check_arms(const rvs_objective_arm *arms, int narm, int npoly, in
     c.npix_max = max(c.npix_max, a.pt.npix);
   }
   for (int i = narm; i < RVS_MAX_ARMS; i++) c.A.a[i] = arms[0];
+  c.bc = make_double4(bc[0], bc[1], bc[2], bc[3]);
+  return true;
+}
+
+// ... of the from-template form: the arms carry no grid (dats, idgrid, uvecs and ndim are
+// not read), the geometry rule is op_geometry_ok.  false: RVS_E_ARG
+inline bool op_check_arms_templ(const rvs_objective_arm *arms, int narm, int npoly,
+                                int vsini_grad, const double *vsini,
+                                const double *basis_const, OpCall &c) {
+  if (narm < 1 || narm > RVS_MAX_ARMS || !arms || npoly < 1 || npoly > OP_MAXP ||
+      vsini_grad < 0 || vsini_grad > 1 || (vsini_grad && !vsini))
+    return false;
+  c.vsini_grad = vsini_grad;
+  c.A.n = narm;
+  c.shm = 0;
+  c.npix_max = 0;
+  double bc[RVS_MAX_ARMS] = {0, 0, 0, 0};
+  for (int i = 0; i < narm; i++) {
+    const rvs_objective_arm &a = arms[i];
+    if (a.pt.fast_interp || a.pt.taps || a.pt.G > 1 || !a.factors || a.pt.ntp != a.ntp ||
+        !op_geometry_ok(npoly, a.pt.npix, a.ntp, vsini_grad))
+      return false;
+    c.A.a[i] = a;
+    c.A.a[i].ndim = 0;   // (documented as not read: no shift by a caller's leftover)
+    if (basis_const) bc[i] = basis_const[i];
+    c.shm = max(c.shm, (size_t)3 * a.ntp * sizeof(double));
+    c.npix_max = max(c.npix_max, a.pt.npix);
+  }
+  for (int i = narm; i < RVS_MAX_ARMS; i++) c.A.a[i] = c.A.a[0];
   c.bc = make_double4(bc[0], bc[1], bc[2], bc[3]);
   return true;
 }

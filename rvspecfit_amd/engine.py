@@ -1387,24 +1387,35 @@ GRAD_FUSED_MAXDIM = 4
 
 
 def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
-                           vsini_grad=False, what=None):
+                           vsini_grad=False, what=None, nn_gradient=False):
     """ValueError naming the option that config['fused_gradient'] does not go with:
     what rvs_objective_grad (csrc/objective_grad.hip) does not cover keeps the chain,
     and the key beside it is an error, never a silent change of path.  `what`: a
     caller's own option that needs tangent rows (the Fisher matrix, the
-    Levenberg-Marquardt polish, the joint-epoch fit)."""
+    Levenberg-Marquardt polish, the joint-epoch fit).  nn_gradient
+    (config['nn_gradient'] of the callers): MLP libraries on every arm are admitted --
+    rvs_objective_grad_from_template hands the adjoint row to the network's reverse
+    pass (rvs_template_nn_vjp), float32 arithmetic as the chain's tangent rows are --
+    where the network is in rvs_template_nn_grad's scope and the arm in the kernel's
+    geometry."""
     key = "config['fused_gradient']"
     if what is not None:
         raise ValueError('%s does not go with %s: it needs the tangent rows of the '
                          'gradient chain, which the fused kernel never forms'
                          % (key, what))
+    if nn_gradient and all(libs[arm.name].kind == 'nn' for arm in batch.arms):
+        _check_fused_scope(key, None, batch, libs, npoly, resols, fast_interp, vsini_grad,
+                           nn=True)
+        return
     _check_fused_scope(key, _lib.lib().rvs_objective_grad_ok, batch, libs, npoly, resols,
                        fast_interp, vsini_grad)
 
 
-def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_grad):
+def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_grad,
+                       nn=False):
     # what rvs_objective_grad and rvs_objective_fisher both leave to the chain; ok: the
-    # kernel's own rvs_objective_*_ok
+    # kernel's own rvs_objective_*_ok; nn: MLP libraries on the from-template form of the
+    # gradient kernel
     if fast_interp:
         raise ValueError('%s does not go with fast_interp (the nearest-knot template '
                          'has no velocity derivative)' % key)
@@ -1420,6 +1431,18 @@ def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_g
         if arm.G > 1:
             raise ValueError('%s does not go with a grid set: arm %s has %d wavelength '
                              'grids' % (key, arm.name, arm.G))
+        if nn:
+            lib.check_nn_grad_scope()
+            if lib.spline_factors is None:
+                raise ValueError('%s needs a (log-)uniform template grid (arm %s)'
+                                 % (key, arm.name))
+            if not _lib.lib().rvs_objective_grad_from_template_ok(
+                    npoly, arm.npix, lib.ntp, int(bool(vsini_grad))):
+                raise ValueError('%s: arm %s of an nn library (npix = %d, ntp = %d) is '
+                                 'outside the kernel\'s geometry: 32 <= ntp, 2 npix <= '
+                                 'ntp, three buffers of ntp doubles in LDS'
+                                 % (key, arm.name, arm.npix, lib.ntp))
+            continue
         if lib.kind != 'regulargrid':
             raise ValueError('%s needs regular-grid (polylinear) libraries: %s is a %s '
                              'library (interpolation_type)' % (key, arm.name, lib.kind))
@@ -1459,22 +1482,129 @@ def fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys=0.0
     return keep
 
 
+def objective_grad_from_template(batch, libs, templs, outsides, vsini, vel, npoly=5,
+                                 rbf=True, job_spec=None, vsini_grad=False,
+                                 espec_sys=0.0):
+    """the from-template form of the fused gradient (rvs_objective_grad_from_template):
+    templs[a] [J, ntp_a] float64 (unbroadened), outsides[a] [J].  Returns chisq [J],
+    grad [J, 1 + vsini_grad] = d/d(vel[, vsini]), status int32 [J], the adjoint rows
+    tbars[a] [J, ntp_a] = d chisq / d templs[a], and the call's scratch (which
+    rvs_objective_grad_join reads the arms' outside flags from)."""
+    import ctypes
+    L = _lib.lib()
+    dev = batch.device
+    vel = vel.to(device=dev, dtype=torch.float64).contiguous()
+    J = vel.shape[0]
+    narm = len(batch.arms)
+    vg = int(bool(vsini_grad))
+    arr = (_lib.ObjectiveArm * narm)()
+    bconst = (ctypes.c_double * narm)()
+    keep = fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys)
+    out = torch.empty(J, dtype=torch.float64, device=dev)
+    grad = torch.empty((J, 1 + vg), dtype=torch.float64, device=dev)
+    status = torch.zeros(J, dtype=torch.int32, device=dev)
+    tbars = [torch.empty((J, libs[arm.name].ntp), dtype=torch.float64, device=dev)
+             for arm in batch.arms]
+    nb = L.rvs_objective_grad_from_template_work_size(J, narm, vg)
+    scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
+    if vsini is not None:
+        vsini = vsini.to(device=dev, dtype=torch.float64).contiguous()
+    if job_spec is not None:
+        job_spec = job_spec.to(device=dev, dtype=torch.int32).contiguous()
+    templs = [t.contiguous() for t in templs]
+    outsides = [o.contiguous() for o in outsides]
+    tp = (ctypes.c_void_p * narm)(*[t.data_ptr() for t in templs])
+    op = (ctypes.c_void_p * narm)(*[o.data_ptr() for o in outsides])
+    bp = (ctypes.c_void_p * narm)(*[t.data_ptr() for t in tbars])
+    with _ktime('objective_grad_from_template', J):
+        rc = L.rvs_objective_grad_from_template(
+            ctypes.addressof(arr), narm, npoly, vg, ctypes.cast(tp, ctypes.c_void_p),
+            ctypes.cast(op, ctypes.c_void_p), _lib.ptr(vsini), _lib.ptr(job_spec), J,
+            _lib.ptr(vel), float(batch.badchi), ctypes.addressof(bconst),
+            _lib.ptr(scratch), ctypes.cast(bp, ctypes.c_void_p), _lib.ptr(out),
+            _lib.ptr(grad), _lib.ptr(status), _lib.stream())
+        _lib.check(rc, 'rvs_objective_grad_from_template')
+    del keep
+    return out, grad, status, tbars, scratch
+
+
+# bytes the rows of one chunk of objective_grad_fused on MLP libraries may take: per job
+# and arm the template row and the adjoint row (2 ntp doubles: 2.4 GB at 8192 jobs on the
+# three DESI arms) and the partial sums of the reverse pass (ceil(ntp / 256) K_L floats:
+# 0.5 GB there)
+TBAR_BUDGET = 4 << 30
+
+
+def _objective_grad_fused_nn(batch, libs, params, vsini, vel, npoly, rbf, job_spec,
+                             vsini_grad, espec_sys, tbar_bytes):
+    # MLP libraries: template rows -> rvs_objective_grad_from_template -> the network's
+    # reverse pass per arm -> the sum over the arms; the jobs in chunks of what the byte
+    # budget of the adjoint rows holds (a job's results do not depend on its chunk)
+    import ctypes
+    L = _lib.lib()
+    dev = batch.device
+    J = vel.shape[0]
+    narm = len(batch.arms)
+    ls = [libs[arm.name] for arm in batch.arms]
+    ndim, vg = ls[0].ndim, int(bool(vsini_grad))
+    per_job = sum(16 * lib.ntp + 4 * ((lib.ntp + 255) // 256) * int(lib.nn_dims[-2])
+                  for lib in ls)
+    budget = TBAR_BUDGET if tbar_bytes is None else int(tbar_bytes)
+    cap = max(1, min(J, budget // per_job))
+    out = torch.empty(J, dtype=torch.float64, device=dev)
+    grad = torch.empty((J, 1 + ndim + vg), dtype=torch.float64, device=dev)
+    status = torch.zeros(J, dtype=torch.int32, device=dev)
+    for j0 in range(0, J, cap):
+        sl = slice(j0, min(J, j0 + cap))
+        n = sl.stop - sl.start
+        p = params[sl].contiguous()
+        rows = [lib.eval_batch(p) for lib in ls]
+        o, gvv, st, tbars, scratch = objective_grad_from_template(
+            batch, libs, [r[0] for r in rows], [r[1] for r in rows],
+            None if vsini is None else vsini[sl], vel[sl], npoly, rbf,
+            None if job_spec is None else job_spec[sl], vsini_grad, espec_sys)
+        gps = [lib.nn_vjp(p, r[0], tb) for lib, r, tb in zip(ls, rows, tbars)]
+        gp = (ctypes.c_void_p * narm)(*[g.data_ptr() for g in gps])
+        g = grad[sl]
+        rc = L.rvs_objective_grad_join(narm, n, ndim, vg, _lib.ptr(scratch),
+                                       ctypes.cast(gp, ctypes.c_void_p), _lib.ptr(o),
+                                       _lib.ptr(gvv), _lib.ptr(g), _lib.stream())
+        _lib.check(rc, 'rvs_objective_grad_join')
+        out[sl] = o
+        status[sl] = st
+    return out, grad, status
+
+
 def objective_grad_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
-                         job_spec=None, vsini_grad=False, espec_sys=0.0):
+                         job_spec=None, vsini_grad=False, espec_sys=0.0,
+                         nn_gradient=False, tbar_bytes=None):
     """get_chisq and its gradient for J (spectrum, parameters, vsini, velocity) jobs
     as ONE kernel per (job, arm) (rvs_objective_grad, the adjoint method): no template
     row, tangent row or spline record in HBM.  Returns chisq [J] (with the outside
     penalty, which is not differentiated), grad [J, 1 + ndim] = d/d(vel, parameters)
     -- [J, 2 + ndim] with vsini_grad, d/dvsini last -- and status int32 [J]: the
     results of build_templates(tangents=True) + chisq_point_grad to rounding.  What
-    the kernel does not cover raises ValueError (check_fused_grad_scope)."""
+    the kernel does not cover raises ValueError (check_fused_grad_scope).
+    nn_gradient: MLP libraries go through the from-template form of the kernel and the
+    network's reverse pass (rvs_objective_grad_from_template, rvs_template_nn_vjp): one
+    template row in and one adjoint row out per (job, arm), the parameter components in
+    float32 arithmetic; tbar_bytes: the byte budget of one chunk's rows (default
+    TBAR_BUDGET, which says what is counted; the results do not depend on it)."""
     import ctypes
     if vsini_grad and vsini is None:
         raise ValueError('vsini_grad=True needs vsini: without rotation there is no '
                          'vsini to differentiate by')
-    check_fused_grad_scope(batch, libs, npoly, None, False, vsini_grad)
+    check_fused_grad_scope(batch, libs, npoly, None, False, vsini_grad,
+                           nn_gradient=nn_gradient)
     L = _lib.lib()
     dev = batch.device
+    if libs[batch.arms[0].name].kind == 'nn':
+        vel = vel.to(device=dev, dtype=torch.float64).contiguous()
+        params = params.to(device=dev, dtype=torch.float64).contiguous()
+        if vsini is not None:
+            vsini = vsini.to(device=dev, dtype=torch.float64).contiguous()
+        return _objective_grad_fused_nn(batch, libs, params, vsini, vel, npoly, rbf,
+                                        job_spec, vsini_grad, espec_sys, tbar_bytes)
     vel = vel.to(device=dev, dtype=torch.float64).contiguous()
     params = params.to(device=dev, dtype=torch.float64).contiguous()
     J = vel.shape[0]

@@ -584,6 +584,43 @@ class TemplateLibrary:
         _lib.check(rc, 'rvs_template_nn_grad')
         return templ, self._nn_outside(params)
 
+    def nn_vjp(self, params, templ, tbar):
+        """the network's reverse pass (rvs_template_nn_vjp): params [J, ndim], templ
+        [J, ntp] (eval_batch's rows for them) and tbar [J, ntp] (d f / d templ) ->
+        gparams [J, ndim] = sum_n tbar_n d templ_n / d p_k, float64 out of float32
+        arithmetic; NaN for a job whose mapped parameters are not all finite.  The
+        networks of check_nn_grad_scope."""
+        import ctypes
+        if self.kind != 'nn':
+            raise ValueError('nn_vjp needs an MLP library, %s is a %s library'
+                             % (self.name, self.kind))
+        self.check_nn_grad_scope()
+        L = _lib.lib()
+        J = params.shape[0]
+        nl = len(self.nn_W)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        params = params.to(**f64).contiguous()
+        templ = templ.to(**f64).contiguous()
+        tbar = tbar.to(**f64).contiguous()
+        if templ.shape != (J, self.ntp) or tbar.shape != (J, self.ntp):
+            raise ValueError('nn_vjp: templ and tbar are [J, ntp] = [%d, %d]'
+                             % (J, self.ntp))
+        nb = L.rvs_template_nn_vjp_work_size(J, nl, _lib.ptr(self.nn_dims))
+        work = torch.empty((nb + 7) // 8, **f64)
+        gparams = torch.empty((J, self.ndim), **f64)
+        Wp = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in self.nn_W])
+        bp = (ctypes.c_void_p * nl)(*[b.data_ptr() for b in self.nn_b])
+        from . import engine
+        with engine._ktime('template_nn_vjp', J):
+            rc = L.rvs_template_nn_vjp(
+                _lib.ptr(params), J, self.ndim, self.log_mask, _lib.ptr(self.nn_M),
+                _lib.ptr(self.nn_S), nl, ctypes.cast(Wp, ctypes.c_void_p),
+                ctypes.cast(bp, ctypes.c_void_p), _lib.ptr(self.nn_dims),
+                _lib.ptr(templ), _lib.ptr(tbar), _lib.ptr(work), _lib.ptr(gparams),
+                _lib.stream())
+        _lib.check(rc, 'rvs_template_nn_vjp')
+        return gparams
+
     def hull_device(self):
         """(xeqs, yeqs) facet equations of the two convex hulls on the device,
         or None for a library without an outside check"""

@@ -363,6 +363,9 @@ class GradChain:
     rvs_objective_grad call per chunk (rvs_bfgs_run_grad_fused; csrc/objective_grad.hip)
     -- the object then holds no template or record buffers, only the arm descriptors,
     the kernel's scratch and the chunk's chi / grad; `rows` goes through the same call.
+    On MLP libraries (the objective's nn_gradient set; rvs_bfgs_run_grad_fused_nn, DESIGN
+    4.25) it also holds a chunk's adjoint rows [cap, ntp] per arm and the work of the
+    networks' reverse pass.
     What that kernel does not cover, fisher=True included, raises ValueError.
     fused_fisher=True (config['fused_fisher']): the Fisher form with the rows' value,
     gradient and matrix from ONE rvs_objective_fisher call per chunk (rvs_lm_run_fused;
@@ -506,8 +509,11 @@ class GradChain:
         fit = pobj.vsini_col >= 0
         engine.check_fused_grad_scope(
             batch, libs, pobj.npoly, pobj.resols, False, vsini_grad=fit,
-            what='the Fisher form of the chain (fisher=True)' if fisher else None)
+            what='the Fisher form of the chain (fisher=True)' if fisher else None,
+            nn_gradient=getattr(pobj, 'nn_gradient', False))
         self.pobj, self.fisher = pobj, False
+        # MLP libraries (admitted with nn_gradient): rvs_bfgs_run_grad_fused_nn
+        self.fused_nn = libs[batch.arms[0].name].kind == 'nn'
         dev = pobj.dev
         narm = len(batch.arms)
         self.ntan = pobj.ndim + (1 if fit else 0)
@@ -523,8 +529,32 @@ class GradChain:
         self.bconst = (ctypes.c_double * narm)()
         self._keep = engine.fill_objective_grad_arms(self.garms, self.bconst, batch, libs,
                                                      pobj.npoly, pobj.rbf)
-        self.nbytes = int(L.rvs_objective_grad_work_size(cap, narm, self.ntan))
-        self.gwork = torch.empty((self.nbytes + 7) // 8, **f64)
+        if self.fused_nn:
+            # the adjoint rows and the reverse pass's work of a chunk are this object's
+            if not pobj.native:
+                raise ValueError("config['fused_gradient'] on MLP libraries needs the "
+                                 'rounds inside the library (the from-template objective)')
+            vg = 1 if fit else 0
+            ls = [libs[a.name] for a in batch.arms]
+            self.nbytes = int(L.rvs_objective_grad_from_template_work_size(cap, narm, vg))
+            self.tbar = [torch.empty((cap, lib.ntp), **f64) for lib in ls]
+            self.gparams = [torch.empty((cap, pobj.ndim), **f64) for lib in ls]
+            self.vjp_work = [torch.empty(
+                (int(L.rvs_template_nn_vjp_work_size(cap, len(lib.nn_W),
+                                                     _lib.ptr(lib.nn_dims))) + 7) // 8,
+                **f64) for lib in ls]
+            self.grad_vv = torch.empty((cap, 1 + vg), **f64)
+            self.tbar_p = (ctypes.c_void_p * narm)(*[t.data_ptr() for t in self.tbar])
+            self.gparams_p = (ctypes.c_void_p * narm)(*[t.data_ptr()
+                                                        for t in self.gparams])
+            self.vjp_work_p = (ctypes.c_void_p * narm)(*[t.data_ptr()
+                                                         for t in self.vjp_work])
+            self.gwork = torch.empty((self.nbytes + 7) // 8, **f64)
+            self.nbytes += sum(t.numel() * 8 for t in
+                               self.tbar + self.gparams + self.vjp_work)
+        else:
+            self.nbytes = int(L.rvs_objective_grad_work_size(cap, narm, self.ntan))
+            self.gwork = torch.empty((self.nbytes + 7) // 8, **f64)
         self.chi = torch.empty(cap, **f64)
         self.grad = torch.empty((cap, 1 + self.ntan), **f64)
         self.njev = torch.zeros(pobj.S, dtype=torch.int32, device=dev)

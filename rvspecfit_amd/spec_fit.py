@@ -510,7 +510,11 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
     With config['fused_gradient'] true value and gradient come from one kernel per
     (spectrum, setup) (rvs_objective_grad, the adjoint method: no template or tangent
     row in HBM) -- regular-grid libraries of up to 4 parameters, npoly <= 10; anything
-    else beside that key raises ValueError naming the option and the key.
+    else beside that key raises ValueError naming the option and the key.  With
+    config['nn_gradient'] beside it MLP libraries are taken too: the kernel's
+    from-template form hands one adjoint row per (spectrum, setup) to the network's
+    reverse pass (rvs_objective_grad_from_template, rvs_template_nn_vjp), the parameter
+    components in float32 arithmetic.
     An MLP library is among them unless config['nn_gradient'] is true: its tangent
     rows (rvs_template_nn_grad) are float32 arithmetic, exact to float32 rounding only.  On a Delaunay library a point that no simplex
     holds has the value's penalty and a zero gradient."""
@@ -595,12 +599,14 @@ def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
         # (rvs_objective_grad); what it does not cover is an error, not the chain
         engine.check_fused_grad_scope(batch, libs, npoly, resols, fast_interp,
                                       vsini_grad,
-                                      what='the Fisher matrix' if fisher else None)
+                                      what='the Fisher matrix' if fisher else None,
+                                      nn_gradient=nn_gradient)
         if not outside_penalty:
             raise ValueError("config['fused_gradient'] does not go with "
                              'outside_penalty=False: the kernel adds the penalty')
         return engine.objective_grad_fused(batch, libs, params, vsini, vel, npoly, rbf,
-                                           js, vsini_grad, esys)
+                                           js, vsini_grad, esys,
+                                           nn_gradient=nn_gradient)
     if fused_fisher and fisher:
         # config['fused_fisher']: value, gradient and Fisher matrix in one forward-mode
         # kernel per (job, arm) (rvs_objective_fisher); what it does not cover is an

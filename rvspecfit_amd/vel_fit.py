@@ -1054,7 +1054,7 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
         engine.check_fused_grad_scope(
             batch, spec_inter.get_libs(batch.names, config), options.get('npoly') or 5,
             spec_fit._resols(batch, resolParams), bool(options.get('fast_interp')),
-            vsini_grad=fitVsini,
+            vsini_grad=fitVsini, nn_gradient=bool(config.get('nn_gradient')),
             what="config['second_minimizer_lm'] (the Levenberg-Marquardt polish on the "
                  "Fisher matrix)" if lm_polish else
                  ("config['fisher_uncertainties'] (the Fisher matrix)"

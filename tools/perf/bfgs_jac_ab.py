@@ -2,10 +2,12 @@
 """The BFGS polish of vel_fit.process on S spectra: the forward-difference polish
 (rvs_bfgs_run) against the polish on the analytic gradient (rvs_bfgs_run_grad,
 config['second_minimizer_jac']), alternating, in one process.
-usage: bfgs_jac_ab.py [--spectra S] [--npoly P] [--rounds R] [--evaluator polylinear|tri]
+usage: bfgs_jac_ab.py [--spectra S] [--npoly P] [--rounds R] [--evaluator polylinear|tri|nn]
                       [--fused]
 --fused: a third polish, the analytic gradient from rvs_objective_grad
 (rvs_bfgs_run_grad_fused, config['fused_gradient']), alternating with the two.
+--evaluator nn: bench.py's MLP libraries; the chain then runs with config['nn_gradient']
+and --fused through rvs_bfgs_run_grad_fused_nn.
 The workload is bench.py's, built as `bench.py --process` builds it (its synthetic
 DESI-shape libraries and seeded spectra, the start parameters from the CCF stage of
 pipeline.fit_batch).  vel_fit.process runs once without the second minimiser; its
@@ -29,7 +31,7 @@ def main():
     ap.add_argument('--spectra', type=int, default=2000)
     ap.add_argument('--npoly', type=int, default=10)
     ap.add_argument('--rounds', type=int, default=3)
-    ap.add_argument('--evaluator', choices=['polylinear', 'tri'], default='polylinear')
+    ap.add_argument('--evaluator', choices=['polylinear', 'tri', 'nn'], default='polylinear')
     ap.add_argument('--fused', action='store_true')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
@@ -55,8 +57,11 @@ def main():
     tp = bench.truth_params(S, seed=3)
     batch = engine.SpecBatch([engine.ArmData(n, lam, sp, es, bad, device=dev)
                               for n, lam, sp, es, bad in
-                              bench.make_spectra_device(tp, dev)])
+                              (bench.make_spectra_device(tp, dev) if args.evaluator != 'nn'
+                               else bench.make_spectra_from_library(tp, dev, bench.CONFIG))])
     cfg, opt = dict(bench.CONFIG), dict(bench.OPTIONS, npoly=args.npoly)
+    if args.evaluator == 'nn':
+        cfg['nn_gradient'] = True
     # the start of process: the CCF stage's parameters (bench.run_process_addon)
     rec = pipeline.fit_batch(batch, cfg, options=opt)
     F = pipeline.RECORD_FIELDS

@@ -11,9 +11,10 @@
 //   rounds_emit_kernel   the requested points into one list (spectrum order)
 //   <objective>          rvs_proc_map -> objective kernel -> rvs_proc_finish per chunk
 //                        of `cap` rows (nm.hip: the objective of rvs_nm_run)
-// with the counts on the device: the host looks (a 128-byte copy) every round while
-// the launches are large, every few rounds in the tail, and only to bound the
-// launches and to see the end -- a run's path does not depend on when it looks.
+// driven by rounds_run (rounds_dev.h), the one round driver of this file and of
+// lm_dev.hip: the counts stay on the device, and when the host looks at them is its
+// policy.  Every entry point here checks its arguments and hands rounds_run, through
+// bfgs_rounds, how a chunk of rows is answered.
 // The host-driven form of the same rounds (bfgs_host.cpp behind a Python objective)
 // cost 1.6 ms per round in torch calls and copies: 0.35 s per 2000 spectra on 0.19 s
 // of objective kernels.
@@ -37,7 +38,7 @@ __device__ inline const double *rounds_request_rows(const Run &r) { return r.row
 
 }  // namespace
 
-#include "rounds_dev.h"   // the scan and the emit of a round (shared with lm_dev.hip)
+#include "rounds_dev.h"   // scan, emit and the round driver (shared with lm_dev.hip)
 
 namespace {
 
@@ -110,210 +111,99 @@ __global__ void __launch_bounds__(256) bfgs_njev_kernel(BfgsDev D, int32_t *njev
 
 extern "C" int64_t rvs_bfgs_run_bytes(void) { return (int64_t)sizeof(Run); }
 
-extern "C" int rvs_bfgs_run(const rvs_bfgs_state *b, const rvs_nm_objective *o,
-                            int sync_every, int64_t *stats, void *stream) {
-  if (!b || !o || b->S < 1 || b->n < 1 || b->n > 8 || b->n != o->n || b->cap < 1 ||
-      sync_every < 1 || !b->runs || !b->x0 || !b->x || !b->fun || !b->nit ||
-      !b->nfev || !b->status || !b->nreq || !b->off || !b->list || !b->X || !b->F ||
-      !b->counts)
-    return RVS_E_ARG;
-  const int S = b->S, n = b->n, cap = b->cap;
-  const int64_t maxrows = (int64_t)S * (n + 1);
-  if ((maxrows + cap - 1) / cap > BF_NCHUNK) return RVS_E_ARG;
-  hipStream_t st = rvs_stream(stream);
-  BfgsDev D;
-  D.runs = static_cast<Run *>(b->runs);
-  D.S = S, D.n = n, D.cap = cap;
-  D.x0 = b->x0, D.H0 = b->hess_inv0;
-  D.gtol = b->gtol, D.c1 = b->c1, D.c2 = b->c2, D.xrtol = b->xrtol;
-  D.maxiter = b->maxiter;
-  D.nreq = b->nreq, D.off = b->off, D.list = b->list, D.counts = b->counts;
-  D.X = b->X, D.F = b->F;
-  const dim3 agrid((S + BF_NT - 1) / BF_NT);
-  const dim3 egrid((int)((maxrows + 255) / 256));
-  auto step = [&](int first) {
-    hipLaunchKernelGGL(bfgs_advance_kernel, agrid, dim3(BF_NT), 0, st, D, first);
-    hipLaunchKernelGGL(rounds_scan_kernel<BfgsDev>, dim3(1), dim3(BF_SCAN_NT), 0, st, D);
-    hipLaunchKernelGGL(rounds_emit_kernel<BfgsDev>, egrid, dim3(256), 0, st, D);
-  };
-  step(1);
-  RVS_LAUNCH_CHECK();
-  int64_t rounds = 0, calls = 0, jobs = 0;
-  int32_t c[BF_NCHUNK + 8];
-  while (true) {
-    if (hipMemcpyAsync(c, b->counts, sizeof(int32_t) * (BF_NCHUNK + 2),
-                       hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return RVS_E_LAUNCH;
-    const int64_t total = c[BF_NCHUNK], live = c[BF_NCHUNK + 1];
-    if (total == 0) break;
-    // (large launches: one look per round, so that every chunk launched has rows;
-    // the tail: every sync_every rounds behind the bound "every live run asks for a
-    // value and a gradient", the rows behind the device count cost next to nothing)
-    const int window = (total > 4096) ? 1 : sync_every;
-    for (int r = 0; r < window; r++) {
-      int64_t bound = (r == 0) ? total : live * (n + 1);
-      if (bound > maxrows) bound = maxrows;
-      for (int64_t a = 0, ch = 0; a < bound; a += cap, ch++) {
-        const int J = (int)((bound - a < cap) ? bound - a : cap);
-        int rc = rvs_internal_nm_eval(o, b->list + a, b->X + a * n, J, b->counts,
-                                      (int)ch, b->F + a, st);
-        if (rc) return rc;
-        calls++;
-        jobs += J;
-      }
-      step(0);
-      RVS_LAUNCH_CHECK();
-      rounds++;
-    }
-  }
-  hipLaunchKernelGGL(bfgs_result_kernel, agrid, dim3(BF_NT), 0, st, D, b->x, b->fun,
-                     b->hess_inv, b->nit, b->nfev, b->status);
-  RVS_LAUNCH_CHECK();
-  if (hipStreamSynchronize(st) != hipSuccess) return RVS_E_LAUNCH;
-  if (stats) {
-    stats[0] = rounds;
-    stats[1] = calls;
-    stats[2] = jobs;
-  }
-  return 0;
-}
-
 namespace {
 
-// what both forms of the exact-gradient polish ask of b and o beside their own checks
-bool bfgs_jac_args_ok(const rvs_bfgs_state *b, const rvs_nm_objective *o,
-                      const rvs_grad_chain *g, int sync_every) {
-  return b && o && g && b->S >= 1 && b->n >= 1 && b->n <= 8 && b->n == o->n &&
+// what every form asks of b and o beside its own checks
+bool bfgs_args_ok(const rvs_bfgs_state *b, const rvs_nm_objective *o, int sync_every) {
+  return b && o && b->S >= 1 && b->n >= 1 && b->n <= 8 && b->n == o->n &&
          sync_every >= 1 && b->runs && b->x0 && b->x && b->fun && b->nit && b->nfev &&
-         b->status && b->nreq && b->off && b->list && b->X && b->F && b->counts &&
-         g->njev;
+         b->status && b->nreq && b->off && b->list && b->X && b->F && b->counts;
 }
 
-// the rounds of rvs_bfgs_run_grad over eval(list, X, J, chunk, F, stream): (f, grad f)
-// of a chunk of rows into F [J, 1 + n]
+// the rounds of the machine (rounds_run) over eval(list, X, J, chunk, F, stream).
+// njev == NULL: rvs_bfgs_run -- a live run asks for up to n + 1 values, F [J]; else the
+// jac form -- a live run asks for its one row, answered with (f, grad f), F [J, 1 + n]
 template <class Eval>
-int bfgs_run_jac(const rvs_bfgs_state *b, const rvs_grad_chain *g, int sync_every,
-                 int64_t *stats, void *stream, Eval eval) {
-  const int S = b->S, n = b->n, cap = g->cap;
-  const int64_t maxrows = S;   // one row per live run
-  if ((maxrows + cap - 1) / cap > BF_NCHUNK) return RVS_E_ARG;
-  hipStream_t st = rvs_stream(stream);
+int bfgs_rounds(const rvs_bfgs_state *b, int cap, int32_t *njev, int sync_every,
+                int64_t *stats, void *stream, Eval eval) {
+  const int S = b->S, n = b->n;
   BfgsDev D;
-  D.runs = static_cast<Run *>(b->runs);
-  D.S = S, D.n = n, D.cap = cap;
+  rounds_fill(D, b, static_cast<Run *>(b->runs), cap);
   D.x0 = b->x0, D.H0 = b->hess_inv0;
   D.gtol = b->gtol, D.c1 = b->c1, D.c2 = b->c2, D.xrtol = b->xrtol;
   D.maxiter = b->maxiter;
-  D.nreq = b->nreq, D.off = b->off, D.list = b->list, D.counts = b->counts;
-  D.X = b->X, D.F = b->F;
   const dim3 agrid((S + BF_NT - 1) / BF_NT);
-  const dim3 egrid((int)(((int64_t)S * (n + 1) + 255) / 256));
-  auto step = [&](int first) {
-    hipLaunchKernelGGL(bfgs_advance_jac_kernel, agrid, dim3(BF_NT), 0, st, D, first);
-    hipLaunchKernelGGL(rounds_scan_kernel<BfgsDev>, dim3(1), dim3(BF_SCAN_NT), 0, st, D);
-    hipLaunchKernelGGL(rounds_emit_kernel<BfgsDev>, egrid, dim3(256), 0, st, D);
-  };
-  step(1);
-  RVS_LAUNCH_CHECK();
-  int64_t rounds = 0, calls = 0, jobs = 0;
-  int32_t c[BF_NCHUNK + 8];
-  while (true) {
-    if (hipMemcpyAsync(c, b->counts, sizeof(int32_t) * (BF_NCHUNK + 2),
-                       hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return RVS_E_LAUNCH;
-    const int64_t total = c[BF_NCHUNK], live = c[BF_NCHUNK + 1];
-    if (total == 0) break;
-    // (the policy of rvs_bfgs_run; behind the look every live run asks for at most
-    // its one row)
-    const int window = (total > 4096) ? 1 : sync_every;
-    for (int r = 0; r < window; r++) {
-      int64_t bound = (r == 0) ? total : live;
-      if (bound > maxrows) bound = maxrows;
-      for (int64_t a = 0, ch = 0; a < bound; a += cap, ch++) {
-        const int J = (int)((bound - a < cap) ? bound - a : cap);
-        int rc = eval(b->list + a, b->X + a * n, J, (int)ch, b->F + a * (n + 1), st);
-        if (rc) return rc;
-        calls++;
-        jobs += J;
-      }
-      step(0);
-      RVS_LAUNCH_CHECK();
-      rounds++;
-    }
-  }
-  hipLaunchKernelGGL(bfgs_result_kernel, agrid, dim3(BF_NT), 0, st, D, b->x, b->fun,
-                     b->hess_inv, b->nit, b->nfev, b->status);
-  hipLaunchKernelGGL(bfgs_njev_kernel, dim3((S + 255) / 256), dim3(256), 0, st, D,
-                     g->njev);
-  RVS_LAUNCH_CHECK();
-  if (hipStreamSynchronize(st) != hipSuccess) return RVS_E_LAUNCH;
-  if (stats) {
-    stats[0] = rounds;
-    stats[1] = calls;
-    stats[2] = jobs;
-  }
-  return 0;
+  return rounds_run(
+      D, njev ? 1 : n + 1, njev ? n + 1 : 1, sync_every, stats, stream,
+      [&](int first, hipStream_t st) {
+        hipLaunchKernelGGL(njev ? bfgs_advance_jac_kernel : bfgs_advance_kernel, agrid,
+                           dim3(BF_NT), 0, st, D, first);
+      },
+      eval,
+      [&](hipStream_t st) {
+        hipLaunchKernelGGL(bfgs_result_kernel, agrid, dim3(BF_NT), 0, st, D, b->x, b->fun,
+                           b->hess_inv, b->nit, b->nfev, b->status);
+        if (njev)
+          hipLaunchKernelGGL(bfgs_njev_kernel, dim3((S + 255) / 256), dim3(256), 0, st, D,
+                             njev);
+      });
 }
 
 }  // namespace
 
+extern "C" int rvs_bfgs_run(const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                            int sync_every, int64_t *stats, void *stream) {
+  if (!bfgs_args_ok(b, o, sync_every)) return RVS_E_ARG;
+  return bfgs_rounds(b, b->cap, nullptr, sync_every, stats, stream,
+                     [&](const int32_t *list, const double *X, int J, int ch, double *F,
+                         hipStream_t st) {
+                       return rvs_internal_nm_eval(o, list, X, J, b->counts, ch, F, st);
+                     });
+}
+
+// The polish on the exact gradient: every form runs bfgs_rounds with g->cap rows per
+// chunk and differs in how a chunk's (f, grad f) come about -- here through the chain
 extern "C" int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective *o,
                                  const rvs_grad_chain *g, int sync_every,
                                  int64_t *stats, void *stream) {
-  if (!bfgs_jac_args_ok(b, o, g, sync_every) || !rvs_internal_grad_chain_ok(g, o))
+  if (!bfgs_args_ok(b, o, sync_every) || !g || !g->njev ||
+      !rvs_internal_grad_chain_ok(g, o))
     return RVS_E_ARG;
-  return bfgs_run_jac(b, g, sync_every, stats, stream,
-                      [&](const int32_t *list, const double *X, int J, int ch, double *F,
-                          hipStream_t st) {
-                        return rvs_internal_grad_chain_eval(o, g, list, X, J, b->counts,
-                                                            ch, F, st);
-                      });
+  return bfgs_rounds(b, g->cap, g->njev, sync_every, stats, stream,
+                     [&](const int32_t *list, const double *X, int J, int ch, double *F,
+                         hipStream_t st) {
+                       return rvs_internal_grad_chain_eval(o, g, list, X, J, b->counts,
+                                                           ch, F, st);
+                     });
 }
 
-// ... with the chain's stages between rvs_proc_map and rvs_proc_finish_grad replaced by
-// one rvs_objective_grad call (objective_grad.hip)
+// ... with the chain's stages between the map and the finish replaced by one
+// rvs_objective_grad call (objective_grad.hip)
 extern "C" int rvs_bfgs_run_grad_fused(const rvs_bfgs_state *b,
                                        const rvs_nm_objective *o,
                                        const rvs_grad_chain *g,
                                        const rvs_objective_arm *garms,
                                        const double *basis_const, void *gwork,
                                        int sync_every, int64_t *stats, void *stream) {
-  if (!bfgs_jac_args_ok(b, o, g, sync_every) || !garms || !gwork || !g->chi ||
-      !g->grad || g->cap < 1 || g->narm < 1 || g->narm > RVS_MAX_ARMS ||
-      g->narm != o->narm || g->vsini_mode < 0 || g->vsini_mode > 2 || o->ndim < 1 ||
-      o->ndim > 4 || g->ntan != o->ndim + (g->vsini_mode == 2 ? 1 : 0) ||
-      (g->vsini_mode == 2) != (o->vsini_col >= 0) ||
-      (g->vsini_mode != 0) != (o->vsini != nullptr) || !o->vel || !o->params ||
-      !o->extra || !o->bad || !o->job_spec || !o->jstatus || !o->status || !o->fixed ||
-      !o->safe)
+  if (!bfgs_args_ok(b, o, sync_every) || !g || !g->njev || !garms || !gwork ||
+      !rvs_internal_grad_rows_ok(g, o, 4))
     return RVS_E_ARG;
   for (int a = 0; a < g->narm; a++)
-    if (garms[a].ndim != o->ndim || garms[a].pt.taps || garms[a].pt.G > 1 ||
-        garms[a].pt.fast_interp ||
+    if (garms[a].ndim != o->ndim || !rvs_internal_arm_plain(garms[a]) ||
         !rvs_objective_grad_ok(o->npoly, garms[a].pt.npix, garms[a].ntp, o->ndim,
                                g->vsini_mode == 2))
       return RVS_E_ARG;
-  return bfgs_run_jac(
-      b, g, sync_every, stats, stream,
+  return bfgs_rounds(
+      b, g->cap, g->njev, sync_every, stats, stream,
       [&](const int32_t *list, const double *X, int J, int ch, double *F,
           hipStream_t st) {
-        int rc = rvs_proc_map(J, o->n, o->ndim, X, list, o->src, o->vsini_col, o->fixed,
-                              o->vsini_fixed, o->safe, o->prior_mean, o->prior_isig,
-                              o->min_vel, o->max_vel, o->max_vsini, o->job_spec, o->vel,
-                              o->vsini, o->params, o->extra, o->bad, st);
-        if (rc) return rc;
-        if (hipMemsetAsync(o->jstatus, 0, sizeof(int32_t) * J, st) != hipSuccess)
-          return RVS_E_LAUNCH;
-        rc = rvs_objective_grad(garms, g->narm, o->npoly, g->ntan, o->params, o->vsini,
-                                o->job_spec, J, o->vel, o->badchi, basis_const, gwork,
-                                g->chi, g->grad, o->jstatus, st);
-        if (rc) return rc;
-        return rvs_proc_finish_grad(J, o->n, o->ndim, g->ntan, b->counts, ch, g->chi,
-                                    g->grad, X, o->params, o->extra, o->bad, o->job_spec,
-                                    o->jstatus, o->src, o->vsini_col, o->prior_mean,
-                                    o->prior_isig, o->max_vsini, F, o->status, st);
+        return rvs_internal_fused_eval(
+            o, g, nullptr, list, X, J, b->counts, ch, F, st, [&] {
+              return rvs_objective_grad(garms, g->narm, o->npoly, g->ntan, o->params,
+                                        o->vsini, o->job_spec, J, o->vel, o->badchi,
+                                        basis_const, gwork, g->chi, g->grad, o->jstatus,
+                                        st);
+            });
       });
 }
 
@@ -330,15 +220,8 @@ extern "C" int rvs_bfgs_run_grad_fused_nn(
     const rvs_objective_arm *garms, const double *basis_const, void *gwork,
     double *const *tbar, void *const *vjp_work, double *const *gparams, double *grad_vv,
     int sync_every, int64_t *stats, void *stream) {
-  if (!bfgs_jac_args_ok(b, o, g, sync_every) || !garms || !gwork || !tbar || !vjp_work ||
-      !gparams || !grad_vv || !g->chi || !g->grad || g->cap < 1 || g->narm < 1 ||
-      g->narm > RVS_MAX_ARMS || g->narm != o->narm || g->vsini_mode < 0 ||
-      g->vsini_mode > 2 || o->ndim < 1 || o->ndim > 6 || !o->nn ||
-      g->ntan != o->ndim + (g->vsini_mode == 2 ? 1 : 0) ||
-      (g->vsini_mode == 2) != (o->vsini_col >= 0) ||
-      (g->vsini_mode != 0) != (o->vsini != nullptr) || !o->vel || !o->params ||
-      !o->extra || !o->bad || !o->job_spec || !o->jstatus || !o->status || !o->fixed ||
-      !o->safe)
+  if (!bfgs_args_ok(b, o, sync_every) || !g || !g->njev || !garms || !gwork || !tbar ||
+      !vjp_work || !gparams || !grad_vv || !rvs_internal_grad_rows_ok(g, o, 6) || !o->nn)
     return RVS_E_ARG;
   const int vg = g->vsini_mode == 2 ? 1 : 0;
   const double *tp[RVS_MAX_ARMS], *op[RVS_MAX_ARMS];
@@ -346,44 +229,35 @@ extern "C" int rvs_bfgs_run_grad_fused_nn(
     const rvs_nm_nn_arm &N = o->nn[a];
     if (!tbar[a] || !vjp_work[a] || !gparams[a] || !N.templ || !N.outside || !N.dims ||
         N.dims[0] != o->ndim || N.nlayer < 1 || N.dims[N.nlayer] != garms[a].ntp ||
-        garms[a].pt.taps || garms[a].pt.G > 1 || garms[a].pt.fast_interp ||
+        !rvs_internal_arm_plain(garms[a]) ||
         !rvs_objective_grad_from_template_ok(o->npoly, garms[a].pt.npix, garms[a].ntp, vg) ||
         rvs_template_nn_vjp_work_size(g->cap, N.nlayer, N.dims) <= 0)
       return RVS_E_ARG;
     tp[a] = N.templ;
     op[a] = N.outside;
   }
-  return bfgs_run_jac(
-      b, g, sync_every, stats, stream,
+  return bfgs_rounds(
+      b, g->cap, g->njev, sync_every, stats, stream,
       [&](const int32_t *list, const double *X, int J, int ch, double *F,
           hipStream_t st) {
-        int rc = rvs_proc_map(J, o->n, o->ndim, X, list, o->src, o->vsini_col, o->fixed,
-                              o->vsini_fixed, o->safe, o->prior_mean, o->prior_isig,
-                              o->min_vel, o->max_vel, o->max_vsini, o->job_spec, o->vel,
-                              o->vsini, o->params, o->extra, o->bad, st);
-        if (rc) return rc;
-        if (hipMemsetAsync(o->jstatus, 0, sizeof(int32_t) * J, st) != hipSuccess)
-          return RVS_E_LAUNCH;
-        rc = rvs_template_nn_arms_n(o->params, J, nullptr, o->ndim, o->narm, o->nn, st);
-        if (rc) return rc;
-        rc = rvs_objective_grad_from_template(garms, g->narm, o->npoly, vg, tp, op,
-                                              o->vsini, o->job_spec, J, o->vel, o->badchi,
-                                              basis_const, gwork, tbar, g->chi, grad_vv,
-                                              o->jstatus, st);
-        if (rc) return rc;
-        for (int a = 0; a < g->narm; a++) {
-          const rvs_nm_nn_arm &N = o->nn[a];
-          rc = rvs_template_nn_vjp(o->params, J, o->ndim, N.log_mask, N.M, N.S, N.nlayer,
-                                   N.W, N.b, N.dims, N.templ, tbar[a], vjp_work[a],
-                                   gparams[a], st);
-          if (rc) return rc;
-        }
-        rc = rvs_objective_grad_join(g->narm, J, o->ndim, vg, gwork, gparams, g->chi,
-                                     grad_vv, g->grad, st);
-        if (rc) return rc;
-        return rvs_proc_finish_grad(J, o->n, o->ndim, g->ntan, b->counts, ch, g->chi,
-                                    g->grad, X, o->params, o->extra, o->bad, o->job_spec,
-                                    o->jstatus, o->src, o->vsini_col, o->prior_mean,
-                                    o->prior_isig, o->max_vsini, F, o->status, st);
+        return rvs_internal_fused_eval(
+            o, g, nullptr, list, X, J, b->counts, ch, F, st, [&] {
+              int rc = rvs_template_nn_arms_n(o->params, J, nullptr, o->ndim, o->narm,
+                                              o->nn, st);
+              if (rc) return rc;
+              rc = rvs_objective_grad_from_template(
+                  garms, g->narm, o->npoly, vg, tp, op, o->vsini, o->job_spec, J, o->vel,
+                  o->badchi, basis_const, gwork, tbar, g->chi, grad_vv, o->jstatus, st);
+              if (rc) return rc;
+              for (int a = 0; a < g->narm; a++) {
+                const rvs_nm_nn_arm &N = o->nn[a];
+                rc = rvs_template_nn_vjp(o->params, J, o->ndim, N.log_mask, N.M, N.S,
+                                         N.nlayer, N.W, N.b, N.dims, N.templ, tbar[a],
+                                         vjp_work[a], gparams[a], st);
+                if (rc) return rc;
+              }
+              return rvs_objective_grad_join(g->narm, J, o->ndim, vg, gwork, gparams,
+                                             g->chi, grad_vv, g->grad, st);
+            });
       });
 }

@@ -21,6 +21,11 @@
 // The chain is engine.build_templates(tangents=True, vsini_tangent=...) +
 // engine.chisq_point_grad: the same entry points with the same arguments, called from
 // C on one stream, so a row has the bits spec_fit.chisq_grad_jobs gives it.
+//
+// The steps the chain shares with the fused forms of bfgs_dev.hip and lm_dev.hip are
+// the internal entries of nm_internal.h: the map (nm.hip), the finish of either form
+// (rvs_internal_proc_finish) and the check that g and o fit each other
+// (rvs_internal_grad_rows_ok); the rounds around a chunk are rounds_run's (rounds_dev.h).
 #include "common.h"
 #include "nm_internal.h"
 
@@ -134,17 +139,23 @@ __global__ void __launch_bounds__(256)
   out_rows[t] = outside[t / R];
 }
 
-int chain_ok(const rvs_grad_chain *g, const rvs_nm_objective *o) {
-  if (!g || !o || !g->arms || !g->point || !g->point_work || !g->chi || !g->grad ||
-      g->narm < 1 || g->narm > RVS_MAX_ARMS || g->narm != o->narm || g->cap < 1 ||
-      g->vsini_mode < 0 || g->vsini_mode > 2 || o->ndim < 1 || o->ndim > 6 ||
-      o->n < 1 || o->n > 8)
-    return 0;
-  if (g->ntan != o->ndim + (g->vsini_mode == 2 ? 1 : 0) || g->ntan > 6) return 0;
-  if ((g->vsini_mode == 2) != (o->vsini_col >= 0)) return 0;
-  if ((g->vsini_mode != 0) != (o->vsini != nullptr)) return 0;
-  if (!o->vel || !o->params || !o->extra || !o->bad || !o->job_spec || !o->jstatus ||
-      !o->status || !o->fixed || !o->safe)
+}  // namespace
+
+int rvs_internal_grad_rows_ok(const rvs_grad_chain *g, const rvs_nm_objective *o,
+                              int max_ndim) {
+  return g && o && g->chi && g->grad && g->cap >= 1 && g->narm >= 1 &&
+         g->narm <= RVS_MAX_ARMS && g->narm == o->narm && g->vsini_mode >= 0 &&
+         g->vsini_mode <= 2 && o->ndim >= 1 && o->ndim <= max_ndim &&
+         g->ntan == o->ndim + (g->vsini_mode == 2 ? 1 : 0) &&
+         (g->vsini_mode == 2) == (o->vsini_col >= 0) &&
+         (g->vsini_mode != 0) == (o->vsini != nullptr) && o->vel && o->params &&
+         o->extra && o->bad && o->job_spec && o->jstatus && o->status && o->fixed &&
+         o->safe;
+}
+
+int rvs_internal_grad_chain_ok(const rvs_grad_chain *g, const rvs_nm_objective *o) {
+  if (!rvs_internal_grad_rows_ok(g, o, 6) || !g->arms || !g->point || !g->point_work ||
+      g->ntan > 6 || o->n < 1 || o->n > 8)
     return 0;
   for (int a = 0; a < g->narm; a++) {
     const rvs_grad_arm &A = g->arms[a];
@@ -168,8 +179,6 @@ int chain_ok(const rvs_grad_chain *g, const rvs_nm_objective *o) {
   }
   return 1;
 }
-
-}  // namespace
 
 namespace {
 
@@ -274,8 +283,19 @@ extern "C" int64_t rvs_fisher_chain_work_size(int cap, int narm, int ntan,
          (int64_t)cap * K * K * sizeof(double);
 }
 
-int rvs_internal_grad_chain_ok(const rvs_grad_chain *g, const rvs_nm_objective *o) {
-  return chain_ok(g, o);
+int rvs_internal_proc_finish(const rvs_nm_objective *o, const rvs_grad_chain *g,
+                             const double *fisher, const double *X, int J,
+                             const int32_t *counts, int cidx, double *F, hipStream_t st) {
+  if (fisher)
+    return rvs_proc_finish_fisher(J, o->n, o->ndim, g->ntan, counts, cidx, g->chi,
+                                  g->grad, fisher, X, o->params, o->extra, o->bad,
+                                  o->job_spec, o->jstatus, o->src, o->vsini_col,
+                                  o->prior_mean, o->prior_isig, o->max_vsini, F,
+                                  o->status, st);
+  return rvs_proc_finish_grad(J, o->n, o->ndim, g->ntan, counts, cidx, g->chi, g->grad, X,
+                              o->params, o->extra, o->bad, o->job_spec, o->jstatus,
+                              o->src, o->vsini_col, o->prior_mean, o->prior_isig,
+                              o->max_vsini, F, o->status, st);
 }
 
 int rvs_internal_grad_chain_eval(const rvs_nm_objective *o, const rvs_grad_chain *g,
@@ -285,10 +305,7 @@ int rvs_internal_grad_chain_eval(const rvs_nm_objective *o, const rvs_grad_chain
   if (J < 1 || J > g->cap || (fc && (!fc->fisher_work || !fc->fisher)))
     return RVS_E_ARG;
   const int ndim = o->ndim, ntan = g->ntan;
-  int rc = rvs_proc_map(J, o->n, ndim, X, list, o->src, o->vsini_col, o->fixed,
-                        o->vsini_fixed, o->safe, o->prior_mean, o->prior_isig,
-                        o->min_vel, o->max_vel, o->max_vsini, o->job_spec, o->vel,
-                        o->vsini, o->params, o->extra, o->bad, st);
+  int rc = rvs_internal_proc_map(J, X, list, o, st);
   if (rc) return rc;
   const int R = 1 + ndim;
   for (int a = 0; a < g->narm; a++) {
@@ -341,29 +358,21 @@ int rvs_internal_grad_chain_eval(const rvs_nm_objective *o, const rvs_grad_chain
                        A.outside, g->pen_scale, o->job_spec, o->badchi, A.penalty);
     RVS_LAUNCH_CHECK();
   }
-  if (hipMemsetAsync(o->jstatus, 0, sizeof(int32_t) * J, st) != hipSuccess)
-    return RVS_E_LAUNCH;
+  rc = rvs_internal_zero_jstatus(o, J, st);
+  if (rc) return rc;
   // arms under a resolution matrix: the _resol entry points (R acts after the
   // resampling, so the template, FIR and spline stages above are as without)
   bool resol = false;
   for (int a = 0; a < g->narm; a++) resol = resol || g->point[a].taps;
-  if (fc) {   // the Fisher form of the last two calls
+  if (fc)   // the Fisher form of the last two calls
     rc = (resol ? rvs_chisq_point_fisher_resol : rvs_chisq_point_fisher)(
         g->point, g->narm, o->npoly, ntan, o->job_spec, nullptr, J, o->vel, o->badchi,
         g->basis_const, fc->fisher_work, g->chi, g->grad, fc->fisher, o->jstatus, st);
-    if (rc) return rc;
-    return rvs_proc_finish_fisher(J, o->n, ndim, ntan, counts, cidx, g->chi, g->grad,
-                                  fc->fisher, X, o->params, o->extra, o->bad,
-                                  o->job_spec, o->jstatus, o->src, o->vsini_col,
-                                  o->prior_mean, o->prior_isig, o->max_vsini, F,
-                                  o->status, st);
-  }
-  rc = (resol ? rvs_chisq_point_grad_resol : rvs_chisq_point_grad)(
-      g->point, g->narm, o->npoly, ntan, o->job_spec, nullptr, J, o->vel, o->badchi,
-      g->basis_const, g->point_work, g->chi, g->grad, o->jstatus, st);
+  else
+    rc = (resol ? rvs_chisq_point_grad_resol : rvs_chisq_point_grad)(
+        g->point, g->narm, o->npoly, ntan, o->job_spec, nullptr, J, o->vel, o->badchi,
+        g->basis_const, g->point_work, g->chi, g->grad, o->jstatus, st);
   if (rc) return rc;
-  return rvs_proc_finish_grad(J, o->n, ndim, ntan, counts, cidx, g->chi, g->grad, X,
-                              o->params, o->extra, o->bad, o->job_spec, o->jstatus,
-                              o->src, o->vsini_col, o->prior_mean, o->prior_isig,
-                              o->max_vsini, F, o->status, st);
+  return rvs_internal_proc_finish(o, g, fc ? fc->fisher : nullptr, X, J, counts, cidx, F,
+                                  st);
 }

@@ -13,7 +13,8 @@
 //                        rvs_proc_finish_fisher), or -- rvs_lm_run_fused -- one
 //                        rvs_objective_fisher call (objective_fisher.hip) between
 //                        rvs_proc_map and rvs_proc_finish_fisher
-// with the counts on the device and the host looking at them under rvs_bfgs_run's policy.
+// driven by rounds_run (rounds_dev.h), the round driver this file shares with
+// bfgs_dev.hip: the counts on the device, the host's looks at them its policy.
 #include "common.h"
 #include "lm_machine.h"
 #include "nm_internal.h"
@@ -96,70 +97,27 @@ bool lm_args_ok(const rvs_lm_state *b, const rvs_nm_objective *o, const rvs_grad
          b->counts;
 }
 
-// the rounds of rvs_lm_run over eval(list, X, J, chunk, F, stream): (f, grad f, H packed)
-// of a chunk of rows into F [J, npack(n)]
+// the rounds of the machine (rounds_run) over eval(list, X, J, chunk, F, stream): a live
+// run asks for its one row, answered with (f, grad f, H packed), F [J, npack(n)]
 template <class Eval>
-int lm_run_rows(const rvs_lm_state *b, int cap, int sync_every, int64_t *stats,
-                void *stream, Eval eval) {
-  const int S = b->S, n = b->n;
-  const int m = rvs_lm::npack(n);
-  const int64_t maxrows = S;   // one row per live run
-  if (cap < 1 || (maxrows + cap - 1) / cap > BF_NCHUNK) return RVS_E_ARG;
-  hipStream_t st = rvs_stream(stream);
+int lm_rounds(const rvs_lm_state *b, int cap, int sync_every, int64_t *stats,
+              void *stream, Eval eval) {
   LmDev D;
-  D.runs = static_cast<Run *>(b->runs);
-  D.S = S, D.n = n, D.cap = cap;
+  rounds_fill(D, b, static_cast<Run *>(b->runs), cap);
   D.x0 = b->x0;
   D.gtol = b->gtol, D.xtol = b->xtol, D.tau = b->tau, D.mu_max = b->mu_max;
   D.maxiter = b->maxiter;
-  D.nreq = b->nreq, D.off = b->off, D.list = b->list, D.counts = b->counts;
-  D.X = b->X, D.F = b->F;
-  const dim3 agrid((S + LM_NT - 1) / LM_NT);
-  const dim3 egrid((int)(((int64_t)S * (n + 1) + 255) / 256));
-  auto step = [&](int first) {
-    hipLaunchKernelGGL(lm_advance_kernel, agrid, dim3(LM_NT), 0, st, D, first);
-    hipLaunchKernelGGL(rounds_scan_kernel<LmDev>, dim3(1), dim3(BF_SCAN_NT), 0, st, D);
-    hipLaunchKernelGGL(rounds_emit_kernel<LmDev>, egrid, dim3(256), 0, st, D);
-  };
-  step(1);
-  RVS_LAUNCH_CHECK();
-  int64_t rounds = 0, calls = 0, jobs = 0;
-  int32_t c[BF_NCHUNK + 8];
-  while (true) {
-    if (hipMemcpyAsync(c, b->counts, sizeof(int32_t) * (BF_NCHUNK + 2),
-                       hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return RVS_E_LAUNCH;
-    const int64_t total = c[BF_NCHUNK], live = c[BF_NCHUNK + 1];
-    if (total == 0) break;
-    // (the policy of rvs_bfgs_run; behind the look every live run asks for at most
-    // its one row)
-    const int window = (total > 4096) ? 1 : sync_every;
-    for (int r = 0; r < window; r++) {
-      int64_t bound = (r == 0) ? total : live;
-      if (bound > maxrows) bound = maxrows;
-      for (int64_t a = 0, ch = 0; a < bound; a += cap, ch++) {
-        const int J = (int)((bound - a < cap) ? bound - a : cap);
-        int rc = eval(b->list + a, b->X + a * n, J, (int)ch, b->F + a * m, st);
-        if (rc) return rc;
-        calls++;
-        jobs += J;
-      }
-      step(0);
-      RVS_LAUNCH_CHECK();
-      rounds++;
-    }
-  }
-  hipLaunchKernelGGL(lm_result_kernel, agrid, dim3(LM_NT), 0, st, D, b->x, b->fun,
-                     b->grad, b->hess, b->mu, b->nit, b->nfev, b->status);
-  RVS_LAUNCH_CHECK();
-  if (hipStreamSynchronize(st) != hipSuccess) return RVS_E_LAUNCH;
-  if (stats) {
-    stats[0] = rounds;
-    stats[1] = calls;
-    stats[2] = jobs;
-  }
-  return 0;
+  const dim3 agrid((b->S + LM_NT - 1) / LM_NT);
+  return rounds_run(
+      D, 1, rvs_lm::npack(b->n), sync_every, stats, stream,
+      [&](int first, hipStream_t st) {
+        hipLaunchKernelGGL(lm_advance_kernel, agrid, dim3(LM_NT), 0, st, D, first);
+      },
+      eval,
+      [&](hipStream_t st) {
+        hipLaunchKernelGGL(lm_result_kernel, agrid, dim3(LM_NT), 0, st, D, b->x, b->fun,
+                           b->grad, b->hess, b->mu, b->nit, b->nfev, b->status);
+      });
 }
 
 }  // namespace
@@ -170,35 +128,28 @@ extern "C" int rvs_lm_run(const rvs_lm_state *b, const rvs_nm_objective *o,
   if (!lm_args_ok(b, o, g, sync_every) || !fc || !fc->fisher_work || !fc->fisher ||
       !rvs_internal_grad_chain_ok(g, o))
     return RVS_E_ARG;
-  return lm_run_rows(b, g->cap, sync_every, stats, stream,
-                     [&](const int32_t *list, const double *X, int J, int ch, double *F,
-                         hipStream_t st) {
-                       return rvs_internal_grad_chain_eval(o, g, list, X, J, b->counts, ch,
-                                                           F, st, fc);
-                     });
+  return lm_rounds(b, g->cap, sync_every, stats, stream,
+                   [&](const int32_t *list, const double *X, int J, int ch, double *F,
+                       hipStream_t st) {
+                     return rvs_internal_grad_chain_eval(o, g, list, X, J, b->counts, ch,
+                                                         F, st, fc);
+                   });
 }
 
-// ... with the chain's stages between rvs_proc_map and rvs_proc_finish_fisher replaced by
-// one rvs_objective_fisher call (objective_fisher.hip).  fwork: the chunk's matrices
+// ... with the chain's stages between the map and the finish replaced by one
+// rvs_objective_fisher call (objective_fisher.hip).  fwork: the chunk's matrices
 // [cap, K, K] first, the kernel's work buffer behind them
 extern "C" int rvs_lm_run_fused(const rvs_lm_state *b, const rvs_nm_objective *o,
                                 const rvs_grad_chain *g, const rvs_objective_arm *garms,
                                 const double *basis_const, void *fwork,
                                 int64_t fwork_bytes, int sync_every, int64_t *stats,
                                 void *stream) {
-  if (!lm_args_ok(b, o, g, sync_every) || !garms || !fwork || !g->chi || !g->grad ||
-      g->cap < 1 || g->narm < 1 || g->narm > RVS_MAX_ARMS || g->narm != o->narm ||
-      g->vsini_mode < 0 || g->vsini_mode > 2 || o->ndim < 1 || o->ndim > 4 ||
-      g->ntan != o->ndim + (g->vsini_mode == 2 ? 1 : 0) ||
-      (g->vsini_mode == 2) != (o->vsini_col >= 0) ||
-      (g->vsini_mode != 0) != (o->vsini != nullptr) || !o->vel || !o->params ||
-      !o->extra || !o->bad || !o->job_spec || !o->jstatus || !o->status || !o->fixed ||
-      !o->safe)
+  if (!lm_args_ok(b, o, g, sync_every) || !garms || !fwork ||
+      !rvs_internal_grad_rows_ok(g, o, 4))
     return RVS_E_ARG;
   int npix_max = 0;
   for (int a = 0; a < g->narm; a++) {
-    if (garms[a].ndim != o->ndim || garms[a].pt.taps || garms[a].pt.G > 1 ||
-        garms[a].pt.fast_interp ||
+    if (garms[a].ndim != o->ndim || !rvs_internal_arm_plain(garms[a]) ||
         !rvs_objective_fisher_ok(o->npoly, garms[a].pt.npix, garms[a].ntp, o->ndim,
                                  g->vsini_mode == 2))
       return RVS_E_ARG;
@@ -212,25 +163,16 @@ extern "C" int rvs_lm_run_fused(const rvs_lm_state *b, const rvs_nm_objective *o
   double *fisher = static_cast<double *>(fwork);
   void *kwork = fisher + (int64_t)g->cap * K * K;
   const int64_t kwork_bytes = fwork_bytes - fisher_bytes;
-  return lm_run_rows(
+  return lm_rounds(
       b, g->cap, sync_every, stats, stream,
       [&](const int32_t *list, const double *X, int J, int ch, double *F,
           hipStream_t st) {
-        int rc = rvs_proc_map(J, o->n, o->ndim, X, list, o->src, o->vsini_col, o->fixed,
-                              o->vsini_fixed, o->safe, o->prior_mean, o->prior_isig,
-                              o->min_vel, o->max_vel, o->max_vsini, o->job_spec, o->vel,
-                              o->vsini, o->params, o->extra, o->bad, st);
-        if (rc) return rc;
-        if (hipMemsetAsync(o->jstatus, 0, sizeof(int32_t) * J, st) != hipSuccess)
-          return RVS_E_LAUNCH;
-        rc = rvs_objective_fisher(garms, g->narm, o->npoly, g->ntan, o->params, o->vsini,
-                                  o->job_spec, J, o->vel, o->badchi, basis_const, kwork,
-                                  kwork_bytes, g->chi, g->grad, fisher, o->jstatus, st);
-        if (rc) return rc;
-        return rvs_proc_finish_fisher(J, o->n, o->ndim, g->ntan, b->counts, ch, g->chi,
-                                      g->grad, fisher, X, o->params, o->extra, o->bad,
-                                      o->job_spec, o->jstatus, o->src, o->vsini_col,
-                                      o->prior_mean, o->prior_isig, o->max_vsini, F,
-                                      o->status, st);
+        return rvs_internal_fused_eval(
+            o, g, fisher, list, X, J, b->counts, ch, F, st, [&] {
+              return rvs_objective_fisher(garms, g->narm, o->npoly, g->ntan, o->params,
+                                          o->vsini, o->job_spec, J, o->vel, o->badchi,
+                                          basis_const, kwork, kwork_bytes, g->chi, g->grad,
+                                          fisher, o->jstatus, st);
+            });
       });
 }

@@ -758,8 +758,10 @@ static MapP map_params(const rvs_nm_objective *o) {
   return P;
 }
 
-static int proc_map(int J, const double *X, const int32_t *list,
-                    const rvs_nm_objective *o, hipStream_t st) {
+// rvs_proc_map on an objective's own tables and row buffers (nm_internal.h: what the
+// round evaluators of this file, bfgs_grad.hip, bfgs_dev.hip and lm_dev.hip call)
+int rvs_internal_proc_map(int J, const double *X, const int32_t *list,
+                          const rvs_nm_objective *o, hipStream_t st) {
   if (J < 1 || o->n < 1 || o->n > NM_MAXN || o->ndim < 1 || o->ndim > NM_MAXN)
     return RVS_E_ARG;
   hipLaunchKernelGGL(proc_map_kernel, dim3((J + 255) / 256), dim3(256), 0, st, J, X,
@@ -785,7 +787,7 @@ extern "C" int rvs_proc_map(int J, int n, int ndim, const double *X,
   o.min_vel = min_vel, o.max_vel = max_vel, o.max_vsini = max_vsini;
   o.job_spec = job_spec, o.vel = vel, o.vsini = vsini, o.params = params;
   o.extra = extra, o.bad = bad;
-  return proc_map(J, X, list, &o, rvs_stream(stream));
+  return rvs_internal_proc_map(J, X, list, &o, rvs_stream(stream));
 }
 
 extern "C" int rvs_proc_finish(int J, const int32_t *counts, int cidx,
@@ -847,7 +849,7 @@ static int nm_objective_rows(const rvs_nm_objective *o, int J, const int32_t *li
 int rvs_internal_nm_eval(const rvs_nm_objective *o, const int32_t *list,
                          const double *X, int J, const int32_t *counts, int cidx,
                          double *F, hipStream_t st) {
-  int rc = proc_map(J, X, list, o, st);
+  int rc = rvs_internal_proc_map(J, X, list, o, st);
   if (rc) return rc;
   // rows behind the device count (simplices that finished since the host's last look,
   // simplices that need no second point this round) are not evaluated: a quarter of

@@ -503,38 +503,51 @@ class GradChain:
             self.fisher_work = torch.empty((nb + 7) // 8, **f64)
             self.fisher_buf = torch.empty((cap, K, K), **f64)
 
-    def _init_fused(self, pobj, cap, fisher):
-        L = _lib.lib()
+    def _init_fused_rows(self, pobj, cap, key, check_scope, fisher, **scope_kw):
+        """What both fused forms begin with: `check_scope` (engine.check_fused_*_scope
+        with its keywords; refused before anything is built), the tangents, the rows of a chunk (ValueError
+        naming the config key `key` where MAX_CHUNKS chunks do not hold a row per run),
+        the kernels' arm descriptors and the chunk's chi / grad.  Returns the library,
+        the tensor keywords and the number of arms for the form's own buffers."""
         batch, libs = pobj.batch, pobj.libs
         fit = pobj.vsini_col >= 0
-        engine.check_fused_grad_scope(
-            batch, libs, pobj.npoly, pobj.resols, False, vsini_grad=fit,
-            what='the Fisher form of the chain (fisher=True)' if fisher else None,
-            nn_gradient=getattr(pobj, 'nn_gradient', False))
-        self.pobj, self.fisher = pobj, False
-        # MLP libraries (admitted with nn_gradient): rvs_bfgs_run_grad_fused_nn
-        self.fused_nn = libs[batch.arms[0].name].kind == 'nn'
-        dev = pobj.dev
+        check_scope(batch, libs, pobj.npoly, pobj.resols, False, vsini_grad=fit,
+                    **scope_kw)
+        self.pobj, self.fisher = pobj, fisher
         narm = len(batch.arms)
         self.ntan = pobj.ndim + (1 if fit else 0)
         self.vsini_mode = 2 if fit else (1 if pobj.has_vsini else 0)
         cap = int(min(pobj.S if cap is None else cap, pobj.cap))
         if cap < 1 or (pobj.S + cap - 1) // cap > GradChain.MAX_CHUNKS:
-            raise ValueError('second_minimizer_jac: a round holds at most %d chunks of '
+            raise ValueError('%s: a round holds at most %d chunks of '
                              '%d rows: %d spectra do not fit one call; pass them in '
-                             'smaller batches' % (GradChain.MAX_CHUNKS, cap, pobj.S))
+                             'smaller batches' % (key, GradChain.MAX_CHUNKS, cap, pobj.S))
         self.cap = cap
-        f64 = dict(dtype=torch.float64, device=dev)
+        f64 = dict(dtype=torch.float64, device=pobj.dev)
         self.garms = (_lib.ObjectiveArm * narm)()
         self.bconst = (ctypes.c_double * narm)()
         self._keep = engine.fill_objective_grad_arms(self.garms, self.bconst, batch, libs,
                                                      pobj.npoly, pobj.rbf)
+        self.chi = torch.empty(cap, **f64)
+        self.grad = torch.empty((cap, 1 + self.ntan), **f64)
+        self.njev = torch.zeros(pobj.S, dtype=torch.int32, device=pobj.dev)
+        return _lib.lib(), f64, narm
+
+    def _init_fused(self, pobj, cap, fisher):
+        batch, libs = pobj.batch, pobj.libs
+        L, f64, narm = self._init_fused_rows(
+            pobj, cap, 'second_minimizer_jac', engine.check_fused_grad_scope, False,
+            what='the Fisher form of the chain (fisher=True)' if fisher else None,
+            nn_gradient=getattr(pobj, 'nn_gradient', False))
+        cap = self.cap
+        # MLP libraries (admitted with nn_gradient): rvs_bfgs_run_grad_fused_nn
+        self.fused_nn = libs[batch.arms[0].name].kind == 'nn'
         if self.fused_nn:
             # the adjoint rows and the reverse pass's work of a chunk are this object's
             if not pobj.native:
                 raise ValueError("config['fused_gradient'] on MLP libraries needs the "
                                  'rounds inside the library (the from-template objective)')
-            vg = 1 if fit else 0
+            vg = 1 if pobj.vsini_col >= 0 else 0
             ls = [libs[a.name] for a in batch.arms]
             self.nbytes = int(L.rvs_objective_grad_from_template_work_size(cap, narm, vg))
             self.tbar = [torch.empty((cap, lib.ntp), **f64) for lib in ls]
@@ -555,43 +568,18 @@ class GradChain:
         else:
             self.nbytes = int(L.rvs_objective_grad_work_size(cap, narm, self.ntan))
             self.gwork = torch.empty((self.nbytes + 7) // 8, **f64)
-        self.chi = torch.empty(cap, **f64)
-        self.grad = torch.empty((cap, 1 + self.ntan), **f64)
-        self.njev = torch.zeros(pobj.S, dtype=torch.int32, device=dev)
 
     def _init_fused_fisher(self, pobj, cap):
-        L = _lib.lib()
-        batch, libs = pobj.batch, pobj.libs
-        fit = pobj.vsini_col >= 0
-        engine.check_fused_fisher_scope(batch, libs, pobj.npoly, pobj.resols, False,
-                                        vsini_grad=fit)
-        self.pobj, self.fisher = pobj, True
-        dev = pobj.dev
-        narm = len(batch.arms)
-        self.ntan = pobj.ndim + (1 if fit else 0)
-        self.vsini_mode = 2 if fit else (1 if pobj.has_vsini else 0)
-        cap = int(min(pobj.S if cap is None else cap, pobj.cap))
-        if cap < 1 or (pobj.S + cap - 1) // cap > GradChain.MAX_CHUNKS:
-            raise ValueError('second_minimizer_lm: a round holds at most %d chunks of '
-                             '%d rows: %d spectra do not fit one call; pass them in '
-                             'smaller batches' % (GradChain.MAX_CHUNKS, cap, pobj.S))
-        self.cap = cap
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.garms = (_lib.ObjectiveArm * narm)()
-        self.bconst = (ctypes.c_double * narm)()
-        self._keep = engine.fill_objective_grad_arms(self.garms, self.bconst, batch, libs,
-                                                     pobj.npoly, pobj.rbf)
-        K = 1 + self.ntan
-        npix_max = max(a.npix for a in batch.arms)
+        L, f64, narm = self._init_fused_rows(pobj, cap, 'second_minimizer_lm',
+                                             engine.check_fused_fisher_scope, True)
+        cap, K = self.cap, 1 + self.ntan
+        npix_max = max(a.npix for a in pobj.batch.arms)
         one = int(L.rvs_objective_fisher_work_size(1, narm, self.ntan, npix_max))
         rows = max(1, min(cap, FISHER_FUSED_WORK_BUDGET // one))
         self.nbytes = cap * K * K * 8 + rows * one
         self.fwork = torch.empty(self.nbytes // 8, **f64)
-        self.chi = torch.empty(cap, **f64)
-        self.grad = torch.empty((cap, K), **f64)
-        self.njev = torch.zeros(pobj.S, dtype=torch.int32, device=dev)
 
-    MAX_CHUNKS = 24     # the chunk counters of the scan kernel (bfgs_dev.hip)
+    MAX_CHUNKS = 24     # the chunk counters of the scan kernel (rounds_dev.h: BF_NCHUNK)
 
     @staticmethod
     def choose_cap(S, ntps, ntan, vsini_mode, cap=None, budget=None,

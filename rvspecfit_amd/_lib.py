@@ -31,6 +31,7 @@ SIGNATURES = {
     'rvs_template_tri_buckets': (I, [P, I, P, P, P, I, I, U, I, P, P, I, P, P, P,
                                      P, P]),
     'rvs_template_tri_grad': (I, [P, I, P, P, P, I, I, U, I, P, I, P, P, P, P, P]),
+    'rvs_template_tri_vjp': (I, [P, I, P, P, I, I, U, I, P, I, P, P, P, P, P]),
     'rvs_template_tri_buckets_grad': (I, [P, I, P, P, P, I, I, U, I, P, P, I, P, P,
                                           P, P, P]),
     'rvs_vsini_convolve': (I, [P, P, P, D, D, I, I, P, P]),
@@ -145,6 +146,7 @@ SIGNATURES = {
     'rvs_objective_fisher': (I, [P, I, I, I, P, P, P, I, P, D, P, P, L, P, P, P, P, P]),
     'rvs_bfgs_run_grad_fused': (I, [P, P, P, P, P, P, I, P, P]),
     'rvs_bfgs_run_grad_fused_nn': (I, [P, P, P, P, P, P, P, P, P, P, I, P, P]),
+    'rvs_bfgs_run_grad_fused_tri': (I, [P, P, P, P, P, P, P, P, P, I, P, P]),
     'rvs_grid_moments': (I, [P, P, L, P, I, I, I, I, P, P, P, P]),
     'rvs_basis_build': (I, [P, P, I, I, I, I, P, P, P, P, P]),
     'rvs_ccf_tables_build': (I, [P, P, I, I, P, I, I, P, P, P, I, P, P, P, P, P, P,

@@ -114,7 +114,9 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     and options the gradient does not cover raise ValueError.  A chain built with
     fused=True runs rvs_bfgs_run_grad_fused: the rows' value and gradient from one
     kernel per (row, arm) -- on MLP libraries rvs_bfgs_run_grad_fused_nn, with the
-    networks' reverse pass behind it."""
+    networks' reverse pass behind it, on Delaunay libraries
+    rvs_bfgs_run_grad_fused_tri, with the contraction of the adjoint row with the
+    simplex's tangents."""
     import ctypes
     import torch
     from . import _lib
@@ -158,6 +160,15 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
             ctypes.cast(chain.vjp_work_p, ctypes.c_void_p),
             ctypes.cast(chain.gparams_p, ctypes.c_void_p), _lib.ptr(chain.grad_vv),
             int(sync_every), st3, _lib.stream()), 'rvs_bfgs_run_grad_fused_nn')
+    elif jac and getattr(chain, 'fused', False) and getattr(chain, 'fused_tri', False):
+        # ... on Delaunay libraries: the adjoint rows onto the simplices' tangents
+        g = chain.desc()
+        _lib.check(L.rvs_bfgs_run_grad_fused_tri(
+            ctypes.addressof(b), ctypes.addressof(o), ctypes.addressof(g),
+            ctypes.addressof(chain.garms), ctypes.addressof(chain.bconst),
+            _lib.ptr(chain.gwork), ctypes.cast(chain.tbar_p, ctypes.c_void_p),
+            ctypes.cast(chain.gparams_p, ctypes.c_void_p), _lib.ptr(chain.grad_vv),
+            int(sync_every), st3, _lib.stream()), 'rvs_bfgs_run_grad_fused_tri')
     elif jac and getattr(chain, 'fused', False):
         # optimizer.GradChain(fused=True): one rvs_objective_grad call per chunk
         g = chain.desc()

@@ -261,3 +261,58 @@ extern "C" int rvs_bfgs_run_grad_fused_nn(
             });
       });
 }
+
+// ... on Delaunay libraries: the form above with the triangulations of
+// o->tri as the evaluator -- the rows' template rows, outside flags and simplex ids from
+// rvs_internal_template_tri_arms_n into the buffers of o->tri[a], and the parameter
+// components from rvs_template_tri_vjp per arm on the simplex the evaluator found (the
+// search is not repeated).  float64 throughout; the reverse step needs no work buffer.
+// tbar, gparams: HOST arrays of narm device pointers ([cap, ntp], [cap, ndim]), grad_vv
+// [cap, 1 + (vsini fitted)].
+extern "C" int rvs_bfgs_run_grad_fused_tri(
+    const rvs_bfgs_state *b, const rvs_nm_objective *o, const rvs_grad_chain *g,
+    const rvs_objective_arm *garms, const double *basis_const, void *gwork,
+    double *const *tbar, double *const *gparams, double *grad_vv, int sync_every,
+    int64_t *stats, void *stream) {
+  if (!bfgs_args_ok(b, o, sync_every) || !g || !g->njev || !garms || !gwork || !tbar ||
+      !gparams || !grad_vv || !rvs_internal_grad_rows_ok(g, o, 6) || !o->tri)
+    return RVS_E_ARG;
+  const int vg = g->vsini_mode == 2 ? 1 : 0;
+  const double *tp[RVS_MAX_ARMS], *op[RVS_MAX_ARMS];
+  for (int a = 0; a < g->narm; a++) {
+    const rvs_nm_tri_arm &T = o->tri[a];
+    if (!tbar[a] || !gparams[a] || !T.templ || !T.outside || !T.simplex || !T.dats ||
+        !T.simplices || !T.transform || !T.buckets.cell_start || !T.buckets.cell_list ||
+        T.nsimplex < 1 || T.ntp != garms[a].ntp ||
+        !rvs_internal_arm_plain(garms[a]) ||
+        !rvs_objective_grad_from_template_ok(o->npoly, garms[a].pt.npix, garms[a].ntp, vg))
+      return RVS_E_ARG;
+    tp[a] = T.templ;
+    op[a] = T.outside;
+  }
+  return bfgs_rounds(
+      b, g->cap, g->njev, sync_every, stats, stream,
+      [&](const int32_t *list, const double *X, int J, int ch, double *F,
+          hipStream_t st) {
+        return rvs_internal_fused_eval(
+            o, g, nullptr, list, X, J, b->counts, ch, F, st, [&] {
+              int rc = rvs_internal_template_tri_arms_n(o->params, J, nullptr, o->ndim,
+                                                        o->narm, o->tri, st);
+              if (rc) return rc;
+              rc = rvs_objective_grad_from_template(
+                  garms, g->narm, o->npoly, vg, tp, op, o->vsini, o->job_spec, J, o->vel,
+                  o->badchi, basis_const, gwork, tbar, g->chi, grad_vv, o->jstatus, st);
+              if (rc) return rc;
+              for (int a = 0; a < g->narm; a++) {
+                const rvs_nm_tri_arm &T = o->tri[a];
+                rc = rvs_template_tri_vjp(T.dats, T.ntp, T.simplices, T.transform,
+                                          T.nsimplex, o->ndim, T.log_mask, T.exp_flag,
+                                          o->params, J, T.simplex, T.templ, tbar[a],
+                                          gparams[a], st);
+                if (rc) return rc;
+              }
+              return rvs_objective_grad_join(g->narm, J, o->ndim, vg, gwork, gparams,
+                                             g->chi, grad_vv, g->grad, st);
+            });
+      });
+}

@@ -273,6 +273,23 @@ __global__ void __launch_bounds__(64)
   if (active && finite && found != 0x7fffffff) atomicMin(&simplex[b], found);
 }
 
+// column k of the table db_i/dp_k [i][k] of the simplex with transform T, for the
+// job's physical parameters p
+__device__ __forceinline__ void tri_db_column(const double *__restrict__ T, int nd,
+                                              uint32_t log_mask,
+                                              const double *__restrict__ p, int k,
+                                              double *sh_db) {
+  double s = 1.0;
+  if ((log_mask >> k) & 1u) s = 1.0 / (p[k] * 2.302585092994046);
+  double sum = 0;
+  for (int i = 0; i < nd; i++) {
+    const double d = T[i * nd + k] * s;
+    sh_db[i * TRI_MAXDIM + k] = d;
+    sum += d;
+  }
+  sh_db[nd * TRI_MAXDIM + k] = -sum;
+}
+
 template <bool GRAD>
 __device__ __forceinline__ void
     tri_eval_body(const double *__restrict__ dats, int ntp,
@@ -318,19 +335,9 @@ __device__ __forceinline__ void
     for (int i = 0; i <= nd; i++) sh_id[i] = simplices[(int64_t)sx * (nd + 1) + i];
   }
   if constexpr (GRAD) {
-    if (tid < nd) {   // column tid of the table
-      const double *T = transform + (int64_t)sx * (nd + 1) * nd;
-      double s = 1.0;
-      if ((log_mask >> tid) & 1u)
-        s = 1.0 / (params[(int64_t)b * nd + tid] * 2.302585092994046);
-      double sum = 0;
-      for (int i = 0; i < nd; i++) {
-        const double d = T[i * nd + tid] * s;
-        sh_db[i * TRI_MAXDIM + tid] = d;
-        sum += d;
-      }
-      sh_db[nd * TRI_MAXDIM + tid] = -sum;
-    }
+    if (tid < nd)
+      tri_db_column(transform + (int64_t)sx * (nd + 1) * nd, nd, log_mask,
+                    params + (int64_t)b * nd, tid, sh_db);
   }
   __syncthreads();
   double mx = 0;
@@ -648,6 +655,87 @@ extern "C" int rvs_template_tri_grad(const double *dats, int ntp,
   return tri_launch<true>(dats, ntp, simplices, transform, extraflags, nsimplex, ndim,
                           log_mask, exp_flag, params, B, templ, outside, simplex,
                           weights, stream);
+}
+
+// The reverse step of the same evaluator: gparams[b, k] = sum_n tbar[b, n]
+// dtempl[b, n]/dp_k, the adjoint row contracted with the tangent rows tri_eval_body<true>
+// would have written, which are never formed.  One block per job on the simplex the
+// evaluator found; per knot the nd sums sum_i (db_i/dp_k) L_i[n] by the tangent rows' own
+// statements, times tbar_n (t_n tbar_n under exp_flag), added up per thread.  (Not the
+// nd + 1 vertex dot products sum_n u_n L_i[n] combined afterwards: the db_ik sum to zero
+// over i and the rows L_i share a large common part, so that form cancels.)  The
+// threads' sums go through the wave's butterfly and the four wave totals are added in
+// wave order by one thread per k: no atomics, a job's bits depend on its own inputs only.
+// No containing simplex (the templ row is NaN there and is not read): exact zeros.
+__global__ void __launch_bounds__(256)
+    tri_vjp_kernel(const double *__restrict__ dats, int ntp,
+                   const int32_t *__restrict__ simplices,
+                   const double *__restrict__ transform, int ns, int nd,
+                   uint32_t log_mask, int exp_flag, const double *__restrict__ params,
+                   const int32_t *__restrict__ simplex, const double *__restrict__ templ,
+                   const double *__restrict__ tbar, double *__restrict__ gparams) {
+  __shared__ int sh_id[TRI_MAXDIM + 1];
+  __shared__ double sh_db[(TRI_MAXDIM + 1) * TRI_MAXDIM];
+  __shared__ double red[4][TRI_MAXDIM];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int sx = simplex[b];
+  if (sx < 0 || sx >= ns) {   // (0x7fffffff: no simplex holds the point)
+    if (tid < nd) gparams[(int64_t)b * nd + tid] = 0.0;
+    return;
+  }
+  if (tid < nd)
+    tri_db_column(transform + (int64_t)sx * (nd + 1) * nd, nd, log_mask,
+                  params + (int64_t)b * nd, tid, sh_db);
+  if (tid >= 64 && tid <= 64 + nd)
+    sh_id[tid - 64] = simplices[(int64_t)sx * (nd + 1) + tid - 64];
+  __syncthreads();
+  const double *t = templ + (int64_t)b * ntp, *tb = tbar + (int64_t)b * ntp;
+  double acc[TRI_MAXDIM] = {};
+  for (int k = tid; k < ntp; k += 256) {
+    // (static indices: the vertex values and the sums in registers)
+    double L[TRI_MAXDIM + 1], g[TRI_MAXDIM] = {};
+#pragma unroll
+    for (int i = 0; i <= TRI_MAXDIM; i++)
+      L[i] = (i <= nd) ? dats[(int64_t)sh_id[i] * ntp + k] : 0.0;
+#pragma unroll
+    for (int i = 0; i <= TRI_MAXDIM; i++)
+      if (i <= nd) {
+#pragma unroll
+        for (int d = 0; d < TRI_MAXDIM; d++)
+          if (d < nd) g[d] = fma(sh_db[i * TRI_MAXDIM + d], L[i], g[d]);
+      }
+    const double u = exp_flag ? tb[k] * t[k] : tb[k];
+#pragma unroll
+    for (int d = 0; d < TRI_MAXDIM; d++)
+      if (d < nd) acc[d] = fma(u, g[d], acc[d]);
+  }
+#pragma unroll
+  for (int d = 0; d < TRI_MAXDIM; d++) {
+    if (d < nd) {   // (block-uniform)
+      const double w = wave_sum(acc[d]);
+      if ((tid & 63) == 0) red[tid >> 6][d] = w;
+    }
+  }
+  __syncthreads();
+  if (tid < nd)
+    gparams[(int64_t)b * nd + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// spec_inter.py:11-59 differentiated and contracted: gparams [B, ndim]
+extern "C" int rvs_template_tri_vjp(const double *dats, int ntp, const int32_t *simplices,
+                                    const double *transform, int nsimplex, int ndim,
+                                    uint32_t log_mask, int exp_flag, const double *params,
+                                    int B, const int32_t *simplex, const double *templ,
+                                    const double *tbar, double *gparams, void *stream) {
+  if (ndim < 1 || ndim > TRI_MAXDIM || ntp < 1 || nsimplex < 1 || B < 0 || !dats ||
+      !simplices || !transform || !params || !simplex || !templ || !tbar || !gparams)
+    return RVS_E_ARG;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(tri_vjp_kernel, dim3(B), dim3(256), 0, rvs_stream(stream), dats, ntp,
+                     simplices, transform, nsimplex, ndim, log_mask, exp_flag, params,
+                     simplex, templ, tbar, gparams);
+  RVS_LAUNCH_CHECK();
+  return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -1384,10 +1384,12 @@ def objective_from_template(batch, libs, templs, outsides, vsini, vel, npoly=5,
 
 GRAD_FUSED_MAXP = 10     # OP_MAXP of csrc/objective_point_dev.h
 GRAD_FUSED_MAXDIM = 4
+TRI_VJP_MAXDIM = 6       # TRI_MAXDIM of csrc/template.hip
 
 
 def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
-                           vsini_grad=False, what=None, nn_gradient=False):
+                           vsini_grad=False, what=None, nn_gradient=False,
+                           tri_gradient=False):
     """ValueError naming the option that config['fused_gradient'] does not go with:
     what rvs_objective_grad (csrc/objective_grad.hip) does not cover keeps the chain,
     and the key beside it is an error, never a silent change of path.  `what`: a
@@ -1397,7 +1399,9 @@ def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
     rvs_objective_grad_from_template hands the adjoint row to the network's reverse
     pass (rvs_template_nn_vjp), float32 arithmetic as the chain's tangent rows are --
     where the network is in rvs_template_nn_grad's scope and the arm in the kernel's
-    geometry."""
+    geometry.  tri_gradient (config['tri_gradient']): Delaunay libraries on every arm
+    are admitted the same way, the adjoint row going to rvs_template_tri_vjp (float64),
+    for ndim <= 6; a Delaunay arm beside arms of another kind is refused."""
     key = "config['fused_gradient']"
     if what is not None:
         raise ValueError('%s does not go with %s: it needs the tangent rows of the '
@@ -1407,15 +1411,26 @@ def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
         _check_fused_scope(key, None, batch, libs, npoly, resols, fast_interp, vsini_grad,
                            nn=True)
         return
+    kinds = [libs[arm.name].kind for arm in batch.arms]
+    if tri_gradient and 'triangulation' in kinds:
+        for arm, kind in zip(batch.arms, kinds):
+            if kind != 'triangulation':
+                raise ValueError('%s with config[\'tri_gradient\'] needs Delaunay '
+                                 'libraries on every arm: %s is a %s library beside '
+                                 'triangulation libraries (interpolation_type)'
+                                 % (key, arm.name, kind))
+        _check_fused_scope(key, None, batch, libs, npoly, resols, fast_interp, vsini_grad,
+                           tri=True)
+        return
     _check_fused_scope(key, _lib.lib().rvs_objective_grad_ok, batch, libs, npoly, resols,
                        fast_interp, vsini_grad)
 
 
 def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_grad,
-                       nn=False):
+                       nn=False, tri=False):
     # what rvs_objective_grad and rvs_objective_fisher both leave to the chain; ok: the
-    # kernel's own rvs_objective_*_ok; nn: MLP libraries on the from-template form of the
-    # gradient kernel
+    # kernel's own rvs_objective_*_ok; nn / tri: MLP / Delaunay libraries on the
+    # from-template form of the gradient kernel
     if fast_interp:
         raise ValueError('%s does not go with fast_interp (the nearest-knot template '
                          'has no velocity derivative)' % key)
@@ -1431,17 +1446,23 @@ def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_g
         if arm.G > 1:
             raise ValueError('%s does not go with a grid set: arm %s has %d wavelength '
                              'grids' % (key, arm.name, arm.G))
-        if nn:
-            lib.check_nn_grad_scope()
+        if nn or tri:
+            if nn:
+                lib.check_nn_grad_scope()
+            elif lib.ndim > TRI_VJP_MAXDIM:
+                raise ValueError('%s takes Delaunay libraries of up to %d parameters, '
+                                 '%s has ndim = %d'
+                                 % (key, TRI_VJP_MAXDIM, arm.name, lib.ndim))
             if lib.spline_factors is None:
                 raise ValueError('%s needs a (log-)uniform template grid (arm %s)'
                                  % (key, arm.name))
             if not _lib.lib().rvs_objective_grad_from_template_ok(
                     npoly, arm.npix, lib.ntp, int(bool(vsini_grad))):
-                raise ValueError('%s: arm %s of an nn library (npix = %d, ntp = %d) is '
+                raise ValueError('%s: arm %s of %s library (npix = %d, ntp = %d) is '
                                  'outside the kernel\'s geometry: 32 <= ntp, 2 npix <= '
                                  'ntp, three buffers of ntp doubles in LDS'
-                                 % (key, arm.name, arm.npix, lib.ntp))
+                                 % (key, arm.name, 'an nn' if nn else 'a triangulation',
+                                    arm.npix, lib.ntp))
             continue
         if lib.kind != 'regulargrid':
             raise ValueError('%s needs regular-grid (polylinear) libraries: %s is a %s '
@@ -1459,11 +1480,12 @@ def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_g
 
 
 def can_fuse_objective_grad(batch, libs, resols=None, fast_interp=False, npoly=10,
-                            vsini_grad=False):
-    """whether rvs_objective_grad covers this batch (check_fused_grad_scope says why
+                            vsini_grad=False, nn_gradient=False, tri_gradient=False):
+    """whether the fused gradient covers this batch (check_fused_grad_scope says why
     not)"""
     try:
-        check_fused_grad_scope(batch, libs, npoly, resols, fast_interp, vsini_grad)
+        check_fused_grad_scope(batch, libs, npoly, resols, fast_interp, vsini_grad,
+                               nn_gradient=nn_gradient, tri_gradient=tri_gradient)
     except ValueError:
         return False
     return True
@@ -1531,15 +1553,34 @@ def objective_grad_from_template(batch, libs, templs, outsides, vsini, vel, npol
 # bytes the rows of one chunk of objective_grad_fused on MLP libraries may take: per job
 # and arm the template row and the adjoint row (2 ntp doubles: 2.4 GB at 8192 jobs on the
 # three DESI arms) and the partial sums of the reverse pass (ceil(ntp / 256) K_L floats:
-# 0.5 GB there)
+# 0.5 GB there); on Delaunay libraries the two rows, the simplex id and the ndim results
 TBAR_BUDGET = 4 << 30
 
 
-def _objective_grad_fused_nn(batch, libs, params, vsini, vel, npoly, rbf, job_spec,
-                             vsini_grad, espec_sys, tbar_bytes):
-    # MLP libraries: template rows -> rvs_objective_grad_from_template -> the network's
-    # reverse pass per arm -> the sum over the arms; the jobs in chunks of what the byte
-    # budget of the adjoint rows holds (a job's results do not depend on its chunk)
+def _nn_reverse(lib, p, row, tb):
+    return lib.nn_vjp(p, row[0], tb)
+
+
+def _nn_row_bytes(lib):
+    return 16 * lib.ntp + 4 * ((lib.ntp + 255) // 256) * int(lib.nn_dims[-2])
+
+
+def _tri_reverse(lib, p, row, tb):
+    return lib.tri_vjp(p, row[0], row[2], tb)
+
+
+def _tri_row_bytes(lib):
+    # the template row and the adjoint row, the parameter components, the simplex id
+    return 16 * lib.ntp + 8 * lib.ndim + 4
+
+
+def _objective_grad_fused_rows(batch, libs, params, vsini, vel, npoly, rbf, job_spec,
+                               vsini_grad, espec_sys, tbar_bytes, reverse, row_bytes):
+    # MLP and Delaunay libraries: template rows -> rvs_objective_grad_from_template ->
+    # the evaluator's reverse step per arm (reverse(lib, params, row, tbar): the network's
+    # reverse pass, the contraction with the simplex's tangents) -> the sum over the
+    # arms; the jobs in chunks of what the byte budget of the rows (row_bytes(lib) per
+    # job and arm) holds (a job's results do not depend on its chunk)
     import ctypes
     L = _lib.lib()
     dev = batch.device
@@ -1547,8 +1588,7 @@ def _objective_grad_fused_nn(batch, libs, params, vsini, vel, npoly, rbf, job_sp
     narm = len(batch.arms)
     ls = [libs[arm.name] for arm in batch.arms]
     ndim, vg = ls[0].ndim, int(bool(vsini_grad))
-    per_job = sum(16 * lib.ntp + 4 * ((lib.ntp + 255) // 256) * int(lib.nn_dims[-2])
-                  for lib in ls)
+    per_job = sum(row_bytes(lib) for lib in ls)
     budget = TBAR_BUDGET if tbar_bytes is None else int(tbar_bytes)
     cap = max(1, min(J, budget // per_job))
     out = torch.empty(J, dtype=torch.float64, device=dev)
@@ -1558,12 +1598,12 @@ def _objective_grad_fused_nn(batch, libs, params, vsini, vel, npoly, rbf, job_sp
         sl = slice(j0, min(J, j0 + cap))
         n = sl.stop - sl.start
         p = params[sl].contiguous()
-        rows = [lib.eval_batch(p) for lib in ls]
+        rows = [lib.eval_batch(p, details=lib.kind == 'triangulation') for lib in ls]
         o, gvv, st, tbars, scratch = objective_grad_from_template(
             batch, libs, [r[0] for r in rows], [r[1] for r in rows],
             None if vsini is None else vsini[sl], vel[sl], npoly, rbf,
             None if job_spec is None else job_spec[sl], vsini_grad, espec_sys)
-        gps = [lib.nn_vjp(p, r[0], tb) for lib, r, tb in zip(ls, rows, tbars)]
+        gps = [reverse(lib, p, r, tb) for lib, r, tb in zip(ls, rows, tbars)]
         gp = (ctypes.c_void_p * narm)(*[g.data_ptr() for g in gps])
         g = grad[sl]
         rc = L.rvs_objective_grad_join(narm, n, ndim, vg, _lib.ptr(scratch),
@@ -1577,7 +1617,7 @@ def _objective_grad_fused_nn(batch, libs, params, vsini, vel, npoly, rbf, job_sp
 
 def objective_grad_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
                          job_spec=None, vsini_grad=False, espec_sys=0.0,
-                         nn_gradient=False, tbar_bytes=None):
+                         nn_gradient=False, tbar_bytes=None, tri_gradient=False):
     """get_chisq and its gradient for J (spectrum, parameters, vsini, velocity) jobs
     as ONE kernel per (job, arm) (rvs_objective_grad, the adjoint method): no template
     row, tangent row or spline record in HBM.  Returns chisq [J] (with the outside
@@ -1589,22 +1629,27 @@ def objective_grad_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
     network's reverse pass (rvs_objective_grad_from_template, rvs_template_nn_vjp): one
     template row in and one adjoint row out per (job, arm), the parameter components in
     float32 arithmetic; tbar_bytes: the byte budget of one chunk's rows (default
-    TBAR_BUDGET, which says what is counted; the results do not depend on it)."""
+    TBAR_BUDGET, which says what is counted; the results do not depend on it).
+    tri_gradient: Delaunay libraries take the same form with rvs_template_tri_vjp as the
+    reverse step, float64 throughout (16 ntp + 8 ndim + 4 bytes per job and arm)."""
     import ctypes
     if vsini_grad and vsini is None:
         raise ValueError('vsini_grad=True needs vsini: without rotation there is no '
                          'vsini to differentiate by')
     check_fused_grad_scope(batch, libs, npoly, None, False, vsini_grad,
-                           nn_gradient=nn_gradient)
+                           nn_gradient=nn_gradient, tri_gradient=tri_gradient)
     L = _lib.lib()
     dev = batch.device
-    if libs[batch.arms[0].name].kind == 'nn':
+    kind = libs[batch.arms[0].name].kind
+    if kind in ('nn', 'triangulation'):
         vel = vel.to(device=dev, dtype=torch.float64).contiguous()
         params = params.to(device=dev, dtype=torch.float64).contiguous()
         if vsini is not None:
             vsini = vsini.to(device=dev, dtype=torch.float64).contiguous()
-        return _objective_grad_fused_nn(batch, libs, params, vsini, vel, npoly, rbf,
-                                        job_spec, vsini_grad, espec_sys, tbar_bytes)
+        return _objective_grad_fused_rows(
+            batch, libs, params, vsini, vel, npoly, rbf, job_spec, vsini_grad, espec_sys,
+            tbar_bytes, *((_nn_reverse, _nn_row_bytes) if kind == 'nn'
+                          else (_tri_reverse, _tri_row_bytes)))
     vel = vel.to(device=dev, dtype=torch.float64).contiguous()
     params = params.to(device=dev, dtype=torch.float64).contiguous()
     J = vel.shape[0]

@@ -472,6 +472,37 @@ class TemplateLibrary:
             _lib.ptr(params), J, _lib.ptr(templ), _lib.ptr(outside),
             _lib.ptr(sx), _lib.ptr(wts), stream)
 
+    def tri_vjp(self, params, templ, simplex, tbar):
+        """the Delaunay evaluator's reverse step (rvs_template_tri_vjp): params
+        [J, ndim], templ [J, ntp] and simplex int32 [J] (what eval_batch(params,
+        details=True) returned for them) and tbar [J, ntp] (d f / d templ) ->
+        gparams [J, ndim] = sum_n tbar_n d templ_n / d p_k in float64; exact zeros
+        for a job no simplex holds."""
+        if self.kind != 'triangulation':
+            raise ValueError('tri_vjp needs a Delaunay library, %s is a %s library'
+                             % (self.name, self.kind))
+        L = _lib.lib()
+        J = params.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        params = params.to(**f64).contiguous()
+        templ = templ.to(**f64).contiguous()
+        tbar = tbar.to(**f64).contiguous()
+        simplex = simplex.to(dtype=torch.int32, device=self.device).contiguous()
+        if (templ.shape != (J, self.ntp) or tbar.shape != (J, self.ntp) or
+                simplex.shape != (J, ) or params.shape != (J, self.ndim)):
+            raise ValueError('tri_vjp: params [J, ndim], templ and tbar [J, ntp] = '
+                             '[%d, %d], simplex [J]' % (J, self.ntp))
+        gparams = torch.empty((J, self.ndim), **f64)
+        from . import engine
+        with engine._ktime('template_tri_vjp', J):
+            rc = L.rvs_template_tri_vjp(
+                _lib.ptr(self.dats), self.ntp, _lib.ptr(self.tri_simplices),
+                _lib.ptr(self.tri_transform), self.tri_nsimplex, self.ndim,
+                self.log_mask, self.exp_flag, _lib.ptr(params), J, _lib.ptr(simplex),
+                _lib.ptr(templ), _lib.ptr(tbar), _lib.ptr(gparams), _lib.stream())
+        _lib.check(rc, 'rvs_template_tri_vjp')
+        return gparams
+
     def eval_into(self, params, J, templ, outside, stream, scratch=None):
         """launch-only variant of eval_batch on caller-owned buffers (no
         allocation, no synchronisation): params [>=J, ndim], templ [>=J, ntp],

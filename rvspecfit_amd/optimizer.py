@@ -81,6 +81,8 @@ class ProcessObjective:
         self.max_vsini = float(config['max_vsini'])
         # (MLP libraries in the gradient chain are opt-in: engine.check_grad_scope)
         self.nn_gradient = bool(config.get('nn_gradient'))
+        # (Delaunay libraries in the fused gradient too: engine.check_fused_grad_scope)
+        self.tri_gradient = bool(config.get('tri_gradient'))
         # (and so are resolution matrices)
         self.resol_gradient = bool(config.get('resol_gradient'))
         cap = S
@@ -365,7 +367,9 @@ class GradChain:
     the kernel's scratch and the chunk's chi / grad; `rows` goes through the same call.
     On MLP libraries (the objective's nn_gradient set; rvs_bfgs_run_grad_fused_nn, DESIGN
     4.25) it also holds a chunk's adjoint rows [cap, ntp] per arm and the work of the
-    networks' reverse pass.
+    networks' reverse pass; on Delaunay libraries (the objective's tri_gradient set;
+    rvs_bfgs_run_grad_fused_tri) the adjoint rows and the arms' parameter
+    components.
     What that kernel does not cover, fisher=True included, raises ValueError.
     fused_fisher=True (config['fused_fisher']): the Fisher form with the rows' value,
     gradient and matrix from ONE rvs_objective_fisher call per chunk (rvs_lm_run_fused;
@@ -538,33 +542,43 @@ class GradChain:
         L, f64, narm = self._init_fused_rows(
             pobj, cap, 'second_minimizer_jac', engine.check_fused_grad_scope, False,
             what='the Fisher form of the chain (fisher=True)' if fisher else None,
-            nn_gradient=getattr(pobj, 'nn_gradient', False))
+            nn_gradient=getattr(pobj, 'nn_gradient', False),
+            tri_gradient=getattr(pobj, 'tri_gradient', False))
         cap = self.cap
-        # MLP libraries (admitted with nn_gradient): rvs_bfgs_run_grad_fused_nn
+        # MLP libraries (admitted with nn_gradient): rvs_bfgs_run_grad_fused_nn;
+        # Delaunay libraries (with tri_gradient): rvs_bfgs_run_grad_fused_tri
         self.fused_nn = libs[batch.arms[0].name].kind == 'nn'
-        if self.fused_nn:
+        self.fused_tri = libs[batch.arms[0].name].kind == 'triangulation'
+        if self.fused_nn or self.fused_tri:
             # the adjoint rows and the reverse pass's work of a chunk are this object's
-            if not pobj.native:
-                raise ValueError("config['fused_gradient'] on MLP libraries needs the "
-                                 'rounds inside the library (the from-template objective)')
+            # (library.TRI_BUCKETS = False: the exhaustive search, which the rounds in the
+            # library do not take)
+            from . import library
+            if not pobj.native or (self.fused_tri and not library.TRI_BUCKETS):
+                raise ValueError("config['fused_gradient'] on %s libraries needs the "
+                                 'rounds inside the library (the from-template objective%s)'
+                                 % (('MLP', '') if self.fused_nn else
+                                    ('Delaunay', ' with a bucket grid on every arm')))
             vg = 1 if pobj.vsini_col >= 0 else 0
             ls = [libs[a.name] for a in batch.arms]
             self.nbytes = int(L.rvs_objective_grad_from_template_work_size(cap, narm, vg))
             self.tbar = [torch.empty((cap, lib.ntp), **f64) for lib in ls]
             self.gparams = [torch.empty((cap, pobj.ndim), **f64) for lib in ls]
-            self.vjp_work = [torch.empty(
-                (int(L.rvs_template_nn_vjp_work_size(cap, len(lib.nn_W),
-                                                     _lib.ptr(lib.nn_dims))) + 7) // 8,
-                **f64) for lib in ls]
             self.grad_vv = torch.empty((cap, 1 + vg), **f64)
             self.tbar_p = (ctypes.c_void_p * narm)(*[t.data_ptr() for t in self.tbar])
             self.gparams_p = (ctypes.c_void_p * narm)(*[t.data_ptr()
                                                         for t in self.gparams])
-            self.vjp_work_p = (ctypes.c_void_p * narm)(*[t.data_ptr()
-                                                         for t in self.vjp_work])
             self.gwork = torch.empty((self.nbytes + 7) // 8, **f64)
-            self.nbytes += sum(t.numel() * 8 for t in
-                               self.tbar + self.gparams + self.vjp_work)
+            self.nbytes += sum(t.numel() * 8 for t in self.tbar + self.gparams)
+            if self.fused_nn:
+                # (the contraction with a simplex's tangents needs no work buffer)
+                self.vjp_work = [torch.empty(
+                    (int(L.rvs_template_nn_vjp_work_size(cap, len(lib.nn_W),
+                                                         _lib.ptr(lib.nn_dims))) + 7) // 8,
+                    **f64) for lib in ls]
+                self.vjp_work_p = (ctypes.c_void_p * narm)(*[t.data_ptr()
+                                                             for t in self.vjp_work])
+                self.nbytes += sum(t.numel() * 8 for t in self.vjp_work)
         else:
             self.nbytes = int(L.rvs_objective_grad_work_size(cap, narm, self.ntan))
             self.gwork = torch.empty((self.nbytes + 7) // 8, **f64)
@@ -667,6 +681,7 @@ class GradChain:
                 None if p.vsini is None else p.vsini[:n], p.npoly, p.rbf, 0.0, True,
                 p.resols, False, p.vsini_col >= 0, self.fisher,
                 nn_gradient=getattr(p, 'nn_gradient', False),
+                tri_gradient=getattr(p, 'tri_gradient', False),
                 resol_gradient=getattr(p, 'resol_gradient', False), fused=self.fused,
                 fused_fisher=self.fused_fisher)
             chi, grad, status = res[0], res[1], res[-1]

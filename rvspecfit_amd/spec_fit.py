@@ -514,7 +514,9 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
     config['nn_gradient'] beside it MLP libraries are taken too: the kernel's
     from-template form hands one adjoint row per (spectrum, setup) to the network's
     reverse pass (rvs_objective_grad_from_template, rvs_template_nn_vjp), the parameter
-    components in float32 arithmetic.
+    components in float32 arithmetic.  With config['tri_gradient'] beside it Delaunay
+    libraries of up to 6 parameters likewise: the adjoint row is contracted with the
+    tangents of the point's simplex (rvs_template_tri_vjp), float64 throughout.
     An MLP library is among them unless config['nn_gradient'] is true: its tangent
     rows (rvs_template_nn_grad) are float32 arithmetic, exact to float32 rounding only.  On a Delaunay library a point that no simplex
     holds has the value's penalty and a zero gradient."""
@@ -554,6 +556,7 @@ def _get_chisq_grad(specdata, vel, atm_params, rot_params, options, config,
     res = _chisq_grad(batch, libs, None, velt[:, 0], params, vsini, npoly, rbf, esys,
                       outside_penalty, resols, fast_interp, vsini_grad, fisher,
                       nn_gradient=bool((config or {}).get('nn_gradient')),
+                      tri_gradient=bool((config or {}).get('tri_gradient')),
                       resol_gradient=bool((config or {}).get('resol_gradient')),
                       fused=bool((config or {}).get('fused_gradient')),
                       fused_fisher=bool((config or {}).get('fused_fisher')))
@@ -592,7 +595,7 @@ def get_chisq_fisher(specdata, vel, atm_params, rot_params=None, options=None,
 def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
                 outside_penalty, resols, fast_interp, vsini_grad=False, fisher=False,
                 nn_gradient=False, resol_gradient=False, fused=False,
-                fused_fisher=False):
+                fused_fisher=False, tri_gradient=False):
     # (the checks come first: nothing is built for a call that is refused)
     if fused:
         # config['fused_gradient']: value and gradient in one kernel per (job, arm)
@@ -600,13 +603,15 @@ def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
         engine.check_fused_grad_scope(batch, libs, npoly, resols, fast_interp,
                                       vsini_grad,
                                       what='the Fisher matrix' if fisher else None,
-                                      nn_gradient=nn_gradient)
+                                      nn_gradient=nn_gradient,
+                                      tri_gradient=tri_gradient)
         if not outside_penalty:
             raise ValueError("config['fused_gradient'] does not go with "
                              'outside_penalty=False: the kernel adds the penalty')
         return engine.objective_grad_fused(batch, libs, params, vsini, vel, npoly, rbf,
                                            js, vsini_grad, esys,
-                                           nn_gradient=nn_gradient)
+                                           nn_gradient=nn_gradient,
+                                           tri_gradient=tri_gradient)
     if fused_fisher and fisher:
         # config['fused_fisher']: value, gradient and Fisher matrix in one forward-mode
         # kernel per (job, arm) (rvs_objective_fisher); what it does not cover is an
@@ -779,6 +784,7 @@ def _chisq_grad_jobs(batch, idx, vel, params, vsini, options, config, outside_pe
     return _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
                        outside_penalty, resols, False, vsini_grad, fisher,
                        nn_gradient=bool((config or {}).get('nn_gradient')),
+                       tri_gradient=bool((config or {}).get('tri_gradient')),
                        resol_gradient=bool((config or {}).get('resol_gradient')),
                        fused=bool((config or {}).get('fused_gradient')),
                        fused_fisher=bool((config or {}).get('fused_fisher')))

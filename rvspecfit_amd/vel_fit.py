@@ -1055,6 +1055,7 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
             batch, spec_inter.get_libs(batch.names, config), options.get('npoly') or 5,
             spec_fit._resols(batch, resolParams), bool(options.get('fast_interp')),
             vsini_grad=fitVsini, nn_gradient=bool(config.get('nn_gradient')),
+            tri_gradient=bool(config.get('tri_gradient')),
             what="config['second_minimizer_lm'] (the Levenberg-Marquardt polish on the "
                  "Fisher matrix)" if lm_polish else
                  ("config['fisher_uncertainties'] (the Fisher matrix)"

@@ -8,14 +8,16 @@ usage: bfgs_jac_ab.py [--spectra S] [--npoly P] [--rounds R] [--evaluator polyli
 (rvs_bfgs_run_grad_fused, config['fused_gradient']), alternating with the two.
 --evaluator nn: bench.py's MLP libraries; the chain then runs with config['nn_gradient']
 and --fused through rvs_bfgs_run_grad_fused_nn.
+--evaluator tri: bench.py's Delaunay libraries; --fused then runs with
+config['tri_gradient'] through rvs_bfgs_run_grad_fused_tri.
 The workload is bench.py's, built as `bench.py --process` builds it (its synthetic
 DESI-shape libraries and seeded spectra, the start parameters from the CCF stage of
 pipeline.fit_batch).  vel_fit.process runs once without the second minimiser; its
 simplex optimum is the start of both polishes, which then run on ONE
 optimizer.ProcessObjective with get_hess_inv's hess_inv0 and scipy's default gtol and
 Wolfe constants, as the BFGS stage of process runs them.  R rounds after a warm-up;
-one JSON line: stage seconds per mode (median, minimum), nit / nfev / njev per spectrum,
-the histogram of scipy's statuses per mode, and the distribution of f_jac - f_fd at the
+one JSON line: stage seconds per mode (median, minimum, maximum), nit / nfev / njev per
+spectrum, the histogram of scipy's statuses per mode, and the distribution of f_jac - f_fd at the
 end (negative: the jac polish ended lower)."""
 import argparse
 import json
@@ -62,6 +64,8 @@ def main():
     cfg, opt = dict(bench.CONFIG), dict(bench.OPTIONS, npoly=args.npoly)
     if args.evaluator == 'nn':
         cfg['nn_gradient'] = True
+    if args.evaluator == 'tri' and args.fused:
+        cfg['tri_gradient'] = True     # (read by GradChain(fused=True) alone)
     # the start of process: the CCF stage's parameters (bench.run_process_addon)
     rec = pipeline.fit_batch(batch, cfg, options=opt)
     F = pipeline.RECORD_FIELDS
@@ -132,7 +136,8 @@ def main():
         dj = (c['fun'] - b['fun']).cpu().numpy()
         more = dict(
             fused=dict(stage_s_median=round(float(np.median(t_fu)), 4),
-                       stage_s_min=round(min(t_fu), 4), lockstep_rounds=c['rounds'],
+                       stage_s_min=round(min(t_fu), 4),
+                       stage_s_max=round(max(t_fu), 4), lockstep_rounds=c['rounds'],
                        rows_launched=c['rows_launched'], nit=per(c, 'nit'),
                        nfev=per(c, 'nfev'), njev=per(c, 'njev'), status_counts=hist(c),
                        work_bytes=fchain.nbytes),
@@ -148,11 +153,13 @@ def main():
         spectra=S, npoly=args.npoly, evaluator=args.evaluator, rounds=args.rounds,
         n=len(cols), chain_cap=chain.cap, chain_bytes=chain.nbytes,
         fd=dict(stage_s_median=round(float(np.median(t_fd)), 4),
-                stage_s_min=round(min(t_fd), 4), lockstep_rounds=a['rounds'],
+                stage_s_min=round(min(t_fd), 4), stage_s_max=round(max(t_fd), 4),
+                lockstep_rounds=a['rounds'],
                 rows_launched=a['rows_launched'], nit=per(a, 'nit'),
                 nfev=per(a, 'nfev'), status_counts=hist(a)),
         jac=dict(stage_s_median=round(float(np.median(t_jac)), 4),
-                 stage_s_min=round(min(t_jac), 4), lockstep_rounds=b['rounds'],
+                 stage_s_min=round(min(t_jac), 4), stage_s_max=round(max(t_jac), 4),
+                 lockstep_rounds=b['rounds'],
                  rows_launched=b['rows_launched'], nit=per(b, 'nit'),
                  nfev=per(b, 'nfev'), njev=per(b, 'njev'), status_counts=hist(b)),
         jac_over_fd_time=round(float(np.median(t_jac) / np.median(t_fd)), 3),

@@ -135,7 +135,10 @@ extern "C" {
  *      rvs_template_tri_vjp (spec_inter.py:11-59 differentiated and contracted with one
  *      adjoint row), the reverse step of the Delaunay evaluator, with
  *      rvs_bfgs_run_grad_fused_tri (vel_fit.py:653-658 on that gradient), the BFGS
- *      rounds on it) */
+ *      rounds on it; and rvs_objective_grad_resol, rvs_objective_grad_from_template_resol
+ *      and rvs_objective_grad_resol_ok, value and gradient in one kernel under resolution
+ *      matrices, with rvs_bfgs_run_grad_fused_resol / _nn_resol / _tri_resol, the BFGS
+ *      rounds on them: the entry points without the suffix go on refusing taps) */
 #define RVS_ABI_VERSION 18
 int rvs_abi_version(void);
 
@@ -943,6 +946,38 @@ int rvs_objective_grad_join(int narm, int J, int ndim, int vsini_grad, const voi
                             const double *const *gparams, const double *out,
                             const double *grad_vv, double *grad, void *stream);
 
+/* rvs_objective_grad and rvs_objective_grad_from_template under per-spectrum resolution
+ * matrices (A9): arms may carry pt.taps / pt.taps_stride / pt.nd as for rvs_objective_fused
+ * (arms with and without a matrix may be mixed: an arm without one is a band of one
+ * diagonal).  The band runs over the pixels' spline values in LDS,
+ *   m_k = sum_d taps[s][k][d] raw[k - (nd-1)/2 + d]    (d ascending, s = job_spec[j]),
+ * the products of rvs_objective_fused in its order, so the value is its value; the
+ * band's transpose is applied to the one adjoint row,
+ *   rawbar_j = sum_d taps[s][j + (nd-1)/2 - d][d] mbar[j + (nd-1)/2 - d]   (d ascending),
+ * and the velocity component is formed behind it.  Every other argument, the outputs,
+ * the scratch sizes and the rules for skipped arms are those of the call without the
+ * suffix; with nd = 1 and taps of 1 the results are its bits.
+ * rvs_objective_grad_resol_ok (host arithmetic only): 1 where the kernel covers an arm of
+ * this geometry under a band of nd diagonals -- nd odd, 1..33; what rvs_objective_grad_ok
+ * asks (ndim = 0: what rvs_objective_grad_from_template_ok asks, for the from-template
+ * form); and 2*npix + nd - 1 <= ntp: the sigma-scaled row and the zero-padded row of the
+ * band share one buffer of ntp doubles.  RVS_E_ARG, before any launch: what the call
+ * without the suffix refuses except pt.taps, an arm rvs_objective_grad_resol_ok refuses,
+ * a taps_stride that is neither 0 nor >= npix*nd. */
+int rvs_objective_grad_resol_ok(int npoly, int npix, int ntp, int ndim, int nd,
+                                int vsini_grad);
+int rvs_objective_grad_resol(const rvs_objective_arm *arms, int narm, int npoly, int ntan,
+                             const double *params, const double *vsini,
+                             const int32_t *job_spec, int J, const double *vel,
+                             double badchi, const double *basis_const, void *scratch,
+                             double *out, double *grad, int32_t *status, void *stream);
+int rvs_objective_grad_from_template_resol(
+    const rvs_objective_arm *arms, int narm, int npoly, int vsini_grad,
+    const double *const *templ, const double *const *outside, const double *vsini,
+    const int32_t *job_spec, int J, const double *vel, double badchi,
+    const double *basis_const, void *scratch, double *const *tbar, double *out,
+    double *grad, int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------------
  * The objective of rvs_objective_grad WITH the Fisher matrix of the marginalised fit
  * (rvs_chisq_point_fisher's F = J^T (1 - U U^T) J), as one kernel per (job, arm), in
@@ -1667,6 +1702,29 @@ int rvs_bfgs_run_grad_fused_tri(const rvs_bfgs_state *b, const rvs_nm_objective 
                                 double *const *tbar, double *const *gparams,
                                 double *grad_vv, int sync_every, int64_t *stats,
                                 void *stream);
+
+/* The three runs above under resolution matrices: the rows' (value, gradient) from
+ * rvs_objective_grad_resol / rvs_objective_grad_from_template_resol, garms with pt.taps /
+ * pt.nd as those calls take them; every other argument as for the run without the
+ * suffix.  RVS_E_ARG also for an arm rvs_objective_grad_resol_ok refuses. */
+int rvs_bfgs_run_grad_fused_resol(const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                                  const rvs_grad_chain *g, const rvs_objective_arm *garms,
+                                  const double *basis_const, void *gwork, int sync_every,
+                                  int64_t *stats, void *stream);
+int rvs_bfgs_run_grad_fused_nn_resol(const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                                     const rvs_grad_chain *g,
+                                     const rvs_objective_arm *garms,
+                                     const double *basis_const, void *gwork,
+                                     double *const *tbar, void *const *vjp_work,
+                                     double *const *gparams, double *grad_vv,
+                                     int sync_every, int64_t *stats, void *stream);
+int rvs_bfgs_run_grad_fused_tri_resol(const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                                      const rvs_grad_chain *g,
+                                      const rvs_objective_arm *garms,
+                                      const double *basis_const, void *gwork,
+                                      double *const *tbar, double *const *gparams,
+                                      double *grad_vv, int sync_every, int64_t *stats,
+                                      void *stream);
 
 /* ------------------------------------------------------------------------
  * The second minimiser as Levenberg-Marquardt on the Fisher matrix

@@ -139,6 +139,10 @@ SIGNATURES = {
     'rvs_objective_grad_from_template': (I, [P, I, I, I, P, P, P, P, I, P, D, P, P, P, P,
                                              P, P, P]),
     'rvs_objective_grad_join': (I, [I, I, I, I, P, P, P, P, P, P]),
+    'rvs_objective_grad_resol_ok': (I, [I, I, I, I, I, I]),
+    'rvs_objective_grad_resol': (I, [P, I, I, I, P, P, P, I, P, D, P, P, P, P, P, P]),
+    'rvs_objective_grad_from_template_resol': (I, [P, I, I, I, P, P, P, P, I, P, D, P, P,
+                                                   P, P, P, P, P]),
     'rvs_template_nn_vjp_work_size': (L, [I, I, P]),
     'rvs_template_nn_vjp': (I, [P, I, I, U, P, P, I, P, P, P, P, P, P, P, P]),
     'rvs_objective_fisher_ok': (I, [I, I, I, I, I]),
@@ -147,6 +151,9 @@ SIGNATURES = {
     'rvs_bfgs_run_grad_fused': (I, [P, P, P, P, P, P, I, P, P]),
     'rvs_bfgs_run_grad_fused_nn': (I, [P, P, P, P, P, P, P, P, P, P, I, P, P]),
     'rvs_bfgs_run_grad_fused_tri': (I, [P, P, P, P, P, P, P, P, P, I, P, P]),
+    'rvs_bfgs_run_grad_fused_resol': (I, [P, P, P, P, P, P, I, P, P]),
+    'rvs_bfgs_run_grad_fused_nn_resol': (I, [P, P, P, P, P, P, P, P, P, P, I, P, P]),
+    'rvs_bfgs_run_grad_fused_tri_resol': (I, [P, P, P, P, P, P, P, P, P, I, P, P]),
     'rvs_grid_moments': (I, [P, P, L, P, I, I, I, I, P, P, P, P]),
     'rvs_basis_build': (I, [P, P, I, I, I, I, P, P, P, P, P]),
     'rvs_ccf_tables_build': (I, [P, P, I, I, P, I, I, P, P, P, I, P, P, P, P, P, P,

@@ -116,7 +116,8 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     kernel per (row, arm) -- on MLP libraries rvs_bfgs_run_grad_fused_nn, with the
     networks' reverse pass behind it, on Delaunay libraries
     rvs_bfgs_run_grad_fused_tri, with the contraction of the adjoint row with the
-    simplex's tangents."""
+    simplex's tangents; under resolution matrices (the objective's resol_gradient) the
+    _resol forms of the three."""
     import ctypes
     import torch
     from . import _lib
@@ -150,10 +151,13 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     b.S, b.n, b.cap, b.maxiter = S, n, int(pobj.cap), int(maxiter or 0)
     o = pobj.native_desc()
     st3 = (ctypes.c_int64 * 3)()
+    # (arms under resolution matrices: the _resol forms of the fused runs)
+    resol = bool(getattr(chain, 'fused_resol', False))
     if jac and getattr(chain, 'fused', False) and getattr(chain, 'fused_nn', False):
         # ... on MLP libraries: the adjoint rows back through the networks
         g = chain.desc()
-        _lib.check(L.rvs_bfgs_run_grad_fused_nn(
+        _lib.check((L.rvs_bfgs_run_grad_fused_nn_resol if resol else
+                    L.rvs_bfgs_run_grad_fused_nn)(
             ctypes.addressof(b), ctypes.addressof(o), ctypes.addressof(g),
             ctypes.addressof(chain.garms), ctypes.addressof(chain.bconst),
             _lib.ptr(chain.gwork), ctypes.cast(chain.tbar_p, ctypes.c_void_p),
@@ -163,7 +167,8 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     elif jac and getattr(chain, 'fused', False) and getattr(chain, 'fused_tri', False):
         # ... on Delaunay libraries: the adjoint rows onto the simplices' tangents
         g = chain.desc()
-        _lib.check(L.rvs_bfgs_run_grad_fused_tri(
+        _lib.check((L.rvs_bfgs_run_grad_fused_tri_resol if resol else
+                    L.rvs_bfgs_run_grad_fused_tri)(
             ctypes.addressof(b), ctypes.addressof(o), ctypes.addressof(g),
             ctypes.addressof(chain.garms), ctypes.addressof(chain.bconst),
             _lib.ptr(chain.gwork), ctypes.cast(chain.tbar_p, ctypes.c_void_p),
@@ -172,7 +177,8 @@ def minimize_lockstep_device(pobj, x0, hess_inv0=None, gtol=1e-5, c1=1e-4, c2=0.
     elif jac and getattr(chain, 'fused', False):
         # optimizer.GradChain(fused=True): one rvs_objective_grad call per chunk
         g = chain.desc()
-        _lib.check(L.rvs_bfgs_run_grad_fused(
+        _lib.check((L.rvs_bfgs_run_grad_fused_resol if resol else
+                    L.rvs_bfgs_run_grad_fused)(
             ctypes.addressof(b), ctypes.addressof(o), ctypes.addressof(g),
             ctypes.addressof(chain.garms), ctypes.addressof(chain.bconst),
             _lib.ptr(chain.gwork), int(sync_every), st3, _lib.stream()),

@@ -177,19 +177,34 @@ extern "C" int rvs_bfgs_run_grad(const rvs_bfgs_state *b, const rvs_nm_objective
                      });
 }
 
+namespace {
+
+// an arm of a fused polish: plain (nm_internal.h), or -- resol: the _resol forms, DESIGN
+// 4.27 -- with a resolution matrix the RESOL form of the gradient kernel takes (ndim 0:
+// the from-template form)
+bool bfgs_fused_arm_ok(bool resol, const rvs_objective_arm &A, int npoly, int ndim, int vg) {
+  if (!resol) return rvs_internal_arm_plain(A);
+  // (the band as rvs_objective_grad_resol takes it, refused here, before any launch: the
+  // geometry, and taps of one matrix for all or of whole matrices per spectrum)
+  return A.pt.G <= 1 && !A.pt.fast_interp &&
+         (!A.pt.taps ||
+          (rvs_objective_grad_resol_ok(npoly, A.pt.npix, A.ntp, ndim, A.pt.nd, vg) &&
+           (A.pt.taps_stride == 0 ||
+            A.pt.taps_stride >= (int64_t)A.pt.npix * A.pt.nd)));
+}
+
 // ... with the chain's stages between the map and the finish replaced by one
-// rvs_objective_grad call (objective_grad.hip)
-extern "C" int rvs_bfgs_run_grad_fused(const rvs_bfgs_state *b,
-                                       const rvs_nm_objective *o,
-                                       const rvs_grad_chain *g,
-                                       const rvs_objective_arm *garms,
-                                       const double *basis_const, void *gwork,
-                                       int sync_every, int64_t *stats, void *stream) {
+// rvs_objective_grad call (objective_grad.hip); resol: rvs_objective_grad_resol
+int bfgs_run_grad_fused(bool resol, const rvs_bfgs_state *b, const rvs_nm_objective *o,
+                        const rvs_grad_chain *g, const rvs_objective_arm *garms,
+                        const double *basis_const, void *gwork, int sync_every,
+                        int64_t *stats, void *stream) {
   if (!bfgs_args_ok(b, o, sync_every) || !g || !g->njev || !garms || !gwork ||
       !rvs_internal_grad_rows_ok(g, o, 4))
     return RVS_E_ARG;
   for (int a = 0; a < g->narm; a++)
-    if (garms[a].ndim != o->ndim || !rvs_internal_arm_plain(garms[a]) ||
+    if (garms[a].ndim != o->ndim ||
+        !bfgs_fused_arm_ok(resol, garms[a], o->npoly, o->ndim, g->vsini_mode == 2) ||
         !rvs_objective_grad_ok(o->npoly, garms[a].pt.npix, garms[a].ntp, o->ndim,
                                g->vsini_mode == 2))
       return RVS_E_ARG;
@@ -199,12 +214,33 @@ extern "C" int rvs_bfgs_run_grad_fused(const rvs_bfgs_state *b,
           hipStream_t st) {
         return rvs_internal_fused_eval(
             o, g, nullptr, list, X, J, b->counts, ch, F, st, [&] {
-              return rvs_objective_grad(garms, g->narm, o->npoly, g->ntan, o->params,
-                                        o->vsini, o->job_spec, J, o->vel, o->badchi,
-                                        basis_const, gwork, g->chi, g->grad, o->jstatus,
-                                        st);
+              return (resol ? rvs_objective_grad_resol : rvs_objective_grad)(
+                  garms, g->narm, o->npoly, g->ntan, o->params, o->vsini, o->job_spec, J,
+                  o->vel, o->badchi, basis_const, gwork, g->chi, g->grad, o->jstatus, st);
             });
       });
+}
+
+}  // namespace
+
+extern "C" int rvs_bfgs_run_grad_fused(const rvs_bfgs_state *b,
+                                       const rvs_nm_objective *o,
+                                       const rvs_grad_chain *g,
+                                       const rvs_objective_arm *garms,
+                                       const double *basis_const, void *gwork,
+                                       int sync_every, int64_t *stats, void *stream) {
+  return bfgs_run_grad_fused(false, b, o, g, garms, basis_const, gwork, sync_every, stats,
+                             stream);
+}
+extern "C" int rvs_bfgs_run_grad_fused_resol(const rvs_bfgs_state *b,
+                                             const rvs_nm_objective *o,
+                                             const rvs_grad_chain *g,
+                                             const rvs_objective_arm *garms,
+                                             const double *basis_const, void *gwork,
+                                             int sync_every, int64_t *stats,
+                                             void *stream) {
+  return bfgs_run_grad_fused(true, b, o, g, garms, basis_const, gwork, sync_every, stats,
+                             stream);
 }
 
 // ... on MLP libraries: the rows' template rows from the networks of o->nn,
@@ -215,11 +251,12 @@ extern "C" int rvs_bfgs_run_grad_fused(const rvs_bfgs_state *b,
 // caller: tbar, vjp_work, gparams are HOST arrays of narm device pointers ([cap, ntp],
 // rvs_template_nn_vjp_work_size(cap, ...) bytes, [cap, ndim]), grad_vv [cap, 1 + (vsini
 // fitted)].
-extern "C" int rvs_bfgs_run_grad_fused_nn(
-    const rvs_bfgs_state *b, const rvs_nm_objective *o, const rvs_grad_chain *g,
-    const rvs_objective_arm *garms, const double *basis_const, void *gwork,
-    double *const *tbar, void *const *vjp_work, double *const *gparams, double *grad_vv,
-    int sync_every, int64_t *stats, void *stream) {
+namespace {
+int bfgs_run_grad_fused_nn(
+    bool resol, const rvs_bfgs_state *b, const rvs_nm_objective *o,
+    const rvs_grad_chain *g, const rvs_objective_arm *garms, const double *basis_const,
+    void *gwork, double *const *tbar, void *const *vjp_work, double *const *gparams,
+    double *grad_vv, int sync_every, int64_t *stats, void *stream) {
   if (!bfgs_args_ok(b, o, sync_every) || !g || !g->njev || !garms || !gwork || !tbar ||
       !vjp_work || !gparams || !grad_vv || !rvs_internal_grad_rows_ok(g, o, 6) || !o->nn)
     return RVS_E_ARG;
@@ -229,7 +266,7 @@ extern "C" int rvs_bfgs_run_grad_fused_nn(
     const rvs_nm_nn_arm &N = o->nn[a];
     if (!tbar[a] || !vjp_work[a] || !gparams[a] || !N.templ || !N.outside || !N.dims ||
         N.dims[0] != o->ndim || N.nlayer < 1 || N.dims[N.nlayer] != garms[a].ntp ||
-        !rvs_internal_arm_plain(garms[a]) ||
+        !bfgs_fused_arm_ok(resol, garms[a], o->npoly, 0, vg) ||
         !rvs_objective_grad_from_template_ok(o->npoly, garms[a].pt.npix, garms[a].ntp, vg) ||
         rvs_template_nn_vjp_work_size(g->cap, N.nlayer, N.dims) <= 0)
       return RVS_E_ARG;
@@ -245,7 +282,8 @@ extern "C" int rvs_bfgs_run_grad_fused_nn(
               int rc = rvs_template_nn_arms_n(o->params, J, nullptr, o->ndim, o->narm,
                                               o->nn, st);
               if (rc) return rc;
-              rc = rvs_objective_grad_from_template(
+              rc = (resol ? rvs_objective_grad_from_template_resol
+                          : rvs_objective_grad_from_template)(
                   garms, g->narm, o->npoly, vg, tp, op, o->vsini, o->job_spec, J, o->vel,
                   o->badchi, basis_const, gwork, tbar, g->chi, grad_vv, o->jstatus, st);
               if (rc) return rc;
@@ -262,6 +300,25 @@ extern "C" int rvs_bfgs_run_grad_fused_nn(
       });
 }
 
+}  // namespace
+
+extern "C" int rvs_bfgs_run_grad_fused_nn(
+    const rvs_bfgs_state *b, const rvs_nm_objective *o, const rvs_grad_chain *g,
+    const rvs_objective_arm *garms, const double *basis_const, void *gwork,
+    double *const *tbar, void *const *vjp_work, double *const *gparams, double *grad_vv,
+    int sync_every, int64_t *stats, void *stream) {
+  return bfgs_run_grad_fused_nn(false, b, o, g, garms, basis_const, gwork, tbar, vjp_work,
+                                gparams, grad_vv, sync_every, stats, stream);
+}
+extern "C" int rvs_bfgs_run_grad_fused_nn_resol(
+    const rvs_bfgs_state *b, const rvs_nm_objective *o, const rvs_grad_chain *g,
+    const rvs_objective_arm *garms, const double *basis_const, void *gwork,
+    double *const *tbar, void *const *vjp_work, double *const *gparams, double *grad_vv,
+    int sync_every, int64_t *stats, void *stream) {
+  return bfgs_run_grad_fused_nn(true, b, o, g, garms, basis_const, gwork, tbar, vjp_work,
+                                gparams, grad_vv, sync_every, stats, stream);
+}
+
 // ... on Delaunay libraries: the form above with the triangulations of
 // o->tri as the evaluator -- the rows' template rows, outside flags and simplex ids from
 // rvs_internal_template_tri_arms_n into the buffers of o->tri[a], and the parameter
@@ -269,11 +326,12 @@ extern "C" int rvs_bfgs_run_grad_fused_nn(
 // search is not repeated).  float64 throughout; the reverse step needs no work buffer.
 // tbar, gparams: HOST arrays of narm device pointers ([cap, ntp], [cap, ndim]), grad_vv
 // [cap, 1 + (vsini fitted)].
-extern "C" int rvs_bfgs_run_grad_fused_tri(
-    const rvs_bfgs_state *b, const rvs_nm_objective *o, const rvs_grad_chain *g,
-    const rvs_objective_arm *garms, const double *basis_const, void *gwork,
-    double *const *tbar, double *const *gparams, double *grad_vv, int sync_every,
-    int64_t *stats, void *stream) {
+namespace {
+int bfgs_run_grad_fused_tri(
+    bool resol, const rvs_bfgs_state *b, const rvs_nm_objective *o,
+    const rvs_grad_chain *g, const rvs_objective_arm *garms, const double *basis_const,
+    void *gwork, double *const *tbar, double *const *gparams, double *grad_vv,
+    int sync_every, int64_t *stats, void *stream) {
   if (!bfgs_args_ok(b, o, sync_every) || !g || !g->njev || !garms || !gwork || !tbar ||
       !gparams || !grad_vv || !rvs_internal_grad_rows_ok(g, o, 6) || !o->tri)
     return RVS_E_ARG;
@@ -284,7 +342,7 @@ extern "C" int rvs_bfgs_run_grad_fused_tri(
     if (!tbar[a] || !gparams[a] || !T.templ || !T.outside || !T.simplex || !T.dats ||
         !T.simplices || !T.transform || !T.buckets.cell_start || !T.buckets.cell_list ||
         T.nsimplex < 1 || T.ntp != garms[a].ntp ||
-        !rvs_internal_arm_plain(garms[a]) ||
+        !bfgs_fused_arm_ok(resol, garms[a], o->npoly, 0, vg) ||
         !rvs_objective_grad_from_template_ok(o->npoly, garms[a].pt.npix, garms[a].ntp, vg))
       return RVS_E_ARG;
     tp[a] = T.templ;
@@ -299,7 +357,8 @@ extern "C" int rvs_bfgs_run_grad_fused_tri(
               int rc = rvs_internal_template_tri_arms_n(o->params, J, nullptr, o->ndim,
                                                         o->narm, o->tri, st);
               if (rc) return rc;
-              rc = rvs_objective_grad_from_template(
+              rc = (resol ? rvs_objective_grad_from_template_resol
+                          : rvs_objective_grad_from_template)(
                   garms, g->narm, o->npoly, vg, tp, op, o->vsini, o->job_spec, J, o->vel,
                   o->badchi, basis_const, gwork, tbar, g->chi, grad_vv, o->jstatus, st);
               if (rc) return rc;
@@ -315,4 +374,23 @@ extern "C" int rvs_bfgs_run_grad_fused_tri(
                                              g->chi, grad_vv, g->grad, st);
             });
       });
+}
+
+}  // namespace
+
+extern "C" int rvs_bfgs_run_grad_fused_tri(
+    const rvs_bfgs_state *b, const rvs_nm_objective *o, const rvs_grad_chain *g,
+    const rvs_objective_arm *garms, const double *basis_const, void *gwork,
+    double *const *tbar, double *const *gparams, double *grad_vv, int sync_every,
+    int64_t *stats, void *stream) {
+  return bfgs_run_grad_fused_tri(false, b, o, g, garms, basis_const, gwork, tbar, gparams,
+                                 grad_vv, sync_every, stats, stream);
+}
+extern "C" int rvs_bfgs_run_grad_fused_tri_resol(
+    const rvs_bfgs_state *b, const rvs_nm_objective *o, const rvs_grad_chain *g,
+    const rvs_objective_arm *garms, const double *basis_const, void *gwork,
+    double *const *tbar, double *const *gparams, double *grad_vv, int sync_every,
+    int64_t *stats, void *stream) {
+  return bfgs_run_grad_fused_tri(true, b, o, g, garms, basis_const, gwork, tbar, gparams,
+                                 grad_vv, sync_every, stats, stream);
 }

@@ -57,7 +57,26 @@ struct OgTempl {
   double *tbar[RVS_MAX_ARMS];           // [J, ntp] per arm
 };
 
-template <int P, bool FROMT = false>
+// RESOL (rvs_objective_grad_resol, rvs_objective_grad_from_template_resol): arms
+// with a banded resolution matrix of nd <= 33 diagonals (rvs_point_arm.taps), applied in
+// LDS as objective_kernel<.., RESOL> applies it, and its transpose applied to the one
+// adjoint row.  The third buffer then holds
+//   F[0, npix)                     m/e of the model pass; behind the transposed band rawbar
+//   PAD = F + npix: [hb zeros] [npix: raw, from pass 2 on mbar] [hb zeros],  hb = (nd - 1) / 2
+// (the data column D/e is read from sig[k].y, the same double), and the first-pixel table
+// lies over PAD once the transposed band has read it: 2 npix + nd - 1 <= ntp
+// (rvs_objective_grad_resol_ok).
+//   model pass   raw[k] -> PAD[hb + k]; barrier; m_k = sum_d taps[s, k, d] PAD[k + d], d
+//                ascending: the products of resolution_band (objective.hip) in its order
+//   pass 2       mbar_k -> PAD[hb + k] (the pads stay zero); barrier
+//   band^T       rawbar_j = sum_d taps[s, j + hb - d, d] PAD[j + 2 hb - d], d ascending,
+//                threads = pixels: stride nd - 1 in taps; a row outside [0, npix) meets a
+//                loaded zero (its tap is read from the nearest row inside), no atomic
+//   velocity     gvel = sum_j rawbar_j S'(x_j) lam_j df/dvel: behind the band, so y and z
+//                stay live until here
+// and from there on rawbar is what mbar is without a matrix.  An arm without a matrix
+// beside arms that have one is a band of one diagonal.
+template <int P, bool FROMT = false, bool RESOL = false>
 __global__ void __launch_bounds__(OP_NT)
     objective_grad_kernel(ObjArms A, const double *__restrict__ params,
                           const double *__restrict__ vsini, int vsini_grad,
@@ -150,14 +169,40 @@ __global__ void __launch_bounds__(OP_NT)
     p.c3 = (zi1 - zi) * t1;
     return p;
   };
+  // RESOL: the band of this spectrum, the padded row (see above)
+  const int rnd = (RESOL && S.taps) ? S.nd : 1, hb = (rnd - 1) >> 1;
+  const double *tps = (RESOL && S.taps) ? S.taps + (int64_t)s * S.taps_stride : nullptr;
+  double *PAD = F + npix;
+  if (RESOL && tid < hb) {
+    PAD[tid] = 0.0;
+    PAD[hb + npix + tid] = 0.0;
+  }
   // (a loop of its own, which holds no accumulators, as in objective_kernel)
   for (int k = tid; k < npix; k += OP_NT) {
     const int pos = pix_pos(k);
     const double dl = AG.lam[k] * f - S.knots[pos];
     const double tv = obj_piece_value(piece(pos), dl);
-    const double2 sg = sig[k];
-    F[k] = tv * sg.x;
-    F[npix + k] = sg.y;
+    if constexpr (RESOL) {
+      PAD[hb + k] = tv;
+    } else {
+      const double2 sg = sig[k];
+      F[k] = tv * sg.x;
+      F[npix + k] = sg.y;
+    }
+  }
+  if constexpr (RESOL) {
+    // ---- resolution band (A9): m_k = sum_d taps[s, k, d] raw[k - hb + d], then m/e ----------
+    __syncthreads();
+    for (int k = tid; k < npix; k += OP_NT) {
+      const double *rk = PAD + k;   // raw[k - hb]
+      double a = rk[0];
+      if (tps) {
+        const double *tk = tps + (int64_t)k * rnd;
+        a = 0;
+        for (int d = 0; d < rnd; d++) a = fma(tk[d], rk[d], a);
+      }
+      F[k] = a * sig[k].x;
+    }
   }
   // ---- normal equations (A10): the sums per lane, waves' totals into sh.red ---------------
   {
@@ -165,7 +210,8 @@ __global__ void __launch_bounds__(OP_NT)
 #pragma unroll
     for (int i = 0; i < NV; i++) vals[i] = 0;
     for (int k = tid; k < npix; k += OP_NT) {
-      const double te = F[k], dk = F[npix + k];   // (written by this same thread)
+      // (written by this same thread; RESOL: the data column from the pixel's record)
+      const double te = F[k], dk = RESOL ? sig[k].y : F[npix + k];
       // (the rows ST = phi m/e themselves: one register row where the value kernel
       // keeps phi and phi (m/e)^2 -- this kernel has the adjoint's state beside it)
       const double *pr = AG.polysT + (int64_t)k * P;
@@ -254,7 +300,7 @@ __global__ void __launch_bounds__(OP_NT)
   const double dfdv = -f / (RVS_C_KMS * (1.0 - bb * bb));
   double rr = 0, gvel = 0;
   for (int k = tid; k < npix; k += OP_NT) {
-    const double te = F[k], dk = F[npix + k];
+    const double te = F[k], dk = RESOL ? sig[k].y : F[npix + k];
     const double ie = sig[k].x;
     const double *pr = AG.polysT + (int64_t)k * P;
     double yv[P], mk = 0, qk = 0;
@@ -271,14 +317,40 @@ __global__ void __launch_bounds__(OP_NT)
     const double r = dk - mk * te;
     rr = fma(r, r, rr);
     const double mbar = 2.0 * ie * (te * qk - r * mk);
-    const int pos = pix_pos(k);
-    const double lamk = AG.lam[k];
-    const double dl = lamk * f - S.knots[pos];
-    const double dtv = obj_piece_deriv(piece(pos), dl);
-    gvel = fma(mbar, dtv * (lamk * dfdv), gvel);
-    F[k] = mbar;
+    if constexpr (RESOL) {
+      PAD[hb + k] = mbar;
+    } else {
+      const int pos = pix_pos(k);
+      const double lamk = AG.lam[k];
+      const double dl = lamk * f - S.knots[pos];
+      const double dtv = obj_piece_deriv(piece(pos), dl);
+      gvel = fma(mbar, dtv * (lamk * dfdv), gvel);
+      F[k] = mbar;
+    }
   }
-  __syncthreads();   // y, z and the data column of F are dead
+  if constexpr (RESOL) {
+    // ---- resolution band, transposed: rawbar = R^T mbar; the velocity component ---------------
+    // hands over: gvel; rawbar in F[0, npix)
+    __syncthreads();
+    for (int k = tid; k < npix; k += OP_NT) {
+      const double *mk = PAD + k + 2 * hb;   // mbar[k + hb]
+      double rawbar = mk[0];
+      if (tps) {
+        rawbar = 0;
+        for (int d = 0; d < rnd; d++) {
+          const int row = min(max(k + hb - d, 0), npix - 1);
+          rawbar = fma(tps[(int64_t)row * rnd + d], mk[-d], rawbar);
+        }
+      }
+      const int pos = pix_pos(k);
+      const double lamk = AG.lam[k];
+      const double dl = lamk * f - S.knots[pos];
+      const double dtv = obj_piece_deriv(piece(pos), dl);
+      gvel = fma(rawbar, dtv * (lamk * dfdv), gvel);
+      F[k] = rawbar;
+    }
+  }
+  __syncthreads();   // y, z and the data column of F (RESOL: the padded row) are dead
 
   // ---- resampling, transposed -------------------------------------------------------
   // first[n] = the number of pixels in intervals below n (pixels ascend in wavelength,
@@ -442,15 +514,30 @@ extern "C" int64_t rvs_objective_grad_work_size(int J, int narm, int ntan) {
   return (int64_t)narm * J * (int64_t)((4 + ntan) * sizeof(double));
 }
 
-extern "C" int rvs_objective_grad(const rvs_objective_arm *arms, int narm, int npoly,
-                                  int ntan, const double *params, const double *vsini,
-                                  const int32_t *job_spec, int J, const double *vel,
-                                  double badchi, const double *basis_const,
-                                  void *scratch, double *out, double *grad,
-                                  int32_t *status, void *stream) {
+// What the kernel covers under a resolution matrix of nd diagonals, the one statement of
+// the condition (host arithmetic only): nd odd, 1 .. 33; everything op_point_ok asks (ndim
+// = 0: the from-template form, which reads no cell -- op_geometry_ok); and the LDS layout
+// of objective_grad_kernel<.., RESOL>: the third buffer of ntp doubles holds m/e in
+// [0, npix) and behind it the padded row [hb zeros][npix][hb zeros], hb = (nd - 1) / 2, so
+//   npix + (npix + nd - 1) <= ntp.
+// The first-pixel table ((ntp + 1) / 2 doubles behind rawbar in [0, npix)) lies over the
+// padded row once the transposed band has read it: npix + (ntp + 1) / 2 <= ntp already
+// follows from 2 npix <= ntp.
+extern "C" int rvs_objective_grad_resol_ok(int npoly, int npix, int ntp, int ndim, int nd,
+                                           int vsini_grad) {
+  if (ndim < 0 || ndim > OP_MAXDIM) return 0;
+  return op_resol_geometry_ok(npoly, npix, ntp, nd, vsini_grad);
+}
+
+namespace {
+int objective_grad_call(bool resol, const rvs_objective_arm *arms, int narm, int npoly,
+                        int ntan, const double *params, const double *vsini,
+                        const int32_t *job_spec, int J, const double *vel, double badchi,
+                        const double *basis_const, void *scratch, double *out,
+                        double *grad, int32_t *status, void *stream) {
   OpCall c;
   if (J < 1 || !params || !vel || !scratch || !out || !grad || !status ||
-      !op_check_arms(arms, narm, npoly, ntan, vsini, basis_const, c))
+      !op_check_arms(arms, narm, npoly, ntan, vsini, basis_const, c, resol))
     return RVS_E_ARG;
   hipStream_t st = rvs_stream(stream);
   const int K = 1 + ntan;
@@ -460,15 +547,45 @@ extern "C" int rvs_objective_grad(const rvs_objective_arm *arms, int narm, int n
   int32_t *armst = (int32_t *)(armgrad + (int64_t)narm * J * K);
   op_for_npoly(npoly, [&](auto p) {
     constexpr int PP = decltype(p)::value;
-    op_launch<objective_grad_kernel<PP>, (int)sizeof(OgShared<PP>)>(
-        dim3(J, narm), c.shm, st, c.A, params, vsini, c.vsini_grad, job_spec, J, vel, 0.6,
-        armchi, armgrad, armst, armout, OgNoTempl());
+    if (resol)
+      op_launch<objective_grad_kernel<PP, false, true>, (int)sizeof(OgShared<PP>)>(
+          dim3(J, narm), c.shm, st, c.A, params, vsini, c.vsini_grad, job_spec, J, vel,
+          0.6, armchi, armgrad, armst, armout, OgNoTempl());
+    else
+      op_launch<objective_grad_kernel<PP>, (int)sizeof(OgShared<PP>)>(
+          dim3(J, narm), c.shm, st, c.A, params, vsini, c.vsini_grad, job_spec, J, vel,
+          0.6, armchi, armgrad, armst, armout, OgNoTempl());
   });
   hipLaunchKernelGGL(objective_point_sum_kernel, dim3((J + 255) / 256), dim3(256), 0, st,
                      narm, J, 0, K, badchi, c.bc, arms[0].pt.pen_scale, job_spec, armchi,
                      armgrad, nullptr, armst, armout, out, grad, nullptr, status);
   RVS_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int rvs_objective_grad(const rvs_objective_arm *arms, int narm, int npoly,
+                                  int ntan, const double *params, const double *vsini,
+                                  const int32_t *job_spec, int J, const double *vel,
+                                  double badchi, const double *basis_const,
+                                  void *scratch, double *out, double *grad,
+                                  int32_t *status, void *stream) {
+  return objective_grad_call(false, arms, narm, npoly, ntan, params, vsini, job_spec, J,
+                             vel, badchi, basis_const, scratch, out, grad, status, stream);
+}
+
+// ... with the arms' resolution matrices (pt.taps / pt.nd) applied: the RESOL form of the
+// kernel; scratch as for rvs_objective_grad
+extern "C" int rvs_objective_grad_resol(const rvs_objective_arm *arms, int narm, int npoly,
+                                        int ntan, const double *params,
+                                        const double *vsini, const int32_t *job_spec,
+                                        int J, const double *vel, double badchi,
+                                        const double *basis_const, void *scratch,
+                                        double *out, double *grad, int32_t *status,
+                                        void *stream) {
+  return objective_grad_call(true, arms, narm, npoly, ntan, params, vsini, job_spec, J,
+                             vel, badchi, basis_const, scratch, out, grad, status, stream);
 }
 
 // ---- the from-template form ---------------------------------------------------
@@ -487,15 +604,17 @@ extern "C" int64_t rvs_objective_grad_from_template_work_size(int J, int narm,
   return (int64_t)narm * J * (int64_t)((4 + vsini_grad) * sizeof(double));
 }
 
-extern "C" int rvs_objective_grad_from_template(
-    const rvs_objective_arm *arms, int narm, int npoly, int vsini_grad,
+namespace {
+int objective_grad_from_template_call(
+    bool resol, const rvs_objective_arm *arms, int narm, int npoly, int vsini_grad,
     const double *const *templ, const double *const *outside, const double *vsini,
     const int32_t *job_spec, int J, const double *vel, double badchi,
     const double *basis_const, void *scratch, double *const *tbar, double *out,
     double *grad, int32_t *status, void *stream) {
   OpCall c;
   if (J < 1 || !templ || !outside || !tbar || !vel || !scratch || !out || !grad ||
-      !status || !op_check_arms_templ(arms, narm, npoly, vsini_grad, vsini, basis_const, c))
+      !status ||
+      !op_check_arms_templ(arms, narm, npoly, vsini_grad, vsini, basis_const, c, resol))
     return RVS_E_ARG;
   OgTempl tt = {};
   for (int i = 0; i < RVS_MAX_ARMS; i++) {
@@ -513,15 +632,48 @@ extern "C" int rvs_objective_grad_from_template(
   int32_t *armst = (int32_t *)(armgrad + (int64_t)narm * J * K);
   op_for_npoly(npoly, [&](auto p) {
     constexpr int PP = decltype(p)::value;
-    op_launch<objective_grad_kernel<PP, true>, (int)sizeof(OgShared<PP>)>(
-        dim3(J, narm), c.shm, st, c.A, (const double *)nullptr, vsini, c.vsini_grad,
-        job_spec, J, vel, 0.6, armchi, armgrad, armst, armout, tt);
+    if (resol)
+      op_launch<objective_grad_kernel<PP, true, true>, (int)sizeof(OgShared<PP>)>(
+          dim3(J, narm), c.shm, st, c.A, (const double *)nullptr, vsini, c.vsini_grad,
+          job_spec, J, vel, 0.6, armchi, armgrad, armst, armout, tt);
+    else
+      op_launch<objective_grad_kernel<PP, true>, (int)sizeof(OgShared<PP>)>(
+          dim3(J, narm), c.shm, st, c.A, (const double *)nullptr, vsini, c.vsini_grad,
+          job_spec, J, vel, 0.6, armchi, armgrad, armst, armout, tt);
   });
   hipLaunchKernelGGL(objective_point_sum_kernel, dim3((J + 255) / 256), dim3(256), 0, st,
                      narm, J, 0, K, badchi, c.bc, arms[0].pt.pen_scale, job_spec, armchi,
                      armgrad, nullptr, armst, armout, out, grad, nullptr, status);
   RVS_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int rvs_objective_grad_from_template(
+    const rvs_objective_arm *arms, int narm, int npoly, int vsini_grad,
+    const double *const *templ, const double *const *outside, const double *vsini,
+    const int32_t *job_spec, int J, const double *vel, double badchi,
+    const double *basis_const, void *scratch, double *const *tbar, double *out,
+    double *grad, int32_t *status, void *stream) {
+  return objective_grad_from_template_call(false, arms, narm, npoly, vsini_grad, templ,
+                                           outside, vsini, job_spec, J, vel, badchi,
+                                           basis_const, scratch, tbar, out, grad, status,
+                                           stream);
+}
+
+// ... with the arms' resolution matrices applied: the adjoint row behind the
+// transposed band; scratch as for rvs_objective_grad_from_template
+extern "C" int rvs_objective_grad_from_template_resol(
+    const rvs_objective_arm *arms, int narm, int npoly, int vsini_grad,
+    const double *const *templ, const double *const *outside, const double *vsini,
+    const int32_t *job_spec, int J, const double *vel, double badchi,
+    const double *basis_const, void *scratch, double *const *tbar, double *out,
+    double *grad, int32_t *status, void *stream) {
+  return objective_grad_from_template_call(true, arms, narm, npoly, vsini_grad, templ,
+                                           outside, vsini, job_spec, J, vel, badchi,
+                                           basis_const, scratch, tbar, out, grad, status,
+                                           stream);
 }
 
 // ---- the sum over the arms of the evaluator's reverse pass --------------------------------

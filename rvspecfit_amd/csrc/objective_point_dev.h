@@ -556,6 +556,22 @@ inline int op_point_ok(int npoly, int npix, int ntp, int ndim, int vsini_grad) {
   if (ndim < 1 || ndim > OP_MAXDIM) return 0;
   return op_geometry_ok(npoly, npix, ntp, vsini_grad);
 }
+// ... of the gradient kernel under a resolution matrix of nd diagonals (objective_grad_kernel
+// <.., RESOL>): the arithmetic of rvs_objective_grad_resol_ok, where the
+// inequality is derived from the layout (objective_grad.hip)
+#define OP_MAXND 33
+inline int op_resol_geometry_ok(int npoly, int npix, int ntp, int nd, int vsini_grad) {
+  if (nd < 1 || nd > OP_MAXND || !(nd & 1)) return 0;
+  if (!op_geometry_ok(npoly, npix, ntp, vsini_grad)) return 0;
+  if (2 * (int64_t)npix + nd - 1 > ntp) return 0;
+  return 1;
+}
+// an arm's matrix as the RESOL form takes it (an arm without one: a band of one diagonal)
+inline bool op_arm_resol_ok(const rvs_objective_arm &a, int npoly, int vsini_grad) {
+  if (!a.pt.taps) return true;   // (2 npix <= ntp: op_geometry_ok)
+  return op_resol_geometry_ok(npoly, a.pt.npix, a.ntp, a.pt.nd, vsini_grad) &&
+         (a.pt.taps_stride == 0 || a.pt.taps_stride >= (int64_t)a.pt.npix * a.pt.nd);
+}
 
 // the arms of a call, checked and copied for the launch
 struct OpCall {
@@ -564,10 +580,11 @@ struct OpCall {
   size_t shm;                // dynamic LDS: the widest arm's three buffers
   int vsini_grad, npix_max;
 };
-// ntan = ndim: vel and the parameters; ndim + 1: vsini fitted, its column last.  false:
-// RVS_E_ARG
+// ntan = ndim: vel and the parameters; ndim + 1: vsini fitted, its column last.  resol:
+// the RESOL form of the gradient kernel, which reads pt.taps / pt.nd.  false: RVS_E_ARG
 inline bool op_check_arms(const rvs_objective_arm *arms, int narm, int npoly, int ntan,
-                          const double *vsini, const double *basis_const, OpCall &c) {
+                          const double *vsini, const double *basis_const, OpCall &c,
+                          bool resol = false) {
   static_assert(RVS_MAX_ARMS == 4, "basis constants travel as a double4");
   if (narm < 1 || narm > RVS_MAX_ARMS || !arms || npoly < 1 || npoly > OP_MAXP ||
       ntan < 1 || ntan > OP_MAXDIM + 1)
@@ -581,9 +598,10 @@ inline bool op_check_arms(const rvs_objective_arm *arms, int narm, int npoly, in
   double bc[RVS_MAX_ARMS] = {0, 0, 0, 0};
   for (int i = 0; i < narm; i++) {
     const rvs_objective_arm &a = arms[i];
-    if (a.ndim != ndim || a.pt.fast_interp || a.pt.taps || a.pt.G > 1 || !a.factors ||
-        !a.dats || !a.idgrid || !a.uvecs || !a.vecs_s || a.pt.ntp != a.ntp ||
-        !op_point_ok(npoly, a.pt.npix, a.ntp, ndim, c.vsini_grad))
+    if (a.ndim != ndim || a.pt.fast_interp || (a.pt.taps && !resol) || a.pt.G > 1 ||
+        !a.factors || !a.dats || !a.idgrid || !a.uvecs || !a.vecs_s || a.pt.ntp != a.ntp ||
+        !op_point_ok(npoly, a.pt.npix, a.ntp, ndim, c.vsini_grad) ||
+        !op_arm_resol_ok(a, npoly, c.vsini_grad))
       return false;
     c.A.a[i] = a;
     if (basis_const) bc[i] = basis_const[i];
@@ -599,7 +617,7 @@ inline bool op_check_arms(const rvs_objective_arm *arms, int narm, int npoly, in
 // not read), the geometry rule is op_geometry_ok.  false: RVS_E_ARG
 inline bool op_check_arms_templ(const rvs_objective_arm *arms, int narm, int npoly,
                                 int vsini_grad, const double *vsini,
-                                const double *basis_const, OpCall &c) {
+                                const double *basis_const, OpCall &c, bool resol = false) {
   if (narm < 1 || narm > RVS_MAX_ARMS || !arms || npoly < 1 || npoly > OP_MAXP ||
       vsini_grad < 0 || vsini_grad > 1 || (vsini_grad && !vsini))
     return false;
@@ -610,8 +628,9 @@ inline bool op_check_arms_templ(const rvs_objective_arm *arms, int narm, int npo
   double bc[RVS_MAX_ARMS] = {0, 0, 0, 0};
   for (int i = 0; i < narm; i++) {
     const rvs_objective_arm &a = arms[i];
-    if (a.pt.fast_interp || a.pt.taps || a.pt.G > 1 || !a.factors || a.pt.ntp != a.ntp ||
-        !op_geometry_ok(npoly, a.pt.npix, a.ntp, vsini_grad))
+    if (a.pt.fast_interp || (a.pt.taps && !resol) || a.pt.G > 1 || !a.factors ||
+        a.pt.ntp != a.ntp || !op_geometry_ok(npoly, a.pt.npix, a.ntp, vsini_grad) ||
+        !op_arm_resol_ok(a, npoly, vsini_grad))
       return false;
     c.A.a[i] = a;
     c.A.a[i].ndim = 0;   // (documented as not read: no shift by a caller's leftover)

@@ -1384,12 +1384,13 @@ def objective_from_template(batch, libs, templs, outsides, vsini, vel, npoly=5,
 
 GRAD_FUSED_MAXP = 10     # OP_MAXP of csrc/objective_point_dev.h
 GRAD_FUSED_MAXDIM = 4
+GRAD_FUSED_MAXND = 33    # OP_MAXND: the diagonals of a resolution matrix in the kernel
 TRI_VJP_MAXDIM = 6       # TRI_MAXDIM of csrc/template.hip
 
 
 def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
                            vsini_grad=False, what=None, nn_gradient=False,
-                           tri_gradient=False):
+                           tri_gradient=False, resol_gradient=False):
     """ValueError naming the option that config['fused_gradient'] does not go with:
     what rvs_objective_grad (csrc/objective_grad.hip) does not cover keeps the chain,
     and the key beside it is an error, never a silent change of path.  `what`: a
@@ -1401,7 +1402,13 @@ def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
     where the network is in rvs_template_nn_grad's scope and the arm in the kernel's
     geometry.  tri_gradient (config['tri_gradient']): Delaunay libraries on every arm
     are admitted the same way, the adjoint row going to rvs_template_tri_vjp (float64),
-    for ndim <= 6; a Delaunay arm beside arms of another kind is refused."""
+    for ndim <= 6; a Delaunay arm beside arms of another kind is refused.
+    resol_gradient (config['resol_gradient']): arms under a resolution matrix are
+    admitted -- the RESOL form of the kernel applies the band and its transpose in LDS
+    (rvs_objective_grad_resol, rvs_objective_grad_from_template_resol) -- where the
+    library's rvs_objective_grad_resol_ok admits the arm: an odd number of up to 33
+    diagonals, 2 npix + nd - 1 <= ntp; anything else is a ValueError naming the key, the
+    arm and the limit."""
     key = "config['fused_gradient']"
     if what is not None:
         raise ValueError('%s does not go with %s: it needs the tangent rows of the '
@@ -1409,7 +1416,7 @@ def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
                          % (key, what))
     if nn_gradient and all(libs[arm.name].kind == 'nn' for arm in batch.arms):
         _check_fused_scope(key, None, batch, libs, npoly, resols, fast_interp, vsini_grad,
-                           nn=True)
+                           nn=True, resol_gradient=resol_gradient)
         return
     kinds = [libs[arm.name].kind for arm in batch.arms]
     if tri_gradient and 'triangulation' in kinds:
@@ -1420,14 +1427,32 @@ def check_fused_grad_scope(batch, libs, npoly, resols=None, fast_interp=False,
                                  'triangulation libraries (interpolation_type)'
                                  % (key, arm.name, kind))
         _check_fused_scope(key, None, batch, libs, npoly, resols, fast_interp, vsini_grad,
-                           tri=True)
+                           tri=True, resol_gradient=resol_gradient)
         return
     _check_fused_scope(key, _lib.lib().rvs_objective_grad_ok, batch, libs, npoly, resols,
-                       fast_interp, vsini_grad)
+                       fast_interp, vsini_grad, resol_gradient=resol_gradient)
+
+
+def _check_fused_resol(key, arm, lib, rs, npoly, ndim, vsini_grad):
+    # an arm's resolution matrix beside config['fused_gradient'] and
+    # config['resol_gradient'] (ndim 0: the from-template form, which reads no cell)
+    nd = int(rs['nd'])
+    if nd < 1 or nd > GRAD_FUSED_MAXND or nd % 2 == 0:
+        raise ValueError('%s with config[\'resol_gradient\']: the resolution matrix of '
+                         'arm %s has %d diagonals; the kernel takes an odd number of at '
+                         'most %d (a wider band keeps the gradient chain: unset '
+                         'fused_gradient)' % (key, arm.name, nd, GRAD_FUSED_MAXND))
+    if not _lib.lib().rvs_objective_grad_resol_ok(npoly, arm.npix, lib.ntp, ndim, nd,
+                                                  int(bool(vsini_grad))):
+        raise ValueError('%s with config[\'resol_gradient\']: arm %s (npix = %d, ntp = '
+                         '%d) under a resolution matrix of %d diagonals is outside the '
+                         'kernel\'s geometry: 2 npix + nd - 1 <= ntp (at most %d pixels '
+                         'here)' % (key, arm.name, arm.npix, lib.ntp, nd,
+                                    (lib.ntp - nd + 1) // 2))
 
 
 def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_grad,
-                       nn=False, tri=False):
+                       nn=False, tri=False, resol_gradient=False):
     # what rvs_objective_grad and rvs_objective_fisher both leave to the chain; ok: the
     # kernel's own rvs_objective_*_ok; nn / tri: MLP / Delaunay libraries on the
     # from-template form of the gradient kernel
@@ -1440,7 +1465,8 @@ def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_g
                          % (key, GRAD_FUSED_MAXP, npoly))
     for ia, arm in enumerate(batch.arms):
         lib = libs[arm.name]
-        if _arm_resol(arm, ia, resols) is not None:
+        rs = _arm_resol(arm, ia, resols)
+        if rs is not None and not resol_gradient:
             raise ValueError('%s does not go with a resolution matrix (resol_params / '
                              'the spectra\'s own, arm %s)' % (key, arm.name))
         if arm.G > 1:
@@ -1463,6 +1489,8 @@ def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_g
                                  'ntp, three buffers of ntp doubles in LDS'
                                  % (key, arm.name, 'an nn' if nn else 'a triangulation',
                                     arm.npix, lib.ntp))
+            if rs is not None:
+                _check_fused_resol(key, arm, lib, rs, npoly, 0, vsini_grad)
             continue
         if lib.kind != 'regulargrid':
             raise ValueError('%s needs regular-grid (polylinear) libraries: %s is a %s '
@@ -1477,25 +1505,30 @@ def _check_fused_scope(key, ok, batch, libs, npoly, resols, fast_interp, vsini_g
             raise ValueError('%s: arm %s (npix = %d, ntp = %d) is outside the kernel\'s '
                              'geometry: 32 <= ntp, 2 npix <= ntp, three buffers of ntp '
                              'doubles in LDS' % (key, arm.name, arm.npix, lib.ntp))
+        if rs is not None:
+            _check_fused_resol(key, arm, lib, rs, npoly, lib.ndim, vsini_grad)
 
 
 def can_fuse_objective_grad(batch, libs, resols=None, fast_interp=False, npoly=10,
-                            vsini_grad=False, nn_gradient=False, tri_gradient=False):
+                            vsini_grad=False, nn_gradient=False, tri_gradient=False,
+                            resol_gradient=False):
     """whether the fused gradient covers this batch (check_fused_grad_scope says why
     not)"""
     try:
         check_fused_grad_scope(batch, libs, npoly, resols, fast_interp, vsini_grad,
-                               nn_gradient=nn_gradient, tri_gradient=tri_gradient)
+                               nn_gradient=nn_gradient, tri_gradient=tri_gradient,
+                               resol_gradient=resol_gradient)
     except ValueError:
         return False
     return True
 
 
-def fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys=0.0):
+def fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys=0.0,
+                             resols=None):
     """fill_objective_arms for rvs_objective_grad: the orthonormal basis of the same
     continuum space (ArmData.basis_ortho) with its constant, as chisq_point_grad wires
     the chain's descriptors; returns the tensors to keep alive"""
-    keep = fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys)
+    keep = fill_objective_arms(arr, batch, libs, npoly, rbf, espec_sys, resols)
     for ia, arm in enumerate(batch.arms):
         qt, const = arm.basis_ortho(npoly, rbf)
         arr[ia].pt.polysT = qt.data_ptr()
@@ -1504,10 +1537,24 @@ def fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys=0.0
     return keep
 
 
+def _fused_grad_resol(batch, resols, resol_gradient):
+    # whether a fused-gradient call goes to the _resol entry points: an arm carries a
+    # matrix (without resol_gradient that is the callers' ValueError, here too)
+    any_resol = any(_arm_resol(arm, ia, resols) is not None
+                    for ia, arm in enumerate(batch.arms))
+    if any_resol and not resol_gradient:
+        raise ValueError("config['fused_gradient'] does not go with a resolution matrix "
+                         "(resol_params / the spectra's own) unless "
+                         "config['resol_gradient'] is set")
+    return any_resol
+
+
 def objective_grad_from_template(batch, libs, templs, outsides, vsini, vel, npoly=5,
                                  rbf=True, job_spec=None, vsini_grad=False,
-                                 espec_sys=0.0):
-    """the from-template form of the fused gradient (rvs_objective_grad_from_template):
+                                 espec_sys=0.0, resols=None, resol_gradient=False):
+    """the from-template form of the fused gradient (rvs_objective_grad_from_template;
+    resol_gradient: rvs_objective_grad_from_template_resol, which applies the arms'
+    resolution matrices -- `resols` or the spectra's own -- and their transposes):
     templs[a] [J, ntp_a] float64 (unbroadened), outsides[a] [J].  Returns chisq [J],
     grad [J, 1 + vsini_grad] = d/d(vel[, vsini]), status int32 [J], the adjoint rows
     tbars[a] [J, ntp_a] = d chisq / d templs[a], and the call's scratch (which
@@ -1521,7 +1568,9 @@ def objective_grad_from_template(batch, libs, templs, outsides, vsini, vel, npol
     vg = int(bool(vsini_grad))
     arr = (_lib.ObjectiveArm * narm)()
     bconst = (ctypes.c_double * narm)()
-    keep = fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys)
+    keep = fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys,
+                                    resols)
+    resol = _fused_grad_resol(batch, resols, resol_gradient)
     out = torch.empty(J, dtype=torch.float64, device=dev)
     grad = torch.empty((J, 1 + vg), dtype=torch.float64, device=dev)
     status = torch.zeros(J, dtype=torch.int32, device=dev)
@@ -1539,7 +1588,9 @@ def objective_grad_from_template(batch, libs, templs, outsides, vsini, vel, npol
     op = (ctypes.c_void_p * narm)(*[o.data_ptr() for o in outsides])
     bp = (ctypes.c_void_p * narm)(*[t.data_ptr() for t in tbars])
     with _ktime('objective_grad_from_template', J):
-        rc = L.rvs_objective_grad_from_template(
+        call = L.rvs_objective_grad_from_template_resol if resol else \
+            L.rvs_objective_grad_from_template
+        rc = call(
             ctypes.addressof(arr), narm, npoly, vg, ctypes.cast(tp, ctypes.c_void_p),
             ctypes.cast(op, ctypes.c_void_p), _lib.ptr(vsini), _lib.ptr(job_spec), J,
             _lib.ptr(vel), float(batch.badchi), ctypes.addressof(bconst),
@@ -1575,7 +1626,8 @@ def _tri_row_bytes(lib):
 
 
 def _objective_grad_fused_rows(batch, libs, params, vsini, vel, npoly, rbf, job_spec,
-                               vsini_grad, espec_sys, tbar_bytes, reverse, row_bytes):
+                               vsini_grad, espec_sys, tbar_bytes, reverse, row_bytes,
+                               resols=None, resol_gradient=False):
     # MLP and Delaunay libraries: template rows -> rvs_objective_grad_from_template ->
     # the evaluator's reverse step per arm (reverse(lib, params, row, tbar): the network's
     # reverse pass, the contraction with the simplex's tangents) -> the sum over the
@@ -1602,7 +1654,8 @@ def _objective_grad_fused_rows(batch, libs, params, vsini, vel, npoly, rbf, job_
         o, gvv, st, tbars, scratch = objective_grad_from_template(
             batch, libs, [r[0] for r in rows], [r[1] for r in rows],
             None if vsini is None else vsini[sl], vel[sl], npoly, rbf,
-            None if job_spec is None else job_spec[sl], vsini_grad, espec_sys)
+            None if job_spec is None else job_spec[sl], vsini_grad, espec_sys,
+            resols, resol_gradient)
         gps = [reverse(lib, p, r, tb) for lib, r, tb in zip(ls, rows, tbars)]
         gp = (ctypes.c_void_p * narm)(*[g.data_ptr() for g in gps])
         g = grad[sl]
@@ -1617,7 +1670,8 @@ def _objective_grad_fused_rows(batch, libs, params, vsini, vel, npoly, rbf, job_
 
 def objective_grad_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
                          job_spec=None, vsini_grad=False, espec_sys=0.0,
-                         nn_gradient=False, tbar_bytes=None, tri_gradient=False):
+                         nn_gradient=False, tbar_bytes=None, tri_gradient=False,
+                         resols=None, resol_gradient=False):
     """get_chisq and its gradient for J (spectrum, parameters, vsini, velocity) jobs
     as ONE kernel per (job, arm) (rvs_objective_grad, the adjoint method): no template
     row, tangent row or spline record in HBM.  Returns chisq [J] (with the outside
@@ -1631,13 +1685,19 @@ def objective_grad_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
     float32 arithmetic; tbar_bytes: the byte budget of one chunk's rows (default
     TBAR_BUDGET, which says what is counted; the results do not depend on it).
     tri_gradient: Delaunay libraries take the same form with rvs_template_tri_vjp as the
-    reverse step, float64 throughout (16 ntp + 8 ndim + 4 bytes per job and arm)."""
+    reverse step, float64 throughout (16 ntp + 8 ndim + 4 bytes per job and arm).
+    resol_gradient: the arms' resolution matrices -- `resols` (spec_fit._resols) or the
+    spectra's own -- are applied inside the kernel, the band on the pixels' spline values
+    and its transpose on the adjoint row (rvs_objective_grad_resol,
+    rvs_objective_grad_from_template_resol; DESIGN 4.27), on every kind of library above;
+    without it a matrix raises ValueError."""
     import ctypes
     if vsini_grad and vsini is None:
         raise ValueError('vsini_grad=True needs vsini: without rotation there is no '
                          'vsini to differentiate by')
-    check_fused_grad_scope(batch, libs, npoly, None, False, vsini_grad,
-                           nn_gradient=nn_gradient, tri_gradient=tri_gradient)
+    check_fused_grad_scope(batch, libs, npoly, resols, False, vsini_grad,
+                           nn_gradient=nn_gradient, tri_gradient=tri_gradient,
+                           resol_gradient=resol_gradient)
     L = _lib.lib()
     dev = batch.device
     kind = libs[batch.arms[0].name].kind
@@ -1649,7 +1709,8 @@ def objective_grad_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
         return _objective_grad_fused_rows(
             batch, libs, params, vsini, vel, npoly, rbf, job_spec, vsini_grad, espec_sys,
             tbar_bytes, *((_nn_reverse, _nn_row_bytes) if kind == 'nn'
-                          else (_tri_reverse, _tri_row_bytes)))
+                          else (_tri_reverse, _tri_row_bytes)),
+            resols=resols, resol_gradient=resol_gradient)
     vel = vel.to(device=dev, dtype=torch.float64).contiguous()
     params = params.to(device=dev, dtype=torch.float64).contiguous()
     J = vel.shape[0]
@@ -1657,7 +1718,9 @@ def objective_grad_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
     ntan = libs[batch.arms[0].name].ndim + (1 if vsini_grad else 0)
     arr = (_lib.ObjectiveArm * narm)()
     bconst = (ctypes.c_double * narm)()
-    keep = fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys)
+    keep = fill_objective_grad_arms(arr, bconst, batch, libs, npoly, rbf, espec_sys,
+                                    resols)
+    resol = _fused_grad_resol(batch, resols, resol_gradient)
     out = torch.empty(J, dtype=torch.float64, device=dev)
     grad = torch.empty((J, 1 + ntan), dtype=torch.float64, device=dev)
     status = torch.zeros(J, dtype=torch.int32, device=dev)
@@ -1668,13 +1731,14 @@ def objective_grad_fused(batch, libs, params, vsini, vel, npoly=5, rbf=True,
     if job_spec is not None:
         job_spec = job_spec.to(device=dev, dtype=torch.int32).contiguous()
     with _ktime('objective_grad', J):
-        rc = L.rvs_objective_grad(ctypes.addressof(arr), narm, npoly, ntan,
-                                  _lib.ptr(params), _lib.ptr(vsini), _lib.ptr(job_spec),
-                                  J, _lib.ptr(vel), float(batch.badchi),
-                                  ctypes.addressof(bconst), _lib.ptr(scratch),
-                                  _lib.ptr(out), _lib.ptr(grad), _lib.ptr(status),
-                                  _lib.stream())
-        _lib.check(rc, 'rvs_objective_grad')
+        call = L.rvs_objective_grad_resol if resol else L.rvs_objective_grad
+        rc = call(ctypes.addressof(arr), narm, npoly, ntan,
+                  _lib.ptr(params), _lib.ptr(vsini), _lib.ptr(job_spec),
+                  J, _lib.ptr(vel), float(batch.badchi),
+                  ctypes.addressof(bconst), _lib.ptr(scratch),
+                  _lib.ptr(out), _lib.ptr(grad), _lib.ptr(status),
+                  _lib.stream())
+        _lib.check(rc, 'rvs_objective_grad_resol' if resol else 'rvs_objective_grad')
     del keep
     return out, grad, status
 

@@ -369,7 +369,9 @@ class GradChain:
     4.25) it also holds a chunk's adjoint rows [cap, ntp] per arm and the work of the
     networks' reverse pass; on Delaunay libraries (the objective's tri_gradient set;
     rvs_bfgs_run_grad_fused_tri) the adjoint rows and the arms' parameter
-    components.
+    components.  Under resolution matrices (the objective's resol_gradient set; DESIGN
+    4.27) the arm descriptors carry the taps and the runs are the _resol forms of the
+    three (rvs_bfgs_run_grad_fused_resol, _nn_resol, _tri_resol): still no row buffers.
     What that kernel does not cover, fisher=True included, raises ValueError.
     fused_fisher=True (config['fused_fisher']): the Fisher form with the rows' value,
     gradient and matrix from ONE rvs_objective_fisher call per chunk (rvs_lm_run_fused;
@@ -531,7 +533,8 @@ class GradChain:
         self.garms = (_lib.ObjectiveArm * narm)()
         self.bconst = (ctypes.c_double * narm)()
         self._keep = engine.fill_objective_grad_arms(self.garms, self.bconst, batch, libs,
-                                                     pobj.npoly, pobj.rbf)
+                                                     pobj.npoly, pobj.rbf,
+                                                     resols=pobj.resols)
         self.chi = torch.empty(cap, **f64)
         self.grad = torch.empty((cap, 1 + self.ntan), **f64)
         self.njev = torch.zeros(pobj.S, dtype=torch.int32, device=pobj.dev)
@@ -543,8 +546,13 @@ class GradChain:
             pobj, cap, 'second_minimizer_jac', engine.check_fused_grad_scope, False,
             what='the Fisher form of the chain (fisher=True)' if fisher else None,
             nn_gradient=getattr(pobj, 'nn_gradient', False),
-            tri_gradient=getattr(pobj, 'tri_gradient', False))
+            tri_gradient=getattr(pobj, 'tri_gradient', False),
+            resol_gradient=getattr(pobj, 'resol_gradient', False))
         cap = self.cap
+        # arms under a resolution matrix (admitted with resol_gradient): the _resol forms
+        # of the three runs
+        self.fused_resol = any(engine._arm_resol(arm, ia, pobj.resols) is not None
+                               for ia, arm in enumerate(batch.arms))
         # MLP libraries (admitted with nn_gradient): rvs_bfgs_run_grad_fused_nn;
         # Delaunay libraries (with tri_gradient): rvs_bfgs_run_grad_fused_tri
         self.fused_nn = libs[batch.arms[0].name].kind == 'nn'

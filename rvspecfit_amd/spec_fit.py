@@ -516,7 +516,11 @@ def get_chisq_grad(specdata, vel, atm_params, rot_params=None, options=None,
     reverse pass (rvs_objective_grad_from_template, rvs_template_nn_vjp), the parameter
     components in float32 arithmetic.  With config['tri_gradient'] beside it Delaunay
     libraries of up to 6 parameters likewise: the adjoint row is contracted with the
-    tangents of the point's simplex (rvs_template_tri_vjp), float64 throughout.
+    tangents of the point's simplex (rvs_template_tri_vjp), float64 throughout.  With
+    config['resol_gradient'] beside it resolution matrices of up to 33 diagonals are
+    applied inside that kernel, the band on the model and its transpose on the adjoint
+    row (rvs_objective_grad_resol); a wider band or an arm with 2 npix + nd - 1 > ntp
+    raises ValueError naming the arm and the limit.
     An MLP library is among them unless config['nn_gradient'] is true: its tangent
     rows (rvs_template_nn_grad) are float32 arithmetic, exact to float32 rounding only.  On a Delaunay library a point that no simplex
     holds has the value's penalty and a zero gradient."""
@@ -604,14 +608,16 @@ def _chisq_grad(batch, libs, js, vel, params, vsini, npoly, rbf, esys,
                                       vsini_grad,
                                       what='the Fisher matrix' if fisher else None,
                                       nn_gradient=nn_gradient,
-                                      tri_gradient=tri_gradient)
+                                      tri_gradient=tri_gradient,
+                                      resol_gradient=resol_gradient)
         if not outside_penalty:
             raise ValueError("config['fused_gradient'] does not go with "
                              'outside_penalty=False: the kernel adds the penalty')
         return engine.objective_grad_fused(batch, libs, params, vsini, vel, npoly, rbf,
                                            js, vsini_grad, esys,
                                            nn_gradient=nn_gradient,
-                                           tri_gradient=tri_gradient)
+                                           tri_gradient=tri_gradient, resols=resols,
+                                           resol_gradient=resol_gradient)
     if fused_fisher and fisher:
         # config['fused_fisher']: value, gradient and Fisher matrix in one forward-mode
         # kernel per (job, arm) (rvs_objective_fisher); what it does not cover is an

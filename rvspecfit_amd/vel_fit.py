@@ -1048,7 +1048,9 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
                          "config['second_minimizer_jac'] name two polishes: set one")
     # config['fused_gradient']: the polish's rows from rvs_objective_grad, one kernel
     # per (row, arm) (rvs_bfgs_run_grad_fused).  What needs the chain's tangent rows
-    # beside the key is an error that says so; nothing changes path silently
+    # beside the key is an error that says so; nothing changes path silently.  With
+    # config['resol_gradient'] beside it resolution matrices go into the kernel
+    # (rvs_bfgs_run_grad_fused_resol); a band it does not take is an error too
     fused_grad = bool(config.get('fused_gradient'))
     if fused_grad:
         engine.check_fused_grad_scope(
@@ -1056,6 +1058,7 @@ def _process_one(specdata, paramDict0, fixParam=None, options=None, config=None,
             spec_fit._resols(batch, resolParams), bool(options.get('fast_interp')),
             vsini_grad=fitVsini, nn_gradient=bool(config.get('nn_gradient')),
             tri_gradient=bool(config.get('tri_gradient')),
+            resol_gradient=bool(config.get('resol_gradient')),
             what="config['second_minimizer_lm'] (the Levenberg-Marquardt polish on the "
                  "Fisher matrix)" if lm_polish else
                  ("config['fisher_uncertainties'] (the Fisher matrix)"

@@ -3,13 +3,18 @@
 (rvs_bfgs_run) against the polish on the analytic gradient (rvs_bfgs_run_grad,
 config['second_minimizer_jac']), alternating, in one process.
 usage: bfgs_jac_ab.py [--spectra S] [--npoly P] [--rounds R] [--evaluator polylinear|tri|nn]
-                      [--fused]
+                      [--fused] [--resolution-matrix]
 --fused: a third polish, the analytic gradient from rvs_objective_grad
 (rvs_bfgs_run_grad_fused, config['fused_gradient']), alternating with the two.
 --evaluator nn: bench.py's MLP libraries; the chain then runs with config['nn_gradient']
 and --fused through rvs_bfgs_run_grad_fused_nn.
 --evaluator tri: bench.py's Delaunay libraries; --fused then runs with
 config['tri_gradient'] through rvs_bfgs_run_grad_fused_tri.
+--resolution-matrix: every spectrum carries resolution matrices of 11 diagonals
+(tools/perf/_resol.py, what `bench.py --resolution-matrix` puts on its batch) and every
+polish runs with config['resol_gradient']: the differenced one on the value kernel's
+band, the chain through rvs_chisq_point_grad_resol, --fused through
+rvs_bfgs_run_grad_fused_resol.
 The workload is bench.py's, built as `bench.py --process` builds it (its synthetic
 DESI-shape libraries and seeded spectra, the start parameters from the CCF stage of
 pipeline.fit_batch).  vel_fit.process runs once without the second minimiser; its
@@ -35,6 +40,7 @@ def main():
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--evaluator', choices=['polylinear', 'tri', 'nn'], default='polylinear')
     ap.add_argument('--fused', action='store_true')
+    ap.add_argument('--resolution-matrix', action='store_true')
     args = ap.parse_args()
     sys.path.insert(0, REPO)
     import numpy as np
@@ -62,6 +68,10 @@ def main():
                               (bench.make_spectra_device(tp, dev) if args.evaluator != 'nn'
                                else bench.make_spectra_from_library(tp, dev, bench.CONFIG))])
     cfg, opt = dict(bench.CONFIG), dict(bench.OPTIONS, npoly=args.npoly)
+    if args.resolution_matrix:
+        import _resol
+        _resol.attach(batch, S, dev)
+        cfg['resol_gradient'] = True
     if args.evaluator == 'nn':
         cfg['nn_gradient'] = True
     if args.evaluator == 'tri' and args.fused:
@@ -151,6 +161,7 @@ def main():
             f_fused_equals_f_jac=int((dj == 0).sum()))
     print(json.dumps(dict(
         spectra=S, npoly=args.npoly, evaluator=args.evaluator, rounds=args.rounds,
+        resolution_matrix=args.resolution_matrix,
         n=len(cols), chain_cap=chain.cap, chain_bytes=chain.nbytes,
         fd=dict(stage_s_median=round(float(np.median(t_fd)), 4),
                 stage_s_min=round(min(t_fd), 4), stage_s_max=round(max(t_fd), 4),

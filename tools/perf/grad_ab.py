@@ -19,6 +19,10 @@ the largest difference of the fused gradient from the chain's).
 config['resol_gradient'] (rvs_chisq_point_grad_resol), the forward difference under the
 same matrices, and a third arm is the same analytic call on the same spectra WITHOUT
 matrices, alternating with the two (no_matrix_s_*, resol_over_no_matrix_median).
+With --fused beside it the fused leg runs under the same matrices with both keys
+(rvs_objective_grad_resol: the band and its transpose inside the kernel),
+and one more leg is the fused call on the same spectra WITHOUT matrices
+(fused_no_matrix_s_*, fused_resol_over_fused_no_matrix_median: what the band costs there).
 The workload is bench.py's (its synthetic DESI-shape libraries and
 spectra); the jobs are its truth parameters, jittered inside the grid, spread over the
 S spectra.  Both arms run alternately in one process, R rounds after a warm-up; one
@@ -111,6 +115,10 @@ def main():
         return spec_fit.chisq_grad_jobs(batch, idx, vel, par, vs, opt, fcfg,
                                         vsini_grad=vg)
 
+    def fused_no_matrix():
+        return spec_fit.chisq_grad_jobs(plain, idx, vel, par, vs, opt, fcfg,
+                                        vsini_grad=vg)
+
     def differenced():
         f0, _ = spec_fit.chisq_jobs(batch, idx, vel, par, vs, opt, cfg)
         cols = []
@@ -135,7 +143,9 @@ def main():
         timed(no_matrix)
     if args.fused:
         timed(fused)
-    ta, td, tn, tf = [], [], [], []
+        if plain is not None:
+            timed(fused_no_matrix)
+    ta, td, tn, tf, tfn = [], [], [], [], []
     for _ in range(args.rounds):
         t, (ca, ga, st) = timed(analytic)
         ta.append(t)
@@ -146,6 +156,8 @@ def main():
         if args.fused:
             t, (cf, gf, sf) = timed(fused)
             tf.append(t)
+            if plain is not None:
+                tfn.append(timed(fused_no_matrix)[0])
     more = {}
     if args.fused:
         okf = (st == 0) & (sf == 0)
@@ -162,6 +174,11 @@ def main():
                 ((gf - ga).abs() / ga.abs().max(dim=1, keepdim=True).values)[okf].max()),
             fused_vs_chain_value_max_rel=float(
                 ((cf - ca).abs() / ca.abs().clamp(min=1e3))[okf].max()))
+    if tfn:
+        more.update(fused_no_matrix_s_median=round(float(np.median(tfn)), 6),
+                    fused_no_matrix_s_min=round(min(tfn), 6),
+                    fused_resol_over_fused_no_matrix_median=round(
+                        float(np.median(tf) / np.median(tfn)), 3))
     if plain is not None:
         more.update(no_matrix_s_median=round(float(np.median(tn)), 6),
                     no_matrix_s_min=round(min(tn), 6),
